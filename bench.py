@@ -16,7 +16,13 @@ in TM_INNER_RELAX mode, run through the C-ABI handle with the coordinates reside
   --config 5            BASELINE configs[4]: independent 2048^2 slices, 8 per GPU ("replicas only": no communication).
 
 `python bench.py --gpus N` starts its own N ranks (one process per GPU, torch.distributed.run as a child process)
-when it is not already running under a launcher.  Prints ONE JSON line on rank 0."""
+when it is not already running under a launcher.  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set-up, settling, the W warm-up steps, the K timed steps, the line.
+`--full` adds the rest, outside the timed region: W + K steps timed on the cold device before the settling (cold_ms_per_step),
+the copy / triad probe and the single-sweep reference of the roofline, the solve-to-tolerance and Krylov reports and the CPU
+baseline (`--no-solve` / `--no-cpu-baseline` drop parts of it again).
+`--dump-outputs DIR` writes what the last timed step left on the device as DIR/*.npy (dump_outputs)."""
 from __future__ import annotations
 
 import argparse
@@ -241,6 +247,30 @@ def krylov_iteration(n, smooth, solver, configs, iters=100):
             "frac": gbps / HBM_PEAK_GBPS, "what": "hip/bicgstab, two fused kernels per iteration, wall time of one capped Picard solve / iterations (set-up kernels included)"}
 
 
+DUMP_MAX_NODES = 1 << 21      # --dump-outputs: at most 2^21 sampled nodes over all ranks (2 x float64 each: 32 MiB)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, mesh, owned, st, rank, world):
+    """--dump-outputs: what the timed path hands its caller after the last timed step -- the device-resident coordinates of this
+    rank's blocks (downloaded into the mesh) and the residual norm the last iterate() call returned.  coords.npy is (k, 2) float64:
+    the owned blocks' nodes flattened in block order, row-major within a block, all of them when they fit DUMP_MAX_NODES / world,
+    else a sorted sample drawn with a fixed seed (the same nodes in every run with the same arguments).  With several ranks every
+    rank writes its own coords_rank<r>.npy.  The state is that after config.sweeps_before_timed + K sweeps (the line): --full runs
+    W + K cold sweeps more than a plain run, and so does not dump the same coordinates as a plain run with the same W and K."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    xy = np.concatenate([mesh.blocks[b].points.data.reshape(-1, 2) for b in owned])
+    cap = DUMP_MAX_NODES // max(1, world)
+    if len(xy) > cap:
+        idx = np.sort(np.random.default_rng(DUMP_SEED + rank).choice(len(xy), cap, replace=False))
+        xy = xy[idx]
+    suffix = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(out_dir, f"coords{suffix}.npy"), np.ascontiguousarray(xy, dtype=np.float64))
+    np.save(os.path.join(out_dir, f"residual{suffix}.npy"), np.array([st["last_residual"]], dtype=np.float64))
+
+
 def self_launch(args):
     """--gpus N without a launcher: start N fresh ranks as a CHILD process (this process has not touched the GPU and never
     will) and relay rank 0's JSON line."""
@@ -267,8 +297,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", type=int, default=2, choices=[2, 4, 5], help="SURVEY 8d config: 2 = 4096^2 block(s) (default), 4 = 8 x 2048^2 strip strong scaling, 5 = independent 2048^2 slices")
     ap.add_argument("--size", dest="n", type=int, default=0, help="block edge (nodes); default 4096 (config 2) / 2048 (configs 4, 5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-solve", action="store_true", help="skip the (untimed) solve-to-1e-8 and T106 reports")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: W + K steps timed before the settling (cold_ms_per_step), the copy / triad probe and the single-sweep reference of the roofline, "
+                         "the (untimed) solve and Krylov reports and the CPU baseline (without it: set-up, warm-up, the timed steps, the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float64): the coordinates at a fixed seeded sample of "
+                         "the nodes (all of them up to 2^21 nodes) and the residual norm of the last step")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-solve", action="store_true", help="with --full: skip the (untimed) solve-to-1e-8 and T106 reports")
     ap.add_argument("--force-dist", action="store_true", help="run the multi-GPU code path (RCCL hooks) even with one rank")
     ap.add_argument("--verify", action="store_true",
                     help="after the timed region: gather every rank's blocks on rank 0 and compare them, bit for bit, with a single-handle run of the "
@@ -461,10 +497,11 @@ def main():
     settle_steps = 0 if args.settle_ms <= 0 else max(60, min(60000, int(args.settle_ms * 1e3 / max(est_us, 0.5)) // 6 * 6))
     ok = 1
     cold_dt = None
-    pre_steps = (args.warmup + args.steps + settle_steps) if settle_steps else 0   # untimed sweeps in front of the W warm-up steps
+    cold = args.full and settle_steps > 0
+    pre_steps = settle_steps + (args.warmup + args.steps if cold else 0)   # untimed sweeps in front of the W warm-up steps
     try:
-        if settle_steps:
-            # the figure a W + K run WITHOUT the settling phase reads (kernels loaded by the W steps, clocks not yet settled):
+        if cold:
+            # (--full) the figure a W + K run WITHOUT the settling phase reads (kernels loaded by the W steps, clocks not yet settled):
             # reported as config.cold_ms_per_step beside ms_per_step, never used for `value`
             sm.iterate(args.warmup)
             torch.cuda.synchronize()
@@ -472,6 +509,7 @@ def main():
             sm.iterate(args.steps)
             torch.cuda.synchronize()
             cold_dt = time.perf_counter() - tc
+        if settle_steps:
             sm.iterate(settle_steps)
         sm.iterate(args.warmup)
         torch.cuda.synchronize()
@@ -504,6 +542,9 @@ def main():
     dt = time.perf_counter() - t0
     k2_ms, k2_timed, k2_launches = sm.profile_read()
     sm.profile(0)
+    if args.dump_outputs:
+        sm.download()
+        dump_outputs(args.dump_outputs, mesh, owned, st, rank, world)
 
     verified = None
     if args.verify and dist is not None and coupled:
@@ -562,20 +603,21 @@ def main():
                                    + (f", {tj.get('date')}" if tj.get("date") else "") + ("; STALE (kernel source changed since), dropped" if stale else ""))
             except Exception:
                 traffic = None
-        # the measured ceiling beside the specification: copy / triad at this workload's footprint, in this run
-        import ctypes as C
+        # the measured ceiling beside the specification: copy / triad at this workload's footprint, in this run (--full)
+        stream = None
+        if args.full:
+            import ctypes as C
 
-        cp, tr = C.c_double(0), C.c_double(0)
-        try:
-            _capi.check(_capi.lib().tm_stream_probe(int(16 * nodes_rank), 20, C.byref(cp), C.byref(tr)))
-            stream = {"copy": cp.value, "triad": tr.value}
-        except Exception as e:   # noqa: BLE001 -- a diagnostic must not cost the line
-            print(f"[bench] stream probe failed: {e}", file=sys.stderr)
-            stream = None
-        # north_star's "single 4096^2 elliptic sweep >= 60 % of the HBM roofline" in the same line: ONE sweep per launch (K2) on the same
+            cp, tr = C.c_double(0), C.c_double(0)
+            try:
+                _capi.check(_capi.lib().tm_stream_probe(int(16 * nodes_rank), 20, C.byref(cp), C.byref(tr)))
+                stream = {"copy": cp.value, "triad": tr.value}
+            except Exception as e:   # noqa: BLE001 -- a diagnostic must not cost the line
+                print(f"[bench] stream probe failed: {e}", file=sys.stderr)
+        # north_star's "single 4096^2 elliptic sweep >= 60 % of the HBM roofline" in the same line (--full): ONE sweep per launch (K2) on the same
         # block, 96 launches event-timed outside the timed region, behind 480 untimed ones (that pass is bandwidth-bound and runs below the power cap)
         single_ref = None
-        if world == 1 and args.config == 2 and fused:
+        if args.full and world == 1 and args.config == 2 and fused:
             try:
                 m1 = configs.single_block(n, n)
                 with smooth.Smoother(m1, solver.Option.hip(inner=solver.Inner.relax, single_sweep=True), stream=torch.cuda.current_stream().cuda_stream) as s1:
@@ -607,7 +649,9 @@ def main():
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": workload, "nodes_total": nodes_total, "nodes_per_gpu": nodes_rank,
                        "solver": "hip/relax (fused Jacobi elliptic sweep" + (f", {spl} sweeps per kernel pass)" if fused else ")"), "omega": 1.0,
-                       "settle_steps": settle_steps, "cold_ms_per_step": (cold_dt / args.steps * 1e3 if cold_dt else None),
+                       "full": args.full, "settle_steps": settle_steps,
+                       "sweeps_before_timed": pre_steps + args.warmup,   # the state the timed steps (and a dump) start from: settle [+ W + K cold] + W
+                       "cold_ms_per_step": (cold_dt / args.steps * 1e3 if cold_dt else None),
                        "cold_value": (nodes_rank * args.steps / cold_dt if cold_dt and dist is None else None),
                        "settle": {"steps": settle_steps, "why": "untimed sweeps of the same workload before the W warm-up steps: the pass runs at the board power cap and "
                                   "the clock needs ~50 ms of load to settle (tools/dev/ramp_probe.py); --settle-ms 0 turns it off"},
@@ -654,7 +698,7 @@ def main():
                     ref1 = None
             out["config"]["value_1gpu_stored"] = ref1
             out["config"]["vs_1gpu"] = (value / ref1) if ref1 else None
-        if world == 1 and args.config == 2 and not args.no_solve:
+        if args.full and world == 1 and args.config == 2 and not args.no_solve:
             c = out["config"]
             c["solve_to_1e-8"] = solve_to_tolerance(n, smooth, solver, configs)
             c["solve_to_converged"] = solve_to_converged(n, smooth, solver, configs)
@@ -672,7 +716,8 @@ def main():
                 out["roofline"]["krylov_frac"] = kr["frac"]
             except Exception as e:   # noqa: BLE001 -- a diagnostic must not cost the line
                 print(f"[bench] Krylov iteration probe failed: {e}", file=sys.stderr)
-        if not args.no_cpu_baseline and world == 1 and args.config == 2:
+        cpu_leg = args.full and not args.no_cpu_baseline
+        if cpu_leg and world == 1 and args.config == 2:
             cb = cpu_baseline(n)
             if not args.no_solve and "t106_json_as_written" in cb:
                 cb["t106_json_as_written"]["gpu_same_job"] = t106_gpu(smooth, solver, wcf)
@@ -681,7 +726,7 @@ def main():
             cb["mirror_sweep_nodes_per_s_1_thread"] = cb["mirror_sweep"]["value"]
             cb["mirror_sweep_nodes_per_s_all_threads"] = cb["mirror_sweep"]["all_threads"]["value"]
             out["cpu_baseline"] = cb
-        elif not args.no_cpu_baseline:
+        elif cpu_leg:
             out["cpu_baseline"] = None
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())

@@ -13,12 +13,12 @@ prof() { name=$1; shift; rocprofv3 --kernel-trace --stats --output-format csv -d
   # the same run without the clock ramp of the cold device (launches starting within 60 ms of a kernel's first launch dropped): the file the bench line's `frac` is checked against
   python3 "$root/tools/steady_stats.py" "$out/$name"/p_kernel_trace.csv "$out/${tag}_${name}_kernel_steady.csv" --skip-ms 60 > "$out/$name.steady.txt" 2>&1;
   grep -h '^{' "$out/$name.out" > "$out/${tag}_${name}_line.json" 2>/dev/null; }
-prof bench4096_k2x3 python3 "$root/bench.py" --no-cpu-baseline --no-solve
-TM_FUSE_3=0 prof bench4096_k2x2 python3 "$root/bench.py" --no-cpu-baseline --no-solve
-prof bench4096_k2_single python3 "$root/bench.py" --no-cpu-baseline --no-solve --single-sweep
+prof bench4096_k2x3 python3 "$root/bench.py" --full --no-cpu-baseline --no-solve
+TM_FUSE_3=0 prof bench4096_k2x2 python3 "$root/bench.py" --full --no-cpu-baseline --no-solve
+prof bench4096_k2_single python3 "$root/bench.py" --full --no-cpu-baseline --no-solve --single-sweep
 prof bicgstab4096 python3 "$root/tools/prof_sweep.py" 4096 24 bicgstab
 prof mg_solve4096 python3 "$root/tools/solve_probe.py" 4096 1e-6
-prof config4_8x2048 python3 "$root/bench.py" --config 4 --no-cpu-baseline --steps 100
+prof config4_8x2048 python3 "$root/bench.py" --full --config 4 --no-cpu-baseline --steps 100
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -o p -- python3 "$root/tools/prof_sweep.py" 4096 20 relax > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$out/pmc_write" -o p -- python3 "$root/tools/prof_sweep.py" 4096 20 relax > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAVES --output-format csv -d "$out/pmc_sq" -o p -- python3 "$root/tools/prof_sweep.py" 4096 21 relax > /dev/null 2>&1
