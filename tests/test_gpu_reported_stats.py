@@ -1,0 +1,442 @@
+"""GPU: every statistic the smoother reports (include/tm_hip.h tm_stats: last_dx2, last_dy2, last_residual, scaled_residual_rms), and
+the stop decisions taken on them, against sums formed on the HOST from downloaded coordinates -- independently of the device's
+per-workgroup partial sums and their fixed-order finalize (Smoother::reduce).
+
+Definitions restated on the host:
+  * last_dx2 / last_dy2 = sum over the nodes the handle owns of (x_before - x_after)^2, (y...)^2.  The owned set (tm_plan.cpp: whole
+    blocks, LocalPlan::n_owned = sum ni * nj) stores an interface node once per block that holds it, so the sum runs over every node of
+    every block's array -- duplicates included, ghost rows nowhere; dof (tm_smoother_dof, topology_from_desc) counts the same rows.
+  * last_residual = (last_dx2 + last_dy2)^2, exactly (smooth.zig:136).
+  * scaled_residual_rms = sqrt(||D^-1 (b - A(X) X)||^2 / (2 dof)) at the start of the last outer iteration, A and b assembled at that X by
+    the faithful oracle (oracle.System, as tests/residual_check.py does), evaluated in extended precision.  Relax mode derives it from
+    the last sweep's displacement divided by omega: omega = 0.8 below, so that a missing or doubled division shows.
+
+Every case runs with TM_PARTIALS_GUARD=1: the handle keeps a guard region behind each partial-sum buffer and behind the reduction
+output and raises TM_E_HIP from the iterate call when a launch wrote into one.
+
+Launch regimes (the cases are chosen around them, and each case asserts it is where it was meant to be, from the host arithmetic of
+vec_nwg and the figures the handle prints under TM_DEBUG_RUNS): the vector kernels take vec_nwg(n) = min(ceil(n / 256), 2048)
+workgroups, except on a two-kernel BiCGStab handle (one process, bicgstab, no eager scalars) whose operator launch fits 512
+workgroups: there the partial-sum buffers hold 512 rows and the vector kernels must launch 512.  362^2 = 131 044 nodes is the last
+size with vec_nwg <= 512; 363^2 .. 1900^2 are capped; 2048^2's operator launch needs 978 workgroups, above the cap."""
+import json
+import os
+import re
+import threading
+
+import numpy as np
+import pytest
+
+from oracle import oracle
+from tests import residual_check
+from tests.conftest import OracleMesh, mesh_flat
+from turbomesh_amd import configs
+from turbomesh_amd.smoothing import smooth, solver
+from turbomesh_amd.smoothing import wall_control_function as wcf
+
+pytestmark = pytest.mark.gpu
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+UPDATE_RTOL = 1e-11      # host vs device update sums: reduction order only (the truncated sums were off by >= 30 %)
+RESIDUAL_RTOL = 1e-9     # host extended-precision residual vs the device's fp64 one
+LAZY_ROWS = 512          # partial rows of a two-kernel BiCGStab handle whose operator launch fits them (tm_smoother.cpp)
+
+
+@pytest.fixture(autouse=True)
+def _guard(monkeypatch):
+    monkeypatch.setenv("TM_PARTIALS_GUARD", "1")
+    monkeypatch.setenv("TM_DEBUG_RUNS", "1")
+
+
+def vec_nwg(n):
+    """tm_kernels.hip vec_nwg: one 256-lane workgroup per 256 rows, at most 8 per CU (2048), grid-stride beyond."""
+    return max(1, min((n + 255) // 256, 2048))
+
+
+def _launch_figures(err):
+    """The handle's partial-sum figures (TM_DEBUG_RUNS line of Smoother::create): allocated rows, operator, vector kernels."""
+    m = re.findall(r"partial-sum rows: (\d+) allocated; operator (\d+), overlapping strips (\d+), pairs (\d+), triples (\d+), "
+                   r"vector kernels (\d+) \(vec_nwg (\d+)\)", err)
+    assert m, "no partial-sum line from the handle"
+    rows, op, ov, pairs, triples, vec, vn = map(int, m[-1])
+    return dict(rows=rows, operator=max(op, ov), pairs=pairs, triples=triples, vector=vec, vec_nwg=vn)
+
+
+def _host_update(before, after):
+    d = before.astype(np.longdouble) - after.astype(np.longdouble)
+    return float((d[:, 0] * d[:, 0]).sum()), float((d[:, 1] * d[:, 1]).sum())
+
+
+def _check_update(st, before, after, what):
+    hx, hy = _host_update(before, after)
+    assert st["last_dx2"] == pytest.approx(hx, rel=UPDATE_RTOL, abs=1e-300), (what, st["last_dx2"], hx)
+    assert st["last_dy2"] == pytest.approx(hy, rel=UPDATE_RTOL, abs=1e-300), (what, st["last_dy2"], hy)
+    s = st["last_dx2"] + st["last_dy2"]
+    assert st["last_residual"] == s * s, what
+    return hx + hy
+
+
+def _host_scaled_rms(om, dof):
+    """sqrt(||D^-1 (b - A(X) X)||^2 / (2 dof)) with A, b the oracle's system at the coordinates of `om` (an OracleMesh)."""
+    s = oracle.System(om)
+    try:
+        s.fill(0)
+        assert s.dof == dof
+        p, i, v = s.lhs_p.copy(), s.lhs_i.copy(), s.lhs_values.copy()
+        b = np.stack([s.rhs_x, s.rhs_y], axis=1).copy()
+    finally:
+        s.close()
+    num, _ = residual_check.scaled_residual(p, i, v, b, om.flat())
+    return float(np.sqrt((num.astype(np.longdouble) ** 2).sum() / (2 * dof)))
+
+
+def _check_scaled(st, om, dof, what):
+    h = _host_scaled_rms(om, dof)
+    assert st["scaled_residual_rms"] == pytest.approx(h, rel=RESIDUAL_RTOL), (what, st["scaled_residual_rms"], h)
+
+
+INNERS = {
+    "bicgstab": dict(inner=solver.Inner.bicgstab),
+    "eager": dict(inner=solver.Inner.bicgstab, eager_scalars=True),
+    "fuse2_off": dict(inner=solver.Inner.bicgstab),   # + TM_FUSE_2=0: the vector kernels inside the loop
+    "mg_bicgstab": dict(inner=solver.Inner.mg_bicgstab),
+    "gmres": dict(inner=solver.Inner.gmres),
+}
+
+
+def _regime(n, inner, fig):
+    """Assert the launch regime the case was chosen for, from the host arithmetic."""
+    nodes = n * n
+    assert fig["vec_nwg"] == vec_nwg(nodes)
+    two_kernel = inner in ("bicgstab", "fuse2_off")
+    capped = two_kernel and fig["operator"] <= LAZY_ROWS and vec_nwg(nodes) > LAZY_ROWS
+    if two_kernel:
+        if n <= 362:
+            assert vec_nwg(nodes) <= LAZY_ROWS, n
+        elif n <= 1900:
+            assert capped, (n, fig)        # the range the cap applies to
+        else:
+            assert fig["operator"] > LAZY_ROWS and not capped, (n, fig)
+    assert fig["vector"] == (LAZY_ROWS if capped else vec_nwg(nodes)), (n, inner, fig)
+    for k in ("operator", "pairs", "triples", "vector"):
+        assert fig[k] <= fig["rows"], (k, fig)
+
+
+def _single_block_updates(n, inner, monkeypatch, capfd, iterations=2):
+    if inner == "fuse2_off":
+        monkeypatch.setenv("TM_FUSE_2", "0")
+    mesh = configs.single_block(n, n, perturb=0.25)
+    # a loose inner tolerance: the statistics do not depend on how far the inner solve goes, and the large sizes stay cheap
+    opt = solver.Option.hip(rtol_initial=True, rtol=1e-6, **INNERS[inner])
+    capfd.readouterr()
+    with smooth.Smoother(mesh, opt) as sm:
+        fig = _launch_figures(capfd.readouterr().err)
+        _regime(n, inner, fig)
+        assert sm.dof == n * n
+        for k in range(iterations):
+            before = mesh_flat(mesh).copy()
+            # the oracle's assembly up to 600^2 for every route, at 1024^2 for the default one
+            om = OracleMesh(mesh) if n <= 600 or (n <= 1024 and inner == "bicgstab") else None
+            st = sm.iterate(1)
+            sm.download()
+            moved = _check_update(st, before, mesh_flat(mesh), (n, inner, k))
+            assert moved > 0.0
+            if om is not None:
+                _check_scaled(st, om, sm.dof, (n, inner, k))
+
+
+# GMRES(30) with the diagonal alone up to 600^2
+@pytest.mark.parametrize("n,inner", [(n, inner) for n in (33, 362, 363, 600, 1024, 1448) for inner in INNERS if inner != "gmres" or n <= 600])
+def test_update_norms_and_scaled_residual_single_block(n, inner, monkeypatch, capfd):
+    _single_block_updates(n, inner, monkeypatch, capfd)
+
+
+def _refined_example(name, factor):
+    from turbomesh_amd.input import Input
+
+    j = json.load(open(os.path.join(GOLD, "examples", name, name + ".json")))
+    nc = j["template"]["O4H"]["num_cells"]
+    for k in nc:
+        nc[k] *= (2 if k == "o_grid" else factor) if factor > 2 else factor   # as tests/test_gpu_round3_api.py refines T106
+    inp = Input.parse(json.dumps(j))
+    mesh = inp.template.run(inp.geometry(GOLD))
+    w = inp.wall_control_function.white
+    return mesh, wcf.Algorithm(wcf.White(w.ds_target, w.theta_target))
+
+
+def _example_updates(name, factor, iterations, capfd, **option):
+    # the production route: Inner.auto resolves to the two-kernel BiCGStab on these clustered O-grids with the White control function,
+    # more than 131 072 nodes in operator launches of <= 512 workgroups -- the capped regime: LS89 x 2 (147 398 nodes), T106 x 4
+    # (279 488), T106 x 8 (891 608 nodes, 508 operator workgroups)
+    mesh, cf = _refined_example(name, factor)
+    capfd.readouterr()
+    with smooth.Smoother(mesh, solver.Option.hip(inner=solver.Inner.auto, **option), cf) as sm:
+        fig = _launch_figures(capfd.readouterr().err)
+        assert sm.inner == solver.Inner.bicgstab
+        nodes = sum(b.points.size[0] * b.points.size[1] for b in mesh.blocks)
+        assert sm.dof == nodes and vec_nwg(nodes) > LAZY_ROWS and fig["operator"] <= LAZY_ROWS and fig["vector"] == LAZY_ROWS, fig
+        for k in range(iterations):
+            before = mesh_flat(mesh).copy()
+            st = sm.iterate(1)
+            sm.download()
+            assert st["not_converged"] == 0, st
+            _check_update(st, before, mesh_flat(mesh), (name, factor, k))
+
+
+@pytest.mark.parametrize("name,factor", [("LS89", 2), ("T106", 4)])
+def test_update_norms_refined_examples(name, factor, capfd):
+    _example_updates(name, factor, 2, capfd)
+
+
+@pytest.mark.parametrize("case", ["block1900", "block2048", "t106x8"])
+def test_update_norms_slowest_cases(case, monkeypatch, capfd):
+    # the expensive end of the table in one place (--durations): the top of the capped range, the first size above it, and the
+    # T106 example refined 8 x with its White control function -- host update sums only (no oracle assembly above 1024^2)
+    if case == "t106x8":
+        # a loose inner tolerance as for the single blocks: at the library's default one the first inner solve of this mesh runs to
+        # max_inner (11 330 iterations) without converging, which is not what this test is about
+        _example_updates("T106", 8, 1, capfd, rtol_initial=True, rtol=1e-6)
+        return
+    n = int(case[len("block"):])
+    for inner in ("bicgstab", "eager", "fuse2_off", "mg_bicgstab"):
+        with monkeypatch.context() as m:
+            _single_block_updates(n, inner, m, capfd, iterations=1)
+
+
+def _perturbed(mesh, amplitude=0.15, seed=7):
+    """The builders' coupled meshes start a few ulps from their discrete fixed point: an update there is rounding noise (per-node
+    displacements of 1e-16), where the difference of two stored iterates and the device's own increment disagree by 20 %.  Move every
+    interior node by up to `amplitude` x its shortest adjacent edge (perimeter nodes, and so the interfaces, stay as built)."""
+    rng = np.random.default_rng(seed)
+    for b in mesh.blocks:
+        x = b.points.data
+        di = np.linalg.norm(np.diff(x, axis=0), axis=-1)
+        dj = np.linalg.norm(np.diff(x, axis=1), axis=-1)
+        h = np.minimum(np.minimum(di[:-1, 1:-1], di[1:, 1:-1]), np.minimum(dj[1:-1, :-1], dj[1:-1, 1:]))
+        x[1:-1, 1:-1] += rng.uniform(-amplitude, amplitude, x[1:-1, 1:-1].shape) * h[..., None]
+    return mesh
+
+
+COUPLED = {
+    "strip3": lambda: _perturbed(configs.strip(3, 400, 400)),
+    "two_by_two": lambda: _perturbed(configs.two_by_two(150)),
+    "periodic_channel": lambda: _perturbed(configs.periodic_channel(200, 120)),
+}
+
+
+@pytest.mark.parametrize("inner", ["bicgstab", "relax"])
+@pytest.mark.parametrize("name", list(COUPLED))
+def test_update_norms_coupled_blocks(name, inner, capfd):
+    # coupled perimeter rows: the perimeter-row workgroups write their partial rows behind the interior ones (poff_edge, and
+    # poff_edge_ov of the overlapping-strip layout).  strip(3, 400, 400) lies in the capped regime (480 000 nodes).  Host update sums
+    # only: the oracle's System wants the two copies of an interface node bit-equal, which a device iterate does not promise, and its
+    # periodic rows of the sliding channel carry no diagonal entry for D^-1 -- the scaled residual is pinned on single blocks above.
+    # Relax mode's scaled residual is the last sweep's displacement over omega.
+    omega = 0.8
+    mesh = COUPLED[name]()
+    if inner == "relax":
+        opt = solver.Option.hip(inner=solver.Inner.relax, omega=omega)
+    else:
+        opt = solver.Option.hip(inner=solver.Inner.bicgstab, rtol_initial=True, rtol=1e-6)
+    capfd.readouterr()
+    with smooth.Smoother(mesh, opt) as sm:
+        fig = _launch_figures(capfd.readouterr().err)
+        nodes = sum(b.points.size[0] * b.points.size[1] for b in mesh.blocks)
+        assert sm.dof == nodes
+        for k in ("operator", "pairs", "triples", "vector"):
+            assert fig[k] <= fig["rows"], fig
+        if name == "strip3" and inner == "bicgstab":
+            assert vec_nwg(nodes) > LAZY_ROWS and fig["operator"] <= LAZY_ROWS and fig["vector"] == LAZY_ROWS, fig
+        for it in range(2):
+            before = mesh_flat(mesh).copy()
+            st = sm.iterate(1)
+            sm.download()
+            moved = _check_update(st, before, mesh_flat(mesh), (name, inner, it))
+            if inner == "relax":
+                assert st["scaled_residual_rms"] == pytest.approx(np.sqrt(moved / (2 * sm.dof)) / omega, rel=1e-12), (name, it)
+
+
+RELAX_MESHES = {
+    "block600": lambda: configs.single_block(600, 600, perturb=0.25),
+    "strip3": lambda: _perturbed(configs.strip(3, 200, 200)),
+}
+
+
+@pytest.mark.parametrize("schedule", ["default", "pairs"])
+@pytest.mark.parametrize("name", list(RELAX_MESHES))
+def test_relax_last_sweep_sums_behind_triples_pairs_and_remainder(name, schedule, monkeypatch, capfd):
+    # the statistics of a relax call are the LAST sweep's partial sums, reduced over that pass's grid (reduce(last_nwg)): behind a
+    # triple, a pair or the odd single sweep.  The reference handle steps one sweep per pass; the handle under test runs k sweeps
+    # per call with the library's default schedule (both TM_TRIPLES_* overrides of tests/conftest.py removed: triples for every block
+    # of at least 16 x 16 nodes, in one process with coupled blocks as well) or with pairs only.
+    omega = 0.8
+    ks = (1, 2, 3, 4, 5, 7)
+    ref_mesh = RELAX_MESHES[name]()
+    states = [mesh_flat(ref_mesh).copy()]
+    with smooth.Smoother(ref_mesh, solver.Option.hip(inner=solver.Inner.relax, single_sweep=True, omega=omega)) as sm:
+        for _ in range(sum(ks)):
+            sm.iterate(1)
+            sm.download()
+            states.append(mesh_flat(ref_mesh).copy())
+    monkeypatch.delenv("TM_TRIPLES_MIN_NODES", raising=False)
+    monkeypatch.delenv("TM_TRIPLES_SINGLE_MIN_NODES", raising=False)
+    if schedule == "pairs":
+        monkeypatch.setenv("TM_TRIPLES_COUPLED", "0")   # coupled blocks: pairs instead of triples
+        monkeypatch.setenv("TM_FUSE_3", "0")            # a block with fixed walls: the same
+    mesh = RELAX_MESHES[name]()
+    capfd.readouterr()
+    with smooth.Smoother(mesh, solver.Option.hip(inner=solver.Inner.relax, omega=omega)) as sm:
+        fig = _launch_figures(capfd.readouterr().err)
+        assert (fig["triples"] > 0) == (schedule == "default") and fig["pairs"] > 0, fig
+        done = 0
+        for k in ks:
+            st = sm.iterate(k)
+            sm.download()
+            done += k
+            assert np.array_equal(mesh_flat(mesh), states[done]), (name, schedule, k)
+            moved = _check_update(st, states[done - 1], states[done], (name, schedule, k))
+            # relax mode's scaled residual is the last sweep's displacement over omega ...
+            assert st["scaled_residual_rms"] == pytest.approx(np.sqrt(moved / (2 * sm.dof)) / omega, rel=1e-12), (name, schedule, k)
+        if name == "block600":   # ... which is the oracle's scaled residual at the last sweep's input
+            om = OracleMesh(mesh)
+            st = sm.iterate(1)
+            _check_scaled(st, om, sm.dof, (name, schedule))
+
+
+def _host_rms_update(a, b, dof):
+    hx, hy = _host_update(a, b)
+    return float(np.sqrt((hx + hy) / dof))
+
+
+def test_iterate_until_update_stops_where_the_host_update_says():
+    # a capped-range mesh: iterate_until_update reads last_dx2 / last_dy2, which came out too small there while the vector kernels
+    # launched more workgroups than their buffers had rows
+    n = 600
+    opt = solver.Option.hip()
+    mesh = configs.single_block(n, n, perturb=0.25)
+    states = [mesh_flat(mesh).copy()]
+    with smooth.Smoother(mesh, opt) as sm:
+        dof = sm.dof
+        for _ in range(4):
+            sm.iterate(1)
+            sm.download()
+            states.append(mesh_flat(mesh).copy())
+    u = [_host_rms_update(states[k], states[k + 1], dof) for k in range(4)]
+    assert u[0] > u[1] > u[2] > u[3], u
+    fresh = configs.single_block(n, n, perturb=0.25)
+    assert np.array_equal(mesh_flat(fresh), states[0])
+    with smooth.Smoother(fresh, opt) as sm:
+        reached, st = sm.iterate_until_update(float(np.sqrt(u[2] * u[3])), 20)
+        sm.download()
+    assert reached and st["outer_iterations"] == 4, (st, u)
+    # the same handle kind and the same kernels as the stepped run, reductions in a fixed order: the same bits
+    assert np.array_equal(mesh_flat(fresh), states[4])
+
+
+def test_iterate_until_stops_where_the_host_scaled_residual_says():
+    # iterate_until tests the scaled residual at the start of each outer iteration (the inner solve's start residual): with tol between
+    # the host's values at X^4 and X^3 it completes four iterations, finds X^4 below tol and leaves it untouched
+    n = 600
+    opt = solver.Option.hip()
+    mesh = configs.single_block(n, n, perturb=0.25)
+    states, scaled = [mesh_flat(mesh).copy()], [_host_scaled_rms(OracleMesh(mesh), n * n)]
+    with smooth.Smoother(mesh, opt) as sm:
+        for _ in range(4):
+            sm.iterate(1)
+            sm.download()
+            states.append(mesh_flat(mesh).copy())
+            scaled.append(_host_scaled_rms(OracleMesh(mesh), n * n))
+    assert scaled[0] > scaled[1] > scaled[2] > scaled[3] > scaled[4], scaled
+    fresh = configs.single_block(n, n, perturb=0.25)
+    with smooth.Smoother(fresh, opt) as sm:
+        reached, st = sm.iterate_until(float(np.sqrt(scaled[3] * scaled[4])), 20)
+        sm.download()
+    assert reached and st["outer_iterations"] == 4, (st, scaled)
+    assert np.array_equal(mesh_flat(fresh), states[4])
+    # the residual it reports is the one it stopped on, X^4's
+    assert st["scaled_residual_rms"] == pytest.approx(scaled[4], rel=RESIDUAL_RTOL)
+
+
+@pytest.mark.parametrize("switch", ["TM_FUSE_2", "TM_FUSE_P"])
+def test_unfused_in_loop_vector_kernels_match_the_eager_handle(switch, monkeypatch):
+    # TM_FUSE_2=0: the p-update folded into the first apply, k_xr_update_vs inside the loop; TM_FUSE_P=0: k_p_update as well.  Both
+    # keep the lazy scalar steps of the capped regime, which read the vector kernels' partial rows for rho.  The eager handle takes no
+    # cap (a launch per scalar step, vec_nwg workgroups): its iterates are the yardstick.
+    n = 600
+    iters = 3
+    ref, ref_inner = [], 0
+    mesh = configs.single_block(n, n, perturb=0.25)
+    with smooth.Smoother(mesh, solver.Option.hip(eager_scalars=True)) as sm:
+        for _ in range(iters):
+            st = sm.iterate(1)
+            sm.download()
+            assert st["not_converged"] == 0, st
+            ref.append(mesh_flat(mesh).copy())
+            ref_inner += st["inner_iterations"]
+    monkeypatch.setenv(switch, "0")
+    mesh = configs.single_block(n, n, perturb=0.25)
+    inner = 0
+    with smooth.Smoother(mesh, solver.Option.hip()) as sm:
+        for k in range(iters):
+            st = sm.iterate(1)
+            sm.download()
+            assert st["not_converged"] == 0, (switch, k, st)
+            rms = float(np.sqrt(np.mean((mesh_flat(mesh) - ref[k]) ** 2)))
+            assert rms <= 1e-10, (switch, k, rms)
+            inner += st["inner_iterations"]
+    # measured: 4992 inner iterations over the three Picard iterations with either switch, 5200 for the eager handle
+    print(f"[{switch}=0] inner iterations {inner}, eager handle {ref_inner}")
+    assert inner <= 1.1 * ref_inner, (switch, inner, ref_inner)
+
+
+@pytest.mark.parametrize("inner", ["bicgstab", "relax"])
+def test_all_reduced_statistics_equal_the_whole_mesh_host_sums(inner):
+    # two virtual ranks (one handle per thread, tests/test_gpu_virtual_ranks.py's transport) on a 2-block strip: every rank reports the
+    # all-reduced sums, which must be the sums over all blocks of the whole mesh -- each block counted by its owner, ghost rows by nobody
+    from tests.test_gpu_virtual_ranks import ThreadHooks, _Shared
+
+    builder = lambda: _perturbed(configs.strip(2, 200, 300))
+    owner = [0, 1]
+    if inner == "relax":
+        option = solver.Option.hip(inner=solver.Inner.relax, omega=0.8)
+    else:
+        option = solver.Option.hip(rtol=1e-13, max_inner=5000)
+    world = 2
+    shared = _Shared(world)
+    meshes = [builder() for _ in range(world)]
+    before = mesh_flat(meshes[0]).copy()
+    om = OracleMesh(meshes[0])
+    hooks, stats, errors = [None] * world, [None] * world, []
+    create_lock = threading.Lock()
+
+    def work(r):
+        try:
+            with create_lock:
+                hooks[r] = ThreadHooks(shared, meshes[r], owner, r, world, option)
+            shared.barrier.wait()
+            stats[r] = hooks[r].iterate(1)
+            hooks[r].smoother.download()
+        except BaseException as e:  # pragma: no cover
+            errors.append((r, e))
+            shared.barrier.abort()
+
+    threads = [threading.Thread(target=work, args=(r,)) for r in range(world)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(timeout=300)
+    assert not errors, errors
+    dof = hooks[0].smoother.dof
+    for h in hooks:
+        h.smoother.close()
+    out = builder()
+    for b, o in enumerate(owner):
+        out.blocks[b].points.data[...] = meshes[o].blocks[b].points.data
+    after = mesh_flat(out)
+    assert dof == len(after)
+    for r in range(world):
+        moved = _check_update(stats[r], before, after, (inner, r))
+        if inner == "relax":
+            assert stats[r]["scaled_residual_rms"] == pytest.approx(np.sqrt(moved / (2 * dof)) / 0.8, rel=1e-12), r
+        else:   # the first iterate's system: the interface copies of the input are the builder's, equal
+            _check_scaled(stats[r], om, dof, (inner, r))

@@ -630,18 +630,18 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
             while (it_total < opt.max_inner) {
                 if (use_ilu) {   // the preconditioned recurrence, as Smoother::picard_bicgstab with the multigrid cycle in this place
                     double2 *p_hat = d_ph.as<double2>(), *s_hat = d_sh.as<double2>();
-                    HIPCHK(launch_p_update(scalars_for(), r, p, v, n, st));
+                    HIPCHK(launch_p_update(scalars_for(), r, p, v, n, nwg_vec, st));
                     ilu->apply(p, p_hat, st);
                     hipLaunchKernelGGL((k_csr_apply<false, DOT_AUX>), dim3(nwg), dim3(256), 0, st, A, p_hat, nullptr, r_hat, v, partials);
                     HIPCHK(hipGetLastError());
                     reduce_update(nwg, STEP_SIGMA);
-                    HIPCHK(launch_s_update(scalars_for(), r, v, s, n, partials, st));
+                    HIPCHK(launch_s_update(scalars_for(), r, v, s, n, nwg_vec, partials, st));
                     reduce_update(nwg_vec, STEP_SS);
                     ilu->apply(s, s_hat, st);
                     hipLaunchKernelGGL((k_csr_apply<false, DOT_AUX2>), dim3(nwg), dim3(256), 0, st, A, s_hat, nullptr, s, t, partials);   // t.s, t.t with the unpreconditioned s
                     HIPCHK(hipGetLastError());
                     reduce_update(nwg, STEP_TSTT);
-                    HIPCHK(launch_xr_update(scalars_for(), u, p_hat, s_hat, s, t, r, r_hat, n, partials, st));
+                    HIPCHK(launch_xr_update(scalars_for(), u, p_hat, s_hat, s, t, r, r_hat, n, nwg_vec, partials, st));
                     reduce_update(nwg_vec, STEP_RHO);
                     it_total += 1;
                     if (it_total % opt.check_every == 0 || it_total == opt.max_inner) {
@@ -654,16 +654,16 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
                     }
                     continue;
                 }
-                HIPCHK(launch_p_update(scalars_for(), r, p, v, n, st));
+                HIPCHK(launch_p_update(scalars_for(), r, p, v, n, nwg_vec, st));
                 hipLaunchKernelGGL((k_csr_apply<false, DOT_AUX>), dim3(nwg), dim3(256), 0, st, A, p, nullptr, r_hat, v, partials);
                 HIPCHK(hipGetLastError());
                 reduce_update(nwg, STEP_SIGMA);
-                HIPCHK(launch_s_update(scalars_for(), r, v, s, n, partials, st));
+                HIPCHK(launch_s_update(scalars_for(), r, v, s, n, nwg_vec, partials, st));
                 reduce_update(nwg_vec, STEP_SS);
                 hipLaunchKernelGGL((k_csr_apply<false, DOT_IN>), dim3(nwg), dim3(256), 0, st, A, s, nullptr, nullptr, t, partials);
                 HIPCHK(hipGetLastError());
                 reduce_update(nwg, STEP_TSTT);
-                HIPCHK(launch_xr_update(scalars_for(), u, p, s, s, t, r, r_hat, n, partials, st));
+                HIPCHK(launch_xr_update(scalars_for(), u, p, s, s, t, r, r_hat, n, nwg_vec, partials, st));
                 reduce_update(nwg_vec, STEP_RHO);
                 it_total += 1;
                 if (it_total % opt.check_every == 0 || it_total == opt.max_inner) {

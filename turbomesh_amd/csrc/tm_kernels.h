@@ -285,18 +285,20 @@ inline LazyScalars plain_scalars(const KrylovScalars* S) {
     L.S_in = S;
     return L;
 }
+// The vector kernels below are grid-stride: `nwg` is the launch's workgroup count, which the caller sizes its partial-sum buffer for
+// (one row of MAX_PARTIALS per workgroup; vec_nwg(n) unless the caller caps it).
 // p = r + beta (p - omega v)
-hipError_t launch_p_update(const LazyScalars& S, const double2* r, double2* p, const double2* v, int64_t n, hipStream_t stream);
+hipError_t launch_p_update(const LazyScalars& S, const double2* r, double2* p, const double2* v, int64_t n, int nwg, hipStream_t stream);
 // s = r - alpha v ; partials: ||s||^2 (x,y)
-hipError_t launch_s_update(const LazyScalars& S, const double2* r, const double2* v, double2* s, int64_t n, double* partials,
+hipError_t launch_s_update(const LazyScalars& S, const double2* r, const double2* v, double2* s, int64_t n, int nwg, double* partials,
                            hipStream_t stream);
 // u += alpha p + omega s ; r = s - omega t ; partials: r_hat.r (x,y), r.r (x,y)
 // u += alpha*p_hat + omega*s_hat; r = s - omega*t (p_hat = p, s_hat = s without a preconditioner)
 hipError_t launch_xr_update(const LazyScalars& S, double2* u, const double2* p_hat, const double2* s_hat, const double2* s, const double2* t, double2* r,
-                            const double2* r_hat, int64_t n, double* partials, hipStream_t stream);
+                            const double2* r_hat, int64_t n, int nwg, double* partials, hipStream_t stream);
 // the same with s = r - alpha v formed on the fly (s was never stored): reads p, r, v, t, r_hat, u; r is updated in place
 hipError_t launch_xr_update_vs(const LazyScalars& S, double2* u, const double2* p, const double2* v, const double2* t, double2* r, const double2* r_hat,
-                               int64_t n, double* partials, hipStream_t stream);
+                               int64_t n, int nwg, double* partials, hipStream_t stream);
 // ---- GMRES(m) (csrc/tm_gmres.hip; GMRES.zig:300-423): device-resident state of one solve, index = component (0 x, 1 y)
 constexpr int GMRES_M = 30;   // restart length, GMRES.zig:21
 struct GmresScalars {
@@ -324,7 +326,7 @@ hipError_t launch_gm_column(GmresScalars* G, const double* red, hipStream_t stre
 hipError_t launch_gm_backsub(GmresScalars* G, hipStream_t stream);
 
 // K7: partials sum (xk-u)^2 (x,y); xk <- u
-hipError_t launch_residual_copyback(double2* xk, const double2* u, int64_t n, double* partials, hipStream_t stream);
+hipError_t launch_residual_copyback(double2* xk, const double2* u, int64_t n, int nwg, double* partials, hipStream_t stream);
 // gather rows for the halo exchange: dst[k] = src[ids[k]]
 hipError_t launch_stream(int kind, double2* a, const double2* b, const double2* c, double s, int64_t n, hipStream_t stream);
 hipError_t launch_gather_rows(const double2* src, const int32_t* ids, int64_t n, double2* dst, hipStream_t stream);

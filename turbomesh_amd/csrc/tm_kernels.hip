@@ -2697,8 +2697,8 @@ __global__ __launch_bounds__(VEC_BLOCK) void k_p_update(LazyScalars L, const dou
         }
     }
 }
-hipError_t launch_p_update(const LazyScalars& S, const double2* r, double2* p, const double2* v, int64_t n, hipStream_t st) {
-    hipLaunchKernelGGL(k_p_update, dim3(vec_nwg(n)), dim3(VEC_BLOCK), 0, st, S, r, p, v, n);
+hipError_t launch_p_update(const LazyScalars& S, const double2* r, double2* p, const double2* v, int64_t n, int nwg, hipStream_t st) {
+    hipLaunchKernelGGL(k_p_update, dim3(nwg), dim3(VEC_BLOCK), 0, st, S, r, p, v, n);
     return hipGetLastError();
 }
 
@@ -2730,9 +2730,9 @@ __global__ __launch_bounds__(VEC_BLOCK) void k_s_update(LazyScalars L, const dou
     }
     block_partials<VEC_BLOCK, 2>(acc, partials + static_cast<size_t>(blockIdx.x) * MAX_PARTIALS);
 }
-hipError_t launch_s_update(const LazyScalars& S, const double2* r, const double2* v, double2* s, int64_t n, double* partials,
+hipError_t launch_s_update(const LazyScalars& S, const double2* r, const double2* v, double2* s, int64_t n, int nwg, double* partials,
                            hipStream_t st) {
-    hipLaunchKernelGGL(k_s_update, dim3(vec_nwg(n)), dim3(VEC_BLOCK), 0, st, S, r, v, s, n, partials);
+    hipLaunchKernelGGL(k_s_update, dim3(nwg), dim3(VEC_BLOCK), 0, st, S, r, v, s, n, partials);
     return hipGetLastError();
 }
 
@@ -2778,8 +2778,8 @@ __global__ __launch_bounds__(VEC_BLOCK) void k_xr_update(LazyScalars L, double2*
     block_partials<VEC_BLOCK, 4>(acc, partials + static_cast<size_t>(blockIdx.x) * MAX_PARTIALS);
 }
 hipError_t launch_xr_update(const LazyScalars& S, double2* u, const double2* p_hat, const double2* s_hat, const double2* s, const double2* t, double2* r,
-                            const double2* r_hat, int64_t n, double* partials, hipStream_t st) {
-    hipLaunchKernelGGL(k_xr_update, dim3(vec_nwg(n)), dim3(VEC_BLOCK), 0, st, S, u, p_hat, s_hat, s, t, r, r_hat, n, partials);
+                            const double2* r_hat, int64_t n, int nwg, double* partials, hipStream_t st) {
+    hipLaunchKernelGGL(k_xr_update, dim3(nwg), dim3(VEC_BLOCK), 0, st, S, u, p_hat, s_hat, s, t, r, r_hat, n, partials);
     return hipGetLastError();
 }
 
@@ -2826,8 +2826,8 @@ __global__ __launch_bounds__(VEC_BLOCK) void k_xr_update_vs(LazyScalars L, doubl
     block_partials<VEC_BLOCK, 4>(acc, partials + static_cast<size_t>(blockIdx.x) * MAX_PARTIALS);
 }
 hipError_t launch_xr_update_vs(const LazyScalars& S, double2* u, const double2* p, const double2* v, const double2* t, double2* r, const double2* r_hat, int64_t n,
-                               double* partials, hipStream_t st) {
-    hipLaunchKernelGGL(k_xr_update_vs, dim3(vec_nwg(n)), dim3(VEC_BLOCK), 0, st, S, u, p, v, t, r, r_hat, n, partials);
+                               int nwg, double* partials, hipStream_t st) {
+    hipLaunchKernelGGL(k_xr_update_vs, dim3(nwg), dim3(VEC_BLOCK), 0, st, S, u, p, v, t, r, r_hat, n, partials);
     return hipGetLastError();
 }
 
@@ -2858,8 +2858,8 @@ __global__ __launch_bounds__(VEC_BLOCK) void k_residual_copyback(double2* __rest
     }
     block_partials<VEC_BLOCK, 2>(acc, partials + static_cast<size_t>(blockIdx.x) * MAX_PARTIALS);
 }
-hipError_t launch_residual_copyback(double2* xk, const double2* u, int64_t n, double* partials, hipStream_t st) {
-    hipLaunchKernelGGL(k_residual_copyback, dim3(vec_nwg(n)), dim3(VEC_BLOCK), 0, st, xk, u, n, partials);
+hipError_t launch_residual_copyback(double2* xk, const double2* u, int64_t n, int nwg, double* partials, hipStream_t st) {
+    hipLaunchKernelGGL(k_residual_copyback, dim3(nwg), dim3(VEC_BLOCK), 0, st, xk, u, n, partials);
     return hipGetLastError();
 }
 

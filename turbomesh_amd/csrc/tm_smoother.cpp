@@ -783,9 +783,43 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
         v_alt = arena.alloc_n<double2>(static_cast<uint64_t>(n_local));
     }
     if (fuse2) r_alt = arena.alloc_n<double2>(static_cast<uint64_t>(n_local));
-    for (int k = 0; k < (lazy ? 3 : 1); ++k) part_buf[k] = arena.alloc_n<double>(npart);
+    // Every launch that writes partial sums must fit the rows allocated for them (one row of MAX_PARTIALS per workgroup): the operator
+    // launches (perimeter rows behind the interior workgroups), the sweep pairs / triples, the vector kernels (launched with nwg_vec, the
+    // grid npart was sized for -- capped at 512 above), GMRES's Gram-Schmidt passes (vec_nwg) and the perimeter-row pass that forms
+    // ||D^-1 b||^2 of a Krylov solve
+    {
+        const int rows = static_cast<int>(npart / MAX_PARTIALS);
+        const struct {
+            const char* what;
+            int nwg;
+        } producers[] = {{"operator", nwg_apply},
+                         {"operator (overlapping strips)", nwg_apply_ov},
+                         {"sweep pairs", nwg_apply2},
+                         {"sweep triples", nwg3_all},
+                         {"vector kernels", nwg_vec},
+                         {"GMRES Gram-Schmidt", opt.inner == TM_INNER_GMRES ? vec_nwg(n_owned) : 0},
+                         {"perimeter-row right-hand side", opt.inner != TM_INNER_RELAX ? edge.nwg : 0}};
+        if (std::getenv("TM_DEBUG_RUNS"))
+            std::fprintf(stderr, "[tm] partial-sum rows: %d allocated; operator %d, overlapping strips %d, pairs %d, triples %d, vector kernels %d (vec_nwg %d)\n", rows,
+                         nwg_apply, nwg_apply_ov, nwg_apply2, nwg3_all, nwg_vec, vec_nwg(n_owned));
+        for (const auto& q : producers)
+            if (q.nwg > rows)
+                throw TmError(TM_E_HIP, std::string("internal: the ") + q.what + " launch has " + std::to_string(q.nwg) + " workgroups, the partial-sum buffer " +
+                                            std::to_string(rows) + " rows");
+    }
+    // TM_PARTIALS_GUARD=1: a guard region behind each partial-sum buffer and behind `red`, filled with a byte pattern here and compared when
+    // an iterate call returns (check_guards) -- a write past the rows a buffer was sized for shows as a TM_E_HIP error naming the buffer.
+    // Off: the arena layout is what it always was.
+    partials_guard = false;
+    if (const char* e = std::getenv("TM_PARTIALS_GUARD")) partials_guard = std::atoi(e) != 0;
+    const uint64_t nguard = partials_guard ? GUARD_DOUBLES : 0;
+    for (int k = 0; k < (lazy ? 3 : 1); ++k) part_buf[k] = arena.alloc_n<double>(npart + nguard);
     partials = part_buf[0];
-    red = arena.alloc_n<double>(MAX_PARTIALS);
+    red = arena.alloc_n<double>(MAX_PARTIALS + nguard);
+    if (partials_guard) {
+        for (int k = 0; k < 3; ++k) guard[k] = part_buf[k] ? part_buf[k] + npart : nullptr;
+        guard[3] = red ? red + MAX_PARTIALS : nullptr;
+    }
     S_buf[0] = arena.alloc_n<KrylovScalars>(1);
     S_buf[1] = lazy ? arena.alloc_n<KrylovScalars>(1) : S_buf[0];
     S = S_buf[0];
@@ -817,6 +851,8 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
     HIPCHK(hipMemsetAsync(S_buf[0], 0, sizeof(KrylovScalars), stream));
     if (S_buf[1] != S_buf[0]) HIPCHK(hipMemsetAsync(S_buf[1], 0, sizeof(KrylovScalars), stream));
     HIPCHK(hipMemsetAsync(sync_flags, 0, sizeof(uint32_t) * 64, stream));
+    for (double* g : guard)
+        if (g) HIPCHK(hipMemsetAsync(g, GUARD_BYTE, sizeof(double) * GUARD_DOUBLES, stream));
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h_flags), sizeof(uint32_t) * 8, hipHostMallocDefault));   // [0..3] pairs, [4..7] triples
     std::memset(h_flags, 0, sizeof(uint32_t) * 8);
     for (double2* q : {p_hat, s_hat, mg_w0, mg_w1})
@@ -925,6 +961,21 @@ void Smoother::exchange_finish(hipStream_t on) {
     exchange_pending = false;
     const int rc = hooks.exchange_wait(hooks.ctx, on ? on : stream);
     if (rc != 0) throw TmError(TM_E_COMM, "halo exchange wait hook failed with code " + std::to_string(rc));
+}
+
+void Smoother::check_guards() {
+    if (!partials_guard) return;
+    static const char* const names[4] = {"part_buf[0]", "part_buf[1]", "part_buf[2]", "red"};
+    std::vector<unsigned char> h(sizeof(double) * GUARD_DOUBLES);
+    for (int k = 0; k < 4; ++k) {
+        if (!guard[k]) continue;
+        HIPCHK(hipMemcpyAsync(h.data(), guard[k], h.size(), hipMemcpyDeviceToHost, stream));
+        sync();
+        for (size_t i = 0; i < h.size(); ++i)
+            if (h[i] != GUARD_BYTE)
+                throw TmError(TM_E_HIP, std::string("TM_PARTIALS_GUARD: the guard behind ") + names[k] + " was overwritten (first changed byte at offset " +
+                                            std::to_string(i) + " past the buffer's end)");
+    }
 }
 
 void Smoother::fence(hipStream_t from, hipStream_t to, hipEvent_t ev) {
@@ -1344,7 +1395,7 @@ int Smoother::picard_bicgstab(tm_stats& st) {
                 std::swap(p, p_alt);
                 std::swap(v, v_alt);
             } else {
-                HIPCHK(launch_p_update(scalars_for(), r, p, v, n_owned, stream));
+                HIPCHK(launch_p_update(scalars_for(), r, p, v, n_owned, nwg_vec, stream));
                 if (use_mg) {   // right preconditioning (BiCGStab.zig:314-316, 340-342 with M = one V-cycle)
                     precondition(p, p_hat);
                     apply(p_hat, v, MODE_SCALED, DOT_AUX, r_hat, X, 0.0, STEP_SIGMA);
@@ -1356,7 +1407,7 @@ int Smoother::picard_bicgstab(tm_stats& st) {
                 // s = r - alpha v is never stored: the second apply forms it as the rows enter its window (interior rows and
                 // perimeter rows), with ||s||^2 beside t.s and t.t in one reduction; k_xr_update_vs forms it again
                 apply_virtual(VK_S, r, v, nullptr, nullptr, t);
-                HIPCHK(launch_xr_update_vs(scalars_for(), U, p, v, t, r, r_hat, n_owned, partials, stream));
+                HIPCHK(launch_xr_update_vs(scalars_for(), U, p, v, t, r, r_hat, n_owned, nwg_vec, partials, stream));
                 reduce_update(nwg_vec, STEP_RHO);
                 st.operator_sweeps += 2;
                 it_total += 1;
@@ -1370,7 +1421,7 @@ int Smoother::picard_bicgstab(tm_stats& st) {
                 }
                 continue;
             }
-            HIPCHK(launch_s_update(scalars_for(), r, v, s, n_owned, partials, stream));
+            HIPCHK(launch_s_update(scalars_for(), r, v, s, n_owned, nwg_vec, partials, stream));
             reduce_update(nwg_vec, STEP_SS);
             if (use_mg) {
                 precondition(s, s_hat);
@@ -1378,7 +1429,7 @@ int Smoother::picard_bicgstab(tm_stats& st) {
             } else {
                 apply(s, t, MODE_SCALED, DOT_IN, nullptr, X, 0.0, STEP_TSTT);
             }
-            HIPCHK(launch_xr_update(scalars_for(), U, use_mg ? p_hat : p, use_mg ? s_hat : s, s, t, r, r_hat, n_owned, partials, stream));
+            HIPCHK(launch_xr_update(scalars_for(), U, use_mg ? p_hat : p, use_mg ? s_hat : s, s, t, r, r_hat, n_owned, nwg_vec, partials, stream));
             reduce_update(nwg_vec, STEP_RHO);
             st.operator_sweeps += 2;
             it_total += 1;
@@ -1393,7 +1444,7 @@ int Smoother::picard_bicgstab(tm_stats& st) {
         }
         if (fuse2) {   // the last iteration's x / r update is still pending (zero scalars once a component has finished)
             flush_pending();
-            HIPCHK(launch_xr_update_vs(scalars_for(), U, p, v, t, r, r_hat, n_owned, partials, stream));   // its partial sums are not used
+            HIPCHK(launch_xr_update_vs(scalars_for(), U, p, v, t, r, r_hat, n_owned, nwg_vec, partials, stream));   // its partial sums are not used
         }
         if (converged || !breakdown || stalled || restarts >= 8 || it_total >= opt.max_inner) break;
         restarts += 1;   // breakdown (rho or omega vanished): restart from the current iterate
@@ -1402,7 +1453,7 @@ int Smoother::picard_bicgstab(tm_stats& st) {
     flush_pending();
 
     // residual + copy-back (smooth.zig:112-153); X becomes the new frozen field
-    HIPCHK(launch_residual_copyback(X, U, n_owned, partials, stream));
+    HIPCHK(launch_residual_copyback(X, U, n_owned, nwg_vec, partials, stream));
     reduce(nwg_vec);
     HIPCHK(hipMemcpyAsync(h_red, red, sizeof(double) * MAX_PARTIALS, hipMemcpyDeviceToHost, stream));
     sync();
@@ -1485,7 +1536,7 @@ int Smoother::picard_gmres(tm_stats& st) {
     st.inner_iterations += it_total;
 
     // residual + copy-back (smooth.zig:112-153); X becomes the new frozen field
-    HIPCHK(launch_residual_copyback(X, U, n_owned, partials, stream));
+    HIPCHK(launch_residual_copyback(X, U, n_owned, nwg_vec, partials, stream));
     reduce(nwg_vec);
     HIPCHK(hipMemcpyAsync(h_red, red, sizeof(double) * MAX_PARTIALS, hipMemcpyDeviceToHost, stream));
     sync();
@@ -1908,6 +1959,7 @@ void Smoother::iterate(uint64_t iterations, tm_stats* stats) {
         }
     }
     sync();
+    check_guards();
     st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = st;
 }
@@ -1939,6 +1991,7 @@ bool Smoother::iterate_until_update(uint64_t max_iterations, double tol, tm_stat
         }
     }
     sync();
+    check_guards();
     st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = st;
     return reached;
@@ -1985,6 +2038,7 @@ bool Smoother::iterate_until(uint64_t max_iterations, double tol, tm_stats* stat
         stop_tol = 0.0;
     }
     sync();
+    check_guards();
     st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (stats) *stats = st;
     return reached;

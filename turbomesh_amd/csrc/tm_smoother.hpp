@@ -224,6 +224,12 @@ struct Smoother {
                        double2* rout = nullptr, double2* uio = nullptr);
     bool lazy = false;
     double* part_buf[3] = {nullptr, nullptr, nullptr};
+    // TM_PARTIALS_GUARD (see create): a guard region behind part_buf[0..2] and behind red, compared by check_guards
+    static constexpr uint64_t GUARD_DOUBLES = 2048 * MAX_PARTIALS;
+    static constexpr int GUARD_BYTE = 0xA5;
+    bool partials_guard = false;
+    double* guard[4] = {nullptr, nullptr, nullptr, nullptr};
+    void check_guards();
     int part_rot = 0;
     KrylovScalars* S_buf[2] = {nullptr, nullptr};
     LazyStep pending[2];
