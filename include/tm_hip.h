@@ -122,8 +122,19 @@ enum {
     TM_INNER_GMRES = 4,      /* the Picard outer iteration with the reference's OTHER Krylov solver restated on the device: restarted GMRES(30),
                                 left-preconditioned with the diagonal, modified Gram-Schmidt Arnoldi, Givens rotations (GMRES.zig:300-423,
                                 510-524; restart 30 as GMRES.zig:21).  Same scale-aware stop test as TM_INNER_BICGSTAB.  What a front end
-                                maps "solver": {"gmres": {"preconditioner": "diagonal"}} of an input file to; ILU(0) (GMRES.zig:199-298) is a
-                                sequential recurrence with no device counterpart                                                      */
+                                maps "solver": {"gmres": {"preconditioner": "diagonal"}} of an input file to; ILU(0) (GMRES.zig:199-298) is served
+                                on the assembled system -- tm_csr_solve and TM_INNER_REFERENCE_GMRES -- the matrix-free modes use the diagonal */
+    TM_INNER_REFERENCE_GMRES = 5, /* the reference's route as its example inputs write it ("gmres" + "ilu0"), same algorithm, same tolerances: per outer
+                                iteration system.fill into a device-resident CSR (the reference's assembled, UNSCALED system, bit for bit), then
+                                GMRES(30) left-preconditioned with ILU(0) (TM_OPT_PRECOND_ILU0; factor and substitutions bit-identical to
+                                GMRES.zig:199-298, 437-475) or with the diagonal (flag clear), mat-vec in CSR order, stop test
+                                ||M^-1 (b - A x)|| <= max(atol, rtol ||b||_2) per component on the unscaled b (GMRES.zig:305-306, 319, 388).
+                                Defaults in this mode: rtol 0 -> 1e-6, atol 0 -> 1e-8, max_inner 0 -> 1000 per component and solve
+                                (GMRES.zig:21-24), check_every 0 -> 1.  The iterates are the REFERENCE's (they differ from the exact-solve
+                                iterates of the other modes by what its loose stop test leaves: 1e-7 .. 2e-5 RMS); what differs from a run of
+                                the reference is the summation order of dot products and norms.  Nothing travels to or from the host per
+                                iteration but the flags.  Single-process handles only (rank hooks: TM_E_UNSUPPORTED at create and in
+                                tm_smoother_workspace_bytes); its buffers are allocated at create (TM_E_MEMORY there, not in a solve)      */
     TM_INNER_AUTO = 3        /* resolved when the handle is created, from the mesh alone (every rank of a job decides alike):
                                 TM_INNER_MG_BICGSTAB when the largest block has >= 100 000 nodes, TM_INNER_BICGSTAB below -- on the
                                 reference's example meshes (T106 / LS89: 8 blocks of 10^2..10^4 nodes) every multigrid level is a handful
@@ -146,10 +157,11 @@ enum {
                                 are formed inside the two operator applications (two kernels per iteration; rho from r_hat.s -
                                 omega r_hat.t, equal in exact arithmetic) and, on small meshes, the scalar steps travel with the
                                 kernels that consume them.  Same method, iterates equal to rounding */
-    TM_OPT_PRECOND_ILU0 = 8, /* tm_csr_solve ONLY (the slot that has the assembled matrix): ILU(0) -- the reference's second preconditioner
+    TM_OPT_PRECOND_ILU0 = 8, /* tm_csr_solve and TM_INNER_REFERENCE_GMRES ONLY (the two places that have the assembled matrix): ILU(0) -- the reference's second preconditioner
                                 (preconditioner.zig:1-4; BiCGStab.zig:178-277, 384-422) -- as right preconditioner of the device BiCGStab: factor
-                                and substitutions level by level on the device, bit-identical to the reference's recurrence.  The matrix-free
-                                entry points answer TM_E_UNSUPPORTED: they never assemble a matrix to factorise                        */
+                                and substitutions level by level on the device, bit-identical to the reference's recurrence (left preconditioner of
+                                GMRES(30) in TM_INNER_REFERENCE_GMRES).  The matrix-free inner strategies answer TM_E_UNSUPPORTED: they never
+                                assemble a matrix to factorise                                                                          */
     TM_OPT_RTOL_INITIAL = 4  /* Krylov modes: `rtol` is relative to the INITIAL residual of each inner solve (inexact Picard: stop at
                                 ||D^-1(b-Ax)|| <= max(atol, rtol ||D^-1(b-A x0)||), rtol = 0 -> 1e-2) instead of ||D^-1 b||.  Every solve then
                                 does work in proportion to what is left -- same fixed point, several times fewer inner iterations on the way
@@ -339,6 +351,10 @@ int tm_smoother_row_kinds(const tm_smoother* s, int32_t* kinds /* [dof] */);
 uint64_t tm_smoother_dof(const tm_smoother* s);
 /* The inner strategy the handle runs (TM_INNER_*): what TM_INNER_AUTO resolved to, else the option as given. */
 int tm_smoother_inner(const tm_smoother* s);
+/* Inner iterations of the LAST outer iteration per component (x, y): the reference solves the two systems one after the other and each has
+ * its own count (solver.zig:69-78).  TM_INNER_REFERENCE_GMRES: the columns each component built; the older Krylov modes, where both
+ * components advance together: the common count twice; TM_INNER_RELAX answers 0, 0. */
+int tm_smoother_inner_counts(const tm_smoother* s, uint64_t* x_iterations, uint64_t* y_iterations);
 /* Current control function (P,Q) per node, 2*dof doubles (wall_control_function.zig:22-54). */
 int tm_smoother_control_function(tm_smoother* s, double* pq);
 

@@ -7,7 +7,8 @@ without UMFPACK answers error.ExternalSolverNotEnabled, this program refuses the
 by {"hip": {"inner": "auto"}} (what a user would write into the JSON): the plain Picard + BiCGStab solve on meshes of small blocks
 like the reference's examples (T106 / LS89: 7x faster there than the multigrid-preconditioned one), the multigrid-preconditioned
 solve once a block has 100 000 nodes or more (1000 when the blocks are not coupled) and the cells' aspect ratio does not vary strongly inside any block (refined O-grids with
-boundary-layer clustering keep the plain solve)."""
+boundary-layer clustering keep the plain solve).  --hip reference runs the file's own solver AS WRITTEN on the device: GMRES(30) with ILU(0) or the
+diagonal on the assembled system, the reference's tolerances -- the iterates a run of the reference gives (solver.Option.as_written)."""
 from __future__ import annotations
 
 import argparse
@@ -22,9 +23,10 @@ from .smoothing import smooth, solver
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m turbomesh_amd", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("config", help="input file in the reference's JSON schema (examples/T106/T106.json)")
-    ap.add_argument("--hip", nargs="?", const="auto", choices=["auto", "bicgstab", "mg_bicgstab", "gmres", "relax", "file"],
+    ap.add_argument("--hip", nargs="?", const="auto", choices=["auto", "bicgstab", "mg_bicgstab", "gmres", "relax", "file", "reference"],
                     help="use the hip solver with this inner strategy instead of the solver named in the file; `file` = the device counterpart of "
-                         "the solver the file names (gmres -> GMRES(30) on the device, bicgstab -> BiCGStab; ilu0 -> diagonal)")
+                         "the solver the file names (gmres -> GMRES(30) on the device, bicgstab -> BiCGStab; ilu0 -> diagonal); `reference` = the file's "
+                         "solver as written: gmres + ilu0 / diagonal on the assembled system with the reference's tolerances")
     ap.add_argument("--iterations", type=int, help="override smoothing.iterations")
     ap.add_argument("--output", help="override the output file (.xyz / .p3d: multi-block PLOT3D)")
     ap.add_argument("--until", type=float, metavar="TOL",
@@ -38,6 +40,10 @@ def main(argv=None):
         inp.solver, note = inp.solver.served_by_hip()
         if note:
             logging.getLogger("smoothing").warning(note)
+    elif args.hip == "reference":
+        inp.solver, note = inp.solver.as_written()
+        if note:
+            logging.getLogger("smoothing").warning(note)
     elif args.hip:
         inp.solver = solver.Option.hip(inner=getattr(solver.Inner, args.hip))
     if inp.solver.tag != solver.Tag.hip:
@@ -48,7 +54,8 @@ def main(argv=None):
     iterations = inp.iterations if args.iterations is None else args.iterations
     slog = logging.getLogger("smoothing")
     with smooth.per_iteration_log(slog.isEnabledFor(logging.INFO) and not args.until), smooth.Smoother(mesh, inp.solver, inp.wall_control_function) as sm:
-        slog.info("hip solver, inner strategy: %s%s", sm.inner.name, " (chosen from the block sizes and the spread of the cells' aspect ratios)" if inp.solver.inner == solver.Inner.auto else "")
+        slog.info("hip solver, inner strategy: %s%s", sm.inner.name, " (chosen from the block sizes and the spread of the cells' aspect ratios)" if inp.solver.inner == solver.Inner.auto else
+                  f", preconditioner: {inp.solver.preconditioner.name}" if sm.inner == solver.Inner.reference_gmres else "")
         if args.until:
             reached, stats = sm.iterate_until(args.until, iterations or 100)
             slog.info("scaled residual %.3e after %d iterations (%s)", stats["scaled_residual_rms"], stats["outer_iterations"], "reached" if reached else "NOT reached")

@@ -21,7 +21,7 @@ TM_E_SIZE, TM_E_TOPOLOGY, TM_E_MISMATCH, TM_E_OVERFLOW, TM_E_UNSUPPORTED, TM_E_A
 _ERR_NAMES = {-1: "InconsistentSize", -2: "Topology", -3: "Mismatch", -4: "Overflow", -5: "ExternalSolverNotEnabled", -6: "Argument",
               -7: "OutOfMemory", -8: "Hip", -9: "Comm"}
 TM_SOLVER_GMRES, TM_SOLVER_BICGSTAB, TM_SOLVER_UMFPACK, TM_SOLVER_PETSC, TM_SOLVER_HIP = 0, 1, 2, 3, 4
-TM_INNER_BICGSTAB, TM_INNER_RELAX, TM_INNER_MG_BICGSTAB, TM_INNER_AUTO, TM_INNER_GMRES = 0, 1, 2, 3, 4
+TM_INNER_BICGSTAB, TM_INNER_RELAX, TM_INNER_MG_BICGSTAB, TM_INNER_AUTO, TM_INNER_GMRES, TM_INNER_REFERENCE_GMRES = 0, 1, 2, 3, 4, 5
 TM_CF_LAPLACE, TM_CF_WHITE = 0, 1
 
 
@@ -117,6 +117,7 @@ EXPORTS = [
     "tm_smoother_control_function", "tm_smoother_profile", "tm_smoother_profile_read", "tm_plan_build", "tm_plan_free", "tm_plan_local", "tm_plan_local_free", "tm_dev_tfi_block", "tm_dev_relax_sweep",
     "tm_dev_relax_partials_needed", "tm_export_soa", "tm_smoother_export_soa", "tm_rccl_unique_id", "tm_rccl_comm_create", "tm_rccl_comm_destroy", "tm_rccl_hooks",
     "tm_rccl_peer_table_build", "tm_rccl_peer_table_free", "tm_white_math_probe", "tm_stream_probe", "tm_smoother_queue_ordering", "tm_smoother_inner", "tm_csr_ilu0_probe", "tm_rccl_hooks_for", "tm_smoother_assemble_csr", "tm_smoother_apply_reference_order",
+    "tm_smoother_inner_counts",
 ]
 
 _lib = None
@@ -189,6 +190,7 @@ def lib():
         L.tm_smoother_profile_read.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.tm_smoother_queue_ordering.argtypes = [C.c_void_p]
         L.tm_smoother_inner.argtypes = [C.c_void_p]
+        L.tm_smoother_inner_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.tm_csr_ilu0_probe.argtypes = [C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp, _dp, _dp]
         L.tm_plan_build.argtypes = [C.POINTER(tm_mesh_desc), C.POINTER(tm_plan_rows)]
         L.tm_plan_free.argtypes = [C.POINTER(tm_plan_rows)]

@@ -9,6 +9,7 @@
 using namespace tmh;
 
 #include "tm_api_util.hpp"
+#include "tm_ilu.hpp"
 
 static void require_gfx950() {
     static int checked = 0;
@@ -55,6 +56,48 @@ void tm_set_log(tm_log_fn sink, void* ctx) {
 }
 
 #ifdef TM_DEBUG_EXPORTS   // measurement build only (libtm_hip_dbg.so, tools/): not in include/tm_hip.h
+// one ILU(0) application M^-1 r on a caller-assembled system, timed with an event pair per repeat (tools/reference_solve_timing.py):
+// packed != 0 the level-packed substitution kernels, 0 the level-by-level kernels; ms_out[repeats]; *levels = forward + backward levels
+int tm_debug_ilu0_apply_ms(uint64_t n64, const int32_t* Ap, const int32_t* Ai, const double* Ax, int packed, int repeats, double* ms_out, int32_t* levels) {
+    return guarded([&]() {
+        if (!Ap || !Ai || !Ax || !ms_out || repeats < 1) throw TmError(TM_E_ARG, "null argument");
+        if (n64 == 0 || n64 >= (uint64_t{1} << 31)) throw TmError(TM_E_SIZE, "system size out of range");
+        require_gfx950();
+        const int n = static_cast<int>(n64);
+        const size_t nnz = static_cast<size_t>(Ap[n]);
+        for (size_t k = 0; k < nnz; ++k)
+            if (Ai[k] < 0 || Ai[k] >= n) throw TmError(TM_E_ARG, "InvalidMatrix: column index out of range");
+        Dev d_p(sizeof(int32_t) * (static_cast<size_t>(n) + 1)), d_i(sizeof(int32_t) * nnz), d_v(sizeof(double) * nnz), d_r(sizeof(double2) * static_cast<size_t>(n)),
+            d_z(sizeof(double2) * static_cast<size_t>(n));
+        HIPCHK(hipMemcpy(d_p.p, Ap, sizeof(int32_t) * (static_cast<size_t>(n) + 1), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_i.p, Ai, sizeof(int32_t) * nnz, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_v.p, Ax, sizeof(double) * nnz, hipMemcpyHostToDevice));
+        std::vector<double2> r(static_cast<size_t>(n));
+        for (int k = 0; k < n; ++k) r[k] = make_double2(1.0 + 1e-3 * (k % 97), 1.0 - 1e-3 * (k % 89));
+        HIPCHK(hipMemcpy(d_r.p, r.data(), sizeof(double2) * r.size(), hipMemcpyHostToDevice));
+        IluState ilu(n, Ap, Ai, nnz, false, packed ? 1 : 0);
+        if (packed && !ilu.packed) throw TmError(TM_E_UNSUPPORTED, "this pattern has no packed form (a row with more than 16 entries on one side of the diagonal)");
+        if (levels) *levels = static_cast<int32_t>(ilu.L.ptr.size() + ilu.U.ptr.size()) - 2;
+        ilu.factor(n, d_p.as<int32_t>(), d_i.as<int32_t>(), d_v.as<double>(), nullptr, nnz, nullptr, nullptr);
+        ilu.apply(d_r.as<double2>(), d_z.as<double2>(), nullptr, false);   // warm-up
+        HIPCHK(hipDeviceSynchronize());
+        hipEvent_t e0, e1;
+        HIPCHK(hipEventCreate(&e0));
+        HIPCHK(hipEventCreate(&e1));
+        for (int q = 0; q < repeats; ++q) {
+            HIPCHK(hipEventRecord(e0, nullptr));
+            ilu.apply(d_r.as<double2>(), d_z.as<double2>(), nullptr, false);
+            HIPCHK(hipEventRecord(e1, nullptr));
+            HIPCHK(hipEventSynchronize(e1));
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+            ms_out[q] = ms;
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        return TM_OK;
+    });
+}
 // internal tuning knob used by the benchmark sweeps (not part of the drop-in surface)
 int tm_tune_apply(int rows_per_chunk, int unroll, int pipe, int nt) {
     tune_apply(rows_per_chunk, unroll, pipe, nt);
@@ -430,6 +473,14 @@ int tm_smoother_profile_read(tm_smoother* s, double* k2_ms_total, uint64_t* k2_l
 }
 
 int tm_smoother_inner(const tm_smoother* s) { return s ? s->impl.opt.inner : static_cast<int>(TM_E_ARG); }
+int tm_smoother_inner_counts(const tm_smoother* s, uint64_t* x_iterations, uint64_t* y_iterations) {
+    return guarded([&]() {
+        if (!s || !x_iterations || !y_iterations) throw TmError(TM_E_ARG, "null argument");
+        *x_iterations = s->impl.inner_counts[0];
+        *y_iterations = s->impl.inner_counts[1];
+        return TM_OK;
+    });
+}
 
 // how the handle orders the two queues of a pipelined pass (include/tm_hip_diag.h)
 int tm_smoother_queue_ordering(const tm_smoother* s) { return s ? s->impl.queue_ordering : static_cast<int>(TM_E_ARG); }

@@ -10,6 +10,7 @@
 // the matrix-free kernels.
 #include "tm_api_util.hpp"
 #include "tm_devutil.hpp"
+#include "tm_ilu.hpp"
 #include <array>
 #include <chrono>
 #include <cstring>
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(256) void k_deinterleave(int n, const double2* __re
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// ILU(0) on the device (TM_OPT_PRECOND_ILU0, seam 2 only): the reference's second preconditioner (preconditioner.zig:1-4; factorisation
+// ILU(0) on the device (TM_OPT_PRECOND_ILU0: seam 2 and TM_INNER_REFERENCE_GMRES; IluState in tm_ilu.hpp): the reference's second preconditioner (preconditioner.zig:1-4; factorisation
 // BiCGStab.zig:178-277, application :384-422 -- identical copies in GMRES.zig:199-298, 437-475), which its example inputs select.
 // The recurrence is sequential row by row; what is parallel are the LEVEL SETS of its dependency graph: row i needs the finished rows
 // k < i of its own pattern (factorisation and forward substitution alike), the backward substitution the rows k > i.  The host sorts the
@@ -138,16 +139,11 @@ __global__ __launch_bounds__(256) void k_deinterleave(int n, const double2* __re
 // the update `lu[pos] -= l_ik * lu[k, j]` un-fused -- so the factor and M^-1 r equal the reference's bit for bit (tests/test_gpu_ilu0.py
 // against the faithful oracle).  Levels of the reference's systems are narrow (T106: 1790 levels of ~14 rows): runs of levels with at most
 // 256 rows execute inside ONE single-workgroup launch with a barrier between levels; a wider level gets a launch of its own.
-// It is here so that the solver slot is complete and the reference's preconditioner can be cross-checked bit for bit, not for speed: a level
-// is a chain of dependent loads (~2.6 us), T106's 2655 levels make an application ~7 ms and the solve 2.8 s where the diagonal-only solve
-// takes 26 ms (tools/dev/csr_seam_probe.py; the CPU oracle: 65 ms per component).  Tried and dropped: fetching a level's matrix data one
-// level ahead into per-thread arrays (the dynamic indexing sends them to scratch: 43 ms per iteration instead of 14).
-struct IluDev {
-    int n;
-    const int32_t *p, *ci, *diag_pos;
-    double *lux, *luy;       // the factors, in the pattern of A (unit lower part below the diagonal, U on and above it); luy == lux: one system
-    const double2* dvec;     // a_ii per row and component: the forward substitution multiplies its right-hand side by it (see ilu_apply)
-};
+// k_ilu_levels serves the factorisation (once per outer iteration) and, for patterns with more than 16 entries on one side of the diagonal,
+// the substitutions: there a level is a chain of dependent loads (~1.8-2.3 us; T106's 2655 levels: 4.8 ms per application).  The
+// substitutions of every other pattern run on the level-packed form below (k_ilu_subst_packed: T106 2.2 ms; tools/reference_solve_timing.py).
+// Tried and dropped: fetching a level's matrix data one level ahead into DYNAMICALLY indexed per-thread arrays (they go to scratch: 43 ms per
+// iteration instead of 14) -- the packed kernel's arrays have a template width and index statically.
 enum { ILU_FACTOR = 0, ILU_FORWARD = 1, ILU_BACKWARD = 2 };
 
 __device__ __forceinline__ double ilu_pivot(const double* lu, int pos) {   // a missing or zero diagonal counts as 1 (BiCGStab.zig:240-249, 413-418)
@@ -227,117 +223,280 @@ __global__ __launch_bounds__(256) void k_ilu_levels(IluDev M, const int32_t* __r
     }
 }
 
-// host side: level sets of the lower (factorisation, forward substitution) and of the upper (backward substitution) dependency graph
-struct IluLevels {
-    std::vector<int32_t> order, ptr;              // rows sorted by level; ptr[l] .. ptr[l+1]
-    std::vector<std::array<int, 2>> chunks;       // launches: [lv0, lv1); a chunk of several levels has only levels of <= 256 rows
-    void build(int n, const int32_t* p, const int32_t* ci, bool lower) {
-        std::vector<int32_t> lev(static_cast<size_t>(n), 0);
-        int32_t nlev = 0;
-        auto visit = [&](int row) {
-            int32_t l = 0;
-            for (int k = p[row]; k < p[row + 1]; ++k) {
-                const int col = ci[k];
-                if (lower ? col < row : col > row) l = std::max(l, lev[col] + 1);
-            }
-            lev[row] = l;
-            nlev = std::max(nlev, l + 1);
-        };
-        if (lower) for (int row = 0; row < n; ++row) visit(row);
-        else for (int row = n - 1; row >= 0; --row) visit(row);
-        ptr.assign(static_cast<size_t>(nlev) + 1, 0);
-        for (int row = 0; row < n; ++row) ptr[lev[row] + 1] += 1;
-        for (int l = 0; l < nlev; ++l) ptr[l + 1] += ptr[l];
-        order.resize(static_cast<size_t>(n));
-        std::vector<int32_t> at(ptr.begin(), ptr.end() - 1);
-        for (int row = 0; row < n; ++row) order[at[lev[row]]++] = row;   // ascending row id inside a level
-        chunks.clear();
-        for (int l = 0; l < nlev;) {
-            if (ptr[l + 1] - ptr[l] > 256) {
-                chunks.push_back({l, l + 1});
-                ++l;
-                continue;
-            }
-            int e = l;
-            while (e < nlev && ptr[e + 1] - ptr[e] <= 256 && e - l < (1 << 20)) ++e;
-            chunks.push_back({l, e});
-            l = e;
+// ---- the substitutions on the level-packed form (IluPacked, tm_ilu.hpp).  In k_ilu_levels a row of a level walks order[k] -> p[row] ->
+// ci[idx] -> lu[idx], out[col] -> diag_pos -> lu[diag]: four to five DEPENDENT loads, of which only out[col] depends on the previous level.
+// Here position k of the level order owns WIDTH slots (column, both factors' values) at unit stride, the pivot and its right-hand side, all
+// independent of `out`: a lane fetches them ONE LEVEL AHEAD into registers (WIDTH is a template constant: the slot loops unroll fully and
+// index statically), so that a level costs one gather of out[col], the subtraction chain in the row's CSR order and a barrier.
+// One workgroup per launch: the hand-off between levels is the workgroup barrier (NT == 64: one wave).  A level wider than the workgroup is
+// taken in strides of NT rows, the later strides loading on demand.
+template <int WIDTH>
+struct PackedRow {
+    int32_t row;
+    int32_t c[WIDTH];
+    double2 v[WIDTH];
+    double2 piv, rhs;
+};
+template <int WIDTH, bool BACK>
+__device__ __forceinline__ void packed_load(const IluPackedDev& P, size_t k, const double2* rhs, const double2* dvec, PackedRow<WIDTH>& R) {
+    R.row = P.order[k];
+#pragma unroll
+    for (int s = 0; s < WIDTH; ++s) {
+        R.c[s] = P.col[static_cast<size_t>(s) * P.n + k];
+        R.v[s] = P.val[static_cast<size_t>(s) * P.n + k];
+    }
+    R.rhs = rhs[R.row];   // backward: what the forward pass left in out[row] -- only this row's own store changes it
+    if (BACK) {
+        R.piv = P.piv[k];
+    } else if (dvec) {
+        const double2 d = dvec[R.row];
+        R.rhs.x *= d.x;
+        R.rhs.y *= d.y;
+    }
+}
+template <int WIDTH, bool BACK>
+__device__ __forceinline__ void packed_row(const PackedRow<WIDTH>& R, double2* out) {
+    double2 o[WIDTH];
+#pragma unroll
+    for (int s = 0; s < WIDTH; ++s) o[s] = out[R.c[s] < 0 ? 0 : R.c[s]];   // the one access that depends on the previous level
+    double2 sum = R.rhs;
+#pragma unroll
+    for (int s = 0; s < WIDTH; ++s)
+        if (R.c[s] >= 0) {   // (an empty slot is skipped, not multiplied by zero: -0.0 - 0.0 * o would lose its sign)
+            sum.x -= R.v[s].x * o[s].x;
+            sum.y -= R.v[s].y * o[s].y;
         }
-    }
-};
-
-struct Dev {   // RAII device buffer
-    void* p = nullptr;
-    explicit Dev(size_t bytes) {
-        if (hipMalloc(&p, bytes ? bytes : 256) != hipSuccess) throw TmError(TM_E_MEMORY, "hipMalloc failed (" + std::to_string(bytes) + " bytes)");
-    }
-    ~Dev() { (void)hipFree(p); }
-    void reset(size_t bytes) {
-        (void)hipFree(p);
-        p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 256) != hipSuccess) throw TmError(TM_E_MEMORY, "hipMalloc failed (" + std::to_string(bytes) + " bytes)");
-    }
-    Dev(const Dev&) = delete;
-    Dev& operator=(const Dev&) = delete;
-    template <class T>
-    T* as() { return static_cast<T*>(p); }
-};
-
-// ILU(0) of a system on the device: analysis on the host, factorisation and the two substitutions level by level (see k_ilu_levels)
-struct IluState {
-    IluLevels L, U;
-    Dev d_diag, d_lux, d_luy, d_ordL, d_ptrL, d_ordU, d_ptrU;
-    IluDev M{};
-    IluState(int n, const int32_t* Ap, const int32_t* Ai, size_t nnz, bool two)
-        : d_diag(sizeof(int32_t) * static_cast<size_t>(n)), d_lux(sizeof(double) * nnz), d_luy(two ? sizeof(double) * nnz : 0),
-          d_ordL(sizeof(int32_t) * static_cast<size_t>(n)), d_ptrL(0), d_ordU(sizeof(int32_t) * static_cast<size_t>(n)), d_ptrU(0) {
-        std::vector<int32_t> diag(static_cast<size_t>(n), -1);
-        for (int row = 0; row < n; ++row)
-            for (int k = Ap[row]; k < Ap[row + 1]; ++k)
-                if (Ai[k] == row) {
-                    diag[row] = k;
-                    break;
-                }
-        L.build(n, Ap, Ai, true);
-        U.build(n, Ap, Ai, false);
-        HIPCHK(hipMemcpy(d_diag.p, diag.data(), sizeof(int32_t) * diag.size(), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_ordL.p, L.order.data(), sizeof(int32_t) * L.order.size(), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_ordU.p, U.order.data(), sizeof(int32_t) * U.order.size(), hipMemcpyHostToDevice));
-        d_ptrL.reset(sizeof(int32_t) * L.ptr.size());
-        d_ptrU.reset(sizeof(int32_t) * U.ptr.size());
-        HIPCHK(hipMemcpy(d_ptrL.p, L.ptr.data(), sizeof(int32_t) * L.ptr.size(), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_ptrU.p, U.ptr.data(), sizeof(int32_t) * U.ptr.size(), hipMemcpyHostToDevice));
-    }
-    template <int OP>
-    void run(const IluLevels& lv, const int32_t* order, const int32_t* ptr, const double2* rhs, double2* out, hipStream_t st) {
-        for (const auto& c : lv.chunks) {
-            const int width = lv.ptr[c[0] + 1] - lv.ptr[c[0]];
-            const int grid = (c[1] - c[0] == 1 && width > 256) ? (width + 255) / 256 : 1;
-            hipLaunchKernelGGL((k_ilu_levels<OP>), dim3(grid), dim3(256), 0, st, M, order, ptr, c[0], c[1], rhs, out);
-            HIPCHK(hipGetLastError());
+    if (BACK) sum = make_double2(sum.x / R.piv.x, sum.y / R.piv.y);
+    out[R.row] = sum;
+}
+template <int WIDTH, bool BACK, int NT>
+__global__ __launch_bounds__(NT) void k_ilu_subst_packed(IluPackedDev P, const double2* rhs, const double2* dvec, double2* out) {
+    const int tid = static_cast<int>(threadIdx.x);
+    int beg = P.ptr[0], end = P.ptr[1];
+    PackedRow<WIDTH> cur, nxt;
+    if (beg + tid < end) packed_load<WIDTH, BACK>(P, static_cast<size_t>(beg + tid), rhs, dvec, cur);
+    for (int l = 0; l < P.nlev; ++l) {
+        const int nbeg = end, nend = l + 1 < P.nlev ? P.ptr[l + 2] : end;
+        if (nbeg + tid < nend) packed_load<WIDTH, BACK>(P, static_cast<size_t>(nbeg + tid), rhs, dvec, nxt);
+        if (beg + tid < end) packed_row<WIDTH, BACK>(cur, out);
+        for (int k = beg + tid + NT; k < end; k += NT) {
+            PackedRow<WIDTH> more;
+            packed_load<WIDTH, BACK>(P, static_cast<size_t>(k), rhs, dvec, more);
+            packed_row<WIDTH, BACK>(more, out);
         }
+        __syncthreads();   // (a workgroup-scope release / acquire: the next level reads what this one stored)
+        cur = nxt;
+        beg = nbeg;
+        end = nend;
     }
-    // the factor of (vx, vy) -- device arrays in A's pattern -- into lux / luy
-    void factor(int n, const int32_t* d_p, const int32_t* d_i, const double* d_vx, const double* d_vy, size_t nnz, const double2* dvec, hipStream_t st) {
-        const bool two = d_vy != nullptr && d_vy != d_vx;
-        HIPCHK(hipMemcpyAsync(d_lux.p, d_vx, sizeof(double) * nnz, hipMemcpyDeviceToDevice, st));
-        if (two) HIPCHK(hipMemcpyAsync(d_luy.p, d_vy, sizeof(double) * nnz, hipMemcpyDeviceToDevice, st));
-        M = IluDev{n, d_p, d_i, d_diag.as<int32_t>(), d_lux.as<double>(), two ? d_luy.as<double>() : d_lux.as<double>(), dvec};
-        run<ILU_FACTOR>(L, d_ordL.as<int32_t>(), d_ptrL.as<int32_t>(), nullptr, nullptr, st);
-    }
-    // out = U^-1 L^-1 (dvec .* rhs)   (dvec == nullptr in M: plain M^-1 rhs, BiCGStab.zig:384-422)
-    // times_d = false: plain M^-1 rhs whatever dvec the state was factorised with.  rhs == out is fine (a row reads its own right-hand side
-    // before it stores, and nothing else of rhs)
-    void apply(const double2* rhs, double2* out, hipStream_t st, bool times_d = true) {
-        const double2* keep = M.dvec;
-        if (!times_d) M.dvec = nullptr;
-        run<ILU_FORWARD>(L, d_ordL.as<int32_t>(), d_ptrL.as<int32_t>(), rhs, out, st);
-        run<ILU_BACKWARD>(U, d_ordU.as<int32_t>(), d_ptrU.as<int32_t>(), rhs, out, st);
-        M.dvec = keep;
-    }
-};
+}
+// values of the packed slots from the factors (after every factorisation); src = position in lu, -1 = empty slot
+__global__ __launch_bounds__(256) void k_ilu_pack(size_t nslots, const int32_t* __restrict__ src, const double* __restrict__ lux, const double* __restrict__ luy,
+                                                  double2* __restrict__ val) {
+    const size_t t = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (t >= nslots) return;
+    const int32_t idx = src[t];
+    val[t] = idx < 0 ? make_double2(0.0, 0.0) : make_double2(lux[idx], luy[idx]);
+}
+__global__ __launch_bounds__(256) void k_ilu_pack_pivots(IluDev M, const int32_t* __restrict__ order, double2* __restrict__ piv) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= M.n) return;
+    const int pos = M.diag_pos[order[k]];
+    piv[k] = make_double2(ilu_pivot(M.lux, pos), ilu_pivot(M.luy, pos));
+}
+
+template <int WIDTH, bool BACK>
+void launch_subst_packed(const IluPackedDev& P, int max_width, const double2* rhs, const double2* dvec, double2* out, hipStream_t st) {
+    if (max_width <= 64) hipLaunchKernelGGL((k_ilu_subst_packed<WIDTH, BACK, 64>), dim3(1), dim3(64), 0, st, P, rhs, dvec, out);
+    else hipLaunchKernelGGL((k_ilu_subst_packed<WIDTH, BACK, 256>), dim3(1), dim3(256), 0, st, P, rhs, dvec, out);
+    HIPCHK(hipGetLastError());
+}
+template <bool BACK>
+void subst_packed(int width, const IluPackedDev& P, int max_width, const double2* rhs, const double2* dvec, double2* out, hipStream_t st) {
+    if (width <= 4) launch_subst_packed<4, BACK>(P, max_width, rhs, dvec, out, st);
+    else if (width <= 8) launch_subst_packed<8, BACK>(P, max_width, rhs, dvec, out, st);
+    else launch_subst_packed<16, BACK>(P, max_width, rhs, dvec, out, st);
+}
+
+__global__ __launch_bounds__(256) void k_csr_sub(int n, const double2* b, const double2* w, double2* r) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double2 bi = b[i], wi = w[i];
+    r[i] = make_double2(bi.x - wi.x, bi.y - wi.y);
+}
+__global__ __launch_bounds__(256) void k_csr_diag_precond(int n, const double2* __restrict__ dinv, const double2* r, double2* z) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double2 d = dinv[i], ri = r[i];
+    z[i] = make_double2(ri.x * d.x, ri.y * d.y);
+}
 
 }  // namespace
+
+void IluLevels::build(int n, const int32_t* p, const int32_t* ci, bool lower) {
+    std::vector<int32_t> lev(static_cast<size_t>(n), 0);
+    int32_t nlev = 0;
+    auto visit = [&](int row) {
+        int32_t l = 0;
+        for (int k = p[row]; k < p[row + 1]; ++k) {
+            const int col = ci[k];
+            if (lower ? col < row : col > row) l = std::max(l, lev[col] + 1);
+        }
+        lev[row] = l;
+        nlev = std::max(nlev, l + 1);
+    };
+    if (lower) for (int row = 0; row < n; ++row) visit(row);
+    else for (int row = n - 1; row >= 0; --row) visit(row);
+    ptr.assign(static_cast<size_t>(nlev) + 1, 0);
+    for (int row = 0; row < n; ++row) ptr[lev[row] + 1] += 1;
+    max_width = 0;
+    for (int l = 0; l < nlev; ++l) {
+        max_width = std::max<int>(max_width, ptr[l + 1]);
+        ptr[l + 1] += ptr[l];
+    }
+    order.resize(static_cast<size_t>(n));
+    std::vector<int32_t> at(ptr.begin(), ptr.end() - 1);
+    for (int row = 0; row < n; ++row) order[at[lev[row]]++] = row;   // ascending row id inside a level
+    chunks.clear();
+    for (int l = 0; l < nlev;) {
+        if (ptr[l + 1] - ptr[l] > 256) {
+            chunks.push_back({l, l + 1});
+            ++l;
+            continue;
+        }
+        int e = l;
+        while (e < nlev && ptr[e + 1] - ptr[e] <= 256 && e - l < (1 << 20)) ++e;
+        chunks.push_back({l, e});
+        l = e;
+    }
+}
+
+void IluPacked::build(int n, const int32_t* p, const int32_t* ci, const IluLevels& lv, bool lower) {
+    int most = 0;
+    for (int row = 0; row < n; ++row) {
+        int cnt = 0;
+        for (int k = p[row]; k < p[row + 1]; ++k) cnt += (lower ? ci[k] < row : ci[k] > row) ? 1 : 0;
+        most = std::max(most, cnt);
+    }
+    width = most <= 4 ? 4 : most <= 8 ? 8 : most <= 16 ? 16 : 0;   // the instantiated kernels; 0: not packable
+    if (!width) return;
+    const size_t nslots = static_cast<size_t>(width) * static_cast<size_t>(n);
+    std::vector<int32_t> col(nslots, -1), src(nslots, -1);
+    for (int k = 0; k < n; ++k) {
+        const int row = lv.order[static_cast<size_t>(k)];
+        int s = 0;
+        for (int idx = p[row]; idx < p[row + 1]; ++idx)   // the row's CSR order
+            if (lower ? ci[idx] < row : ci[idx] > row) {
+                col[static_cast<size_t>(s) * n + k] = ci[idx];
+                src[static_cast<size_t>(s) * n + k] = idx;
+                ++s;
+            }
+    }
+    d_col.reset(sizeof(int32_t) * nslots);
+    d_src.reset(sizeof(int32_t) * nslots);
+    d_val.reset(sizeof(double2) * nslots);
+    d_piv.reset(sizeof(double2) * static_cast<size_t>(n));
+    HIPCHK(hipMemcpy(d_col.p, col.data(), sizeof(int32_t) * nslots, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_src.p, src.data(), sizeof(int32_t) * nslots, hipMemcpyHostToDevice));
+}
+
+IluState::IluState(int n_, const int32_t* Ap, const int32_t* Ai, size_t nnz, bool two, int use_packed)
+    : d_diag(sizeof(int32_t) * static_cast<size_t>(n_)), d_lux(sizeof(double) * nnz), d_luy(two ? sizeof(double) * nnz : 0),
+      d_ordL(sizeof(int32_t) * static_cast<size_t>(n_)), d_ptrL(0), d_ordU(sizeof(int32_t) * static_cast<size_t>(n_)), d_ptrU(0), n(n_) {
+    std::vector<int32_t> diag(static_cast<size_t>(n), -1);
+    for (int row = 0; row < n; ++row)
+        for (int k = Ap[row]; k < Ap[row + 1]; ++k)
+            if (Ai[k] == row) {
+                diag[row] = k;
+                break;
+            }
+    L.build(n, Ap, Ai, true);
+    U.build(n, Ap, Ai, false);
+    HIPCHK(hipMemcpy(d_diag.p, diag.data(), sizeof(int32_t) * diag.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_ordL.p, L.order.data(), sizeof(int32_t) * L.order.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_ordU.p, U.order.data(), sizeof(int32_t) * U.order.size(), hipMemcpyHostToDevice));
+    d_ptrL.reset(sizeof(int32_t) * L.ptr.size());
+    d_ptrU.reset(sizeof(int32_t) * U.ptr.size());
+    HIPCHK(hipMemcpy(d_ptrL.p, L.ptr.data(), sizeof(int32_t) * L.ptr.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_ptrU.p, U.ptr.data(), sizeof(int32_t) * U.ptr.size(), hipMemcpyHostToDevice));
+    if (use_packed < 0) {
+        const char* e = std::getenv("TM_ILU_PACKED");   // 0: the substitutions by k_ilu_levels (measurement: tools/reference_solve_timing.py)
+        use_packed = (e && std::atoi(e) == 0) ? 0 : 1;
+    }
+    if (use_packed) {
+        PL.build(n, Ap, Ai, L, true);
+        PU.build(n, Ap, Ai, U, false);
+        packed = PL.width > 0 && PU.width > 0;
+    }
+}
+
+namespace {
+template <int OP>
+void run_levels(const IluDev& M, const IluLevels& lv, const int32_t* order, const int32_t* ptr, const double2* rhs, double2* out, hipStream_t st) {
+    for (const auto& c : lv.chunks) {
+        const int width = lv.ptr[c[0] + 1] - lv.ptr[c[0]];
+        const int grid = (c[1] - c[0] == 1 && width > 256) ? (width + 255) / 256 : 1;
+        hipLaunchKernelGGL((k_ilu_levels<OP>), dim3(grid), dim3(256), 0, st, M, order, ptr, c[0], c[1], rhs, out);
+        HIPCHK(hipGetLastError());
+    }
+}
+}  // namespace
+
+void IluState::factor(int n_, const int32_t* d_p, const int32_t* d_i, const double* d_vx, const double* d_vy, size_t nnz, const double2* dvec, hipStream_t st) {
+    const bool two = d_vy != nullptr && d_vy != d_vx;
+    HIPCHK(hipMemcpyAsync(d_lux.p, d_vx, sizeof(double) * nnz, hipMemcpyDeviceToDevice, st));
+    if (two) HIPCHK(hipMemcpyAsync(d_luy.p, d_vy, sizeof(double) * nnz, hipMemcpyDeviceToDevice, st));
+    M = IluDev{n_, d_p, d_i, d_diag.as<int32_t>(), d_lux.as<double>(), two ? d_luy.as<double>() : d_lux.as<double>(), dvec};
+    run_levels<ILU_FACTOR>(M, L, d_ordL.as<int32_t>(), d_ptrL.as<int32_t>(), nullptr, nullptr, st);
+    if (!packed) return;
+    for (IluPacked* P : {&PL, &PU}) {
+        const size_t nslots = static_cast<size_t>(P->width) * static_cast<size_t>(n);
+        hipLaunchKernelGGL(k_ilu_pack, dim3(static_cast<unsigned>((nslots + 255) / 256)), dim3(256), 0, st, nslots, P->d_src.as<int32_t>(), M.lux, M.luy,
+                           P->d_val.as<double2>());
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_ilu_pack_pivots, dim3((n + 255) / 256), dim3(256), 0, st, M, d_ordU.as<int32_t>(), PU.d_piv.as<double2>());
+    HIPCHK(hipGetLastError());
+}
+
+void IluState::apply(const double2* rhs, double2* out, hipStream_t st, bool times_d) {
+    if (packed) {
+        const IluPackedDev fw{n, static_cast<int>(L.ptr.size()) - 1, d_ptrL.as<int32_t>(), d_ordL.as<int32_t>(), PL.d_col.as<int32_t>(), PL.d_val.as<double2>(), nullptr};
+        const IluPackedDev bw{n, static_cast<int>(U.ptr.size()) - 1, d_ptrU.as<int32_t>(), d_ordU.as<int32_t>(), PU.d_col.as<int32_t>(), PU.d_val.as<double2>(),
+                              PU.d_piv.as<double2>()};
+        subst_packed<false>(PL.width, fw, L.max_width, rhs, times_d ? M.dvec : nullptr, out, st);
+        subst_packed<true>(PU.width, bw, U.max_width, out, nullptr, out, st);
+        return;
+    }
+    const double2* keep = M.dvec;
+    if (!times_d) M.dvec = nullptr;
+    run_levels<ILU_FORWARD>(M, L, d_ordL.as<int32_t>(), d_ptrL.as<int32_t>(), rhs, out, st);
+    run_levels<ILU_BACKWARD>(M, U, d_ordU.as<int32_t>(), d_ptrU.as<int32_t>(), rhs, out, st);
+    M.dvec = keep;
+}
+
+hipError_t launch_csr_dinv(int n, const int32_t* p, const int32_t* ci, const double* vx, const double* vy, double2* dinv, hipStream_t st) {
+    hipLaunchKernelGGL(k_csr_dinv, dim3(csr_nwg(n)), dim3(256), 0, st, n, p, ci, vx, vy, dinv, static_cast<double2*>(nullptr));
+    return hipGetLastError();
+}
+hipError_t launch_csr_scaled_residual(int n, const int32_t* p, const int32_t* ci, const double* vx, const double* vy, const double2* dinv, const double2* in,
+                                      const double2* b, double2* out, double* partials, hipStream_t st) {
+    const CsrDev A{n, p, ci, vx, vy, dinv};
+    hipLaunchKernelGGL((k_csr_apply<true, DOT_OUT2>), dim3(csr_nwg(n)), dim3(256), 0, st, A, in, b, static_cast<const double2*>(nullptr), out, partials);
+    return hipGetLastError();
+}
+hipError_t launch_csr_norm2(int n, const double2* v, double* partials, hipStream_t st) {
+    hipLaunchKernelGGL(k_csr_norm2, dim3(csr_nwg(n)), dim3(256), 0, st, n, v, partials);
+    return hipGetLastError();
+}
+hipError_t launch_csr_sub(int n, const double2* b, const double2* w, double2* r, hipStream_t st) {
+    hipLaunchKernelGGL(k_csr_sub, dim3(csr_nwg(n)), dim3(256), 0, st, n, b, w, r);
+    return hipGetLastError();
+}
+hipError_t launch_csr_diag_precond(int n, const double2* dinv, const double2* r, double2* z, hipStream_t st) {
+    hipLaunchKernelGGL(k_csr_diag_precond, dim3(csr_nwg(n)), dim3(256), 0, st, n, dinv, r, z);
+    return hipGetLastError();
+}
 
 }  // namespace tmh
 

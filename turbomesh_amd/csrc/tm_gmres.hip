@@ -1,8 +1,9 @@
 // GMRES(m) on the device -- the reference's other Krylov solver (reference src/core/smoothing/GMRES.zig:300-423: left-preconditioned
 // restarted GMRES, modified Gram-Schmidt Arnoldi, Givens rotations :510-524, back substitution :394-409), served as an inner strategy of
 // the hip solver (TM_INNER_GMRES) with the diagonal preconditioner (GMRES.zig:425-431): z = D^-1 (A v) is exactly K2's MODE_SCALED, so the
-// operator application is the same matrix-free kernel the BiCGStab path uses.  ILU(0) (GMRES.zig:199-298) is a sequential recurrence and
-// stays on the CPU side (oracle only).
+// operator application is the same matrix-free kernel the BiCGStab path uses.  ILU(0) (GMRES.zig:199-298) is served on the ASSEMBLED
+// system -- tm_csr_solve and TM_INNER_REFERENCE_GMRES (csrc/tm_csr.hip, Smoother::picard_reference), which run these kernels on it with the
+// reference's own unscaled stop test -- and the matrix-free modes use the diagonal.
 //
 // Both coordinate components advance together (double2 vectors, independent scalars per component -- the reference solves the x- and the
 // y-system one after the other with the same code, smooth.zig / solver.zig:69-78); a component that has converged inside a restart cycle
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(VEC_BLOCK) void k_gm_update(double2* __restrict__ u
 
 // ---- scalar kernels: one thread per component
 // tolerance from ||D^-1 b||^2 (red[0..1]): tol = max(atol, rtol ||D^-1 b||)
-__global__ void k_gm_tol(GmresScalars* G, const double* red, double rtol, double atol) {
+__global__ void k_gm_tol(GmresScalars* G, const double* red, double rtol, double atol, int sticky) {
     const int c = threadIdx.x;
     if (c >= 2) return;
     G->tol[c] = fmax(atol, rtol * sqrt(red[c]));
@@ -117,6 +118,8 @@ __global__ void k_gm_tol(GmresScalars* G, const double* red, double rtol, double
         G->rtol_initial = -rtol;
     }
     G->cycle = 0;
+    G->sticky = sticky;
+    G->iters[c] = 0;
 }
 // start of a restart cycle: red[0..1] = ||D^-1 (b - A x)||^2 (GMRES.zig:312-336)
 __global__ void k_gm_begin(GmresScalars* G, const double* red) {
@@ -130,7 +133,10 @@ __global__ void k_gm_begin(GmresScalars* G, const double* red) {
     }
     G->resid[c] = beta;
     G->cols_used[c] = 0;
-    G->done[c] = beta <= G->tol[c] ? 1 : 0;   // if (beta <= tol) return
+    // if (beta <= tol) return.  The reference solves one component at a time and is gone once it returned (GMRES.zig:388-391, 418-419); here a
+    // finished component rides along while the other iterates, and in sticky mode its flag survives the cycle starts that follow
+    const bool was_done = G->sticky && G->cycle > 0 && G->done[c];
+    G->done[c] = (was_done || beta <= G->tol[c]) ? 1 : 0;
     G->scale[c] = beta;
     G->scale_skip[c] = G->done[c] ? 2 : 0;    // a finished component gets a zero v0 instead of 0 / 0
     for (int k = 0; k < (GMRES_M + 1) * GMRES_M; ++k) G->H[c][k] = 0.0;
@@ -187,6 +193,7 @@ __global__ void k_gm_column(GmresScalars* G, const double* red) {
         G->g[c][j + 1] = -rs * g_j + rc * g_jp1;
         G->resid[c] = fabs(G->g[c][j + 1]);
         G->cols_used[c] = j + 1;
+        G->iters[c] += 1;
         if (G->resid[c] <= G->tol[c]) G->done[c] = 1;                   // converged: this component's cycle ends here
     } else if (c < 2) {
         G->scale_skip[c] = 1;   // finished earlier in this cycle: its basis is not extended
@@ -228,8 +235,8 @@ hipError_t launch_gm_update(double2* u, const double2* V, int64_t ld, const Gmre
     hipLaunchKernelGGL(k_gm_update, dim3(vec_nwg(n)), dim3(VEC_BLOCK), 0, st, u, V, ld, G, n);
     return hipGetLastError();
 }
-hipError_t launch_gm_tol(GmresScalars* G, const double* red, double rtol, double atol, hipStream_t st) {
-    hipLaunchKernelGGL(k_gm_tol, dim3(1), dim3(64), 0, st, G, red, rtol, atol);
+hipError_t launch_gm_tol(GmresScalars* G, const double* red, double rtol, double atol, hipStream_t st, int sticky) {
+    hipLaunchKernelGGL(k_gm_tol, dim3(1), dim3(64), 0, st, G, red, rtol, atol, sticky);
     return hipGetLastError();
 }
 hipError_t launch_gm_begin(GmresScalars* G, const double* red, hipStream_t st) {

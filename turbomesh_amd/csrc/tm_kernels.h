@@ -313,6 +313,8 @@ struct GmresScalars {
     int32_t done[2];                        // resid <= tol (the component's solve is over)
     int32_t scale_skip[2];                  // see k_gm_divide
     int32_t j, cycle;
+    int32_t sticky;                         // TM_INNER_REFERENCE_GMRES: a component that met its tolerance stays finished for the rest of the solve
+    int32_t iters[2];                       // columns each component has built in this solve (the reference's iter_total, GMRES.zig:384)
 };
 // one modified-Gram-Schmidt step in one pass: w -= red_prev[c] v_prev (and H[row_prev, j] = red_prev), partials = w . v_next (or ||w||^2
 // when v_next == nullptr); v_prev == nullptr: the first step, nothing to subtract yet
@@ -320,7 +322,7 @@ hipError_t launch_gm_mgs(double2* w, const double2* v_prev, const double2* v_nex
                          double* partials, hipStream_t stream);
 hipError_t launch_gm_divide(double2* dst, const double2* src, const GmresScalars* G, int64_t n, hipStream_t stream);   // dst = src / G->scale[c]
 hipError_t launch_gm_update(double2* u, const double2* V, int64_t ld, const GmresScalars* G, int64_t n, hipStream_t stream);   // u += V y
-hipError_t launch_gm_tol(GmresScalars* G, const double* red, double rtol, double atol, hipStream_t stream);
+hipError_t launch_gm_tol(GmresScalars* G, const double* red, double rtol, double atol, hipStream_t stream, int sticky = 0);
 hipError_t launch_gm_begin(GmresScalars* G, const double* red, hipStream_t stream);
 hipError_t launch_gm_column(GmresScalars* G, const double* red, hipStream_t stream);
 hipError_t launch_gm_backsub(GmresScalars* G, hipStream_t stream);

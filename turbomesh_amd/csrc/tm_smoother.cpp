@@ -8,6 +8,7 @@
 //                      computes the reference's residual and copies back (smooth.zig:112-153).
 //   TM_INNER_RELAX     every outer iteration is one fused Jacobi sweep of the nonlinear system.
 #include "tm_smoother.hpp"
+#include "tm_ilu.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -119,6 +120,13 @@ static void connection_data_check(const Topology& t, const tm_mesh_desc* m, cons
 
 void Smoother::sync() { HIPCHK(hipStreamSynchronize(stream)); }
 
+// device state of TM_INNER_REFERENCE_GMRES beside the arena's vectors (picard_reference)
+struct Smoother::ReferenceSolve {
+    std::unique_ptr<IluState> ilu;   // TM_OPT_PRECOND_ILU0; else the diagonal
+    Dev dinv, part;                  // 1 / a_ii per row and component; the partial sums of the CSR kernels (256 rows per workgroup)
+    ReferenceSolve(int64_t n) : dinv(sizeof(double2) * static_cast<size_t>(n)), part(sizeof(double) * MAX_PARTIALS * static_cast<size_t>(csr_nwg(n))) {}
+};
+
 // Everything the handle owns outside the arena; also runs when create() throws half-way (pinned buffers already allocated).
 Smoother::~Smoother() {
     if (counted) g_multirank_handles.fetch_sub(1);
@@ -147,7 +155,9 @@ Smoother::~Smoother() {
         (void)hipStreamDestroy(side);
     }
     if (export_buf) (void)hipFree(export_buf);
-    csr_release();
+    delete ref;
+    ref = nullptr;
+    csr_free();
 }
 
 // ------------------------------------------------------------------ create
@@ -156,11 +166,22 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
     if (!o) throw TmError(TM_E_ARG, "null solver option");
     if (o->tag != TM_SOLVER_HIP)
         throw TmError(TM_E_UNSUPPORTED, "ExternalSolverNotEnabled: libtm_hip serves only solver tag `hip` (gmres/bicgstab/umfpack/petsc stay on the Zig side)");
-    if (o->inner != TM_INNER_BICGSTAB && o->inner != TM_INNER_RELAX && o->inner != TM_INNER_MG_BICGSTAB && o->inner != TM_INNER_AUTO && o->inner != TM_INNER_GMRES)
+    if (o->inner != TM_INNER_BICGSTAB && o->inner != TM_INNER_RELAX && o->inner != TM_INNER_MG_BICGSTAB && o->inner != TM_INNER_AUTO && o->inner != TM_INNER_GMRES &&
+        o->inner != TM_INNER_REFERENCE_GMRES)
         throw TmError(TM_E_ARG, "unknown inner strategy");
     opt = *o;
-    if (opt.flags & TM_OPT_PRECOND_ILU0)
-        throw TmError(TM_E_UNSUPPORTED, "ILU(0) needs the assembled matrix: it is served by tm_csr_solve (seam 2); the matrix-free path preconditions with the diagonal or the multigrid cycle");
+    const bool reference = opt.inner == TM_INNER_REFERENCE_GMRES;
+    if ((opt.flags & TM_OPT_PRECOND_ILU0) && !reference)
+        throw TmError(TM_E_UNSUPPORTED, "ILU(0) needs the assembled matrix: it is served by tm_csr_solve (seam 2) and by TM_INNER_REFERENCE_GMRES; the matrix-free path preconditions with the diagonal or the multigrid cycle");
+    if (reference) {
+        if (h != nullptr && h->nranks >= 1 && h->exchange != nullptr && h->allreduce_sum != nullptr)
+            throw TmError(TM_E_UNSUPPORTED, "TM_INNER_REFERENCE_GMRES solves the assembled system, which is available on single-process handles only");
+        // the reference's own constants (GMRES.zig:21-24); every column is polled: an ILU(0) application is thousands of dependent levels
+        if (!(opt.rtol > 0)) opt.rtol = 1e-6;
+        if (!(opt.atol > 0)) opt.atol = 1e-8;
+        if (opt.max_inner == 0) opt.max_inner = 1000;
+        if (opt.check_every == 0) opt.check_every = 1;
+    }
     if (opt.inner == TM_INNER_AUTO) {   // size-aware choice, from the global topology alone (include/tm_hip.h)
         uint64_t largest = 0;
         if (mesh && mesh->blocks)
@@ -257,7 +278,8 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
     if (const char* e = std::getenv("TM_MG_PERIMETER_SWEEPS")) mg_perimeter_sweeps = std::max(1, std::atoi(e));
     mg_dirichlet = mg_perimeter_step;   // ... and the perimeter values as Dirichlet data in front of the cycles (block-local: no exchange)
     if (const char* e = std::getenv("TM_MG_DIRICHLET")) mg_dirichlet = mg_dirichlet && std::atoi(e) != 0;
-    if (opt.inner == TM_INNER_GMRES) {   // w / z of GMRES.zig:27-38 in one vector, the basis v_0 .. v_m contiguous behind it
+    if (opt.inner == TM_INNER_GMRES || reference) {   // w / z of GMRES.zig:27-38 in one vector, the basis v_0 .. v_m contiguous behind it
+        if (reference) ref_b = vec();
         r = vec();
         gm_V = arena.alloc_n<double2>(static_cast<uint64_t>(n_local) * (GMRES_M + 1));
         gm_S = arena.alloc_n<GmresScalars>(1);
@@ -797,7 +819,7 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
                          {"sweep pairs", nwg_apply2},
                          {"sweep triples", nwg3_all},
                          {"vector kernels", nwg_vec},
-                         {"GMRES Gram-Schmidt", opt.inner == TM_INNER_GMRES ? vec_nwg(n_owned) : 0},
+                         {"GMRES Gram-Schmidt", (opt.inner == TM_INNER_GMRES || reference) ? vec_nwg(n_owned) : 0},
                          {"perimeter-row right-hand side", opt.inner != TM_INNER_RELAX ? edge.nwg : 0}};
         if (std::getenv("TM_DEBUG_RUNS"))
             std::fprintf(stderr, "[tm] partial-sum rows: %d allocated; operator %d, overlapping strips %d, pairs %d, triples %d, vector kernels %d (vec_nwg %d)\n", rows,
@@ -860,6 +882,7 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
     if (PQ) HIPCHK(hipMemsetAsync(PQ, 0, sizeof(double2) * n_local, stream));
     upload(mesh);
     if (white) white_launch(0);   // ControlFunction.init, wall_control_function.zig:27-42
+    if (reference) reference_create();   // everything the mode needs, now: a mesh that does not fit fails here, not in the middle of a solve
     sync();
 }
 
@@ -1547,6 +1570,130 @@ int Smoother::picard_gmres(tm_stats& st) {
     return converged ? 0 : 1;
 }
 
+// ------------------------------------------------------------------ Picard + the reference's own inner solve (TM_INNER_REFERENCE_GMRES)
+void Smoother::reference_create() {
+    ref = new ReferenceSolve(n_owned);
+    try {
+        csr_fill_values();   // pattern uploaded once; the values of the first outer iteration's system come again in picard_reference
+        // two factors: the x- and the y-system differ in the sliding rows (smooth.zig:1115-1165); where they do not, the second equals the first
+        if (opt.flags & TM_OPT_PRECOND_ILU0) ref->ilu = std::make_unique<IluState>(static_cast<int>(n_owned), csr.h_p.data(), csr.h_i.data(), csr.nnz, true);
+    } catch (...) {
+        delete ref;
+        ref = nullptr;
+        csr_free();
+        throw;
+    }
+}
+
+// One outer iteration as the reference runs it with "gmres" in its input file (smooth.zig:104-154, solver.zig:69-78): system.fill ->
+// GMRES(30), left-preconditioned, on the assembled UNSCALED system with the stop test ||M^-1 (b - A x)|| <= max(atol, rtol ||b||) ->
+// residual and copy-back.  GMRES.zig:300-423 operation by operation: w = A v in CSR order (launch_csr_product), r = b - w, z = M^-1 r
+// (ILU(0): bit-identical factor and substitutions, tm_csr.hip; diagonal: r_i * (1 / a_ii)), then the Arnoldi / Givens / back-substitution
+// kernels of tm_gmres.hip.  Both components in one double2 vector with their own scalars; a component that met its tolerance stays finished
+// (sticky, k_gm_begin) while the other goes on, so each sees the cycles and columns the reference's separate solves give it.  What differs
+// from the reference is the summation order of the dot products and norms.  Returns like picard_gmres.
+int Smoother::picard_reference(tm_stats& st) {
+    if (white && outer_done > 0) white_launch(1);   // system.fill(n): control_function.update for n > 0 (smooth.zig:1107-1110)
+    const int n = static_cast<int>(n_owned);
+    const int nwg = csr_nwg(n);
+    csr_fill_values();
+    HIPCHK(hipMemsetAsync(ref_b, 0, sizeof(double2) * n_local, stream));   // interior rows have b = 0
+    HIPCHK(launch_edge_rhs(edge, X, PQ, ref_b, 0, nullptr, stream));
+    double2* const W = r;
+    double* const part = ref->part.as<double>();
+    double2* const dinv = ref->dinv.as<double2>();
+    // stats.scaled_residual_rms keeps its meaning: D^-1 (b - A x) of this iteration's system at its start
+    HIPCHK(launch_csr_dinv(n, csr.p, csr.i, csr.vx, csr.vy, dinv, stream));
+    HIPCHK(launch_csr_scaled_residual(n, csr.p, csr.i, csr.vx, csr.vy, dinv, X, ref_b, W, part, stream));
+    HIPCHK(launch_finalize(part, nwg, red, stream));
+    HIPCHK(hipMemcpyAsync(h_red, red, sizeof(double) * MAX_PARTIALS, hipMemcpyDeviceToHost, stream));
+    sync();
+    st.scaled_residual_rms = std::sqrt((h_red[0] + h_red[1]) / (2.0 * static_cast<double>(dof_global)));
+    if (stop_tol > 0.0 && st.scaled_residual_rms <= stop_tol) return 2;
+    if (ref->ilu) ref->ilu->factor(n, csr.p, csr.i, csr.vx, csr.vy, csr.nnz, nullptr, stream);
+    HIPCHK(launch_csr_norm2(n, ref_b, part, stream));   // tol = max(atol, rtol ||b||), GMRES.zig:305-306
+    HIPCHK(launch_finalize(part, nwg, red, stream));
+    HIPCHK(launch_gm_tol(gm_S, red, opt.rtol, opt.atol, stream, 1));
+    const int64_t ld = n_local;
+    auto V = [&](int k) { return gm_V + static_cast<int64_t>(k) * ld; };
+    auto precondition_W = [&]() {   // z = M^-1 r, in place
+        if (ref->ilu) ref->ilu->apply(W, W, stream, false);
+        else HIPCHK(launch_csr_diag_precond(n, dinv, W, W, stream));
+    };
+    auto poll = [&]() {
+        HIPCHK(hipMemcpyAsync(h_gm, gm_S, sizeof(GmresScalars), hipMemcpyDeviceToHost, stream));
+        sync();
+        return h_gm->done[0] == 1 && h_gm->done[1] == 1;
+    };
+    uint64_t it_total = 0;
+    bool converged = false, first = true;
+    while (it_total < opt.max_inner) {
+        HIPCHK(launch_csr_product(n_owned, csr.p, csr.i, csr.vx, csr.vy, first ? X : U, W, stream));   // w = A x (warm start: the current field)
+        HIPCHK(launch_csr_sub(n, ref_b, W, W, stream));                                                // r = b - w
+        precondition_W();
+        st.operator_sweeps += 1;
+        HIPCHK(launch_csr_norm2(n, W, part, stream));
+        HIPCHK(launch_finalize(part, nwg, red, stream));
+        HIPCHK(launch_gm_begin(gm_S, red, stream));   // beta = ||z||; if (beta <= tol) return
+        const bool all_done = poll();
+        if (first) {
+            HIPCHK(hipMemcpyAsync(U, X, sizeof(double2) * n_local, hipMemcpyDeviceToDevice, stream));
+            first = false;
+        }
+        if (all_done) {
+            converged = true;
+            break;
+        }
+        HIPCHK(launch_gm_divide(V(0), W, gm_S, n_owned, stream));   // v0 = z / beta
+        bool cycle_done = false;
+        for (int j = 0; j < GMRES_M && it_total < opt.max_inner; ++j) {
+            HIPCHK(launch_csr_product(n_owned, csr.p, csr.i, csr.vx, csr.vy, V(j), W, stream));   // w = A v_j
+            precondition_W();                                                                     // z = M^-1 w (GMRES.zig:339-340)
+            st.operator_sweeps += 1;
+            HIPCHK(launch_gm_mgs(W, nullptr, V(0), nullptr, gm_S, 0, n_owned, partials, stream));
+            reduce(nwg_vec);
+            for (int i = 1; i <= j; ++i) {
+                HIPCHK(launch_gm_mgs(W, V(i - 1), V(i), red, gm_S, i - 1, n_owned, partials, stream));
+                reduce(nwg_vec);
+            }
+            HIPCHK(launch_gm_mgs(W, V(j), nullptr, red, gm_S, j, n_owned, partials, stream));
+            reduce(nwg_vec);
+            HIPCHK(launch_gm_column(gm_S, red, stream));
+            HIPCHK(launch_gm_divide(V(j + 1), W, gm_S, n_owned, stream));
+            it_total += 1;
+            if ((j + 1) % static_cast<int>(opt.check_every) == 0 || j + 1 == GMRES_M || it_total == opt.max_inner) {
+                if (poll()) {
+                    cycle_done = true;
+                    break;
+                }
+            }
+        }
+        HIPCHK(launch_gm_backsub(gm_S, stream));
+        HIPCHK(launch_gm_update(U, gm_V, ld, gm_S, n_owned, stream));
+        if (cycle_done) {
+            converged = true;
+            break;
+        }
+    }
+    // the counts of the two solves (solver.zig:69-78): a component's columns, wherever the other one stopped
+    HIPCHK(hipMemcpyAsync(h_gm, gm_S, sizeof(GmresScalars), hipMemcpyDeviceToHost, stream));
+    sync();
+    inner_counts[0] = static_cast<uint64_t>(h_gm->iters[0]);
+    inner_counts[1] = static_cast<uint64_t>(h_gm->iters[1]);
+    st.inner_iterations += inner_counts[0] + inner_counts[1];
+
+    // residual + copy-back (smooth.zig:112-153); X becomes the new frozen field
+    HIPCHK(launch_residual_copyback(X, U, n_owned, nwg_vec, partials, stream));
+    reduce(nwg_vec);
+    HIPCHK(hipMemcpyAsync(h_red, red, sizeof(double) * MAX_PARTIALS, hipMemcpyDeviceToHost, stream));
+    sync();
+    st.last_dx2 = h_red[0];
+    st.last_dy2 = h_red[1];
+    st.last_residual = (h_red[0] + h_red[1]) * (h_red[0] + h_red[1]);   // smooth.zig:136
+    outer_done += 1;
+    return converged ? 0 : 1;
+}
+
 // Two sweeps in one pass over the interior rows: X^(k+2) = S(S(X^k)), bit-identical to two single sweeps.
 //   perimeter rows of X^(k+1)  <- perimeter-row kernel on X^k           (into M)
 //   interior rows of X^(k+2)   <- K2x2 (reads X^k and M's perimeter; leaves the first-interior ring of X^(k+1) in M)
@@ -2123,6 +2270,10 @@ void Smoother::csr_build_pattern() {
 }
 
 void Smoother::csr_release() {
+    if (!ref) csr_free();
+}
+
+void Smoother::csr_free() {
     for (void* q : {static_cast<void*>(csr.p), static_cast<void*>(csr.i), static_cast<void*>(csr.vx), static_cast<void*>(csr.vy)})
         if (q) (void)hipFree(q);
     csr.p = csr.i = nullptr;
@@ -2132,10 +2283,15 @@ void Smoother::csr_release() {
 void Smoother::csr_fill_values() {
     csr_build_pattern();
     if (!csr.p) {
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&csr.p), sizeof(int32_t) * csr.h_p.size()));
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&csr.i), sizeof(int32_t) * std::max<size_t>(1, csr.h_i.size())));
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&csr.vx), sizeof(double) * std::max<uint64_t>(1, csr.nnz)));
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&csr.vy), sizeof(double) * std::max<uint64_t>(1, csr.nnz)));
+        // (csr.p never stays set beside a null csr.vx: a failed allocation gives back what the earlier ones took)
+        if (hipMalloc(reinterpret_cast<void**>(&csr.p), sizeof(int32_t) * csr.h_p.size()) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&csr.i), sizeof(int32_t) * std::max<size_t>(1, csr.h_i.size())) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&csr.vx), sizeof(double) * std::max<uint64_t>(1, csr.nnz)) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&csr.vy), sizeof(double) * std::max<uint64_t>(1, csr.nnz)) != hipSuccess) {
+            (void)hipGetLastError();
+            csr_free();
+            throw TmError(TM_E_MEMORY, "hipMalloc failed (assembled system, " + std::to_string(csr.nnz) + " non-zeros)");
+        }
         HIPCHK(hipMemcpyAsync(csr.p, csr.h_p.data(), sizeof(int32_t) * csr.h_p.size(), hipMemcpyHostToDevice, stream));
         HIPCHK(hipMemcpyAsync(csr.i, csr.h_i.data(), sizeof(int32_t) * csr.h_i.size(), hipMemcpyHostToDevice, stream));
     }

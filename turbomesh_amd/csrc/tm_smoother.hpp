@@ -177,7 +177,8 @@ struct Smoother {
     } csr;
     void csr_build_pattern();
     void csr_fill_values();
-    void csr_release();
+    void csr_release();              // frees the device copy -- unless the handle keeps it for its lifetime (ref != nullptr)
+    void csr_free();
     void rhs_host(double* rhs_xy);
     void control_function_host(double* pq);
     void export_soa_host(int64_t block, double* x, double* y, double* p, double* q);
@@ -245,10 +246,26 @@ struct Smoother {
     GmresScalars* gm_S = nullptr;
     GmresScalars* h_gm = nullptr;
 
+    // TM_INNER_REFERENCE_GMRES: the reference's own route on the device -- the ASSEMBLED, unscaled system of every outer iteration (csr, kept
+    // for the handle's lifetime), GMRES(30) left-preconditioned with ILU(0) or the diagonal, the reference's stop test (picard_reference).
+    // Single-process handles only.
+    struct ReferenceSolve;
+    ReferenceSolve* ref = nullptr;
+    void reference_create();
+    double2* ref_b = nullptr;        // the unscaled right-hand side
+    uint64_t inner_counts[2] = {0, 0};   // inner iterations of the last outer iteration per component (tm_smoother_inner_counts)
+
    private:
     int picard_bicgstab(tm_stats& st);
     int picard_gmres(tm_stats& st);
-    int picard_solve(tm_stats& st) { return opt.inner == TM_INNER_GMRES ? picard_gmres(st) : picard_bicgstab(st); }
+    int picard_reference(tm_stats& st);
+    int picard_solve(tm_stats& st) {
+        const uint64_t before = st.inner_iterations;
+        if (opt.inner == TM_INNER_REFERENCE_GMRES) return picard_reference(st);
+        const int rc = opt.inner == TM_INNER_GMRES ? picard_gmres(st) : picard_bicgstab(st);
+        inner_counts[0] = inner_counts[1] = st.inner_iterations - before;   // both components advance together
+        return rc;
+    }
     void relax_sweeps(uint64_t n, tm_stats& st);
     void relax_pair(bool want_partials);
     std::vector<int> relax3_rows_of_owned_blocks() const;

@@ -214,9 +214,12 @@ namespace smoothing {
 enum class Preconditioner { diagonal, ilu0 };   // preconditioner.zig
 namespace solver {                              // solver.zig:10-27 + hip
 enum class Tag : int32_t { gmres = 0, bicgstab = 1, umfpack = 2, petsc = 3, hip = 4 };
+// inner strategies of the hip solver (TM_INNER_* of tm_hip.h); reference_gmres = the file's "gmres" as written: assembled system, GMRES(30) +
+// ilu0 / diagonal, the reference's tolerances
+enum Inner : int32_t { bicgstab = 0, relax = 1, mg_bicgstab = 2, auto_ = 3, gmres = 4, reference_gmres = 5 };
 struct Option {
     Tag tag = Tag::hip;
-    Preconditioner preconditioner = Preconditioner::diagonal;   // payload of gmres / bicgstab
+    Preconditioner preconditioner = Preconditioner::diagonal;   // payload of gmres / bicgstab; with hip + reference_gmres: ilu0 -> TM_OPT_PRECOND_ILU0
     int32_t inner = TM_INNER_BICGSTAB;                          // payload of hip
     double rtol = 0, atol = 0, omega = 0;
     uint64_t max_inner = 0;
@@ -272,7 +275,9 @@ struct Desc {
     }
 };
 inline tm_solver_opt toOpt(const solver::Option& o) {
-    return tm_solver_opt{static_cast<int32_t>(o.tag), o.inner, o.rtol, o.atol, o.max_inner, o.check_every, o.single_sweep ? uint32_t{TM_OPT_SINGLE_SWEEP} : 0u, o.omega};
+    return tm_solver_opt{static_cast<int32_t>(o.tag), o.inner, o.rtol, o.atol, o.max_inner, o.check_every, (o.single_sweep ? uint32_t{TM_OPT_SINGLE_SWEEP} : 0u) |
+                             ((o.tag == solver::Tag::hip && o.inner == TM_INNER_REFERENCE_GMRES && o.preconditioner == Preconditioner::ilu0) ? uint32_t{TM_OPT_PRECOND_ILU0} : 0u),
+                         o.omega};
 }
 inline tm_control_fn toControl(const wall_control_function::Algorithm& a) {
     if (a.white) return tm_control_fn{TM_CF_WHITE, 0, a.white->ds_target, a.white->theta_target};

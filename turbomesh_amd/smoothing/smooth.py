@@ -98,6 +98,12 @@ class Smoother:
         _capi.check(_capi.lib().tm_smoother_iterate(self._h, iterations, C.byref(st)))
         return st.as_dict()
 
+    def inner_counts(self):
+        """Inner iterations of the last outer iteration per component, (x, y) (tm_smoother_inner_counts)."""
+        x, y = C.c_uint64(0), C.c_uint64(0)
+        _capi.check(_capi.lib().tm_smoother_inner_counts(self._h, C.byref(x), C.byref(y)))
+        return int(x.value), int(y.value)
+
     def write(self, filename, with_control_function=True):
         """smooth.zig:396-414 system.write: the coordinates resident on the device (+ P, Q planes)."""
         from .. import output

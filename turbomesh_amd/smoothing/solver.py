@@ -34,6 +34,7 @@ class Inner(enum.IntEnum):
     relax = _capi.TM_INNER_RELAX         # one fused Jacobi elliptic sweep per outer iteration
     mg_bicgstab = _capi.TM_INNER_MG_BICGSTAB   # bicgstab, right-preconditioned by one multigrid V-cycle per block
     gmres = _capi.TM_INNER_GMRES         # Picard + restarted GMRES(30), diagonal left preconditioner (GMRES.zig:300-423 on the device)
+    reference_gmres = _capi.TM_INNER_REFERENCE_GMRES   # the reference's route as written: assembled unscaled system, GMRES(30) + ILU(0) or diagonal, its tolerances
     auto = _capi.TM_INNER_AUTO           # mg_bicgstab when the largest block has >= 100 000 nodes (>= 1000 when no connection couples the blocks) and no block's cell aspect ratio varies strongly (boundary-layer clustering), bicgstab otherwise (decided at create)
 
 
@@ -61,21 +62,33 @@ class Option:
         """The hip option that honours this one -- what `--hip file` of the front end does with the solver an input file names:
         gmres -> Inner.gmres (GMRES(30) on the device), bicgstab -> Inner.bicgstab, the direct backends (umfpack, petsc: exact solves,
         umfpack.zig:18-24) -> Inner.auto with the library's tight default tolerance.  The reference's ILU(0) preconditioner
-        (BiCGStab.zig:178-277) is a sequential recurrence with no device counterpart: the diagonal takes its place (a preconditioner
-        changes the route, not the Picard iterate).  Returns (option, note or None)."""
+        (BiCGStab.zig:178-277) is served on the assembled system -- tm_csr_solve and Inner.reference_gmres (see as_written) -- and the
+        matrix-free modes chosen here use the diagonal in its place (a preconditioner changes the route, not the Picard iterate).
+        Returns (option, note or None)."""
         if self.tag == Tag.hip:
             return self, None
         inner = {Tag.gmres: Inner.gmres, Tag.bicgstab: Inner.bicgstab}.get(self.tag, Inner.auto)
         note = None
         if self.tag in (Tag.gmres, Tag.bicgstab) and self.preconditioner == Preconditioner.ilu0:
-            note = "preconditioner ilu0 has no device counterpart: diagonal scaling is used (same Picard iterates, more inner iterations)"
+            note = ("preconditioner ilu0 has no device counterpart: diagonal scaling is used (same Picard iterates, more inner iterations); "
+                    "`--hip reference` runs the file's gmres + ilu0 as written, on the assembled system")
         elif self.tag not in (Tag.gmres, Tag.bicgstab):
             note = f"direct solver `{self.tag.name}` is served by the iterative device solve at its tight default tolerance"
         return Option.hip(inner=inner), note
 
+    def as_written(self):
+        """The hip option that runs the solver an input file names AS WRITTEN -- what `--hip reference` of the front end does: gmres with
+        ilu0 or diagonal -> Inner.reference_gmres with that preconditioner (the reference's assembled, unscaled system, its GMRES(30), its
+        tolerances: the iterates a run of the reference gives).  Every other tag has no as-written device form: what served_by_hip()
+        answers, with its note.  Returns (option, note or None)."""
+        if self.tag == Tag.gmres:
+            return Option.hip(inner=Inner.reference_gmres, preconditioner=self.preconditioner), None
+        return self.served_by_hip()
+
     def c_struct(self):
         # preconditioner: the payload of the reference's gmres / bicgstab options; with the hip tag it selects ILU(0) in the linear-solver slot
-        # (Solver / tm_csr_solve, TM_OPT_PRECOND_ILU0) -- the matrix-free smoother refuses it (no assembled matrix to factorise)
+        # (Solver / tm_csr_solve, TM_OPT_PRECOND_ILU0) and in Inner.reference_gmres -- the matrix-free inner strategies refuse it (no assembled
+        # matrix to factorise)
         ilu = 8 if (self.tag == Tag.hip and self.preconditioner == Preconditioner.ilu0) else 0
         return _capi.tm_solver_opt(int(self.tag), int(self.inner), self.rtol, self.atol, self.max_inner, self.check_every,
                                    (1 if self.single_sweep else 0) | (2 if self.eager_scalars else 0) | (4 if self.rtol_initial else 0) | ilu, self.omega)
