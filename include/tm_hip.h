@@ -367,6 +367,51 @@ int tm_smoother_control_function(tm_smoother* s, double* pq);
 int tm_export_soa(const double* xy /* ni*nj*2 */, uint64_t ni, uint64_t nj, double* x_out /* ni*nj */, double* y_out /* ni*nj */);
 int tm_smoother_export_soa(tm_smoother* s, uint64_t block, double* x, double* y, double* p, double* q);
 
+/* ------------------------------------------------------------------ mesh quality
+ * Is the mesh usable?  One read of the coordinates gives, per block and for the whole mesh: folded and degenerate cells, the
+ * scaled Jacobian with its worst cell and a histogram, corner angles, aspect ratio, edge growth and areas.  (The reference has no
+ * such report.)  Cell (i, j), 0 <= i < ni-1, 0 <= j < nj-1, has corners A = (i,j), B = (i+1,j), C = (i+1,j+1), D = (i,j+1); at each
+ * corner u = next - corner, v = previous - corner in the order A B C D.  All arithmetic IEEE fp64, nothing fused.
+ *   per corner   J = u.x*v.y - u.y*v.x;  P = (u.x*u.x + u.y*u.y) * (v.x*v.x + v.y*v.y);  s = J / sqrt(P);  c = (u.x*v.x + u.y*v.y) / sqrt(P)
+ *   cell area    a = 0.5*((C.x-A.x)*(D.y-B.y) - (D.x-B.x)*(C.y-A.y))
+ *   orientation  o = sign(sum a) over the block's cells (blocks of one mesh differ in handedness); 0 when |sum a| <= cells * 2^-53 * sum |a|,
+ *                and then everything is reported as for +1
+ *   classes      degenerate: a corner with P == 0 or a non-finite P or J;  else inverted: min over corners of o*J <= 0;  else valid
+ *   min_scaled_jacobian   min of o*s over the corners of non-degenerate cells, (worst_block, worst_i, worst_j) its cell, ties to the
+ *                lowest (block, i, j); NaN and 0, 0, 0 when every cell is degenerate
+ *   hist[k]      valid cells with k/10 <= m < (k+1)/10, m the cell's min o*s; m >= 0.9 in hist[9]; sum hist == cells - inverted - degenerate
+ *   angles       from the largest / smallest c (clamped to [-1, 1]) over corners of non-degenerate cells, acos taken once on the host
+ *   max_aspect   max over non-degenerate cells of max(li, lj) / min(li, lj), li = |AB| + |DC|, lj = |AD| + |BC|
+ *   max_growth_i / _j   max of max(l0, l1) / min(l0, l1) over pairs of consecutive edges along every grid line of that direction, boundary
+ *                lines included, pairs with a zero-length edge skipped; 1.0 with fewer than two edges along the direction.  Inside
+ *                blocks only: growth across a connection is not reported
+ *   areas        min_area / max_area: o*a over non-degenerate cells; total_area = o * sum a
+ * `total`: counts and hist summed, extremes combined, total_area summed, the worst cell the one with the smallest value,
+ * orientation the blocks' common one or 0.  A block with ni < 2 or nj < 2: TM_E_SIZE. */
+typedef struct tm_quality {              /* 208 bytes */
+    uint64_t cells, inverted, degenerate;
+    int32_t  orientation, _pad;
+    double   min_scaled_jacobian;
+    uint64_t worst_block, worst_i, worst_j;
+    double   min_angle_deg, max_angle_deg;
+    double   max_aspect, max_growth_i, max_growth_j;
+    double   min_area, max_area, total_area;
+    uint64_t hist[10];
+} tm_quality;
+
+/* host coordinates in, evaluated on the device */
+int tm_mesh_quality(const tm_mesh_desc* mesh, tm_quality* per_block /* [nblocks], may be NULL */, tm_quality* total /* may be NULL */);
+/* the same definitions evaluated on the host: no GPU touched, works in a process without a device.  Every field equals the device's
+ * bit for bit but total_area (a sum: equal within cells * 2^-53 * sum |a|) */
+int tm_mesh_quality_host(const tm_mesh_desc* mesh, tm_quality* per_block, tm_quality* total);
+/* coordinates resident in the handle; does not modify them nor any solver state.  On a handle with rank hooks the records of
+ * blocks the rank does not own are zeroed and `total` covers the OWNED blocks only: there is no all-reduce -- combine the ranks'
+ * records on the host if the whole mesh is wanted.  The buffers (a few KB of partial records, one cell plane for the field) are
+ * allocated on first use with the HIP allocator, outside a caller-provided workspace, and freed by tm_smoother_destroy. */
+int tm_smoother_quality(tm_smoother* s, tm_quality* per_block, tm_quality* total);
+/* per-cell minimum of o*s of an owned block, i fastest like the export planes: out[j*(ni-1)+i]; NaN for degenerate cells */
+int tm_smoother_quality_field(tm_smoother* s, uint64_t block, double* min_scaled_jacobian /* (ni-1)*(nj-1) */);
+
 /* ------------------------------------------------------------------ host-only planning (no GPU needed)
  * The perimeter-row table the device kernels consume, exported as CSR so it can be compared with
  * the reference's assembled rows (smooth.zig:421-921).  Only sizes/topology are read from `mesh`

@@ -17,6 +17,7 @@ import os
 import sys
 
 from . import input as tm_input
+from . import quality
 from .smoothing import smooth, solver
 
 
@@ -31,6 +32,10 @@ def main(argv=None):
     ap.add_argument("--output", help="override the output file (.xyz / .p3d: multi-block PLOT3D)")
     ap.add_argument("--until", type=float, metavar="TOL",
                     help="iterate until the scaled nonlinear residual is <= TOL (at most `iterations`, default 100) instead of a fixed count")
+    ap.add_argument("--quality", action="store_true",
+                    help="log a mesh quality report (`quality` logger: one line per block and a total) before and after smoothing")
+    ap.add_argument("--fail-on-inverted", action="store_true",
+                    help="exit non-zero when the smoothed mesh has inverted or degenerate cells (implies the quality evaluation)")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(levelname)s(%(name)s): %(message)s")
 
@@ -56,6 +61,12 @@ def main(argv=None):
     with smooth.per_iteration_log(slog.isEnabledFor(logging.INFO) and not args.until), smooth.Smoother(mesh, inp.solver, inp.wall_control_function) as sm:
         slog.info("hip solver, inner strategy: %s%s", sm.inner.name, " (chosen from the block sizes and the spread of the cells' aspect ratios)" if inp.solver.inner == solver.Inner.auto else
                   f", preconditioner: {inp.solver.preconditioner.name}" if sm.inner == solver.Inner.reference_gmres else "")
+        qlog = logging.getLogger("quality")
+        want_quality = args.quality or args.fail_on_inverted
+        if want_quality:
+            before = sm.quality()
+            if args.quality:
+                quality.log_report(qlog, mesh.names, *before, "before")
         if args.until:
             reached, stats = sm.iterate_until(args.until, iterations or 100)
             slog.info("scaled residual %.3e after %d iterations (%s)", stats["scaled_residual_rms"], stats["outer_iterations"], "reached" if reached else "NOT reached")
@@ -66,10 +77,18 @@ def main(argv=None):
             slog.info("elapsed time for smoothing: %.2f s", stats["seconds"])
         sm.download()
         stats["inner"] = sm.inner.name
+        if want_quality:
+            after = sm.quality()
+            if args.quality:
+                quality.log_report(qlog, mesh.names, *after, "after")
+            stats["quality"] = {"before": before, "after": after}
     out = args.output or inp.output
     if out:
         mesh.write(out)
         logging.getLogger("output").info("wrote %s (%d blocks, %d nodes)", out, len(mesh.blocks), sum(b.points.data.shape[0] * b.points.data.shape[1] for b in mesh.blocks))
+    if args.fail_on_inverted and not after[1].ok:
+        sys.exit(f"mesh quality: {after[1].inverted} inverted and {after[1].degenerate} degenerate cells after smoothing "
+                 f"(worst: block {after[1].worst_block}, i {after[1].worst_i}, j {after[1].worst_j})")
     return stats
 
 

@@ -109,6 +109,14 @@ class tm_rccl_peer_table(C.Structure):
                 ("recv_off", C.POINTER(C.c_int64)), ("recv_cnt", C.POINTER(C.c_int64))]
 
 
+class tm_quality(C.Structure):
+    _fields_ = [("cells", C.c_uint64), ("inverted", C.c_uint64), ("degenerate", C.c_uint64), ("orientation", C.c_int32), ("_pad", C.c_int32),
+                ("min_scaled_jacobian", C.c_double), ("worst_block", C.c_uint64), ("worst_i", C.c_uint64), ("worst_j", C.c_uint64),
+                ("min_angle_deg", C.c_double), ("max_angle_deg", C.c_double), ("max_aspect", C.c_double), ("max_growth_i", C.c_double),
+                ("max_growth_j", C.c_double), ("min_area", C.c_double), ("max_area", C.c_double), ("total_area", C.c_double),
+                ("hist", C.c_uint64 * 10)]
+
+
 # every symbol include/tm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "tm_last_error", "tm_abi_version", "tm_set_log", "tm_csr_solve", "tm_tfi_block", "tm_tfi_linear2d", "tm_smooth_mesh", "tm_smoother_create",
@@ -117,7 +125,7 @@ EXPORTS = [
     "tm_smoother_control_function", "tm_smoother_profile", "tm_smoother_profile_read", "tm_plan_build", "tm_plan_free", "tm_plan_local", "tm_plan_local_free", "tm_dev_tfi_block", "tm_dev_relax_sweep",
     "tm_dev_relax_partials_needed", "tm_export_soa", "tm_smoother_export_soa", "tm_rccl_unique_id", "tm_rccl_comm_create", "tm_rccl_comm_destroy", "tm_rccl_hooks",
     "tm_rccl_peer_table_build", "tm_rccl_peer_table_free", "tm_white_math_probe", "tm_stream_probe", "tm_smoother_queue_ordering", "tm_smoother_inner", "tm_csr_ilu0_probe", "tm_rccl_hooks_for", "tm_smoother_assemble_csr", "tm_smoother_apply_reference_order",
-    "tm_smoother_inner_counts",
+    "tm_smoother_inner_counts", "tm_mesh_quality", "tm_mesh_quality_host", "tm_smoother_quality", "tm_smoother_quality_field",
 ]
 
 _lib = None
@@ -197,6 +205,10 @@ def lib():
         L.tm_plan_free.restype = None
         L.tm_export_soa.argtypes = [_dp, C.c_uint64, C.c_uint64, _dp, _dp]
         L.tm_smoother_export_soa.argtypes = [C.c_void_p, C.c_uint64, _dp, _dp, _dp, _dp]
+        L.tm_mesh_quality.argtypes = [C.POINTER(tm_mesh_desc), C.POINTER(tm_quality), C.POINTER(tm_quality)]
+        L.tm_mesh_quality_host.argtypes = [C.POINTER(tm_mesh_desc), C.POINTER(tm_quality), C.POINTER(tm_quality)]
+        L.tm_smoother_quality.argtypes = [C.c_void_p, C.POINTER(tm_quality), C.POINTER(tm_quality)]
+        L.tm_smoother_quality_field.argtypes = [C.c_void_p, C.c_uint64, _dp]
         L.tm_rccl_unique_id.argtypes = [C.c_char_p, C.c_void_p]
         L.tm_rccl_comm_create.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.tm_rccl_comm_destroy.argtypes = [C.c_void_p]

@@ -10,6 +10,7 @@ using namespace tmh;
 
 #include "tm_api_util.hpp"
 #include "tm_ilu.hpp"
+#include "tm_quality_dev.hpp"
 
 static void require_gfx950() {
     static int checked = 0;
@@ -448,6 +449,50 @@ int tm_export_soa(const double* xy, uint64_t ni, uint64_t nj, double* x_out, dou
         HIPCHK(launch_soa_planes(in.as<double2>(), out.as<double>(), out.as<double>() + n, static_cast<int>(ni), static_cast<int>(nj), nullptr));
         HIPCHK(hipMemcpy(x_out, out.p, sizeof(double) * n, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(y_out, out.as<double>() + n, sizeof(double) * n, hipMemcpyDeviceToHost));
+        return TM_OK;
+    });
+}
+
+// ------------------------------------------------------------------ mesh quality (tm_quality.hip; tm_mesh_quality_host: tm_quality_host.cpp)
+int tm_mesh_quality(const tm_mesh_desc* mesh, tm_quality* per_block, tm_quality* total) {
+    return guarded([&]() {
+        if (!mesh || !mesh->blocks || mesh->nblocks == 0) throw TmError(TM_E_ARG, "mesh description without blocks");
+        size_t bytes = 0;
+        for (uint64_t b = 0; b < mesh->nblocks; ++b) {
+            const tm_block& k = mesh->blocks[b];
+            if (!k.xy) throw TmError(TM_E_ARG, "block without coordinates");
+            if (k.ni < 2 || k.nj < 2 || k.ni * k.nj >= (uint64_t{1} << 31)) throw TmError(TM_E_SIZE, "InconsistentSize: a block needs at least 2 x 2 nodes (and fewer than 2^31)");
+            bytes += sizeof(double2) * k.ni * k.nj;
+        }
+        require_gfx950();
+        DevBuf xy(bytes);
+        std::vector<QualityBlock> blocks;
+        size_t off = 0;
+        for (uint64_t b = 0; b < mesh->nblocks; ++b) {
+            const tm_block& k = mesh->blocks[b];
+            HIPCHK(hipMemcpy(xy.as<double2>() + off, k.xy, sizeof(double2) * k.ni * k.nj, hipMemcpyHostToDevice));
+            blocks.push_back(QualityBlock{xy.as<double2>() + off, static_cast<int>(k.ni), static_cast<int>(k.nj), b});
+            off += k.ni * k.nj;
+        }
+        QualityDev dev;
+        std::vector<tm_quality> rec(blocks.size());
+        dev.run(blocks, nullptr, rec.data());
+        if (per_block) std::memcpy(per_block, rec.data(), sizeof(tm_quality) * rec.size());
+        if (total) quality_total(rec.data(), rec.size(), total);
+        return TM_OK;
+    });
+}
+int tm_smoother_quality(tm_smoother* s, tm_quality* per_block, tm_quality* total) {
+    return guarded([&]() {
+        if (!s) throw TmError(TM_E_ARG, "null handle");
+        s->impl.quality_host(per_block, total);
+        return TM_OK;
+    });
+}
+int tm_smoother_quality_field(tm_smoother* s, uint64_t block, double* min_scaled_jacobian) {
+    return guarded([&]() {
+        if (!s || !min_scaled_jacobian) throw TmError(TM_E_ARG, "null argument");
+        s->impl.quality_field_host(static_cast<int64_t>(block), min_scaled_jacobian);
         return TM_OK;
     });
 }

@@ -9,6 +9,7 @@
 //   TM_INNER_RELAX     every outer iteration is one fused Jacobi sweep of the nonlinear system.
 #include "tm_smoother.hpp"
 #include "tm_ilu.hpp"
+#include "tm_quality_dev.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -155,6 +156,7 @@ Smoother::~Smoother() {
         (void)hipStreamDestroy(side);
     }
     if (export_buf) (void)hipFree(export_buf);
+    delete qdev;
     delete ref;
     ref = nullptr;
     csr_free();

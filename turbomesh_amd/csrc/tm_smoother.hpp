@@ -44,6 +44,8 @@ class DeviceArena {
     bool external_ = false, measure_ = false;
 };
 
+struct QualityDev;
+
 struct Smoother {
     Smoother() = default;
     ~Smoother();
@@ -184,6 +186,11 @@ struct Smoother {
     void export_soa_host(int64_t block, double* x, double* y, double* p, double* q);
     void* export_buf = nullptr;     // scratch planes of export_soa_host (hipMalloc, grown on demand)
     size_t export_bytes = 0;
+    // mesh quality report of the resident coordinates (tm_quality.hip): reads X only; its buffers (a few KB of records, one cell plane
+    // for the field) are hipMalloc'ed on first use OUTSIDE the arena, so a caller-provided workspace is sized as before
+    QualityDev* qdev = nullptr;
+    void quality_host(tm_quality* per_block, tm_quality* total);
+    void quality_field_host(int64_t block, double* out);
 
     // building blocks
     void exchange(double2* vec, hipStream_t on = nullptr);   // start (and, without a split hook, finish) the halo exchange of `vec`; on = the handle's stream unless given

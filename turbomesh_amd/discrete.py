@@ -111,3 +111,9 @@ class Mesh:
         from . import output
 
         output.write_mesh(self, filename)
+
+    def quality(self, host=False):
+        """(per_block, total) quality records of the coordinates (turbomesh_amd/quality.py); host=True: on the CPU."""
+        from . import quality
+
+        return quality.mesh(self, host=host)

@@ -225,6 +225,13 @@ int main(int argc, char** argv) {
             else std::printf("info(smoothing): \tresidual: %.17g\n", v);
         }, nullptr);
         tm_stats st{};
+        auto report = [](const char* stage, const tm_quality& q) {
+            std::printf("info(quality): %s: cells %llu inverted %llu degenerate %llu min scaled jacobian %.4f at (block %llu, i %llu, j %llu) angles %.2f..%.2f deg max aspect %.1f\n",
+                        stage, static_cast<unsigned long long>(q.cells), static_cast<unsigned long long>(q.inverted), static_cast<unsigned long long>(q.degenerate),
+                        q.min_scaled_jacobian, static_cast<unsigned long long>(q.worst_block), static_cast<unsigned long long>(q.worst_i),
+                        static_cast<unsigned long long>(q.worst_j), q.min_angle_deg, q.max_angle_deg, q.max_aspect);
+        };
+        report("seed", mesh.quality().total);   // Mesh::quality: host coordinates, evaluated on the device
         if (until > 0.0 || !plot3d.empty()) {
             smoothing::smooth::Smoother sm(mesh, opt, smoothing::wall_control_function::Algorithm::laplace());
             if (until > 0.0) {
@@ -233,10 +240,12 @@ int main(int argc, char** argv) {
             } else {
                 st = sm.iterate(iterations);
             }
+            report("smoothed", sm.quality().total);   // Smoother::quality: the coordinates resident in the handle
             sm.download();
             if (!plot3d.empty()) sm.write(plot3d);
         } else {
             st = smoothing::smooth::mesh(mesh, iterations, opt, smoothing::wall_control_function::Algorithm::laplace());
+            report("smoothed", mesh.quality().total);
         }
         tm_set_log(nullptr, nullptr);
         std::printf("info(smoothing): elapsed time for smoothing: %.2f s\n", st.seconds);   // smooth.zig:159

@@ -198,6 +198,10 @@ struct Block2d {       // :138-164
         return b;
     }
 };
+struct Quality {       // mesh quality report (tm_hip.h "mesh quality"): one record per block and the total
+    std::vector<tm_quality> per_block;
+    tm_quality total{};
+};
 struct Mesh {          // :166-195
     std::vector<Block2d> blocks;
     std::vector<std::string> names;
@@ -207,6 +211,9 @@ struct Mesh {          // :166-195
         blocks.push_back(std::move(block));
         names.push_back(name);
     }
+    // folded / degenerate cells, scaled Jacobian, angles, aspect, growth, areas of the coordinates as they stand: evaluated on the
+    // device (tm_mesh_quality) or, host = true, by the same definitions on the CPU (tm_mesh_quality_host)
+    Quality quality(bool host = false);
 };
 }  // namespace discrete
 
@@ -323,6 +330,13 @@ class Smoother {
         return rc == TM_OK;
     }
     void download() { check(tm_smoother_download(h_, &d_.desc)); }
+    // quality report of the coordinates resident in the handle (reads them only)
+    discrete::Quality quality() {
+        discrete::Quality q;
+        q.per_block.resize(mesh_.blocks.size());
+        check(tm_smoother_quality(h_, q.per_block.data(), &q.total));
+        return q;
+    }
     // multi-block PLOT3D grid file (planes transposed on the device); `.cgns` needs the cgns library like the reference
     void write(const std::string& filename) {
         detail::requirePlot3d(filename);
@@ -350,6 +364,13 @@ class Smoother {
 }  // namespace smoothing
 
 namespace discrete {
+inline Quality Mesh::quality(bool host) {
+    smoothing::smooth::Desc d(*this);
+    Quality q;
+    q.per_block.resize(blocks.size());
+    check((host ? tm_mesh_quality_host : tm_mesh_quality)(&d.desc, q.per_block.data(), &q.total));
+    return q;
+}
 // Mesh.write (discrete.zig:197-216): one plane per coordinate with i fastest (cgns.zig:75-104), transposed on the device
 inline void write(const Mesh& m, const std::string& filename) {
     smoothing::smooth::detail::requirePlot3d(filename);

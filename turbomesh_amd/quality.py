@@ -1,0 +1,74 @@
+"""Mesh quality report: folded / degenerate cells, scaled Jacobian (worst cell, histogram), corner angles, aspect ratio, edge
+growth and areas, per block and for the whole mesh (include/tm_hip.h, "mesh quality"; the reference has no such report).
+
+`mesh(m)` evaluates on the MI355X (tm_mesh_quality), `mesh(m, host=True)` the same definitions on the CPU
+(tm_mesh_quality_host: no GPU needed, every field but the summed total_area equal bit for bit).  A `Smoother` reports on the
+coordinates resident in its handle (`Smoother.quality()`, `Smoother.quality_field(block)`)."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import List, Tuple
+
+from . import _capi
+
+
+@dataclass
+class Quality:
+    """tm_quality as a record."""
+
+    cells: int
+    inverted: int
+    degenerate: int
+    orientation: int           # +1 / -1: handedness of the block (sign of the summed cell areas); 0: none, or blocks differ (total)
+    min_scaled_jacobian: float
+    worst_block: int
+    worst_i: int
+    worst_j: int
+    min_angle_deg: float
+    max_angle_deg: float
+    max_aspect: float
+    max_growth_i: float
+    max_growth_j: float
+    min_area: float
+    max_area: float
+    total_area: float
+    hist: Tuple[int, ...]      # valid cells by min scaled Jacobian, bins [k/10, (k+1)/10)
+
+    @classmethod
+    def from_struct(cls, q: "_capi.tm_quality") -> "Quality":
+        return cls(int(q.cells), int(q.inverted), int(q.degenerate), int(q.orientation), float(q.min_scaled_jacobian), int(q.worst_block),
+                   int(q.worst_i), int(q.worst_j), float(q.min_angle_deg), float(q.max_angle_deg), float(q.max_aspect), float(q.max_growth_i),
+                   float(q.max_growth_j), float(q.min_area), float(q.max_area), float(q.total_area), tuple(int(h) for h in q.hist))
+
+    @property
+    def ok(self) -> bool:
+        return self.inverted == 0 and self.degenerate == 0
+
+    def line(self, name: str) -> str:
+        """One log line: name, cells, inverted, degenerate, min scaled Jacobian with its cell, angle range, max aspect, growth."""
+        return (f"{name}: cells {self.cells} inverted {self.inverted} degenerate {self.degenerate} "
+                f"min scaled jacobian {self.min_scaled_jacobian:.4f} at (block {self.worst_block}, i {self.worst_i}, j {self.worst_j}) "
+                f"angles {self.min_angle_deg:.2f}..{self.max_angle_deg:.2f} deg max aspect {self.max_aspect:.1f} "
+                f"max growth i {self.max_growth_i:.3f} j {self.max_growth_j:.3f}")
+
+
+def records(per_block, total) -> Tuple[List[Quality], Quality]:
+    return [Quality.from_struct(q) for q in per_block], Quality.from_struct(total)
+
+
+def mesh(mesh_data, host: bool = False) -> Tuple[List[Quality], Quality]:
+    """(per_block, total) of a discrete.Mesh; host=True evaluates on the CPU."""
+    md = _capi.MeshDesc(mesh_data)
+    per_block = (_capi.tm_quality * max(1, len(mesh_data.blocks)))()
+    total = _capi.tm_quality()
+    fn = _capi.lib().tm_mesh_quality_host if host else _capi.lib().tm_mesh_quality
+    _capi.check(fn(md.ref(), per_block, C.byref(total)))
+    return records(per_block[:len(mesh_data.blocks)], total)
+
+
+def log_report(logger, names, per_block, total, stage):
+    """One line per block and a total, on `logger` at INFO; every line starts with `stage` ("before" / "after")."""
+    for name, q in zip(names, per_block):
+        logger.info("%s", q.line(f"{stage} {name}"))
+    logger.info("%s", total.line(f"{stage} total"))

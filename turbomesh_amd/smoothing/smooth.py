@@ -110,6 +110,36 @@ class Smoother:
 
         output.write_smoother(self, filename, with_control_function)
 
+    def quality(self):
+        """(per_block, total) quality records of the coordinates resident in the handle (tm_smoother_quality): reads them only.
+        On a handle with rank hooks the records of other ranks' blocks are zero and `total` covers the owned blocks."""
+        from .. import quality
+
+        n = len(self._mesh.blocks)
+        per_block = (_capi.tm_quality * max(1, n))()
+        total = _capi.tm_quality()
+        _capi.check(_capi.lib().tm_smoother_quality(self._h, per_block, C.byref(total)))
+        return quality.records(per_block[:n], total)
+
+    def quality_field(self, block: int):
+        """Per-cell minimum of the oriented scaled Jacobian of an owned block as an (ni-1, nj-1) array indexed [i, j]; NaN where a
+        cell is degenerate (tm_smoother_quality_field hands back the plane with i fastest, like the export planes)."""
+        ni, nj = self._mesh.blocks[block].points.size
+        plane = np.empty((ni - 1) * (nj - 1), dtype=np.float64)
+        _capi.check(_capi.lib().tm_smoother_quality_field(self._h, block, _capi.f64ptr(plane)))
+        return plane.reshape(nj - 1, ni - 1).T
+
+    def write_quality(self, filename):
+        """The per-cell planes of every block as a PLOT3D function file (one variable, sizes (ni-1, nj-1))."""
+        from .. import output
+
+        sizes, fields = [], []
+        for b, blk in enumerate(self._mesh.blocks):
+            ni, nj = blk.points.size
+            sizes.append((ni - 1, nj - 1))
+            fields.append([np.ascontiguousarray(self.quality_field(b).T).reshape(-1)])
+        output.write_plot3d_function(filename, sizes, fields)
+
     def iterate_until(self, scaled_residual_tol: float, max_iterations: int = 1000):
         """Iterate until the scaled nonlinear residual is <= tol.  Returns (reached, stats)."""
         st = _capi.tm_stats()
