@@ -44,6 +44,31 @@ int tm_csr_ilu0_probe(uint64_t n, const int32_t* Ap, const int32_t* Ai, const do
  *    3  events: the self-test found both streams on one hardware queue */
 int tm_smoother_queue_ordering(const tm_smoother* s);
 
+/* ---- The multigrid preconditioner of TM_INNER_MG_BICGSTAB as an operator (tests/test_gpu_mg_operator.py pins it against a host reference). */
+
+/* Diagnostic: ONE of the four stand-alone multigrid transfer kernels on host arrays, launched the way the cycle launches it (grid capping
+ * included).  Interleaved x,y arrays, node (i,j) at i*nj + j.  The fine level has nif x njf nodes; a direction with its flag set is
+ * coarsened to n/2 + 1 nodes, the other keeps its size.
+ *   kind 0  injection      in = fine,            out = coarse (every node written):  out = (scale_x, scale_y) * in(min(2c, n-1))
+ *   kind 1  restriction    in = fine residual,   x_coarse = coarse coordinates, out = coarse right-hand side: interior nodes written, the
+ *                          perimeter keeps what the caller put there
+ *   kind 2  prolong-add    in = coarse,          out = fine, read and written (interior nodes)
+ *   kind 3  scale          in = fine,            out = fine: scale_x * in on interior nodes, 0 on the perimeter (the flags are ignored) */
+int tm_mg_transfer_probe(int32_t kind, uint64_t nif, uint64_t njf, int32_t ci, int32_t cj, const double* in, const double* x_coarse /* kind 1 */,
+                         double scale_x, double scale_y, double* out);
+
+/* Diagnostic: the level hierarchy and the cycle a TM_INNER_MG_BICGSTAB handle uses for one owned block.  shape[4 l + 0..3] = ni, nj, ci, cj of
+ * level l (ci / cj: coarsened from the next finer level in i / j; 0 on level 0) for l < min(*nlevels, capacity);
+ * cycle[0..5] = nu_pre, nu_post, nu_coarsest, mg_dirichlet, mg_perimeter_step, mg_perimeter_sweeps.  TM_E_UNSUPPORTED without multigrid. */
+int tm_smoother_mg_levels(const tm_smoother* s, uint64_t block, int32_t* nlevels, int32_t* shape, uint32_t capacity, int32_t* cycle, double* omega);
+
+/* Diagnostic: z = M^-1 f, one application of the handle's preconditioner (Smoother::precondition) for the coordinates (and P,Q) resident in
+ * the handle: the level hierarchy is refreshed from them as an outer iteration does in front of its solve (P,Q are taken as they stand),
+ * no solve runs and no coordinate moves.  f, z, f_after: interleaved x,y in the handle's local node order (tm_smoother_dof nodes);
+ * f_after (may be NULL) receives the device's input buffer as it stands after the application.  Single-process handles;
+ * TM_E_UNSUPPORTED without multigrid. */
+int tm_smoother_precondition_probe(tm_smoother* s, const double* f, double* z, double* f_after);
+
 #ifdef __cplusplus
 }
 #endif

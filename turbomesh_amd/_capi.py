@@ -126,6 +126,7 @@ EXPORTS = [
     "tm_dev_relax_partials_needed", "tm_export_soa", "tm_smoother_export_soa", "tm_rccl_unique_id", "tm_rccl_comm_create", "tm_rccl_comm_destroy", "tm_rccl_hooks",
     "tm_rccl_peer_table_build", "tm_rccl_peer_table_free", "tm_white_math_probe", "tm_stream_probe", "tm_smoother_queue_ordering", "tm_smoother_inner", "tm_csr_ilu0_probe", "tm_rccl_hooks_for", "tm_smoother_assemble_csr", "tm_smoother_apply_reference_order",
     "tm_smoother_inner_counts", "tm_mesh_quality", "tm_mesh_quality_host", "tm_smoother_quality", "tm_smoother_quality_field",
+    "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe",
 ]
 
 _lib = None
@@ -226,6 +227,9 @@ def lib():
         L.tm_rccl_peer_table_free.restype = None
         L.tm_white_math_probe.argtypes = [_dp, _dp, C.c_uint64, _dp, _dp]
         L.tm_stream_probe.argtypes = [C.c_uint64, C.c_int32, _dp, _dp]
+        L.tm_mg_transfer_probe.argtypes = [C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, _dp, _dp, C.c_double, C.c_double, _dp]
+        L.tm_smoother_mg_levels.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_int32), _dp]
+        L.tm_smoother_precondition_probe.argtypes = [C.c_void_p, _dp, _dp, _dp]
         if hasattr(L, "tm_tune_apply"):   # measurement build (TM_HIP_LIB=.../libtm_hip_dbg.so, tools/)
             L.tm_debug_null_hooks.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(tm_comm_hooks)]
             L.tm_diag_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]

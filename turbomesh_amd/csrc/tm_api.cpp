@@ -204,6 +204,38 @@ int tm_white_math_probe(const double* x, const double* y, uint64_t n, double* ou
     });
 }
 
+// diagnostic (include/tm_hip_diag.h, tests/test_gpu_mg_operator.py): one stand-alone multigrid transfer kernel on host arrays, through the
+// launch_mg_* functions the cycle uses
+int tm_mg_transfer_probe(int32_t kind, uint64_t nif64, uint64_t njf64, int32_t ci, int32_t cj, const double* in, const double* x_coarse, double scale_x,
+                         double scale_y, double* out) {
+    return guarded([&]() {
+        if (!in || !out || (kind == 1 && !x_coarse)) throw TmError(TM_E_ARG, "null argument");
+        if (kind < 0 || kind > 3) throw TmError(TM_E_ARG, "kind must be 0 (inject), 1 (restrict), 2 (prolong-add) or 3 (scale)");
+        if (nif64 < 3 || njf64 < 3 || nif64 * njf64 >= (uint64_t{1} << 31)) throw TmError(TM_E_SIZE, "a level needs at least 3 x 3 nodes (and fewer than 2^31)");
+        require_gfx950();
+        MgPair g;
+        g.nif = static_cast<int>(nif64);
+        g.njf = static_cast<int>(njf64);
+        g.ci = (kind != 3 && ci) ? 1 : 0;
+        g.cj = (kind != 3 && cj) ? 1 : 0;
+        g.nic = g.ci ? g.nif / 2 + 1 : g.nif;
+        g.njc = g.cj ? g.njf / 2 + 1 : g.njf;
+        const size_t nf = sizeof(double2) * static_cast<size_t>(g.nif) * g.njf, nc = sizeof(double2) * static_cast<size_t>(g.nic) * g.njc;
+        const bool in_fine = kind != 2, out_fine = kind >= 2;
+        DevBuf din(in_fine ? nf : nc), dout(out_fine ? nf : nc), dx(kind == 1 ? nc : 0);
+        HIPCHK(hipMemcpy(din.p, in, in_fine ? nf : nc, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dout.p, out, out_fine ? nf : nc, hipMemcpyHostToDevice));   // (what a kernel leaves alone comes back as it went in)
+        if (kind == 1) HIPCHK(hipMemcpy(dx.p, x_coarse, nc, hipMemcpyHostToDevice));
+        if (kind == 0) HIPCHK(launch_mg_inject(din.as<double2>(), dout.as<double2>(), g, scale_x, scale_y, nullptr));
+        else if (kind == 1) HIPCHK(launch_mg_restrict(din.as<double2>(), dx.as<double2>(), dout.as<double2>(), g, nullptr));
+        else if (kind == 2) HIPCHK(launch_mg_prolong_add(din.as<double2>(), dout.as<double2>(), g, nullptr));
+        else HIPCHK(launch_mg_scale(din.as<double2>(), dout.as<double2>(), g.nif, g.njf, scale_x, nullptr));
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(out, dout.p, out_fine ? nf : nc, hipMemcpyDeviceToHost));
+        return TM_OK;
+    });
+}
+
 int tm_tfi_block(double* xy_out, uint64_t ni, uint64_t nj, const double* x_i_min, const double* x_i_max, const double* x_j_min,
                  const double* x_j_max, const double* s1, const double* s2, const double* t1, const double* t2) {
     return guarded([&]() {
@@ -523,6 +555,43 @@ int tm_smoother_inner_counts(const tm_smoother* s, uint64_t* x_iterations, uint6
         if (!s || !x_iterations || !y_iterations) throw TmError(TM_E_ARG, "null argument");
         *x_iterations = s->impl.inner_counts[0];
         *y_iterations = s->impl.inner_counts[1];
+        return TM_OK;
+    });
+}
+
+// the multigrid preconditioner as an operator (include/tm_hip_diag.h)
+int tm_smoother_mg_levels(const tm_smoother* s, uint64_t block, int32_t* nlevels, int32_t* shape, uint32_t capacity, int32_t* cycle, double* omega) {
+    return guarded([&]() {
+        if (!s || !nlevels) throw TmError(TM_E_ARG, "null argument");
+        const Smoother& m = s->impl;
+        if (!m.use_mg) throw TmError(TM_E_UNSUPPORTED, "tm_smoother_mg_levels needs a handle created with TM_INNER_MG_BICGSTAB");
+        const auto it = std::lower_bound(m.lp.owned_blocks.begin(), m.lp.owned_blocks.end(), static_cast<int64_t>(block));
+        if (it == m.lp.owned_blocks.end() || *it != static_cast<int64_t>(block)) throw TmError(TM_E_ARG, "block is not owned by this rank");
+        const BlockMG& h = m.mg[static_cast<size_t>(it - m.lp.owned_blocks.begin())];
+        const std::vector<MgLevel>& L = h.levels();
+        *nlevels = static_cast<int32_t>(L.size());
+        for (size_t l = 0; shape && l < L.size() && l < capacity; ++l) {
+            shape[4 * l + 0] = L[l].ni;
+            shape[4 * l + 1] = L[l].nj;
+            shape[4 * l + 2] = L[l].ci;
+            shape[4 * l + 3] = L[l].cj;
+        }
+        if (cycle) {
+            cycle[0] = h.nu_pre;
+            cycle[1] = h.nu_post;
+            cycle[2] = h.nu_coarsest;
+            cycle[3] = m.mg_dirichlet ? 1 : 0;
+            cycle[4] = m.mg_perimeter_step ? 1 : 0;
+            cycle[5] = m.mg_perimeter_sweeps;
+        }
+        if (omega) *omega = h.omega;
+        return TM_OK;
+    });
+}
+int tm_smoother_precondition_probe(tm_smoother* s, const double* f, double* z, double* f_after) {
+    return guarded([&]() {
+        if (!s || !f || !z) throw TmError(TM_E_ARG, "null argument");
+        s->impl.precondition_probe_host(f, z, f_after);
         return TM_OK;
     });
 }

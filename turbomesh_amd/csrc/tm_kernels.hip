@@ -346,6 +346,16 @@ __device__ __forceinline__ void apply_tile(const ApplyBlock& a, int RI, int nSG,
             h = make_double2(0.0, 0.0);   // NOT `h = c`: that copy would force a vmcnt(0) wait right behind every row load
             if (edge_lane) h = rp[hcol];
         };
+        // MODE_MG_FIRST2: `in` is f and stands for e1 = omega f, an iterate: zero on the perimeter, whatever f itself holds there (the
+        // perimeter residuals of a coupled mesh: Smoother::precondition)
+        auto load_in = [&](int row, double2& c, double2& h) {
+            load_row(a.in, row, c, h);
+            if (MODE == MODE_MG_FIRST2) {
+                const bool prow = (row <= 0) || (row >= ni - 1);
+                if (prow || j <= 0 || j >= nj - 1) c = make_double2(0.0, 0.0);
+                if (prow || hcol <= 0 || hcol >= nj - 1) h = make_double2(0.0, 0.0);
+            }
+        };
         // 3-row window of the vector, rotating by index: slot (r % 3) holds row i0-1+r as (value, e = right - left, h = right + left)
         double2 Wc[3], We[3], Wh[3];
         double2 Xc[3], Xdet = make_double2(0.0, 0.0);   // frozen coordinates when they are a different array; Xdet of the centre row
@@ -406,8 +416,8 @@ __device__ __forceinline__ void apply_tile(const ApplyBlock& a, int RI, int nSG,
         };
         {
             double2 h0, h1;
-            load_row(a.in, i0 - 1, Wc[0], h0);
-            load_row(a.in, i0, Wc[1], h1);
+            load_in(i0 - 1, Wc[0], h0);
+            load_in(i0, Wc[1], h1);
             if (VK == VK_PRO) {
                 double2 a0, b0, a1, b1, c0, d0, c1, d1;
                 load_coarse(i0 - 1, 0, a0, b0);
@@ -467,7 +477,7 @@ __device__ __forceinline__ void apply_tile(const ApplyBlock& a, int RI, int nSG,
                     g.pc[u] = Wc[1];
                     g.ph[u] = Wh[1];
                 } else
-                    load_row(a.in, prow, g.pc[u], g.ph[u]);
+                    load_in(prow, g.pc[u], g.ph[u]);
                 if (VK == VK_PRO) {   // the two coarse rows of this fine row (qc/qh: ci0, zc/zh: ci1)
                     load_coarse(prow, 0, g.qc[u], g.qh[u]);
                     load_coarse(prow, 1, g.zc[u], g.zh[u]);
@@ -1250,6 +1260,9 @@ __device__ __forceinline__ void mg_pair_strip(const MgPairArgs& a, const Relax2T
         }
     };
     auto entering = [&](int row, const Ld& L) {   // the value of `in` at (row, this lane's column) as stage 1 sees it
+        // PRE: the implicit first sweep e1 = omega f is an iterate, zero on the perimeter -- whatever f itself holds there (the perimeter
+        // residuals of a coupled mesh: Smoother::precondition) must not reach the stencil of the first ring
+        if (KIND == 1) return (col_in && row >= 1 && row <= ni - 2) ? L.in : zero;
         if (!PRO) return L.in;
         // k_mg_prolong_add's expression 0.25 ((a + b) + (c + d)), a = (ci0, cj0), b = (ci0, cj1), c = (ci1, cj0), d = (ci1, cj1);
         // coinciding indices just repeat a value.  Shifts with every lane active, then the selects.

@@ -45,6 +45,7 @@ class BlockMG {
     // z = V-cycle(f).  w0, w1: two fine scratch blocks whose perimeter is and stays zero.  z's perimeter is left zero.
     void vcycle(const double2* f, double2* z, double2* w0, double2* w1, hipStream_t stream);
     size_t nlevels() const { return L.size(); }
+    const std::vector<MgLevel>& levels() const { return L; }   // introspection (tm_smoother_mg_levels)
 
    private:
     std::vector<MgLevel> L;

@@ -1285,6 +1285,19 @@ void Smoother::precondition(const double2* in, double2* out) {
     }
 }
 
+// z = M^-1 f for host vectors (include/tm_hip_diag.h): the hierarchy refreshed from the resident field as picard_bicgstab does in front of
+// its solve, then ONE application.  p / p_hat carry nothing between iterate() calls (k_p_update selects in the first iteration of a solve).
+void Smoother::precondition_probe_host(const double* f, double* z, double* f_after) {
+    if (!use_mg) throw TmError(TM_E_UNSUPPORTED, "tm_smoother_precondition_probe needs a handle created with TM_INNER_MG_BICGSTAB");
+    if (has_hooks) throw TmError(TM_E_UNSUPPORTED, "tm_smoother_precondition_probe is available on single-process handles only");
+    for (size_t k = 0; k < lp.owned_blocks.size(); ++k) mg[k].set_field(X + lp.local_start[k], PQ ? PQ + lp.local_start[k] : nullptr, stream);
+    HIPCHK(hipMemcpyAsync(p, f, sizeof(double2) * n_owned, hipMemcpyHostToDevice, stream));
+    precondition(p, p_hat);
+    HIPCHK(hipMemcpyAsync(z, p_hat, sizeof(double2) * n_owned, hipMemcpyDeviceToHost, stream));
+    if (f_after) HIPCHK(hipMemcpyAsync(f_after, p, sizeof(double2) * n_owned, hipMemcpyDeviceToHost, stream));
+    sync();
+}
+
 // Convergence poll of the inner solve: 0 = keep iterating, 1 = both components converged, 2 = a component broke down.
 // A small mesh runs 8 iterations in ~250 us and a blocking read of the scalar block costs ~30 us of idle device: there the copy
 // is only ENQUEUED (after iteration `it`), the next iterations follow it into the queue, and the copy made at the PREVIOUS poll

@@ -78,6 +78,7 @@ struct Smoother {
     hipEvent_t mg_fork = nullptr;
     int mg_perimeter_sweeps = 2;   // passes of the perimeter rows behind the cycles: the first on (e_I, 0), the others Jacobi sweeps on the perimeter system
     void precondition(const double2* in, double2* out);
+    void precondition_probe_host(const double* f, double* z, double* f_after);   // tm_smoother_precondition_probe
     double2* M = nullptr;           // X^(k+1) of a fused pair of relax sweeps (perimeter + first-interior ring only)
     double2* M2 = nullptr;          // coupled triples: X^(k+2) on the perimeter and in the zone next to sides whose perimeter rows move
     bool fuse_pairs = false;

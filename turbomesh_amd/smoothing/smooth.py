@@ -220,6 +220,27 @@ class Smoother:
         code = int(_capi.lib().tm_smoother_queue_ordering(self._h))
         return code, self.QUEUE_ORDERING.get(code, "?")
 
+    def mg_levels(self, block: int = 0):
+        """The multigrid hierarchy and cycle of one block of an Inner.mg_bicgstab handle (tm_smoother_mg_levels): a dict with
+        `levels` = [(ni, nj, ci, cj), ...], nu_pre, nu_post, nu_coarsest, omega, dirichlet, perimeter_step, perimeter_sweeps."""
+        i32 = C.POINTER(C.c_int32)
+        n, omega = C.c_int32(0), C.c_double(0)
+        shape, cycle = np.zeros(4 * 32, dtype=np.int32), np.zeros(6, dtype=np.int32)
+        _capi.check(_capi.lib().tm_smoother_mg_levels(self._h, block, C.byref(n), shape.ctypes.data_as(i32), 32, cycle.ctypes.data_as(i32), C.byref(omega)))
+        return {"levels": [tuple(int(v) for v in shape[4 * l:4 * l + 4]) for l in range(n.value)], "nu_pre": int(cycle[0]), "nu_post": int(cycle[1]),
+                "nu_coarsest": int(cycle[2]), "omega": omega.value, "dirichlet": bool(cycle[3]), "perimeter_step": bool(cycle[4]),
+                "perimeter_sweeps": int(cycle[5])}
+
+    def precondition_probe(self, f, return_input=False):
+        """z = M^-1 f: one application of the multigrid preconditioner for the resident field (tm_smoother_precondition_probe);
+        with return_input also the device's input buffer as it stands afterwards."""
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        assert f.shape == (self.dof, 2)
+        z = np.empty_like(f)
+        after = np.empty_like(f) if return_input else None
+        _capi.check(_capi.lib().tm_smoother_precondition_probe(self._h, _capi.f64ptr(f), _capi.f64ptr(z), _capi.f64ptr(after) if return_input else None))
+        return (z, after) if return_input else z
+
     def control_function(self):
         out = np.empty((self.dof, 2))
         _capi.check(_capi.lib().tm_smoother_control_function(self._h, _capi.f64ptr(out)))
