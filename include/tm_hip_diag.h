@@ -69,6 +69,33 @@ int tm_smoother_mg_levels(const tm_smoother* s, uint64_t block, int32_t* nlevels
  * TM_E_UNSUPPORTED without multigrid. */
 int tm_smoother_precondition_probe(tm_smoother* s, const double* f, double* z, double* f_after);
 
+/* ---- The run tables of the perimeter-row launches and the strip plan of the fused level kernel (csrc/tm_edge_tables.cpp), host only: no
+ * device is touched (tests/test_edge_tables_cpu.py pins them against tm_plan_build / tm_plan_local).
+ * The rank-local plan is the one tm_plan_local reports (owner[b] = rank owning block b; single process: all 0, rank 0, nranks 1).
+ *   table 0  every perimeter row the rank owns            3  level 1 of the coupled sweep triples: the rows of table 1, the interior nodes
+ *         1  the rows that are not `fixed`                    within 4 of a side whose rows move, the depth-2 ghost rows
+ *         2  table 1 + the depth-1 ghost rows              4  level 2: ... within 3, the depth-1 ghost rows      5  level 3: ... within 2
+ * Per run r (flat arrays, malloc'ed, released by tm_edge_tables_free): row k < count[r] of the run sits at position first[r] + k of the run
+ * order and has the local id row0[r] + k row_stride[r], columns col0[9 r + q] + k col_stride[9 r + q] (q < ncols[r]) and, kind 1 (smoothed),
+ * the metric neighbours met0[4 r + q] + k met_stride[4 r + q]; gid[p] = global id of the row at position p; workgroup w serves the points
+ * wg_k0[w] .. of run wg_run[w].  Table 5 also returns the strip plan (the three level tables are built together): strip s runs the tasks
+ * strip_off[4 s + l] .. strip_off[4 s + l + 1] at level l + 1; task t = task[4 t + 0..3] = level (1..3), run of that level's table, first
+ * point, points.  level_strip = positions of a level-3 line per strip; 0 = the library's default (60). */
+typedef struct tm_edge_tables_info {
+    int64_t nrows, nruns, nwg;
+    int32_t *first, *count, *row0, *row_stride;        /* [nruns] */
+    int32_t *col0, *col_stride;                        /* [9 nruns] */
+    int32_t *met0, *met_stride;                        /* [4 nruns] */
+    int32_t *kind, *ncols, *self, *flags;              /* [nruns] */
+    int32_t *wg_run, *wg_k0;                           /* [nwg] */
+    int64_t* gid;                                      /* [nrows] */
+    int64_t nstrips, ntasks;
+    int32_t *strip_off, *task;                         /* [4 nstrips], [4 ntasks] */
+} tm_edge_tables_info;
+int tm_edge_tables_probe(const tm_mesh_desc* mesh, const int32_t* owner, int32_t rank, int32_t nranks, int32_t table, int32_t level_strip,
+                         tm_edge_tables_info* out);
+void tm_edge_tables_free(tm_edge_tables_info* info);
+
 #ifdef __cplusplus
 }
 #endif

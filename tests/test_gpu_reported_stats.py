@@ -5,7 +5,7 @@ per-workgroup partial sums and their fixed-order finalize (Smoother::reduce).
 Definitions restated on the host:
   * last_dx2 / last_dy2 = sum over the nodes the handle owns of (x_before - x_after)^2, (y...)^2.  The owned set (tm_plan.cpp: whole
     blocks, LocalPlan::n_owned = sum ni * nj) stores an interface node once per block that holds it, so the sum runs over every node of
-    every block's array -- duplicates included, ghost rows nowhere; dof (tm_smoother_dof, topology_from_desc) counts the same rows.
+    every block's array -- duplicates included, ghost rows nowhere; dof (tm_smoother_dof, topo_of) counts the same rows.
   * last_residual = (last_dx2 + last_dy2)^2, exactly (smooth.zig:136).
   * scaled_residual_rms = sqrt(||D^-1 (b - A(X) X)||^2 / (2 dof)) at the start of the last outer iteration, A and b assembled at that X by
     the faithful oracle (oracle.System, as tests/residual_check.py does), evaluated in extended precision.  Relax mode derives it from

@@ -109,6 +109,16 @@ class tm_rccl_peer_table(C.Structure):
                 ("recv_off", C.POINTER(C.c_int64)), ("recv_cnt", C.POINTER(C.c_int64))]
 
 
+_i32p = C.POINTER(C.c_int32)
+
+
+class tm_edge_tables_info(C.Structure):
+    _fields_ = ([("nrows", C.c_int64), ("nruns", C.c_int64), ("nwg", C.c_int64)] +
+                [(k, _i32p) for k in ("first", "count", "row0", "row_stride", "col0", "col_stride", "met0", "met_stride", "kind", "ncols", "self", "flags",
+                                     "wg_run", "wg_k0")] +
+                [("gid", C.POINTER(C.c_int64)), ("nstrips", C.c_int64), ("ntasks", C.c_int64), ("strip_off", _i32p), ("task", _i32p)])
+
+
 class tm_quality(C.Structure):
     _fields_ = [("cells", C.c_uint64), ("inverted", C.c_uint64), ("degenerate", C.c_uint64), ("orientation", C.c_int32), ("_pad", C.c_int32),
                 ("min_scaled_jacobian", C.c_double), ("worst_block", C.c_uint64), ("worst_i", C.c_uint64), ("worst_j", C.c_uint64),
@@ -126,7 +136,7 @@ EXPORTS = [
     "tm_dev_relax_partials_needed", "tm_export_soa", "tm_smoother_export_soa", "tm_rccl_unique_id", "tm_rccl_comm_create", "tm_rccl_comm_destroy", "tm_rccl_hooks",
     "tm_rccl_peer_table_build", "tm_rccl_peer_table_free", "tm_white_math_probe", "tm_stream_probe", "tm_smoother_queue_ordering", "tm_smoother_inner", "tm_csr_ilu0_probe", "tm_rccl_hooks_for", "tm_smoother_assemble_csr", "tm_smoother_apply_reference_order",
     "tm_smoother_inner_counts", "tm_mesh_quality", "tm_mesh_quality_host", "tm_smoother_quality", "tm_smoother_quality_field",
-    "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe",
+    "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
 ]
 
 _lib = None
@@ -230,6 +240,9 @@ def lib():
         L.tm_mg_transfer_probe.argtypes = [C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, _dp, _dp, C.c_double, C.c_double, _dp]
         L.tm_smoother_mg_levels.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_int32), _dp]
         L.tm_smoother_precondition_probe.argtypes = [C.c_void_p, _dp, _dp, _dp]
+        L.tm_edge_tables_probe.argtypes = [C.POINTER(tm_mesh_desc), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(tm_edge_tables_info)]
+        L.tm_edge_tables_free.argtypes = [C.POINTER(tm_edge_tables_info)]
+        L.tm_edge_tables_free.restype = None
         if hasattr(L, "tm_tune_apply"):   # measurement build (TM_HIP_LIB=.../libtm_hip_dbg.so, tools/)
             L.tm_debug_null_hooks.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(tm_comm_hooks)]
             L.tm_diag_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]

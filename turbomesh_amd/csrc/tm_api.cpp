@@ -681,6 +681,78 @@ void tm_plan_local_free(tm_plan_local_info* i) {
     std::memset(i, 0, sizeof(*i));
 }
 
+int tm_edge_tables_probe(const tm_mesh_desc* mesh, const int32_t* owner, int32_t rank, int32_t nranks, int32_t table, int32_t level_strip,
+                         tm_edge_tables_info* out) {
+    return guarded([&]() {
+        if (!mesh || !owner || !out) throw TmError(TM_E_ARG, "null argument");
+        if (table < 0 || table > 5 || level_strip < 0) throw TmError(TM_E_ARG, "table outside 0..5 or negative strip length");
+        std::memset(out, 0, sizeof(*out));
+        const Topology t = topo_of(mesh);
+        const std::vector<PlanRow> rows = build_rows(t);
+        const LocalPlan lp = build_local_plan(t, rows, std::vector<int32_t>(owner, owner + t.nblocks()), rank, nranks);
+        const MovingSides moving = moving_sides(t, lp);
+        std::vector<PlanRow> zone[3];
+        auto selection = [&](int tab) {
+            std::vector<const PlanRow*> sel;
+            auto add = [&](const std::vector<PlanRow>& more) {
+                for (const PlanRow& r : more) sel.push_back(&r);
+            };
+            if (tab == 0) add(lp.rows);
+            else for (size_t k : moving.nf_rows) sel.push_back(&lp.rows[k]);
+            if (tab >= 3) add(zone[tab - 3] = zone_rows(t, lp, moving.dyn_mask, tab - 3));
+            if (tab == 3) add(lp.ghost_rows2);
+            if (tab == 2 || tab == 4) add(lp.ghost_rows);
+            return sel;
+        };
+        RunTable level[3];
+        for (int tab = 3; tab < 5 && table == 5; ++tab) level[tab - 3] = build_run_table(t, lp, selection(tab));
+        const std::vector<const PlanRow*> sel = selection(table);
+        const RunTable T = build_run_table(t, lp, sel);
+        std::vector<int32_t> f[12], task;
+        for (const EdgeRun& R : T.runs) {
+            const int32_t scalars[8] = {R.first, R.count, R.row0, R.row_stride, R.kind, R.ncols, R.self, R.flags};
+            for (int q = 0; q < 8; ++q) f[q].push_back(scalars[q]);
+            f[8].insert(f[8].end(), R.col0, R.col0 + 9);
+            f[9].insert(f[9].end(), R.col_stride, R.col_stride + 9);
+            f[10].insert(f[10].end(), R.met0, R.met0 + 4);
+            f[11].insert(f[11].end(), R.met_stride, R.met_stride + 4);
+        }
+        std::vector<int64_t> gid;
+        for (int32_t k : T.order) gid.push_back(sel[k]->gid);
+        StripPlan plan;
+        if (table == 5) {
+            const std::vector<EdgeRun>* const runs[3] = {&level[0].runs, &level[1].runs, &T.runs};
+            plan = build_strip_plan(runs, T.where, level_strip ? level_strip : 60);
+            for (int s = 0; s < plan.nstrips; ++s)
+                for (int l = 0; l < 3; ++l)
+                    for (int32_t k = plan.off[4 * s + l]; k < plan.off[4 * s + l + 1]; ++k)
+                        task.insert(task.end(), {l + 1, plan.tasks[k].run, plan.tasks[k].k0, plan.tasks[k].count});
+        }
+        out->nrows = static_cast<int64_t>(sel.size());
+        out->nruns = static_cast<int64_t>(T.runs.size());
+        out->nwg = static_cast<int64_t>(T.wg_run.size());
+        int32_t** const dst[12] = {&out->first, &out->count, &out->row0, &out->row_stride, &out->kind, &out->ncols, &out->self, &out->flags,
+                                   &out->col0, &out->col_stride, &out->met0, &out->met_stride};
+        for (int q = 0; q < 12; ++q) *dst[q] = dup(f[q]);
+        out->wg_run = dup(T.wg_run);
+        out->wg_k0 = dup(T.wg_k0);
+        out->gid = dup(gid);
+        out->nstrips = plan.nstrips;
+        out->ntasks = static_cast<int64_t>(plan.tasks.size());
+        out->strip_off = dup(plan.off);
+        out->task = dup(task);
+        return TM_OK;
+    });
+}
+void tm_edge_tables_free(tm_edge_tables_info* i) {
+    if (!i) return;
+    int32_t* const arrays[] = {i->first, i->count, i->row0,   i->row_stride, i->col0,   i->col_stride, i->met0,      i->met_stride,
+                               i->kind,  i->ncols, i->self,   i->flags,      i->wg_run, i->wg_k0,      i->strip_off, i->task};
+    for (int32_t* p : arrays) std::free(p);
+    std::free(i->gid);
+    std::memset(i, 0, sizeof(*i));
+}
+
 int tm_plan_build(const tm_mesh_desc* mesh, tm_plan_rows* out) {
     return guarded([&]() {
         if (!mesh || !out) throw TmError(TM_E_ARG, "null argument");

@@ -36,6 +36,7 @@ inline int guarded(F&& f) {
 inline Topology topo_of(const tm_mesh_desc* mesh) {
     Topology t;
     if (!mesh || !mesh->blocks || mesh->nblocks == 0) throw TmError(TM_E_ARG, "mesh description without blocks");
+    if ((mesh->nconns && !mesh->conns) || (mesh->nbcs && !mesh->bcs)) throw TmError(TM_E_ARG, "null connection / condition array");
     for (uint64_t b = 0; b < mesh->nblocks; ++b) {
         t.ni.push_back(static_cast<int64_t>(mesh->blocks[b].ni));
         t.nj.push_back(static_cast<int64_t>(mesh->blocks[b].nj));
@@ -56,6 +57,5 @@ inline Topology topo_of(const tm_mesh_desc* mesh) {
     t.finalize();
     return t;
 }
-
 
 }  // namespace tmh

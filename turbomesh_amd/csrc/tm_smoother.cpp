@@ -8,6 +8,7 @@
 //                      computes the reference's residual and copies back (smooth.zig:112-153).
 //   TM_INNER_RELAX     every outer iteration is one fused Jacobi sweep of the nonlinear system.
 #include "tm_smoother.hpp"
+#include "tm_api_util.hpp"
 #include "tm_ilu.hpp"
 #include "tm_quality_dev.hpp"
 #include <algorithm>
@@ -61,35 +62,6 @@ void* DeviceArena::alloc(uint64_t bytes) {
 }
 
 // ------------------------------------------------------------------ helpers
-static Topology topology_from_desc(const tm_mesh_desc* m) {
-    if (!m || !m->blocks || m->nblocks == 0) throw TmError(TM_E_ARG, "mesh description without blocks");
-    if ((m->nconns && !m->conns) || (m->nbcs && !m->bcs)) throw TmError(TM_E_ARG, "null connection / condition array");
-    Topology t;
-    for (uint64_t b = 0; b < m->nblocks; ++b) {
-        t.ni.push_back(static_cast<int64_t>(m->blocks[b].ni));
-        t.nj.push_back(static_cast<int64_t>(m->blocks[b].nj));
-    }
-    auto rng = [](const tm_range& r) {
-        return TopoRange{static_cast<int64_t>(r.block), r.side, static_cast<int64_t>(r.start), static_cast<int64_t>(r.end)};
-    };
-    for (uint64_t c = 0; c < m->nconns; ++c) {
-        TopoConn tc;
-        tc.r[0] = rng(m->conns[c].r[0]);
-        tc.r[1] = rng(m->conns[c].r[1]);
-        tc.periodic = m->conns[c].has_periodicity != 0;
-        tc.per[0] = m->conns[c].periodicity[0];
-        tc.per[1] = m->conns[c].periodicity[1];
-        t.conns.push_back(tc);
-    }
-    for (uint64_t c = 0; c < m->nbcs; ++c) t.bcs.push_back(TopoCond{rng(m->bcs[c].range), m->bcs[c].kind});
-    try {
-        t.finalize();
-    } catch (const PlanError& e) {
-        throw TmError(e.code, e.what());
-    }
-    return t;
-}
-
 static void check_desc_matches(const Topology& t, const tm_mesh_desc* m) {
     if (!m || static_cast<int64_t>(m->nblocks) != t.nblocks()) throw TmError(TM_E_SIZE, "mesh description does not match the handle");
     for (int64_t b = 0; b < t.nblocks(); ++b)
@@ -163,8 +135,37 @@ Smoother::~Smoother() {
 }
 
 // ------------------------------------------------------------------ create
+// usable hooks = a multi-rank handle (a hooks struct that only carries a workspace has none)
+static bool hooks_usable(const tm_comm_hooks* h) { return h != nullptr && h->nranks >= 1 && h->exchange != nullptr && h->allreduce_sum != nullptr; }
+
+// the module's PlanError as the handle's TmError
+template <class F>
+static auto planned(F&& f) {
+    try {
+        return f();
+    } catch (const PlanError& e) {
+        throw TmError(e.code, e.what());
+    }
+}
+
 void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm_control_fn* c, const tm_comm_hooks* h, void* strm,
                       bool measure) {
+    resolve_options(mesh, o, c, h, measure);
+    stream = static_cast<hipStream_t>(strm);
+    plan_mesh(mesh, h, measure);
+    if (measure) arena.measure_only();
+    else if (h && h->workspace) arena.use_workspace(h->workspace, h->workspace_bytes);
+    alloc_vectors(mesh, measure);
+    decide_schedule();
+    build_row_tables();
+    const uint64_t npart = size_launches();
+    alloc_reductions(npart);
+    if (measure) return;
+    finish_create(mesh);
+}
+
+// validation, defaults that do not depend on the mesh's size, the TM_INNER_AUTO choice
+void Smoother::resolve_options(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm_control_fn* c, const tm_comm_hooks* h, bool measure) {
     if (!o) throw TmError(TM_E_ARG, "null solver option");
     if (o->tag != TM_SOLVER_HIP)
         throw TmError(TM_E_UNSUPPORTED, "ExternalSolverNotEnabled: libtm_hip serves only solver tag `hip` (gmres/bicgstab/umfpack/petsc stay on the Zig side)");
@@ -172,11 +173,10 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
         o->inner != TM_INNER_REFERENCE_GMRES)
         throw TmError(TM_E_ARG, "unknown inner strategy");
     opt = *o;
-    const bool reference = opt.inner == TM_INNER_REFERENCE_GMRES;
-    if ((opt.flags & TM_OPT_PRECOND_ILU0) && !reference)
+    if ((opt.flags & TM_OPT_PRECOND_ILU0) && !reference())
         throw TmError(TM_E_UNSUPPORTED, "ILU(0) needs the assembled matrix: it is served by tm_csr_solve (seam 2) and by TM_INNER_REFERENCE_GMRES; the matrix-free path preconditions with the diagonal or the multigrid cycle");
-    if (reference) {
-        if (h != nullptr && h->nranks >= 1 && h->exchange != nullptr && h->allreduce_sum != nullptr)
+    if (reference()) {
+        if (hooks_usable(h))
             throw TmError(TM_E_UNSUPPORTED, "TM_INNER_REFERENCE_GMRES solves the assembled system, which is available on single-process handles only");
         // the reference's own constants (GMRES.zig:21-24); every column is polled: an ILU(0) application is thousands of dependent levels
         if (!(opt.rtol > 0)) opt.rtol = 1e-6;
@@ -197,8 +197,7 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
         // ... and cells whose aspect ratio does not vary much inside a block.  Read off the caller's coordinates, which only a single-process
         // handle is sure to have for every block (the ranks of a job must decide alike, so with hooks the sizes decide alone; so does
         // the sizing call, whose answer has to cover whatever create decides later)
-        const bool ranks = h != nullptr && h->nranks >= 1 && h->exchange != nullptr && h->allreduce_sum != nullptr;
-        if (cycle && !ranks && !measure && mesh && mesh->blocks)
+        if (cycle && !hooks_usable(h) && !measure && mesh && mesh->blocks)
             for (uint64_t b = 0; b < mesh->nblocks && cycle; ++b)
                 if (mesh->blocks[b].ni * mesh->blocks[b].nj >= 1024 &&
                     BlockMG::aspect_spread_of(mesh->blocks[b].xy, static_cast<int>(mesh->blocks[b].ni), static_cast<int>(mesh->blocks[b].nj)) > AUTO_MG_MAX_ASPECT_SPREAD)
@@ -210,9 +209,11 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
     if (!(opt.omega > 0)) opt.omega = 1.0;
     cf = c ? *c : tm_control_fn{TM_CF_LAPLACE, 0, 0.0, 0.0};
     if (cf.kind != TM_CF_LAPLACE && cf.kind != TM_CF_WHITE) throw TmError(TM_E_ARG, "unknown control function");
-    stream = static_cast<hipStream_t>(strm);
+}
 
-    topo = topology_from_desc(mesh);
+// topology, the defaults that depend on the size of the system, rows, this rank's local plan, the White layout check
+void Smoother::plan_mesh(const tm_mesh_desc* mesh, const tm_comm_hooks* h, bool measure) {
+    topo = planned([&] { return topo_of(mesh); });
     dof_global = topo.dof;
     // size-aware for the diagonal-only solves (default_rtol, tm_smoother.hpp); the multigrid-preconditioned solve leaves a residual with a
     // flat spectrum and sits on the fp64 floor of the exact iterate at EVERY size with 1e-14 (4.9e-12 rms from the
@@ -220,9 +221,9 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
     if (!(opt.rtol > 0))
         opt.rtol = (opt.flags & TM_OPT_RTOL_INITIAL) ? 1e-2 : (opt.inner == TM_INNER_MG_BICGSTAB ? 1e-14 : default_rtol(static_cast<double>(dof_global)));
     if (opt.max_inner == 0) opt.max_inner = default_max_inner(static_cast<double>(dof_global));
-    try {
+    planned([&] {
         all_rows = build_rows(topo);
-        has_hooks = h != nullptr && h->nranks >= 1 && h->exchange != nullptr && h->allreduce_sum != nullptr;
+        has_hooks = hooks_usable(h);
         if (h) hooks = *h;
         owner.assign(topo.nblocks(), 0);
         int rank = 0, nranks = 1;
@@ -241,9 +242,7 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
             if (t >= 0) allow_triples = t != 0;
         }
         lp = build_local_plan(topo, all_rows, owner, rank, nranks, allow_triples);
-    } catch (const PlanError& e) {
-        throw TmError(e.code, e.what());
-    }
+    });
     if (has_hooks && !measure && !counted) {
         counted = true;
         g_multirank_handles.fetch_add(1);
@@ -263,12 +262,10 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
         if (owner[0] != lp.rank || owner[1] != lp.rank) throw TmError(TM_E_UNSUPPORTED, "white control function: blocks 0 and 1 must live on the same rank");
         white_le = conn_shifts(topo, c0);
     }
+}
 
-    if (measure) arena.measure_only();
-    else if (h && h->workspace) arena.use_workspace(h->workspace, h->workspace_bytes);
-
-    // ---- vectors
-    auto vec = [&]() { return arena.alloc_n<double2>(static_cast<uint64_t>(n_local)); };
+// the vectors of the inner strategy and the multigrid hierarchies
+void Smoother::alloc_vectors(const tm_mesh_desc* mesh, bool measure) {
     X = vec();
     U = vec();
     use_mg = opt.inner == TM_INNER_MG_BICGSTAB;
@@ -280,8 +277,8 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
     if (const char* e = std::getenv("TM_MG_PERIMETER_SWEEPS")) mg_perimeter_sweeps = std::max(1, std::atoi(e));
     mg_dirichlet = mg_perimeter_step;   // ... and the perimeter values as Dirichlet data in front of the cycles (block-local: no exchange)
     if (const char* e = std::getenv("TM_MG_DIRICHLET")) mg_dirichlet = mg_dirichlet && std::atoi(e) != 0;
-    if (opt.inner == TM_INNER_GMRES || reference) {   // w / z of GMRES.zig:27-38 in one vector, the basis v_0 .. v_m contiguous behind it
-        if (reference) ref_b = vec();
+    if (opt.inner == TM_INNER_GMRES || reference()) {   // w / z of GMRES.zig:27-38 in one vector, the basis v_0 .. v_m contiguous behind it
+        if (reference()) ref_b = vec();
         r = vec();
         gm_V = arena.alloc_n<double2>(static_cast<uint64_t>(n_local) * (GMRES_M + 1));
         gm_S = arena.alloc_n<GmresScalars>(1);
@@ -324,6 +321,10 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
             }
         }
     }
+}
+
+// sweep pairs, coupled triples, how K2x2 stores, the LDS cap of the interior pass (and the vectors these schedules need)
+void Smoother::decide_schedule() {
     // two sweeps per pass (K2x2): Laplace control function only (White updates P,Q between sweeps), every owned block >= 5 x 5
     fuse_pairs = opt.inner == TM_INNER_RELAX && !white && !(opt.flags & TM_OPT_SINGLE_SWEEP);
     { const char* e = std::getenv("TM_PAIR_SYNC"); pair_sync_events = e && std::strcmp(e, "events") == 0; }
@@ -362,306 +363,100 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
     // kernels, and both the cap and its streaming loads cost more than they give (2048^2, rank 1 of 3: 18.2-19.1 -> 16.1-16.6 us per sweep)
     if (fuse_pairs && has_hooks && lp.n_owned <= 6 * 1024 * 1024 && relax2_store_nt) inside_lds = 54 * 1024;
     if (const char* e = std::getenv("TM_INSIDE_LDS_KB")) inside_lds = static_cast<size_t>(std::max(0, std::atoi(e))) * 1024;
+}
 
-    // ---- perimeter rows -> device SoA with rank-local ids
+void* Smoother::upload_table(const void* src, uint64_t bytes) {
+    void* d = arena.alloc(bytes);
+    if (!arena.measuring() && bytes) HIPCHK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+    return d;
+}
+
+// A selection of rows for one run table, and where the right-hand side of each comes from (a slot of h_rhs, a ghost row's static rhs,
+// the zero pair of an interior row)
+static const double zero_rhs[2] = {0.0, 0.0};   // interior rows have b = 0
+struct Smoother::Selection {
+    std::vector<const PlanRow*> rows;
+    std::vector<const double*> rhs;
+    void add(const PlanRow& r, const double* b) {
+        rows.push_back(&r);
+        rhs.push_back(b);
+    }
+    void add_static(const std::vector<PlanRow>& more) {   // ghost rows: static parts; coordinate parts come from the row's value
+        for (const PlanRow& g : more) add(g, g.rhs);
+    }
+};
+
+// one run table (tm_edge_tables.cpp) on the device; its right-hand sides join the upload list in run order
+RunTable Smoother::make_table(const Selection& sel, EdgeRowsDev& e) {
+    RunTable T = planned([&] { return build_run_table(topo, lp, sel.rows); });
+    if (std::getenv("TM_DEBUG_RUNS")) {
+        int singles = 0;
+        for (const EdgeRun& R : T.runs) singles += R.count == 1;
+        std::fprintf(stderr, "[tm] perimeter-row table: %zu rows -> %zu runs (%d of one row), %zu workgroups\n", sel.rows.size(), T.runs.size(), singles, T.wg_run.size());
+    }
+    e.nrows = static_cast<int>(sel.rows.size());
+    e.nwg = static_cast<int>(T.wg_run.size());
+    e.runs = static_cast<const EdgeRun*>(upload_table(T.runs.data(), T.runs.size() * sizeof(EdgeRun)));
+    e.wg_run = static_cast<const int32_t*>(upload_table(T.wg_run.data(), T.wg_run.size() * 4));
+    e.wg_k0 = static_cast<const int32_t*>(upload_table(T.wg_k0.data(), T.wg_k0.size() * 4));
+    RhsTable rt;
+    rt.dev = arena.alloc_n<double>(sel.rows.size() * 2);
+    for (int32_t k : T.order) rt.src.push_back(sel.rhs[k]);
+    e.rhs = rt.dev;
+    rhs_tables.push_back(std::move(rt));
+    return T;
+}
+
+// ---- perimeter rows -> device SoA with rank-local ids
+void Smoother::build_row_tables() {
     const size_t nr = lp.rows.size();
     h_rhs.assign(nr * 2, 0.0);
-    auto up = [&](const void* src, uint64_t bytes) -> void* {
-        void* d = arena.alloc(bytes);
-        if (!measure && bytes) HIPCHK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-        return d;
-    };
-    // Per-row table -> runs (tm_kernels.h EdgeRun).  Rows are grouped by everything that must be equal along a run (static fields
-    // and the grid line of their block they lie on), sorted by row id within a group and cut wherever an index stops advancing by
-    // the stride of the stretch.  order[p] = position in `sel` of the row whose right-hand side sits at position p of e.rhs.
-    // (keep != nullptr: the host copy of the runs and, per run, where it lies -- block, direction, which half of the block, position of
-    //  its first point along the line and the position step -- for the strip plan of the fused level kernel)
-    struct RunWhere {
-        int64_t side_key;            // (block, runs along rows or columns, lower or upper half of the block)
-        int32_t pos0, pos_stride;
-    };
-    auto build_table = [&](const std::vector<const PlanRow*>& sel, EdgeRowsDev& e, double*& rhs_dev, std::vector<int32_t>& order,
-                           std::vector<EdgeRun>* keep = nullptr, std::vector<RunWhere>* keep_where = nullptr) {
-        const size_t n = sel.size();
-        struct HostRow {
-            int32_t row, col[9], met[4];
-            uint8_t flags;
-            int64_t line;   // (block, grid line) the node lies on: rows of different lines never share a run
-            int64_t side_key;
-            int32_t pos;
-        };
-        std::vector<HostRow> hr(n);
-        auto loc = [&](int64_t gid) {
-            const int64_t l = lp.to_local(gid);
-            if (l < 0) throw TmError(TM_E_TOPOLOGY, "internal: column is neither owned nor ghost");
-            return static_cast<int32_t>(l);
-        };
-        for (size_t k = 0; k < n; ++k) {
-            const PlanRow& pr = *sel[k];
-            HostRow& h = hr[k];
-            std::memset(&h, 0, sizeof(h));
-            h.row = loc(pr.gid);
-            h.flags = pr.flags;
-            // a ghost copy of a row whose rhs is the node's own boundary coordinate takes it from the row's current value
-            if (h.row >= lp.n_owned) h.flags |= static_cast<uint8_t>((pr.rhs_coord & 3) << 2);
-            for (int q = 0; q < pr.ncols; ++q) h.col[q] = loc(pr.col[q]);
-            if (pr.kind == KIND_SMOOTHED)
-                for (int q = 0; q < 4; ++q) h.met[q] = loc(pr.metric[q]);
-            int64_t b = topo.nblocks() - 1;
-            while (pr.gid < topo.start[b]) --b;
-            const int64_t flat = pr.gid - topo.start[b], bi = flat / topo.nj[b], bj = flat % topo.nj[b];
-            bool on_row = bi <= 1 || bi >= topo.ni[b] - 2;
-            if (pr.kind == KIND_INTERIOR) {   // zone rows of the coupled triples: runs along the nearer pair of sides
-                on_row = std::min(bi, topo.ni[b] - 1 - bi) <= std::min(bj, topo.nj[b] - 1 - bj);
-                if (h.row < lp.n_owned) h.flags |= 16;
-            }
-            h.line = (b << 34) | (static_cast<int64_t>(on_row ? 0 : 1) << 33) | (on_row ? bi : bj);
-            const int64_t across = on_row ? bi : bj, across_n = on_row ? topo.ni[b] : topo.nj[b];
-            h.side_key = (b << 2) | (static_cast<int64_t>(on_row ? 0 : 1) << 1) | (2 * across >= across_n ? 1 : 0);
-            h.pos = static_cast<int32_t>(on_row ? bj : bi);
-        }
-        auto same_static = [&](size_t x, size_t y) {
-            const PlanRow &p = *sel[x], &q = *sel[y];
-            return p.kind == q.kind && p.ncols == q.ncols && p.self == q.self && hr[x].flags == hr[y].flags && hr[x].line == hr[y].line &&
-                   std::memcmp(p.slot, q.slot, sizeof(p.slot)) == 0 && std::memcmp(p.cx, q.cx, sizeof(p.cx)) == 0 &&
-                   std::memcmp(p.cy, q.cy, sizeof(p.cy)) == 0 && std::memcmp(p.per, q.per, sizeof(p.per)) == 0;
-        };
-        auto static_less = [&](size_t x, size_t y) {   // any strict weak order that is consistent with same_static
-            const PlanRow &p = *sel[x], &q = *sel[y];
-            if (hr[x].line != hr[y].line) return hr[x].line < hr[y].line;
-            if (p.kind != q.kind) return p.kind < q.kind;
-            if (p.ncols != q.ncols) return p.ncols < q.ncols;
-            if (p.self != q.self) return p.self < q.self;
-            if (hr[x].flags != hr[y].flags) return hr[x].flags < hr[y].flags;
-            int c = std::memcmp(p.slot, q.slot, sizeof(p.slot));
-            if (c) return c < 0;
-            c = std::memcmp(p.cx, q.cx, sizeof(p.cx));
-            if (c) return c < 0;
-            c = std::memcmp(p.cy, q.cy, sizeof(p.cy));
-            if (c) return c < 0;
-            c = std::memcmp(p.per, q.per, sizeof(p.per));
-            if (c) return c < 0;
-            return hr[x].row < hr[y].row;
-        };
-        std::vector<size_t> idx(n);
-        for (size_t k = 0; k < n; ++k) idx[k] = k;
-        std::sort(idx.begin(), idx.end(), static_less);
-        std::vector<EdgeRun> runs;
-        order.clear();
-        for (size_t p = 0; p < n;) {
-            const size_t k0 = idx[p];
-            const PlanRow& pr = *sel[k0];
-            EdgeRun R;
-            std::memset(&R, 0, sizeof(R));
-            R.first = static_cast<int32_t>(p);
-            R.count = 1;
-            R.row0 = hr[k0].row;
-            R.kind = pr.kind;
-            R.ncols = pr.ncols;
-            R.self = pr.self;
-            R.flags = hr[k0].flags;
-            std::memcpy(R.slot, pr.slot, sizeof(R.slot));
-            std::memcpy(R.cx, pr.cx, sizeof(R.cx));
-            std::memcpy(R.cy, pr.cy, sizeof(R.cy));
-            std::memcpy(R.per, pr.per, sizeof(R.per));
-            for (int q = 0; q < 9; ++q) R.col0[q] = hr[k0].col[q];
-            for (int q = 0; q < 4; ++q) R.met0[q] = hr[k0].met[q];
-            size_t e_ = p + 1;
-            if (e_ < n && same_static(k0, idx[e_])) {   // strides from the second row, then as far as they hold
-                const HostRow& h1 = hr[idx[e_]];
-                R.row_stride = h1.row - R.row0;
-                for (int q = 0; q < 9; ++q) R.col_stride[q] = h1.col[q] - R.col0[q];
-                for (int q = 0; q < 4; ++q) R.met_stride[q] = h1.met[q] - R.met0[q];
-                auto fits = [&](size_t j) {
-                    if (!same_static(k0, idx[j])) return false;
-                    const HostRow& h = hr[idx[j]];
-                    const int32_t kk = static_cast<int32_t>(j - p);
-                    if (h.row != R.row0 + kk * R.row_stride) return false;
-                    for (int q = 0; q < 9; ++q)
-                        if (h.col[q] != R.col0[q] + kk * R.col_stride[q]) return false;
-                    for (int q = 0; q < 4; ++q)
-                        if (h.met[q] != R.met0[q] + kk * R.met_stride[q]) return false;
-                    return true;
-                };
-                while (e_ < n && fits(e_)) ++e_;
-                R.count = static_cast<int32_t>(e_ - p);
-            }
-            for (size_t j = p; j < e_; ++j) order.push_back(static_cast<int32_t>(idx[j]));
-            runs.push_back(R);
-            if (keep_where) keep_where->push_back(RunWhere{hr[k0].side_key, hr[k0].pos, e_ - p > 1 ? hr[idx[p + 1]].pos - hr[k0].pos : 0});
-            p = e_;
-        }
-        if (keep) *keep = runs;
-        std::vector<int32_t> wg_run, wg_k0;
-        for (size_t r = 0; r < runs.size(); ++r)
-            for (int32_t k0 = 0; k0 < runs[r].count; k0 += EDGE_BLOCK) {
-                wg_run.push_back(static_cast<int32_t>(r));
-                wg_k0.push_back(k0);
-            }
-        if (std::getenv("TM_DEBUG_RUNS")) {
-            int singles = 0;
-            for (const EdgeRun& R : runs) singles += R.count == 1;
-            std::fprintf(stderr, "[tm] perimeter-row table: %zu rows -> %zu runs (%d of one row), %zu workgroups\n", n, runs.size(), singles, wg_run.size());
-        }
-        e.nrows = static_cast<int>(n);
-        e.nwg = static_cast<int>(wg_run.size());
-        e.runs = static_cast<const EdgeRun*>(up(runs.data(), runs.size() * sizeof(EdgeRun)));
-        e.wg_run = static_cast<const int32_t*>(up(wg_run.data(), wg_run.size() * 4));
-        e.wg_k0 = static_cast<const int32_t*>(up(wg_k0.data(), wg_k0.size() * 4));
-        rhs_dev = arena.alloc_n<double>(n * 2);
-        e.rhs = rhs_dev;
-    };
-    std::vector<const PlanRow*> all(nr);
-    for (size_t k = 0; k < nr; ++k) all[k] = &lp.rows[k];
-    build_table(all, edge, d_rhs, order_all);
-    // Relaxation sweeps never have to touch a `fixed` row: it returns its boundary coordinate (smooth.zig:790-795), which the
-    // perimeter of every field buffer holds from upload() on.  They run the perimeter-row kernel over the other rows only
-    // (none at all for a block with fixed walls), and the K2x2 workgroups along sides without such rows do not have to wait
-    // for it.  dyn_mask: bit 0 = row i = 0 has non-fixed rows, 1 = row ni-1, 2 = column j = 0, 3 = column nj-1.
-    nf_rows.clear();
-    dyn_mask.assign(lp.owned_blocks.size(), 0);
-    for (size_t k = 0; k < nr; ++k) {
-        const PlanRow& pr = lp.rows[k];
-        if (pr.kind == KIND_FIXED) continue;
-        nf_rows.push_back(k);
-        int64_t b = topo.nblocks() - 1;
-        while (pr.gid < topo.start[b]) --b;
-        const size_t kb = std::lower_bound(lp.owned_blocks.begin(), lp.owned_blocks.end(), b) - lp.owned_blocks.begin();
-        const int64_t flat = pr.gid - topo.start[b], bi = flat / topo.nj[b], bj = flat % topo.nj[b];
-        // a corner node counts for its ROW only (the tiles along that row include the corner tile): the end points of an interface
-        // along i = 0 must not turn the two side walls into sides whose workgroups wait for the perimeter-row pass
-        const bool corner_row = bi == 0 || bi == topo.ni[b] - 1;
-        if (bi == 0) dyn_mask[kb] |= 1;
-        if (bi == topo.ni[b] - 1) dyn_mask[kb] |= 2;
-        if (bj == 0 && !corner_row) dyn_mask[kb] |= 4;
-        if (bj == topo.nj[b] - 1 && !corner_row) dyn_mask[kb] |= 8;
+    rhs_tables.clear();
+    Selection all;
+    for (size_t k = 0; k < nr; ++k) all.add(lp.rows[k], &h_rhs[2 * k]);
+    make_table(all, edge);
+    MovingSides moving = moving_sides(topo, lp);
+    dyn_mask = std::move(moving.dyn_mask);
+    if (opt.inner != TM_INNER_RELAX) return;
+    Selection nf;
+    for (size_t k : moving.nf_rows) nf.add(lp.rows[k], &h_rhs[2 * k]);
+    make_table(nf, edge_nf);
+    // multi-rank sweep pairs: the same rows plus the depth-1 ghost rows, evaluated one sweep ahead (LocalPlan::ghost_rows)
+    if (fuse_pairs && has_hooks && !lp.ghost_rows.empty()) {
+        Selection sel = nf;
+        sel.add_static(lp.ghost_rows);
+        make_table(sel, edge_nf_g);
     }
-    if (opt.inner == TM_INNER_RELAX) {
-        std::vector<const PlanRow*> sel;
-        for (size_t k : nf_rows) sel.push_back(&lp.rows[k]);
-        build_table(sel, edge_nf, d_rhs_nf, order_nf);
-        // multi-rank sweep pairs: the same rows plus the depth-1 ghost rows, evaluated one sweep ahead (LocalPlan::ghost_rows)
-        if (fuse_pairs && has_hooks && !lp.ghost_rows.empty()) {
-            for (const PlanRow& g : lp.ghost_rows) sel.push_back(&g);
-            build_table(sel, edge_nf_g, d_rhs_nf_g, order_nf_g);
-        }
-        if (triples_coupled) {
-            // level l (1..3) evaluates the moving perimeter rows and, as KIND_INTERIOR rows (K2's own arithmetic on the gathered 3 x 3
-            // neighbourhood), the interior nodes within 5 - l of a side whose perimeter rows move (Chebyshev distance: the 9-point
-            // stencil's dependency cone); what level l reads at level l - 1 lies within 6 - l of such a side or on the perimeter
-            std::vector<RunWhere> where_L3;
-            for (int lev = 0; lev < 3; ++lev) {
-                const int64_t depth = 4 - lev;
-                zone_rows[lev].clear();
-                for (size_t kb = 0; kb < lp.owned_blocks.size(); ++kb) {
-                    const int64_t b = lp.owned_blocks[kb], bi_n = topo.ni[b], bj_n = topo.nj[b];
-                    const int dyn = dyn_mask[kb];
-                    if (!dyn) continue;
-                    auto add = [&](int64_t i, int64_t j) {
-                        PlanRow r{};
-                        r.gid = topo.start[b] + i * bj_n + j;
-                        r.kind = KIND_INTERIOR;
-                        r.ncols = 9;
-                        r.self = 4;
-                        int q = 0;
-                        for (int64_t di = -1; di <= 1; ++di)
-                            for (int64_t dj = -1; dj <= 1; ++dj) r.col[q++] = r.gid + di * bj_n + dj;
-                        zone_rows[lev].push_back(r);
-                    };
-                    for (int64_t i = 1; i <= bi_n - 2; ++i) {   // ascending gid
-                        const bool row_in = ((dyn & 1) && i <= depth) || ((dyn & 2) && i >= bi_n - 1 - depth);
-                        if (row_in) {
-                            for (int64_t j = 1; j <= bj_n - 2; ++j) add(i, j);
-                            continue;
-                        }
-                        if (dyn & 4)
-                            for (int64_t j = 1; j <= depth; ++j) add(i, j);
-                        if (dyn & 8)
-                            for (int64_t j = bj_n - 1 - depth; j <= bj_n - 2; ++j) add(i, j);
-                    }
-                }
-                std::vector<const PlanRow*> sl;
-                for (size_t k : nf_rows) sl.push_back(&lp.rows[k]);
-                for (const PlanRow& z : zone_rows[lev]) sl.push_back(&z);
-                // several ranks: level 1 also evaluates every row of the depth-2 ghost set, level 2 the depth-1 rows (their owners'
-                // definitions, hence their owners' bits); level 3 reads them
-                if (lev == 0) for (const PlanRow& g : lp.ghost_rows2) sl.push_back(&g);
-                if (lev == 1) for (const PlanRow& g : lp.ghost_rows) sl.push_back(&g);
-                build_table(sl, edge_L[lev], d_rhs_L[lev], order_L[lev], &runs_L[lev], lev == 2 ? &where_L3 : nullptr);
-            }
-            // ---- strip plan of the fused level kernel (k_edge_levels3): level-3 rows by strips of LEVEL_STRIP positions along their lines,
-            // per side of a block; per strip the level-2 rows its level-3 rows read, and the level-1 rows THOSE read (hulls per run)
-            levels_fused = true;
-            if (const char* e = std::getenv("TM_LEVELS_FUSED")) levels_fused = std::atoi(e) != 0;
-            if (levels_fused) {
-                int LEVEL_STRIP = 60;   // positions per strip: 60 + 2 x 2 halo positions make whole 64-point wave tasks at level 1
-                if (const char* e = std::getenv("TM_LEVEL_STRIP")) LEVEL_STRIP = std::max(4, std::atoi(e));
-                std::unordered_map<int32_t, std::pair<int32_t, int32_t>> made[2];   // local row id -> (run, k) in the level-1 / level-2 table
-                for (int lev = 0; lev < 2; ++lev)
-                    for (size_t r = 0; r < runs_L[lev].size(); ++r)
-                        for (int32_t k = 0; k < runs_L[lev][r].count; ++k)
-                            made[lev][runs_L[lev][r].row0 + k * runs_L[lev][r].row_stride] = {static_cast<int32_t>(r), k};
-                auto reads = [&](const EdgeRun& R, int32_t k, auto&& f) {   // every local id row k of run R reads at the previous level
-                    for (int q = 0; q < R.ncols; ++q) f(R.col0[q] + k * R.col_stride[q]);
-                    if (R.kind == KIND_SMOOTHED)
-                        for (int q = 0; q < 4; ++q) f(R.met0[q] + k * R.met_stride[q]);
-                    f(R.row0 + k * R.row_stride);
-                };
-                using Hull = std::map<int32_t, std::pair<int32_t, int32_t>>;   // run -> [kmin, kmax]
-                auto widen = [](Hull& h, int32_t run, int32_t k) {
-                    auto it = h.find(run);
-                    if (it == h.end()) h[run] = {k, k};
-                    else {
-                        it->second.first = std::min(it->second.first, k);
-                        it->second.second = std::max(it->second.second, k);
-                    }
-                };
-                std::map<std::pair<int64_t, int32_t>, Hull> strips;   // (side, strip number) -> level-3 rows
-                for (size_t r = 0; r < runs_L[2].size(); ++r)
-                    for (int32_t k = 0; k < runs_L[2][r].count; ++k)
-                        widen(strips[{where_L3[r].side_key, (where_L3[r].pos0 + k * where_L3[r].pos_stride) / LEVEL_STRIP}], static_cast<int32_t>(r), k);
-                std::vector<LevelTask> tasks;
-                std::vector<int32_t> off;
-                auto emit = [&](const Hull& h) {
-                    for (const auto& kv : h)
-                        for (int32_t k = kv.second.first; k <= kv.second.second; k += 64)
-                            tasks.push_back(LevelTask{kv.first, k, std::min<int32_t>(64, kv.second.second - k + 1)});
-                };
-                for (const auto& st : strips) {
-                    // a strip's level-3 rows need not be one range per run (two strips of one run are separate map entries: they are);
-                    // level 2 = hull of what they read and level 2 makes, level 1 = hull of what THAT hull reads and level 1 makes
-                    Hull h2, h1;
-                    for (const auto& kv : st.second)
-                        for (int32_t k = kv.second.first; k <= kv.second.second; ++k)
-                            reads(runs_L[2][kv.first], k, [&](int32_t id) {
-                                auto it = made[1].find(id);
-                                if (it != made[1].end()) widen(h2, it->second.first, it->second.second);
-                            });
-                    for (const auto& kv : h2)
-                        for (int32_t k = kv.second.first; k <= kv.second.second; ++k)
-                            reads(runs_L[1][kv.first], k, [&](int32_t id) {
-                                auto it = made[0].find(id);
-                                if (it != made[0].end()) widen(h1, it->second.first, it->second.second);
-                            });
-                    off.push_back(static_cast<int32_t>(tasks.size()));
-                    emit(h1);
-                    off.push_back(static_cast<int32_t>(tasks.size()));
-                    emit(h2);
-                    off.push_back(static_cast<int32_t>(tasks.size()));
-                    emit(st.second);
-                    off.push_back(static_cast<int32_t>(tasks.size()));
-                }
-                fused_levels.nstrips = static_cast<int>(strips.size());
-                fused_levels.tasks = static_cast<const LevelTask*>(up(tasks.data(), tasks.size() * sizeof(LevelTask)));
-                fused_levels.off = static_cast<const int32_t*>(up(off.data(), off.size() * 4));
-                if (std::getenv("TM_DEBUG_RUNS"))
-                    std::fprintf(stderr, "[tm] fused level kernel: %d strips, %zu wave tasks (level tables: %d / %d / %d rows)\n", fused_levels.nstrips, tasks.size(),
-                                 edge_L[0].nrows, edge_L[1].nrows, edge_L[2].nrows);
-            }
-        }
+    if (!triples_coupled) return;
+    RunTable level[3];
+    for (int lev = 0; lev < 3; ++lev) {
+        const std::vector<PlanRow> zone = zone_rows(topo, lp, dyn_mask, lev);
+        Selection sl = nf;
+        for (const PlanRow& z : zone) sl.add(z, zero_rhs);
+        // several ranks: level 1 also evaluates every row of the depth-2 ghost set, level 2 the depth-1 rows (their owners'
+        // definitions, hence their owners' bits); level 3 reads them
+        if (lev == 0) sl.add_static(lp.ghost_rows2);
+        if (lev == 1) sl.add_static(lp.ghost_rows);
+        level[lev] = make_table(sl, edge_L[lev]);
     }
+    levels_fused = true;
+    if (const char* e = std::getenv("TM_LEVELS_FUSED")) levels_fused = std::atoi(e) != 0;
+    if (!levels_fused) return;
+    int LEVEL_STRIP = 60;   // positions per strip: 60 + 2 x 2 halo positions make whole 64-point wave tasks at level 1
+    if (const char* e = std::getenv("TM_LEVEL_STRIP")) LEVEL_STRIP = std::max(4, std::atoi(e));
+    const std::vector<EdgeRun>* const runs[3] = {&level[0].runs, &level[1].runs, &level[2].runs};
+    const StripPlan plan = build_strip_plan(runs, level[2].where, LEVEL_STRIP);
+    fused_levels.nstrips = plan.nstrips;
+    fused_levels.tasks = static_cast<const LevelTask*>(upload_table(plan.tasks.data(), plan.tasks.size() * sizeof(LevelTask)));
+    fused_levels.off = static_cast<const int32_t*>(upload_table(plan.off.data(), plan.off.size() * 4));
+    if (std::getenv("TM_DEBUG_RUNS"))
+        std::fprintf(stderr, "[tm] fused level kernel: %d strips, %zu wave tasks (level tables: %d / %d / %d rows)\n", fused_levels.nstrips, plan.tasks.size(),
+                     edge_L[0].nrows, edge_L[1].nrows, edge_L[2].nrows);
+}
 
-    // ---- reductions
+// ---- launch sizing: chunk heights, partial-row offsets of every launch, the schedules that follow from them; returns the doubles of
+// one partial-sum buffer
+uint64_t Smoother::size_launches() {
     // K2 chunk length for this handle: all owned blocks go into one launch -- the shortest chunks (multiples of the 3-row load
     // group) that keep interior + perimeter workgroups within what the lazy scalar steps allow (512 partial rows); large meshes:
     // the per-block rule of tm_kernels.hip (apply_rows = 0)
@@ -726,7 +521,7 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
             off2 += relax2_block_nwg(bi, bj, rows2.back());
             const std::vector<int32_t> ids = relax2_border_tiles(bi, bj, rows2.back(), dyn_mask[poff2.size() - 1]);
             border_n.push_back(static_cast<int>(ids.size()));
-            border_ids.push_back(static_cast<const int32_t*>(up(ids.data(), ids.size() * 4)));
+            border_ids.push_back(static_cast<const int32_t*>(upload_table(ids.data(), ids.size() * 4)));
         }
         poff2_edge = off2;
         nwg_apply2 = off2 + edge_nf.nwg;
@@ -740,7 +535,8 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
     // neighbour to exchange with) -- a single block with prescribed walls, independent slices
     fuse_triples = fuse_pairs && edge_nf.nrows == 0 && !(has_hooks && (!lp.send_ids.empty() || !lp.ghost_gid.empty()));
     if (const char* e = std::getenv("TM_FUSE_3")) fuse_triples = fuse_triples && std::atoi(e) != 0;
-    if (fuse_triples) {
+    // ... and the coupled triples: the same K2x3 grid, plus the level-3 perimeter-row pass behind it in the partial sums
+    if (fuse_triples || triples_coupled) {
         poff3.clear();
         rows3.clear();
         int off3 = 0;
@@ -748,20 +544,7 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
         for (size_t k = 0; k < lp.owned_blocks.size(); ++k) {
             const int64_t b = lp.owned_blocks[k];
             const int bi = static_cast<int>(topo.ni[b]), bj = static_cast<int>(topo.nj[b]);
-            if (!relax3_supported(bi, bj)) fuse_triples = false;
-            poff3.push_back(off3);
-            off3 += relax3_block_nwg(bi, bj, rows3[k]);
-        }
-        nwg_apply3 = off3;
-    }
-    if (triples_coupled) {   // the same K2x3 grid, plus the level-3 perimeter-row pass behind it in the partial sums
-        poff3.clear();
-        rows3.clear();
-        int off3 = 0;
-        rows3 = relax3_rows_of_owned_blocks();
-        for (size_t k = 0; k < lp.owned_blocks.size(); ++k) {
-            const int64_t b = lp.owned_blocks[k];
-            const int bi = static_cast<int>(topo.ni[b]), bj = static_cast<int>(topo.nj[b]);
+            if (!relax3_supported(bi, bj)) fuse_triples = false;   // (the blocks of coupled triples passed this test in decide_schedule)
             poff3.push_back(off3);
             off3 += relax3_block_nwg(bi, bj, rows3[k]);
         }
@@ -803,34 +586,37 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
     fuse2 = fuse_p;
     if (const char* e = std::getenv("TM_FUSE_2")) fuse2 = fuse2 && std::atoi(e) != 0;
     if (fuse_p) {
-        p_alt = arena.alloc_n<double2>(static_cast<uint64_t>(n_local));
-        v_alt = arena.alloc_n<double2>(static_cast<uint64_t>(n_local));
+        p_alt = vec();
+        v_alt = vec();
     }
-    if (fuse2) r_alt = arena.alloc_n<double2>(static_cast<uint64_t>(n_local));
+    if (fuse2) r_alt = vec();
     // Every launch that writes partial sums must fit the rows allocated for them (one row of MAX_PARTIALS per workgroup): the operator
     // launches (perimeter rows behind the interior workgroups), the sweep pairs / triples, the vector kernels (launched with nwg_vec, the
     // grid npart was sized for -- capped at 512 above), GMRES's Gram-Schmidt passes (vec_nwg) and the perimeter-row pass that forms
     // ||D^-1 b||^2 of a Krylov solve
-    {
-        const int rows = static_cast<int>(npart / MAX_PARTIALS);
-        const struct {
-            const char* what;
-            int nwg;
-        } producers[] = {{"operator", nwg_apply},
-                         {"operator (overlapping strips)", nwg_apply_ov},
-                         {"sweep pairs", nwg_apply2},
-                         {"sweep triples", nwg3_all},
-                         {"vector kernels", nwg_vec},
-                         {"GMRES Gram-Schmidt", (opt.inner == TM_INNER_GMRES || reference) ? vec_nwg(n_owned) : 0},
-                         {"perimeter-row right-hand side", opt.inner != TM_INNER_RELAX ? edge.nwg : 0}};
-        if (std::getenv("TM_DEBUG_RUNS"))
-            std::fprintf(stderr, "[tm] partial-sum rows: %d allocated; operator %d, overlapping strips %d, pairs %d, triples %d, vector kernels %d (vec_nwg %d)\n", rows,
-                         nwg_apply, nwg_apply_ov, nwg_apply2, nwg3_all, nwg_vec, vec_nwg(n_owned));
-        for (const auto& q : producers)
-            if (q.nwg > rows)
-                throw TmError(TM_E_HIP, std::string("internal: the ") + q.what + " launch has " + std::to_string(q.nwg) + " workgroups, the partial-sum buffer " +
-                                            std::to_string(rows) + " rows");
-    }
+    const int rows = static_cast<int>(npart / MAX_PARTIALS);
+    const struct {
+        const char* what;
+        int nwg;
+    } producers[] = {{"operator", nwg_apply},
+                     {"operator (overlapping strips)", nwg_apply_ov},
+                     {"sweep pairs", nwg_apply2},
+                     {"sweep triples", nwg3_all},
+                     {"vector kernels", nwg_vec},
+                     {"GMRES Gram-Schmidt", (opt.inner == TM_INNER_GMRES || reference()) ? vec_nwg(n_owned) : 0},
+                     {"perimeter-row right-hand side", opt.inner != TM_INNER_RELAX ? edge.nwg : 0}};
+    if (std::getenv("TM_DEBUG_RUNS"))
+        std::fprintf(stderr, "[tm] partial-sum rows: %d allocated; operator %d, overlapping strips %d, pairs %d, triples %d, vector kernels %d (vec_nwg %d)\n", rows,
+                     nwg_apply, nwg_apply_ov, nwg_apply2, nwg3_all, nwg_vec, vec_nwg(n_owned));
+    for (const auto& q : producers)
+        if (q.nwg > rows)
+            throw TmError(TM_E_HIP, std::string("internal: the ") + q.what + " launch has " + std::to_string(q.nwg) + " workgroups, the partial-sum buffer " +
+                                        std::to_string(rows) + " rows");
+    return npart;
+}
+
+// ---- reductions, scalars, halo buffers
+void Smoother::alloc_reductions(uint64_t npart) {
     // TM_PARTIALS_GUARD=1: a guard region behind each partial-sum buffer and behind `red`, filled with a byte pattern here and compared when
     // an iterate call returns (check_guards) -- a write past the rows a buffer was sized for shows as a TM_E_HIP error naming the buffer.
     // Off: the arena layout is what it always was.
@@ -852,11 +638,13 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
     // ---- halo exchange
     n_send = static_cast<int64_t>(lp.send_ids.size());
     if (n_send) {
-        d_send_ids = static_cast<int32_t*>(up(lp.send_ids.data(), static_cast<uint64_t>(n_send) * 4));
+        d_send_ids = static_cast<int32_t*>(upload_table(lp.send_ids.data(), static_cast<uint64_t>(n_send) * 4));
         d_send_buf = arena.alloc_n<double2>(static_cast<uint64_t>(n_send));
     }
-    if (measure) return;
+}
 
+// what only a handle that runs needs (the sizing call stops in front of it): pinned buffers, cleared device state, the first upload
+void Smoother::finish_create(const tm_mesh_desc* mesh) {
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h_S), sizeof(KrylovScalars), hipHostMallocDefault));
     pipelined_poll = lazy;   // small single-process meshes (see poll_done)
     if (const char* e = std::getenv("TM_PIPELINED_POLL")) pipelined_poll = pipelined_poll && std::atoi(e) != 0;
@@ -884,7 +672,7 @@ void Smoother::create(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm
     if (PQ) HIPCHK(hipMemsetAsync(PQ, 0, sizeof(double2) * n_local, stream));
     upload(mesh);
     if (white) white_launch(0);   // ControlFunction.init, wall_control_function.zig:27-42
-    if (reference) reference_create();   // everything the mode needs, now: a mesh that does not fit fails here, not in the middle of a solve
+    if (reference()) reference_create();   // everything the mode needs, now: a mesh that does not fit fails here, not in the middle of a solve
     sync();
 }
 
@@ -904,42 +692,27 @@ void Smoother::upload(const tm_mesh_desc* mesh) {
         h_rhs[2 * k] = pr.rhs[0];
         h_rhs[2 * k + 1] = pr.rhs[1];
         if (pr.rhs_coord) {
-            int64_t b = topo.nblocks() - 1;
-            while (pr.gid < topo.start[b]) --b;
+            const int64_t b = block_of(topo, pr.gid);
             const double* xy = mesh->blocks[b].xy + 2 * (pr.gid - topo.start[b]);
             if (pr.rhs_coord & 1) h_rhs[2 * k] = xy[0];
             if (pr.rhs_coord & 2) h_rhs[2 * k + 1] = xy[1];
         }
     }
-    // device right-hand sides are stored in run order (build_table: order[p] = row of the selection at position p)
+    // device right-hand sides are stored in run order: every table lists where the right-hand side of each of its positions comes from
+    // (Smoother::make_table)
     std::vector<double> staged;
-    auto put = [&](double* dev, const std::vector<int32_t>& order, const std::function<const double*(int32_t)>& rhs_of) {
-        if (!dev || order.empty()) return;
+    size_t total = 0;
+    for (const RhsTable& t : rhs_tables) total += 2 * t.src.size();
+    staged.reserve(total);   // no reallocation while copies are in flight
+    for (const RhsTable& t : rhs_tables) {
+        if (!t.dev || t.src.empty()) continue;
         const size_t base = staged.size();
-        staged.resize(base + 2 * order.size());
-        for (size_t p = 0; p < order.size(); ++p) {
-            const double* v = rhs_of(order[p]);
-            staged[base + 2 * p] = v[0];
-            staged[base + 2 * p + 1] = v[1];
+        for (const double* v : t.src) {
+            staged.push_back(v[0]);
+            staged.push_back(v[1]);
         }
-        HIPCHK(hipMemcpyAsync(dev, staged.data() + base, sizeof(double) * 2 * order.size(), hipMemcpyHostToDevice, stream));
-    };
-    staged.reserve(2 * (order_all.size() + order_nf.size() + order_nf_g.size() + order_L[0].size() + order_L[1].size() + order_L[2].size()));   // no reallocation while copies are in flight
-    put(d_rhs, order_all, [&](int32_t k) { return &h_rhs[2 * static_cast<size_t>(k)]; });
-    put(d_rhs_nf, order_nf, [&](int32_t k) { return &h_rhs[2 * nf_rows[k]]; });
-    // own rows as above, then the ghost rows' static right-hand sides (coordinate parts come from the row's value)
-    put(d_rhs_nf_g, order_nf_g, [&](int32_t k) {
-        return static_cast<size_t>(k) < nf_rows.size() ? &h_rhs[2 * nf_rows[k]] : lp.ghost_rows[static_cast<size_t>(k) - nf_rows.size()].rhs;
-    });
-    static const double zero_rhs[2] = {0.0, 0.0};   // interior rows have b = 0
-    for (int lev = 0; lev < 3; ++lev)
-        put(d_rhs_L[lev], order_L[lev], [&](int32_t k) -> const double* {
-            const size_t q = static_cast<size_t>(k), nz = zone_rows[lev].size();
-            if (q < nf_rows.size()) return &h_rhs[2 * nf_rows[q]];
-            if (q < nf_rows.size() + nz) return zero_rhs;
-            const std::vector<PlanRow>& g = lev == 0 ? lp.ghost_rows2 : lp.ghost_rows;   // static parts; coordinate parts come from the row's value
-            return g[q - nf_rows.size() - nz].rhs;
-        });
+        HIPCHK(hipMemcpyAsync(t.dev, staged.data() + base, sizeof(double) * (staged.size() - base), hipMemcpyHostToDevice, stream));
+    }
     if (opt.inner == TM_INNER_RELAX) prefill_fixed();
     sync();   // host staging buffers may go away after return
 }

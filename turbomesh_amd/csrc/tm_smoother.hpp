@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/tm_hip.h"
 #include <cstdlib>
+#include "tm_edge_tables.hpp"
 #include "tm_kernels.h"
 #include "tm_multigrid.hpp"
 #include "tm_plan.hpp"
@@ -82,21 +83,23 @@ struct Smoother {
     double2* M = nullptr;           // X^(k+1) of a fused pair of relax sweeps (perimeter + first-interior ring only)
     double2* M2 = nullptr;          // coupled triples: X^(k+2) on the perimeter and in the zone next to sides whose perimeter rows move
     bool fuse_pairs = false;
-    bool relax2_store_nt = true;     // K2x2 result stores streaming (nt) or plain: by the rank's footprint against the Infinity Cache (create())
+    bool relax2_store_nt = true;     // K2x2 result stores streaming (nt) or plain: by the rank's footprint against the Infinity Cache (decide_schedule())
     bool pair_sync_events = false;   // TM_PAIR_SYNC=events when the handle was created: multi-rank sweep pairs ordered by events, not device counters
-    size_t inside_lds = 0;          // dynamic LDS of the interior pass of a multi-rank sweep pair (occupancy cap, see create())
-    // perimeter rows
+    size_t inside_lds = 0;          // dynamic LDS of the interior pass of a multi-rank sweep pair (occupancy cap, see decide_schedule())
+    // perimeter rows (run tables: tm_edge_tables.cpp)
     EdgeRowsDev edge;
-    std::vector<double> h_rhs;   // host copy of the static rhs (refilled on upload), lp.rows order
-    std::vector<int32_t> order_all, order_nf, order_nf_g;   // run order of the three row tables (see build_table)
-    double* d_rhs = nullptr;
+    std::vector<double> h_rhs;   // host copy of the static rhs (refilled on upload), lp.rows order; never resized after create (rhs_tables point into it)
+    // per run table, in the order they were built: the device right-hand sides and, per position in run order, where the pair comes
+    // from -- a slot of h_rhs, a ghost row's static rhs (lp.ghost_rows / ghost_rows2) or the zero pair of an interior row
+    struct RhsTable {
+        double* dev = nullptr;
+        std::vector<const double*> src;
+    };
+    std::vector<RhsTable> rhs_tables;
     // relax mode: the perimeter rows that are not `fixed` (the only ones a sweep has to evaluate), and per owned block which
-    // sides carry such rows
+    // sides carry such rows (moving_sides)
     EdgeRowsDev edge_nf;
-    double* d_rhs_nf = nullptr;
     EdgeRowsDev edge_nf_g;          // the same + the depth-1 ghost rows (multi-rank sweep pairs; empty otherwise)
-    double* d_rhs_nf_g = nullptr;
-    std::vector<size_t> nf_rows;
     std::vector<int> dyn_mask;
     std::vector<const int32_t*> border_ids;   // per owned block: device list of the K2x2 border tiles
     std::vector<int> border_n;
@@ -132,13 +135,9 @@ struct Smoother {
     // Coupled triples (single process): K2x3 with a frozen perimeter stores everything but the nodes within two of a side whose
     // perimeter rows move; three perimeter-row passes evaluate the perimeter and that zone level by level (rows within 4 / 3 / 2 nodes)
     bool triples_coupled = false;
-    EdgeRowsDev edge_L[3];
-    std::vector<EdgeRun> runs_L[3];          // host copies of the three level tables' runs (strip plan of the fused level kernel)
+    EdgeRowsDev edge_L[3];          // zone rows (zone_rows): level 1: distance <= 4, level 2: <= 3, level 3: <= 2
     bool levels_fused = false;               // the three level passes of a coupled triple in one launch (k_edge_levels3; TM_LEVELS_FUSED=0: three launches)
     FusedLevelsDev fused_levels;
-    double* d_rhs_L[3] = {nullptr, nullptr, nullptr};
-    std::vector<int32_t> order_L[3];
-    std::vector<PlanRow> zone_rows[3];   // KIND_INTERIOR rows of the zones (level 1: distance <= 4, level 2: <= 3, level 3: <= 2)
     bool pipelined_single = false;   // single process, coupled blocks: perimeter-row passes on the chain's queue beside the interior pass
     // halo exchange
     int32_t* d_send_ids = nullptr;
@@ -233,7 +232,7 @@ struct Smoother {
                        double2* rout = nullptr, double2* uio = nullptr);
     bool lazy = false;
     double* part_buf[3] = {nullptr, nullptr, nullptr};
-    // TM_PARTIALS_GUARD (see create): a guard region behind part_buf[0..2] and behind red, compared by check_guards
+    // TM_PARTIALS_GUARD (see alloc_reductions): a guard region behind part_buf[0..2] and behind red, compared by check_guards
     static constexpr uint64_t GUARD_DOUBLES = 2048 * MAX_PARTIALS;
     static constexpr int GUARD_BYTE = 0xA5;
     bool partials_guard = false;
@@ -264,6 +263,20 @@ struct Smoother {
     uint64_t inner_counts[2] = {0, 0};   // inner iterations of the last outer iteration per component (tm_smoother_inner_counts)
 
    private:
+    // create(), step by step
+    struct Selection;
+    bool reference() const { return opt.inner == TM_INNER_REFERENCE_GMRES; }
+    double2* vec() { return arena.alloc_n<double2>(static_cast<uint64_t>(n_local)); }
+    void resolve_options(const tm_mesh_desc* mesh, const tm_solver_opt* o, const tm_control_fn* c, const tm_comm_hooks* h, bool measure);
+    void plan_mesh(const tm_mesh_desc* mesh, const tm_comm_hooks* h, bool measure);
+    void alloc_vectors(const tm_mesh_desc* mesh, bool measure);
+    void decide_schedule();
+    void* upload_table(const void* src, uint64_t bytes);   // arena memory holding a host table (the sizing call only counts it)
+    RunTable make_table(const Selection& sel, EdgeRowsDev& e);
+    void build_row_tables();
+    uint64_t size_launches();
+    void alloc_reductions(uint64_t npart);
+    void finish_create(const tm_mesh_desc* mesh);
     int picard_bicgstab(tm_stats& st);
     int picard_gmres(tm_stats& st);
     int picard_reference(tm_stats& st);
