@@ -54,7 +54,10 @@ int tm_abi_version(void);
  * that wants them installs a sink: what = 0 announces iteration `iteration`, what = 1 carries its residual in `value`.
  * Process-wide like the reference's logger; NULL (the default) switches it off.  With a sink installed every outer
  * iteration ends with a reduction and a host round trip -- in TM_INNER_RELAX mode (one sweep = one outer iteration)
- * that means one sweep per kernel pass and one synchronisation per sweep, so install it for diagnosis, not for speed. */
+ * that means one sweep per kernel pass and one synchronisation per sweep, so install it for diagnosis, not for speed.
+ * tm_csr_solve with TM_OPT_REFINE reports its refinement through the same sink, once per call behind the last step (`iteration` = 0):
+ * what = 2: `value` = refinement steps taken (0 .. 3); what = 3 / what = 4: ||d||_2 / ||x||_2 of the last step's update for the x- / the
+ * y-component (0 when no step ran); what = 5: `value` = inner iterations spent in the correction solves. */
 typedef void (*tm_log_fn)(void* ctx, int32_t what, uint64_t iteration, double value);
 void tm_set_log(tm_log_fn sink, void* ctx);
 
@@ -162,6 +165,24 @@ enum {
                                 and substitutions level by level on the device, bit-identical to the reference's recurrence (left preconditioner of
                                 GMRES(30) in TM_INNER_REFERENCE_GMRES).  The matrix-free inner strategies answer TM_E_UNSUPPORTED: they never
                                 assemble a matrix to factorise                                                                          */
+    TM_OPT_REFINE = 16,      /* iterative refinement of every inner solve.  Up to 3 times behind the solve: r = b - A x in double-double arithmetic,
+                                rounded once to fp64 (the kernel of tm_csr_residual); A d = r solved from d = 0 by the same solver and
+                                preconditioner, stop test relative to ||D^-1 r|| with the mode's own rtol (the stall guard ends a correction that
+                                cannot get there); x <- x + d in fp64.  Stops early behind a step with ||d||_2 <= 2^-52 ||x||_2 in both components.
+                                The result is the exact solution of the system rounded to fp64, within an ulp or two at the top of its range,
+                                where the plain solve leaves conditioning x rtol.
+                                tm_csr_solve: all four solver x preconditioner combinations, on the caller's A and b; stats count the correction
+                                iterations too, the figures of the refinement reach the caller through tm_set_log (what = 2 .. 5).
+                                Handles: TM_INNER_BICGSTAB, TM_INNER_MG_BICGSTAB, TM_INNER_GMRES (TM_INNER_AUTO resolves first), single process.
+                                Per outer iteration the handle fills the reference-order assembled system of the frozen coordinates
+                                (tm_smoother_assemble_csr: the reference's matrix bit for bit; allocated at create) and refines the solution
+                                against THAT system and its right-hand side -- the refined Picard iterate is defined by the reference's matrix,
+                                not by the factored matrix-free operator, on which the corrections run (coefficients within 16 eps: harmless for
+                                a correction).  Residual and copy-back, the White update, tm_stats and iterate_until* are as without the flag;
+                                tm_smoother_refine_report has the figures.  TM_E_UNSUPPORTED at create, in tm_smoother_workspace_bytes and in
+                                tm_smooth_mesh with TM_INNER_RELAX (no solve to refine), TM_INNER_REFERENCE_GMRES (its contract is the
+                                reference's loose stop test), TM_OPT_RTOL_INITIAL (inexact Picard by intent) and rank hooks (the assembled system
+                                is single-process).  Flag clear: not one launch more, bit-identical results                                  */
     TM_OPT_RTOL_INITIAL = 4  /* Krylov modes: `rtol` is relative to the INITIAL residual of each inner solve (inexact Picard: stop at
                                 ||D^-1(b-Ax)|| <= max(atol, rtol ||D^-1(b-A x0)||), rtol = 0 -> 1e-2) instead of ||D^-1 b||.  Every solve then
                                 does work in proportion to what is left -- same fixed point, several times fewer inner iterations on the way
@@ -234,6 +255,15 @@ int tm_smooth_mesh(const tm_mesh_desc* mesh, uint64_t iterations, const tm_solve
 int tm_csr_solve(uint64_t n, const int32_t* Ap, const int32_t* Ai, const double* Ax_x, const double* Ax_y /* may be NULL */,
                  const double* bx, const double* by, double* x /* in: guess, out */, double* y, const tm_solver_opt* opt /* may be NULL */,
                  tm_stats* stats /* may be NULL */);
+
+/* The residual of ANY solution of such a system -- this library's or not: r = b - A x per component, every product a_ij x_j formed exactly,
+ * the sum carried in double-double arithmetic (an unevaluated pair of doubles, error-free additions) with b in the same sum, rounded once to
+ * fp64.  Same arguments as tm_csr_solve (host pointers; Ax_y NULL = the x values for both); rx / ry [n] receive the residuals.  Valid for
+ * finite inputs whose products neither overflow nor fall into the subnormal range: there
+ *     |r_i - exact| <= 2^-53 |r_i| + (nnz_i + 1) 2^-104 (sum_j |a_ij x_j| + |b_i|)
+ * however much cancels (an fp64 residual of a good solution is wrong in every digit); outside it the result is an fp64 residual's. */
+int tm_csr_residual(uint64_t n, const int32_t* Ap, const int32_t* Ai, const double* Ax_x, const double* Ax_y /* may be NULL */,
+                    const double* bx, const double* by, const double* x, const double* y, double* rx, double* ry);
 
 /* ------------------------------------------------------------------ persistent handle
  * Same smoother with the coordinates resident in HBM between calls (for callers that iterate,
@@ -346,6 +376,15 @@ int tm_smoother_assemble_csr(tm_smoother* s, int32_t* Ap, int32_t* Ai, double* A
 int tm_smoother_apply_reference_order(tm_smoother* s, const double* in_xy, double* out_xy);
 /* Right-hand side b (2*dof doubles) for the current coordinates (smooth.zig:780-921, 1060-1061). */
 int tm_smoother_rhs(tm_smoother* s, double* rhs_xy);
+/* r = b - A(X) xy by the kernel of tm_csr_residual, against the system ASSEMBLED from the resident coordinates X (tm_smoother_assemble_csr:
+ * the reference's matrix bit for bit) and its right-hand side (tm_smoother_rhs), nothing leaving the device but the result: how far a
+ * field is from solving the frozen-coefficient system of the current coordinates.  xy: 2*dof doubles in global row order, NULL = the
+ * resident coordinates themselves (the nonlinear residual of the mesh); r_xy: 2*dof doubles.  Single-process handles only. */
+int tm_smoother_residual(tm_smoother* s, const double* xy /* NULL = the resident coordinates */, double* r_xy);
+/* What the refinement of a handle created with TM_OPT_REFINE did (TM_E_UNSUPPORTED without the flag); any pointer may be NULL. */
+int tm_smoother_refine_report(const tm_smoother* s, uint32_t* steps_x_y /* [2]: steps of the last outer iteration (both components advance together) */,
+                              double* last_update_rel /* [2]: ||d||_2 / ||x||_2 of its last step */,
+                              uint64_t* correction_iterations /* inner iterations spent in corrections, summed over the handle's life */);
 /* Row kind per global row: -1 interior, else BlockBoundaryPointKind (smooth.zig:1168-1174). */
 int tm_smoother_row_kinds(const tm_smoother* s, int32_t* kinds /* [dof] */);
 uint64_t tm_smoother_dof(const tm_smoother* s);

@@ -28,6 +28,9 @@ def main(argv=None):
                     help="use the hip solver with this inner strategy instead of the solver named in the file; `file` = the device counterpart of "
                          "the solver the file names (gmres -> GMRES(30) on the device, bicgstab -> BiCGStab; ilu0 -> diagonal); `reference` = the file's "
                          "solver as written: gmres + ilu0 / diagonal on the assembled system with the reference's tolerances")
+    ap.add_argument("--refine", action="store_true",
+                    help="refine every inner solve with a double-double residual (up to 3 steps): each Picard iterate is the exact one rounded to fp64; "
+                         "with --hip auto, bicgstab, mg_bicgstab, gmres or file, not with relax or reference")
     ap.add_argument("--iterations", type=int, help="override smoothing.iterations")
     ap.add_argument("--output", help="override the output file (.xyz / .p3d: multi-block PLOT3D)")
     ap.add_argument("--until", type=float, metavar="TOL",
@@ -37,6 +40,8 @@ def main(argv=None):
     ap.add_argument("--fail-on-inverted", action="store_true",
                     help="exit non-zero when the smoothed mesh has inverted or degenerate cells (implies the quality evaluation)")
     args = ap.parse_args(argv)
+    if args.refine and args.hip in ("relax", "reference"):
+        ap.error("--refine goes with --hip auto, bicgstab, mg_bicgstab, gmres or file (relax has no inner solve to refine; reference keeps the reference's stop test)")
     logging.basicConfig(level=logging.INFO, format="%(levelname)s(%(name)s): %(message)s")
 
     with open(args.config) as f:
@@ -51,6 +56,8 @@ def main(argv=None):
             logging.getLogger("smoothing").warning(note)
     elif args.hip:
         inp.solver = solver.Option.hip(inner=getattr(solver.Inner, args.hip))
+    if args.refine:
+        inp.solver.refine = True
     if inp.solver.tag != solver.Tag.hip:
         sys.exit(f"error.ExternalSolverNotEnabled: solver `{inp.solver.tag.name}` is served by the Zig program; "
                  "use \"solver\": {\"hip\": {}} in the input file or pass --hip")
@@ -75,6 +82,10 @@ def main(argv=None):
             if stats["not_converged"]:
                 slog.warning("hip solve did not converge in %d of %d outer iterations", stats["not_converged"], stats["outer_iterations"])
             slog.info("elapsed time for smoothing: %.2f s", stats["seconds"])
+        if args.refine:
+            rep = sm.refine_report()
+            slog.info("refinement: %d steps in the last iteration, last update %.1e / %.1e of the solution, %d inner iterations in corrections",
+                      rep["steps"][0], *rep["last_update_rel"], rep["correction_iterations"])
         sm.download()
         stats["inner"] = sm.inner.name
         if want_quality:

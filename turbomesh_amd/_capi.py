@@ -23,6 +23,7 @@ _ERR_NAMES = {-1: "InconsistentSize", -2: "Topology", -3: "Mismatch", -4: "Overf
 TM_SOLVER_GMRES, TM_SOLVER_BICGSTAB, TM_SOLVER_UMFPACK, TM_SOLVER_PETSC, TM_SOLVER_HIP = 0, 1, 2, 3, 4
 TM_INNER_BICGSTAB, TM_INNER_RELAX, TM_INNER_MG_BICGSTAB, TM_INNER_AUTO, TM_INNER_GMRES, TM_INNER_REFERENCE_GMRES = 0, 1, 2, 3, 4, 5
 TM_CF_LAPLACE, TM_CF_WHITE = 0, 1
+TM_OPT_REFINE = 16
 
 
 class TmError(RuntimeError):
@@ -136,6 +137,7 @@ EXPORTS = [
     "tm_dev_relax_partials_needed", "tm_export_soa", "tm_smoother_export_soa", "tm_rccl_unique_id", "tm_rccl_comm_create", "tm_rccl_comm_destroy", "tm_rccl_hooks",
     "tm_rccl_peer_table_build", "tm_rccl_peer_table_free", "tm_white_math_probe", "tm_stream_probe", "tm_smoother_queue_ordering", "tm_smoother_inner", "tm_csr_ilu0_probe", "tm_rccl_hooks_for", "tm_smoother_assemble_csr", "tm_smoother_apply_reference_order",
     "tm_smoother_inner_counts", "tm_mesh_quality", "tm_mesh_quality_host", "tm_smoother_quality", "tm_smoother_quality_field",
+    "tm_csr_residual", "tm_smoother_residual", "tm_smoother_refine_report",
     "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
 ]
 
@@ -178,6 +180,7 @@ def lib():
         L.tm_last_error.restype = C.c_char_p
         L.tm_csr_solve.argtypes = [C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(tm_solver_opt),
                                    C.POINTER(tm_stats)]
+        L.tm_csr_residual.argtypes = [C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [_dp] * 8
         L.tm_set_log.argtypes = [LOG_FN, C.c_void_p]
         L.tm_set_log.restype = None
         L.tm_smoother_dof.restype = C.c_uint64
@@ -201,6 +204,8 @@ def lib():
         L.tm_smoother_exchange_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_int32))] + [C.POINTER(C.POINTER(C.c_int64))] * 4
         L.tm_smoother_apply.argtypes = [C.c_void_p, _dp, _dp, C.c_int]
         L.tm_smoother_rhs.argtypes = [C.c_void_p, _dp]
+        L.tm_smoother_residual.argtypes = [C.c_void_p, _dp, _dp]
+        L.tm_smoother_refine_report.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), _dp, C.POINTER(C.c_uint64)]
         L.tm_smoother_assemble_csr.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.tm_smoother_apply_reference_order.argtypes = [C.c_void_p, _dp, _dp]
         L.tm_smoother_row_kinds.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]

@@ -10,6 +10,7 @@ using namespace tmh;
 
 #include "tm_api_util.hpp"
 #include "tm_ilu.hpp"
+#include "tm_refine.hpp"
 #include "tm_quality_dev.hpp"
 
 static void require_gfx950() {
@@ -88,6 +89,54 @@ int tm_debug_ilu0_apply_ms(uint64_t n64, const int32_t* Ap, const int32_t* Ai, c
         for (int q = 0; q < repeats; ++q) {
             HIPCHK(hipEventRecord(e0, nullptr));
             ilu.apply(d_r.as<double2>(), d_z.as<double2>(), nullptr, false);
+            HIPCHK(hipEventRecord(e1, nullptr));
+            HIPCHK(hipEventSynchronize(e1));
+            float ms = 0.f;
+            HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+            ms_out[q] = ms;
+        }
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        return TM_OK;
+    });
+}
+// the double-double residual kernel (which != 0: k_csr_residual_dd) or the fp64 one it is measured against (0: k_csr_apply<true, DOT_NONE>) on a
+// caller-assembled system, both components, an event pair per repeat after a warm-up (tools/refine_timing.py); ms_out[repeats]
+int tm_debug_csr_residual_ms(uint64_t n64, const int32_t* Ap, const int32_t* Ai, const double* Ax, int which, int repeats, double* ms_out) {
+    return guarded([&]() {
+        if (!Ap || !Ai || !Ax || !ms_out || repeats < 1) throw TmError(TM_E_ARG, "null argument");
+        if (n64 == 0 || n64 >= (uint64_t{1} << 31)) throw TmError(TM_E_SIZE, "system size out of range");
+        require_gfx950();
+        const int n = static_cast<int>(n64);
+        const size_t nnz = static_cast<size_t>(Ap[n]);
+        for (size_t k = 0; k < nnz; ++k)
+            if (Ai[k] < 0 || Ai[k] >= n) throw TmError(TM_E_ARG, "InvalidMatrix: column index out of range");
+        const size_t vb = sizeof(double2) * static_cast<size_t>(n);
+        Dev d_p(sizeof(int32_t) * (static_cast<size_t>(n) + 1)), d_i(sizeof(int32_t) * nnz), d_v(sizeof(double) * nnz), d_x(vb), d_b(vb), d_r(vb), d_dinv(vb);
+        HIPCHK(hipMemcpy(d_p.p, Ap, sizeof(int32_t) * (static_cast<size_t>(n) + 1), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_i.p, Ai, sizeof(int32_t) * nnz, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_v.p, Ax, sizeof(double) * nnz, hipMemcpyHostToDevice));
+        std::vector<double2> w(static_cast<size_t>(n));
+        for (int k = 0; k < n; ++k) w[k] = make_double2(1.0 + 1e-3 * (k % 97), 1.0 - 1e-3 * (k % 89));
+        HIPCHK(hipMemcpy(d_x.p, w.data(), vb, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_b.p, w.data(), vb, hipMemcpyHostToDevice));
+        HIPCHK(launch_csr_dinv(n, d_p.as<int32_t>(), d_i.as<int32_t>(), d_v.as<double>(), d_v.as<double>(), d_dinv.as<double2>(), nullptr));
+        auto run = [&]() {
+            if (which)
+                HIPCHK(launch_csr_residual_dd(n, d_p.as<int32_t>(), d_i.as<int32_t>(), d_v.as<double>(), d_v.as<double>(), d_x.as<double2>(), d_b.as<double2>(),
+                                              d_r.as<double2>(), nullptr));
+            else
+                HIPCHK(launch_csr_scaled_residual_plain(n, d_p.as<int32_t>(), d_i.as<int32_t>(), d_v.as<double>(), d_v.as<double>(), d_dinv.as<double2>(), d_x.as<double2>(),
+                                                        d_b.as<double2>(), d_r.as<double2>(), nullptr));
+        };
+        run();   // warm-up
+        HIPCHK(hipDeviceSynchronize());
+        hipEvent_t e0, e1;
+        HIPCHK(hipEventCreate(&e0));
+        HIPCHK(hipEventCreate(&e1));
+        for (int q = 0; q < repeats; ++q) {
+            HIPCHK(hipEventRecord(e0, nullptr));
+            run();
             HIPCHK(hipEventRecord(e1, nullptr));
             HIPCHK(hipEventSynchronize(e1));
             float ms = 0.f;
@@ -442,6 +491,25 @@ int tm_smoother_rhs(tm_smoother* s, double* rhs_xy) {
     return guarded([&]() {
         if (!s || !rhs_xy) throw TmError(TM_E_ARG, "null argument");
         s->impl.rhs_host(rhs_xy);
+        return TM_OK;
+    });
+}
+int tm_smoother_residual(tm_smoother* s, const double* xy, double* r_xy) {
+    return guarded([&]() {
+        if (!s || !r_xy) throw TmError(TM_E_ARG, "null argument");
+        s->impl.residual_host(xy, r_xy);
+        return TM_OK;
+    });
+}
+int tm_smoother_refine_report(const tm_smoother* s, uint32_t* steps_x_y, double* last_update_rel, uint64_t* correction_iterations) {
+    return guarded([&]() {
+        if (!s) throw TmError(TM_E_ARG, "null handle");
+        if (!s->impl.refine()) throw TmError(TM_E_UNSUPPORTED, "the handle was created without TM_OPT_REFINE");
+        for (int c = 0; c < 2; ++c) {
+            if (steps_x_y) steps_x_y[c] = s->impl.refine_steps;
+            if (last_update_rel) last_update_rel[c] = s->impl.refine_rel[c];
+        }
+        if (correction_iterations) *correction_iterations = s->impl.refine_iterations;
         return TM_OK;
     });
 }

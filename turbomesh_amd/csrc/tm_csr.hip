@@ -11,6 +11,7 @@
 #include "tm_api_util.hpp"
 #include "tm_devutil.hpp"
 #include "tm_ilu.hpp"
+#include "tm_refine.hpp"
 #include <array>
 #include <chrono>
 #include <cstring>
@@ -485,6 +486,12 @@ hipError_t launch_csr_scaled_residual(int n, const int32_t* p, const int32_t* ci
     hipLaunchKernelGGL((k_csr_apply<true, DOT_OUT2>), dim3(csr_nwg(n)), dim3(256), 0, st, A, in, b, static_cast<const double2*>(nullptr), out, partials);
     return hipGetLastError();
 }
+hipError_t launch_csr_scaled_residual_plain(int n, const int32_t* p, const int32_t* ci, const double* vx, const double* vy, const double2* dinv, const double2* in,
+                                            const double2* b, double2* out, hipStream_t st) {
+    const CsrDev A{n, p, ci, vx, vy, dinv};
+    hipLaunchKernelGGL((k_csr_apply<true, DOT_NONE>), dim3(csr_nwg(n)), dim3(256), 0, st, A, in, b, static_cast<const double2*>(nullptr), out, static_cast<double*>(nullptr));
+    return hipGetLastError();
+}
 hipError_t launch_csr_norm2(int n, const double2* v, double* partials, hipStream_t st) {
     hipLaunchKernelGGL(k_csr_norm2, dim3(csr_nwg(n)), dim3(256), 0, st, n, v, partials);
     return hipGetLastError();
@@ -644,19 +651,29 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
             S = other;
             return L;
         };
-        double2 *u = d_u.as<double2>(), *r = d_r.as<double2>(), *r_hat = d_rh.as<double2>(), *p = d_pv.as<double2>(), *v = d_v.as<double2>(),
+        double2 *r = d_r.as<double2>(), *r_hat = d_rh.as<double2>(), *p = d_pv.as<double2>(), *v = d_v.as<double2>(),
                 *s = d_s.as<double2>(), *t = d_t.as<double2>();
-        hipLaunchKernelGGL(k_csr_bnorm, dim3(nwg), dim3(256), 0, st, n, d_b.as<double2>(), A.dinv, partials);
+        // one solve of A u = bvec from the guess in u, stop test relative to ||D^-1 bvec||: the call's own solve and, with TM_OPT_REFINE, the
+        // corrections behind it (bvec = the double-double residual, u = 0)
+        struct SolveOut {
+            bool converged = false;
+            uint64_t iterations = 0, sweeps = 0;
+            double rr0[2] = {0.0, 0.0};
+        };
+        const bool use_gmres = opt.inner == TM_INNER_GMRES;
+        Dev d_W(use_gmres ? vb : 0), d_V(use_gmres ? vb * (GMRES_M + 1) : 0), d_G(use_gmres ? sizeof(GmresScalars) : 0);
+        auto solve = [&](const double2* bvec, double2* u, double rtol) -> SolveOut {
+        SolveOut out;
+        hipLaunchKernelGGL(k_csr_bnorm, dim3(nwg), dim3(256), 0, st, n, bvec, A.dinv, partials);
         HIPCHK(hipGetLastError());
-        HIPCHK(launch_finalize_scalar(partials, nwg, red, S, STEP_TOL, st, opt.rtol, opt.atol));
+        HIPCHK(launch_finalize_scalar(partials, nwg, red, S, STEP_TOL, st, rtol, opt.atol));
 
-        if (opt.inner == TM_INNER_GMRES) {
+        if (use_gmres) {
             // The reference's other Krylov solver in the slot (GMRES.zig:300-423; csrc/tm_gmres.hip for the kernels): restarted GMRES(30), LEFT
             // preconditioned (GMRES.zig:335-336: z = M^-1 (A v)) with the diagonal -- the row-equilibrated operator the BiCGStab branch uses --
             // or with ILU(0): M^-1 A v = M^-1 (D (D^-1 A v)), the substitution multiplying its right-hand side by the diagonal.  Stop test:
             // GMRES's own residual norm |g_{j+1}| = ||P (b - A x)|| <= max(atol, rtol ||P b||), P the preconditioner (with the diagonal: the
             // scale-aware test of every other path).
-            Dev d_W(vb), d_V(vb * (GMRES_M + 1)), d_G(sizeof(GmresScalars));
             double2 *W = d_W.as<double2>(), *V = d_V.as<double2>();
             GmresScalars* G = d_G.as<GmresScalars>();
             HIPCHK(hipMemsetAsync(G, 0, sizeof(GmresScalars), st));
@@ -668,14 +685,14 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
                 HIPCHK(launch_finalize(partials, nwg, red, st));
             };
             if (use_ilu) {
-                ilu->apply(d_b.as<double2>(), W, st, false);   // M^-1 b
+                ilu->apply(bvec, W, st, false);   // M^-1 b
                 norm2_of(W);
             } else {
-                hipLaunchKernelGGL(k_csr_bnorm, dim3(nwg), dim3(256), 0, st, n, d_b.as<double2>(), A.dinv, partials);
+                hipLaunchKernelGGL(k_csr_bnorm, dim3(nwg), dim3(256), 0, st, n, bvec, A.dinv, partials);
                 HIPCHK(hipGetLastError());
                 HIPCHK(launch_finalize(partials, nwg, red, st));
             }
-            HIPCHK(launch_gm_tol(G, red, opt.rtol, opt.atol, st));
+            HIPCHK(launch_gm_tol(G, red, rtol, opt.atol, st));
             GmresScalars h_G;
             auto poll = [&]() {
                 HIPCHK(hipMemcpyAsync(&h_G, G, sizeof(GmresScalars), hipMemcpyDeviceToHost, st));
@@ -686,7 +703,7 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
             bool converged = false, first = true;
             double rr0[2] = {0.0, 0.0};
             while (it_total < opt.max_inner) {
-                hipLaunchKernelGGL((k_csr_apply<true, DOT_OUT2>), dim3(nwg), dim3(256), 0, st, A, u, d_b.as<double2>(), nullptr, W, partials);   // D^-1 (b - A x)
+                hipLaunchKernelGGL((k_csr_apply<true, DOT_OUT2>), dim3(nwg), dim3(256), 0, st, A, u, bvec, nullptr, W, partials);   // D^-1 (b - A x)
                 HIPCHK(hipGetLastError());
                 if (use_ilu) {
                     ilu->apply(W, W, st);   // M^-1 (b - A x)
@@ -736,21 +753,12 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
                     break;
                 }
             }
-            hipLaunchKernelGGL(k_deinterleave, dim3(nwg), dim3(256), 0, st, n, u, tmp, tmp + n);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(x, tmp, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipMemcpyAsync(y, tmp + n, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            if (stats) {
-                std::memset(stats, 0, sizeof(*stats));
-                stats->outer_iterations = 1;
-                stats->inner_iterations = it_total;
-                stats->operator_sweeps = it_total + (it_total + GMRES_M - 1) / GMRES_M + 1;
-                stats->scaled_residual_rms = std::sqrt((rr0[0] + rr0[1]) / (2.0 * n));   // of P (b - A x0), P the preconditioner
-                stats->not_converged = converged ? 0 : 1;
-                stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            }
-            return converged ? TM_OK : TM_W_NOT_CONVERGED;
+            out.converged = converged;
+            out.iterations = it_total;
+            out.sweeps = it_total + (it_total + GMRES_M - 1) / GMRES_M + 1;
+            out.rr0[0] = rr0[0];   // of P (b - A x0), P the preconditioner
+            out.rr0[1] = rr0[1];
+            return out;
         }
 
         KrylovScalars h_S;
@@ -769,7 +777,7 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
         uint64_t stall_since = 0;
         const uint64_t stall_window = std::max<uint64_t>(4000, static_cast<uint64_t>(4.0 * std::sqrt(static_cast<double>(n))));
         while (true) {
-            hipLaunchKernelGGL((k_csr_apply<true, DOT_OUT2>), dim3(nwg), dim3(256), 0, st, A, u, d_b.as<double2>(), nullptr, r, partials);
+            hipLaunchKernelGGL((k_csr_apply<true, DOT_OUT2>), dim3(nwg), dim3(256), 0, st, A, u, bvec, nullptr, r, partials);
             HIPCHK(hipGetLastError());
             flush_pending();
             HIPCHK(launch_finalize_scalar(partials, nwg, red, S, STEP_INIT, st));
@@ -848,6 +856,54 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
             if (converged || !breakdown || stalled || restarts >= 8 || it_total >= opt.max_inner) break;
             restarts += 1;   // rho or omega vanished: restart from the current iterate (the reference only warns, BiCGStab.zig:368-369)
         }
+        npending = 0;   // scalar steps still pending belong to an iteration nobody reads
+        out.converged = converged;
+        out.iterations = it_total;
+        out.sweeps = 1 + static_cast<uint64_t>(restarts) + 2 * it_total;
+        out.rr0[0] = rr0[0];
+        out.rr0[1] = rr0[1];
+        return out;
+        };
+
+        double2* const u = d_u.as<double2>();
+        const SolveOut first = solve(d_b.as<double2>(), u, opt.rtol);
+        uint64_t it_total = first.iterations, sweeps = first.sweeps;
+        if (opt.flags & TM_OPT_REFINE) {
+            // Iterative refinement (tm_refine.hpp): r = b - A u in double-double, A d = r from d = 0 by the same solver and preconditioner with
+            // the stop test relative to ||D^-1 r||, u += d; at most REFINE_MAX_STEPS times, one poll (four sums) per step.
+            // The corrections keep the call's own rtol: 1e-8 was tried and costs the flat 1e-10 bar on T106;
+            // TM_REFINE_RTOL in the environment overrides it, for measurement.
+            double rtol_c = opt.rtol;
+            if (const char* e = std::getenv("TM_REFINE_RTOL"))
+                if (std::atof(e) > 0.0) rtol_c = std::atof(e);
+            Dev d_rr(vb), d_d(vb);
+            double h_red[MAX_PARTIALS] = {0.0};
+            uint32_t steps = 0;
+            uint64_t it_corr = 0;
+            double rel[2] = {0.0, 0.0};
+            for (int q = 0; q < REFINE_MAX_STEPS; ++q) {
+                HIPCHK(launch_csr_residual_dd(n, A.p, A.i, A.vx, A.vy, u, d_b.as<double2>(), d_rr.as<double2>(), st));
+                HIPCHK(hipMemsetAsync(d_d.p, 0, vb, st));
+                HIPCHK(hipMemsetAsync(S_buf[0], 0, sizeof(KrylovScalars) * 2, st));
+                const SolveOut c = solve(d_rr.as<double2>(), d_d.as<double2>(), rtol_c);
+                it_corr += c.iterations;
+                sweeps += c.sweeps + 1;
+                HIPCHK(launch_refine_update(n, u, d_d.as<double2>(), part_buf[0], st));
+                HIPCHK(launch_finalize(part_buf[0], nwg, red, st));
+                HIPCHK(hipMemcpyAsync(h_red, red, sizeof(double) * MAX_PARTIALS, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                steps += 1;
+                for (int c2 = 0; c2 < 2; ++c2) rel[c2] = h_red[2 + c2] > 0.0 ? std::sqrt(h_red[c2] / h_red[2 + c2]) : (h_red[c2] > 0.0 ? HUGE_VAL : 0.0);
+                if (refine_converged(h_red)) break;
+            }
+            it_total += it_corr;
+            if (const tm_log_fn sink = g_log_sink) {
+                sink(g_log_ctx, 2, 0, static_cast<double>(steps));
+                sink(g_log_ctx, 3, 0, rel[0]);
+                sink(g_log_ctx, 4, 0, rel[1]);
+                sink(g_log_ctx, 5, 0, static_cast<double>(it_corr));
+            }
+        }
         hipLaunchKernelGGL(k_deinterleave, dim3(nwg), dim3(256), 0, st, n, u, tmp, tmp + n);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(x, tmp, sizeof(double) * n, hipMemcpyDeviceToHost, st));
@@ -857,11 +913,60 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
             std::memset(stats, 0, sizeof(*stats));
             stats->outer_iterations = 1;
             stats->inner_iterations = it_total;
-            stats->operator_sweeps = 1 + static_cast<uint64_t>(restarts) + 2 * it_total;
-            stats->scaled_residual_rms = std::sqrt((rr0[0] + rr0[1]) / (2.0 * n));
-            stats->not_converged = converged ? 0 : 1;
+            stats->operator_sweeps = sweeps;
+            stats->scaled_residual_rms = std::sqrt((first.rr0[0] + first.rr0[1]) / (2.0 * n));
+            stats->not_converged = first.converged ? 0 : 1;
             stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         }
-        return converged ? TM_OK : TM_W_NOT_CONVERGED;
+        return first.converged ? TM_OK : TM_W_NOT_CONVERGED;
+    });
+}
+
+// r = b - A x of a caller's system by k_csr_residual_dd (tm_refine.hip): the check a user runs on any solution
+extern "C" int tm_csr_residual(uint64_t n64, const int32_t* Ap, const int32_t* Ai, const double* Ax_x, const double* Ax_y, const double* bx, const double* by,
+                               const double* x, const double* y, double* rx, double* ry) {
+    return guarded([&]() {
+        if (!Ap || !Ai || !Ax_x || !bx || !by || !x || !y || !rx || !ry) throw TmError(TM_E_ARG, "null argument");
+        if (n64 == 0 || n64 >= (uint64_t{1} << 31)) throw TmError(TM_E_SIZE, "system size out of range");
+        const int n = static_cast<int>(n64);
+        if (Ap[0] != 0 || Ap[n] < 0) throw TmError(TM_E_ARG, "InvalidMatrix: row pointers must start at 0");
+        const size_t nnz = static_cast<size_t>(Ap[n]);
+        for (int r = 0; r < n; ++r)
+            if (Ap[r + 1] < Ap[r]) throw TmError(TM_E_ARG, "InvalidMatrix: row pointers must not decrease");
+        for (size_t k = 0; k < nnz; ++k)
+            if (Ai[k] < 0 || Ai[k] >= n) throw TmError(TM_E_ARG, "InvalidMatrix: column index out of range");
+        int dev = 0;
+        HIPCHK(hipGetDevice(&dev));
+        hipDeviceProp_t prop;
+        HIPCHK(hipGetDeviceProperties(&prop, dev));
+        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) throw TmError(TM_E_HIP, std::string("libtm_hip is built for gfx950 (MI355X) only, found ") + prop.gcnArchName);
+
+        const bool two = Ax_y != nullptr && Ax_y != Ax_x;
+        const size_t vb = sizeof(double2) * static_cast<size_t>(n);
+        Dev d_p(sizeof(int32_t) * (static_cast<size_t>(n) + 1)), d_i(sizeof(int32_t) * nnz), d_vx(sizeof(double) * nnz), d_vy(two ? sizeof(double) * nnz : 0);
+        Dev d_b(vb), d_u(vb), d_tmp(sizeof(double) * 2 * static_cast<size_t>(n));
+        const int nwg = csr_nwg(n);
+        hipStream_t st = nullptr;
+        HIPCHK(hipMemcpyAsync(d_p.p, Ap, sizeof(int32_t) * (static_cast<size_t>(n) + 1), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_i.p, Ai, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_vx.p, Ax_x, sizeof(double) * nnz, hipMemcpyHostToDevice, st));
+        if (two) HIPCHK(hipMemcpyAsync(d_vy.p, Ax_y, sizeof(double) * nnz, hipMemcpyHostToDevice, st));
+        double* tmp = d_tmp.as<double>();
+        auto upload2 = [&](const double* a, const double* b, double2* out) {   // two host arrays -> one interleaved device vector
+            HIPCHK(hipMemcpyAsync(tmp, a, sizeof(double) * n, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(tmp + n, b, sizeof(double) * n, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_interleave, dim3(nwg), dim3(256), 0, st, n, tmp, tmp + n, out);
+            HIPCHK(hipGetLastError());
+        };
+        upload2(bx, by, d_b.as<double2>());
+        upload2(x, y, d_u.as<double2>());
+        HIPCHK(launch_csr_residual_dd(n, d_p.as<int32_t>(), d_i.as<int32_t>(), d_vx.as<double>(), two ? d_vy.as<double>() : d_vx.as<double>(), d_u.as<double2>(),
+                                      d_b.as<double2>(), d_b.as<double2>(), st));   // in place: a row reads its own b before it stores
+        hipLaunchKernelGGL(k_deinterleave, dim3(nwg), dim3(256), 0, st, n, d_b.as<double2>(), tmp, tmp + n);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rx, tmp, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ry, tmp + n, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return TM_OK;
     });
 }

@@ -80,6 +80,9 @@ hipError_t launch_csr_dinv(int n, const int32_t* p, const int32_t* ci, const dou
 // out = D^-1 (b - A in), partials: ||out||^2 per component
 hipError_t launch_csr_scaled_residual(int n, const int32_t* p, const int32_t* ci, const double* vx, const double* vy, const double2* dinv, const double2* in,
                                       const double2* b, double2* out, double* partials, hipStream_t st);
+// the same without the norm -- the fp64 residual kernel the double-double one is timed against (tools/refine_timing.py)
+hipError_t launch_csr_scaled_residual_plain(int n, const int32_t* p, const int32_t* ci, const double* vx, const double* vy, const double2* dinv, const double2* in,
+                                            const double2* b, double2* out, hipStream_t st);
 hipError_t launch_csr_norm2(int n, const double2* v, double* partials, hipStream_t st);   // partials: ||v||^2 per component
 hipError_t launch_csr_sub(int n, const double2* b, const double2* w, double2* r, hipStream_t st);          // r = b - w (GMRES.zig:313-315)
 hipError_t launch_csr_diag_precond(int n, const double2* dinv, const double2* r, double2* z, hipStream_t st);   // z = r * dinv (GMRES.zig:427-430)

@@ -10,6 +10,7 @@
 #include "tm_smoother.hpp"
 #include "tm_api_util.hpp"
 #include "tm_ilu.hpp"
+#include "tm_refine.hpp"
 #include "tm_quality_dev.hpp"
 #include <algorithm>
 #include <atomic>
@@ -173,6 +174,12 @@ void Smoother::resolve_options(const tm_mesh_desc* mesh, const tm_solver_opt* o,
         o->inner != TM_INNER_REFERENCE_GMRES)
         throw TmError(TM_E_ARG, "unknown inner strategy");
     opt = *o;
+    if (opt.flags & TM_OPT_REFINE) {   // refused before anything is allocated or launched
+        if (opt.inner == TM_INNER_RELAX) throw TmError(TM_E_UNSUPPORTED, "TM_OPT_REFINE: TM_INNER_RELAX has no inner solve to refine");
+        if (reference()) throw TmError(TM_E_UNSUPPORTED, "TM_OPT_REFINE: the contract of TM_INNER_REFERENCE_GMRES is the reference's loose stop test");
+        if (opt.flags & TM_OPT_RTOL_INITIAL) throw TmError(TM_E_UNSUPPORTED, "TM_OPT_REFINE: TM_OPT_RTOL_INITIAL is inexact Picard by intent");
+        if (hooks_usable(h)) throw TmError(TM_E_UNSUPPORTED, "TM_OPT_REFINE: the assembled system a refinement works against is available on single-process handles only");
+    }
     if ((opt.flags & TM_OPT_PRECOND_ILU0) && !reference())
         throw TmError(TM_E_UNSUPPORTED, "ILU(0) needs the assembled matrix: it is served by tm_csr_solve (seam 2) and by TM_INNER_REFERENCE_GMRES; the matrix-free path preconditions with the diagonal or the multigrid cycle");
     if (reference()) {
@@ -292,6 +299,16 @@ void Smoother::alloc_vectors(const tm_mesh_desc* mesh, bool measure) {
         t = vec();
     }
     if (white) PQ = vec();
+    if (refine()) {   // TM_OPT_REFINE: right-hand side, double-double residual, correction, 1 / a_ii of the assembled system
+        ref_b = vec();
+        rf_r = vec();
+        rf_d = vec();
+        rf_dinv = vec();
+        if (measure) {   // the assembled system itself comes from the HIP allocator, beside a caller's workspace: the sizing call counts it in
+            csr_build_pattern();
+            arena.alloc(sizeof(int32_t) * csr.h_p.size() + sizeof(int32_t) * csr.h_i.size() + 2 * sizeof(double) * csr.nnz);
+        }
+    }
     if (use_mg) {
         p_hat = vec();
         s_hat = vec();
@@ -575,7 +592,8 @@ uint64_t Smoother::size_launches() {
     // 2048 of them in every workgroup's prologue made T106 x 8 115 instead of 95 us)
     if (vk_able && std::max(nwg_apply, nwg_apply_ov) <= 512) nwg_vec = std::min(nwg_vec, 512);
     lazy = !has_hooks && opt.inner != TM_INNER_RELAX && std::max(std::max(nwg_apply, nwg_apply_ov), nwg_vec) <= 512 && !(opt.flags & TM_OPT_EAGER_SCALARS);
-    const uint64_t npart = static_cast<uint64_t>(std::max(std::max(std::max(std::max(nwg_apply, nwg_apply_ov), nwg_apply2), nwg3_all), nwg_vec)) * MAX_PARTIALS;
+    const int nwg_refine = refine() ? csr_nwg(n_owned) : 0;   // the CSR kernels of a refinement step: 256 rows per workgroup
+    const uint64_t npart = static_cast<uint64_t>(std::max(std::max(std::max(std::max(std::max(nwg_apply, nwg_apply_ov), nwg_apply2), nwg3_all), nwg_vec), nwg_refine)) * MAX_PARTIALS;
     // second apply of an iteration with the s-update folded in: single process (nothing of s has to travel) and no preconditioner
     // (which wants s as a stored vector)
     fuse_s = !has_hooks && opt.inner == TM_INNER_BICGSTAB && !(opt.flags & TM_OPT_EAGER_SCALARS);
@@ -604,7 +622,8 @@ uint64_t Smoother::size_launches() {
                      {"sweep triples", nwg3_all},
                      {"vector kernels", nwg_vec},
                      {"GMRES Gram-Schmidt", (opt.inner == TM_INNER_GMRES || reference()) ? vec_nwg(n_owned) : 0},
-                     {"perimeter-row right-hand side", opt.inner != TM_INNER_RELAX ? edge.nwg : 0}};
+                     {"perimeter-row right-hand side", opt.inner != TM_INNER_RELAX ? edge.nwg : 0},
+                     {"refinement step", nwg_refine}};
     if (std::getenv("TM_DEBUG_RUNS"))
         std::fprintf(stderr, "[tm] partial-sum rows: %d allocated; operator %d, overlapping strips %d, pairs %d, triples %d, vector kernels %d (vec_nwg %d)\n", rows,
                      nwg_apply, nwg_apply_ov, nwg_apply2, nwg3_all, nwg_vec, vec_nwg(n_owned));
@@ -672,6 +691,7 @@ void Smoother::finish_create(const tm_mesh_desc* mesh) {
     if (PQ) HIPCHK(hipMemsetAsync(PQ, 0, sizeof(double2) * n_local, stream));
     upload(mesh);
     if (white) white_launch(0);   // ControlFunction.init, wall_control_function.zig:27-42
+    if (refine()) csr_fill_values();       // pattern and value arrays of the assembled system, kept for the handle's lifetime (csr_release)
     if (reference()) reference_create();   // everything the mode needs, now: a mesh that does not fit fails here, not in the middle of a solve
     sync();
 }
@@ -1262,6 +1282,7 @@ int Smoother::picard_bicgstab(tm_stats& st) {
     }
     st.inner_iterations += (converged && poll_iters) ? poll_iters : it_total;
     flush_pending();
+    if (refine()) refine_solution();
 
     // residual + copy-back (smooth.zig:112-153); X becomes the new frozen field
     HIPCHK(launch_residual_copyback(X, U, n_owned, nwg_vec, partials, stream));
@@ -1345,6 +1366,7 @@ int Smoother::picard_gmres(tm_stats& st) {
         }
     }
     st.inner_iterations += it_total;
+    if (refine()) refine_solution();
 
     // residual + copy-back (smooth.zig:112-153); X becomes the new frozen field
     HIPCHK(launch_residual_copyback(X, U, n_owned, nwg_vec, partials, stream));
@@ -1356,6 +1378,147 @@ int Smoother::picard_gmres(tm_stats& st) {
     st.last_residual = (h_red[0] + h_red[1]) * (h_red[0] + h_red[1]);   // smooth.zig:136
     outer_done += 1;
     return converged ? 0 : 1;
+}
+
+// ------------------------------------------------------------------ iterative refinement of an inner solve (TM_OPT_REFINE; tm_refine.hpp)
+// U holds the solution the inner solver returned for the system frozen at X.  Up to REFINE_MAX_STEPS times: r = b - A U in double-double
+// against the REFERENCE-ORDER assembled system of X (csr_fill_values: the matrix the reference assembles, bit for bit -- the refined iterate
+// is defined by it, not by the factored matrix-free operator) and its right-hand side; D^-1 A d = D^-1 r solved from d = 0 by the mode's
+// own solver and preconditioner on the matrix-free operator (its coefficients lie within 16 eps of the assembled ones: harmless for a
+// correction), stop test relative to ||D^-1 r||; U += d.  One host round trip per step beyond the correction's own polls: the four sums
+// of the update.
+void Smoother::refine_solution() {
+    const int n = static_cast<int>(n_owned);
+    const int nwg = csr_nwg(n);
+    csr_fill_values();
+    HIPCHK(hipMemsetAsync(ref_b, 0, sizeof(double2) * n_local, stream));   // interior rows have b = 0
+    HIPCHK(launch_edge_rhs(edge, X, PQ, ref_b, 0, nullptr, stream));
+    HIPCHK(launch_csr_dinv(n, csr.p, csr.i, csr.vx, csr.vy, rf_dinv, stream));
+    refine_steps = 0;
+    refine_rel[0] = refine_rel[1] = 0.0;
+    refine_rtol = opt.rtol;   // the mode's own (TM_REFINE_RTOL overrides it, for measurement: DESIGN.md section 5)
+    if (const char* e = std::getenv("TM_REFINE_RTOL"))
+        if (std::atof(e) > 0.0) refine_rtol = std::atof(e);
+    for (int q = 0; q < REFINE_MAX_STEPS; ++q) {
+        HIPCHK(launch_csr_residual_dd(n, csr.p, csr.i, csr.vx, csr.vy, U, ref_b, rf_r, stream));
+        HIPCHK(launch_csr_diag_precond(n, rf_dinv, rf_r, rf_r, stream));
+        HIPCHK(hipMemsetAsync(rf_d, 0, sizeof(double2) * n_local, stream));
+        refine_iterations += opt.inner == TM_INNER_GMRES ? correct_gmres(rf_r, rf_d) : correct_bicgstab(rf_r, rf_d);
+        HIPCHK(launch_refine_update(n, U, rf_d, partials, stream));
+        HIPCHK(launch_finalize(partials, nwg, red, stream));
+        HIPCHK(hipMemcpyAsync(h_red, red, sizeof(double) * MAX_PARTIALS, hipMemcpyDeviceToHost, stream));
+        sync();
+        refine_steps += 1;
+        for (int c = 0; c < 2; ++c) refine_rel[c] = h_red[2 + c] > 0.0 ? std::sqrt(h_red[c] / h_red[2 + c]) : (h_red[c] > 0.0 ? HUGE_VAL : 0.0);
+        if (refine_converged(h_red)) break;
+    }
+}
+
+// D^-1 A d = rhs from d = 0 by the textbook BiCGStab sequence of picard_bicgstab (one kernel per vector update; with the multigrid cycle as
+// right preconditioner where the mode has it), tolerance rtol ||rhs||.  No restart: a correction that breaks down or stalls ends there, the
+// next refinement step starts from what it reached.  Returns the iterations run.
+uint64_t Smoother::correct_bicgstab(const double2* rhs, double2* d) {
+    const int n = static_cast<int>(n_owned);
+    HIPCHK(hipMemcpyAsync(r, rhs, sizeof(double2) * n_local, hipMemcpyDeviceToDevice, stream));   // r0 = rhs - A 0
+    HIPCHK(hipMemcpyAsync(r_hat, rhs, sizeof(double2) * n_local, hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipMemsetAsync(p, 0, sizeof(double2) * n_local, stream));
+    HIPCHK(hipMemsetAsync(v, 0, sizeof(double2) * n_local, stream));
+    HIPCHK(launch_csr_norm2(n, rhs, partials, stream));
+    reduce_update(csr_nwg(n), STEP_TOL, refine_rtol, opt.atol);   // tol = max(atol, rtol ||rhs||) ...
+    reduce_update(csr_nwg(n), STEP_INIT);                      // ... and ||r0||^2 from the same sums
+    flush_pending();   // (a launch of its own: a lazy step would have every workgroup of the next kernel sum these 256-row partials)
+    poll_iters = 0;
+    poll_open = false;
+    stall_best[0] = stall_best[1] = 0.0;
+    stall_since = 0;
+    stalled = false;
+    uint64_t it = 0;
+    while (it < opt.max_inner) {
+        HIPCHK(launch_p_update(scalars_for(), r, p, v, n_owned, nwg_vec, stream));
+        if (use_mg) {
+            precondition(p, p_hat);
+            apply(p_hat, v, MODE_SCALED, DOT_AUX, r_hat, X, 0.0, STEP_SIGMA);
+        } else {
+            apply(p, v, MODE_SCALED, DOT_AUX, r_hat, X, 0.0, STEP_SIGMA);
+        }
+        HIPCHK(launch_s_update(scalars_for(), r, v, s, n_owned, nwg_vec, partials, stream));
+        reduce_update(nwg_vec, STEP_SS);
+        if (use_mg) {
+            precondition(s, s_hat);
+            apply(s_hat, t, MODE_SCALED, DOT_AUX2, s, X, 0.0, STEP_TSTT);
+        } else {
+            apply(s, t, MODE_SCALED, DOT_IN, nullptr, X, 0.0, STEP_TSTT);
+        }
+        HIPCHK(launch_xr_update(scalars_for(), d, use_mg ? p_hat : p, use_mg ? s_hat : s, s, t, r, r_hat, n_owned, nwg_vec, partials, stream));
+        reduce_update(nwg_vec, STEP_RHO);
+        it += 1;
+        if (it % opt.check_every == 0 || it == opt.max_inner) {
+            const int verdict = poll_done(it, it == opt.max_inner);
+            if (verdict) {
+                if (verdict == 1 && poll_iters) it = poll_iters;
+                break;
+            }
+        }
+    }
+    flush_pending();
+    return it;
+}
+
+// the same by GMRES(30) as picard_gmres runs it: left-preconditioned with the diagonal, the restart residual rhs - D^-1 A d
+uint64_t Smoother::correct_gmres(const double2* rhs, double2* d) {
+    const int n = static_cast<int>(n_owned);
+    double2* const W = r;
+    const int64_t ld = n_local;
+    auto V = [&](int k) { return gm_V + static_cast<int64_t>(k) * ld; };
+    auto poll = [&]() {
+        HIPCHK(hipMemcpyAsync(h_gm, gm_S, sizeof(GmresScalars), hipMemcpyDeviceToHost, stream));
+        sync();
+        return h_gm->done[0] == 1 && h_gm->done[1] == 1;
+    };
+    HIPCHK(launch_csr_norm2(n, rhs, partials, stream));
+    reduce(csr_nwg(n));
+    HIPCHK(launch_gm_tol(gm_S, red, refine_rtol, opt.atol, stream));
+    uint64_t it = 0;
+    bool first = true;
+    while (it < opt.max_inner) {
+        if (first) {
+            HIPCHK(hipMemcpyAsync(W, rhs, sizeof(double2) * n_local, hipMemcpyDeviceToDevice, stream));
+            first = false;
+        } else {
+            apply(d, W, MODE_SCALED, DOT_NONE, nullptr, X, 0.0, -1);
+            HIPCHK(launch_csr_sub(n, rhs, W, W, stream));
+        }
+        HIPCHK(launch_csr_norm2(n, W, partials, stream));
+        reduce(csr_nwg(n));
+        HIPCHK(launch_gm_begin(gm_S, red, stream));
+        if (poll()) break;
+        HIPCHK(launch_gm_divide(V(0), W, gm_S, n_owned, stream));
+        bool cycle_done = false;
+        for (int j = 0; j < GMRES_M && it < opt.max_inner; ++j) {
+            apply(V(j), W, MODE_SCALED, DOT_NONE, nullptr, X, 0.0, -1);
+            HIPCHK(launch_gm_mgs(W, nullptr, V(0), nullptr, gm_S, 0, n_owned, partials, stream));
+            reduce(nwg_vec);
+            for (int i = 1; i <= j; ++i) {
+                HIPCHK(launch_gm_mgs(W, V(i - 1), V(i), red, gm_S, i - 1, n_owned, partials, stream));
+                reduce(nwg_vec);
+            }
+            HIPCHK(launch_gm_mgs(W, V(j), nullptr, red, gm_S, j, n_owned, partials, stream));
+            reduce(nwg_vec);
+            HIPCHK(launch_gm_column(gm_S, red, stream));
+            HIPCHK(launch_gm_divide(V(j + 1), W, gm_S, n_owned, stream));
+            it += 1;
+            if ((j + 1) % static_cast<int>(opt.check_every) == 0 || j + 1 == GMRES_M || it == opt.max_inner) {
+                if (poll()) {
+                    cycle_done = true;
+                    break;
+                }
+            }
+        }
+        HIPCHK(launch_gm_backsub(gm_S, stream));
+        HIPCHK(launch_gm_update(d, gm_V, ld, gm_S, n_owned, stream));
+        if (cycle_done) break;
+    }
+    return it;
 }
 
 // ------------------------------------------------------------------ Picard + the reference's own inner solve (TM_INNER_REFERENCE_GMRES)
@@ -2058,7 +2221,7 @@ void Smoother::csr_build_pattern() {
 }
 
 void Smoother::csr_release() {
-    if (!ref) csr_free();
+    if (!ref && !refine()) csr_free();
 }
 
 void Smoother::csr_free() {
@@ -2112,6 +2275,19 @@ void Smoother::apply_reference_host(const double* in_xy, double* out_xy) {
     HIPCHK(hipMemcpyAsync(tmpA, in_xy, sizeof(double2) * n_owned, hipMemcpyHostToDevice, stream));
     HIPCHK(launch_csr_product(n_owned, csr.p, csr.i, csr.vx, csr.vy, tmpA, tmpB, stream));
     HIPCHK(hipMemcpyAsync(out_xy, tmpB, sizeof(double2) * n_owned, hipMemcpyDeviceToHost, stream));
+    sync();
+    csr_release();
+}
+
+// r = b - A(X) xy in double-double (tm_refine.hip) against the assembled system of the resident coordinates; xy == nullptr: X itself
+void Smoother::residual_host(const double* xy, double* r_xy) {
+    ensure_tmp();
+    csr_fill_values();   // (refuses handles with rank hooks)
+    if (xy) HIPCHK(hipMemcpyAsync(tmpA, xy, sizeof(double2) * n_owned, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemsetAsync(tmpB, 0, sizeof(double2) * n_local, stream));   // interior rows have b = 0
+    HIPCHK(launch_edge_rhs(edge, X, PQ, tmpB, 0, nullptr, stream));
+    HIPCHK(launch_csr_residual_dd(static_cast<int>(n_owned), csr.p, csr.i, csr.vx, csr.vy, xy ? tmpA : X, tmpB, tmpB, stream));
+    HIPCHK(hipMemcpyAsync(r_xy, tmpB, sizeof(double2) * n_owned, hipMemcpyDeviceToHost, stream));
     sync();
     csr_release();
 }

@@ -182,6 +182,7 @@ struct Smoother {
     void csr_release();              // frees the device copy -- unless the handle keeps it for its lifetime (ref != nullptr)
     void csr_free();
     void rhs_host(double* rhs_xy);
+    void residual_host(const double* xy, double* r_xy);   // tm_smoother_residual
     void control_function_host(double* pq);
     void export_soa_host(int64_t block, double* x, double* y, double* p, double* q);
     void* export_buf = nullptr;     // scratch planes of export_soa_host (hipMalloc, grown on demand)
@@ -260,6 +261,14 @@ struct Smoother {
     ReferenceSolve* ref = nullptr;
     void reference_create();
     double2* ref_b = nullptr;        // the unscaled right-hand side
+    // TM_OPT_REFINE (refine_solution): double-double residual, correction and 1 / a_ii of the assembled system (ref_b: its right-hand side);
+    // the figures of tm_smoother_refine_report
+    double2 *rf_r = nullptr, *rf_d = nullptr, *rf_dinv = nullptr;
+    uint32_t refine_steps = 0;        // steps of the last outer iteration (both components advance together)
+    double refine_rel[2] = {0.0, 0.0};   // ||d|| / ||x|| of its last step
+    double refine_rtol = 0.0;         // stop test of the corrections, relative to ||D^-1 r||
+    uint64_t refine_iterations = 0;   // inner iterations spent in corrections over the handle's life
+    bool refine() const { return (opt.flags & TM_OPT_REFINE) != 0; }
     uint64_t inner_counts[2] = {0, 0};   // inner iterations of the last outer iteration per component (tm_smoother_inner_counts)
 
    private:
@@ -280,6 +289,9 @@ struct Smoother {
     int picard_bicgstab(tm_stats& st);
     int picard_gmres(tm_stats& st);
     int picard_reference(tm_stats& st);
+    void refine_solution();
+    uint64_t correct_bicgstab(const double2* rhs, double2* d);
+    uint64_t correct_gmres(const double2* rhs, double2* d);
     int picard_solve(tm_stats& st) {
         const uint64_t before = st.inner_iterations;
         if (opt.inner == TM_INNER_REFERENCE_GMRES) return picard_reference(st);

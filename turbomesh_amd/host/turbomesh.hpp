@@ -232,6 +232,7 @@ struct Option {
     uint64_t max_inner = 0;
     uint32_t check_every = 0;
     bool single_sweep = false;
+    bool refine = false;   // TM_OPT_REFINE: iterative refinement with a double-double residual (Picard modes; refused with relax, reference_gmres, rank hooks)
 };
 }  // namespace solver
 namespace wall_control_function {               // wall_control_function.zig:10-20, 56-68
@@ -283,7 +284,8 @@ struct Desc {
 };
 inline tm_solver_opt toOpt(const solver::Option& o) {
     return tm_solver_opt{static_cast<int32_t>(o.tag), o.inner, o.rtol, o.atol, o.max_inner, o.check_every, (o.single_sweep ? uint32_t{TM_OPT_SINGLE_SWEEP} : 0u) |
-                             ((o.tag == solver::Tag::hip && o.inner == TM_INNER_REFERENCE_GMRES && o.preconditioner == Preconditioner::ilu0) ? uint32_t{TM_OPT_PRECOND_ILU0} : 0u),
+                             ((o.tag == solver::Tag::hip && o.inner == TM_INNER_REFERENCE_GMRES && o.preconditioner == Preconditioner::ilu0) ? uint32_t{TM_OPT_PRECOND_ILU0} : 0u) |
+                             (o.refine ? uint32_t{TM_OPT_REFINE} : 0u),
                          o.omega};
 }
 inline tm_control_fn toControl(const wall_control_function::Algorithm& a) {
@@ -300,6 +302,12 @@ inline tm_stats mesh(discrete::Mesh& mesh_data, std::size_t iterations, const so
     tm_stats st{};
     check(tm_smooth_mesh(&d.desc, iterations, &so, &cf, &st));
     return st;
+}
+
+// b - A x of a caller's CSR system, both components, in double-double arithmetic rounded once to fp64 (tm_csr_residual)
+inline void csrResidual(std::size_t n, const int32_t* Ap, const int32_t* Ai, const double* Ax_x, const double* Ax_y, const double* bx, const double* by,
+                        const double* x, const double* y, double* rx, double* ry) {
+    check(tm_csr_residual(n, Ap, Ai, Ax_x, Ax_y, bx, by, x, y, rx, ry));
 }
 
 // The same smoother with the mesh resident on the device between calls (tm_smoother_*): iterate a fixed count like the
@@ -330,6 +338,20 @@ class Smoother {
         return rc == TM_OK;
     }
     void download() { check(tm_smoother_download(h_, &d_.desc)); }
+    // b - A(X) xy against the system assembled from the resident coordinates, in double-double arithmetic rounded once to fp64
+    // (tm_smoother_residual); xy = nullptr: the resident coordinates themselves.  2 * dof doubles each, global row order
+    void residual(const double* xy, double* r_xy) { check(tm_smoother_residual(h_, xy, r_xy)); }
+    // what the refinement of a handle created with Option::refine did (tm_smoother_refine_report)
+    struct RefineReport {
+        uint32_t steps[2];
+        double last_update_rel[2];
+        uint64_t correction_iterations;
+    };
+    RefineReport refineReport() const {
+        RefineReport r{};
+        check(tm_smoother_refine_report(h_, r.steps, r.last_update_rel, &r.correction_iterations));
+        return r;
+    }
     // quality report of the coordinates resident in the handle (reads them only)
     discrete::Quality quality() {
         discrete::Quality q;

@@ -20,8 +20,14 @@ def _log_sink(ctx, what, iteration, value):
     """The reference's two per-iteration lines (smooth.zig:105, 136-137) through Python's logging."""
     if what == 0:
         log.info("iteration: %d", iteration)
-    else:
+    elif what == 1:
         log.info("\tresidual: %r", value)
+    elif what == 2:   # tm_csr_solve with TM_OPT_REFINE (include/tm_hip.h tm_set_log): steps, last update per component, correction iterations
+        log.info("\trefinement steps: %d", int(value))
+    elif what in (3, 4):
+        log.info("\tlast refinement update |d|/|%s|: %r", "xy"[what - 3], value)
+    elif what == 5:
+        log.info("\tinner iterations in corrections: %d", int(value))
 
 
 _LOG_CB = _capi.LOG_FN(_log_sink)   # kept alive for the lifetime of the module
@@ -193,6 +199,23 @@ class Smoother:
     def rhs(self):
         out = np.empty((self.dof, 2))
         _capi.check(_capi.lib().tm_smoother_rhs(self._h, _capi.f64ptr(out)))
+        return out
+
+    def refine_report(self):
+        """What the refinement of a handle created with Option(refine=True) did (tm_smoother_refine_report): steps of the last outer
+        iteration, |d| / |x| of its last step per component, inner iterations spent in corrections over the handle's life."""
+        steps, rel, its = (C.c_uint32 * 2)(), (C.c_double * 2)(), C.c_uint64(0)
+        _capi.check(_capi.lib().tm_smoother_refine_report(self._h, steps, rel, C.byref(its)))
+        return {"steps": (int(steps[0]), int(steps[1])), "last_update_rel": (float(rel[0]), float(rel[1])), "correction_iterations": int(its.value)}
+
+    def residual(self, xy=None):
+        """b - A(X) xy against the system assembled from the resident coordinates X, in double-double arithmetic rounded once to fp64
+        (tm_smoother_residual); xy: (dof, 2) host array, None = the resident coordinates themselves."""
+        out = np.empty((self.dof, 2))
+        if xy is not None:
+            xy = np.ascontiguousarray(xy, dtype=np.float64)
+            assert xy.shape == (self.dof, 2)
+        _capi.check(_capi.lib().tm_smoother_residual(self._h, None if xy is None else _capi.f64ptr(xy), _capi.f64ptr(out)))
         return out
 
     def row_kinds(self):

@@ -52,6 +52,7 @@ class Option:
     omega: float = 0.0         # 0 -> 1.0
     single_sweep: bool = False # relax: one kernel pass per sweep (default: three per pass with fixed walls, two on coupled blocks)
     rtol_initial: bool = False   # Krylov modes: rtol relative to the initial residual of each inner solve (inexact Picard; rtol 0 -> 1e-2)
+    refine: bool = False         # iterative refinement of every inner solve with a double-double residual, up to 3 steps (TM_OPT_REFINE): Solver / tm_csr_solve and the Picard modes of a handle; refused with relax, reference_gmres, rtol_initial, rank hooks
     eager_scalars: bool = False  # Krylov modes: the textbook launch sequence (a kernel per vector update, a launch per scalar step); default: two fused kernels per iteration
 
     @classmethod
@@ -91,7 +92,8 @@ class Option:
         # matrix to factorise)
         ilu = 8 if (self.tag == Tag.hip and self.preconditioner == Preconditioner.ilu0) else 0
         return _capi.tm_solver_opt(int(self.tag), int(self.inner), self.rtol, self.atol, self.max_inner, self.check_every,
-                                   (1 if self.single_sweep else 0) | (2 if self.eager_scalars else 0) | (4 if self.rtol_initial else 0) | ilu, self.omega)
+                                   (1 if self.single_sweep else 0) | (2 if self.eager_scalars else 0) | (4 if self.rtol_initial else 0) | ilu |
+                                   (_capi.TM_OPT_REFINE if self.refine else 0), self.omega)
 
 
 class Solver:
@@ -136,3 +138,25 @@ class Solver:
                                                   _capi.f64ptr(s.rhs_y), _capi.f64ptr(s.x_new), _capi.f64ptr(s.y_new), C.byref(opt), C.byref(st)))
         self.stats = st.as_dict()
         return rc == 0
+
+
+def csr_residual(Ap, Ai, Ax_x, bx, by, x, y, Ax_y=None):
+    """(rx, ry) = b - A x per component of a CSR system, formed on the device in double-double arithmetic and rounded once to fp64
+    (tm_csr_residual): the check of any solution, this library's or not.  Ax_y = None: the x values serve both components."""
+    import ctypes as C
+
+    import numpy as np
+
+    Ap = np.ascontiguousarray(Ap, dtype=np.int32)
+    Ai = np.ascontiguousarray(Ai, dtype=np.int32)
+    n = len(Ap) - 1
+    vx = np.ascontiguousarray(Ax_x, dtype=np.float64)
+    vy = None if Ax_y is None else np.ascontiguousarray(Ax_y, dtype=np.float64)
+    vecs = [np.ascontiguousarray(v, dtype=np.float64) for v in (bx, by, x, y)]
+    if any(v.shape != (n,) for v in vecs) or len(vx) != len(Ai) or (vy is not None and len(vy) != len(Ai)):
+        raise _capi.TmError(_capi.TM_E_SIZE, "csr_residual: array lengths do not match the row pointers")
+    rx, ry = np.empty(n), np.empty(n)
+    ip = C.POINTER(C.c_int32)
+    _capi.check(_capi.lib().tm_csr_residual(n, Ap.ctypes.data_as(ip), Ai.ctypes.data_as(ip), _capi.f64ptr(vx), None if vy is None else _capi.f64ptr(vy),
+                                            *[_capi.f64ptr(v) for v in vecs], _capi.f64ptr(rx), _capi.f64ptr(ry)))
+    return rx, ry
