@@ -1,0 +1,175 @@
+"""K2x4 (four Jacobi sweeps per kernel pass on blocks whose perimeter rows are all fixed) against the one-sweep-per-pass path: the same
+relax_row applied once more, so the coordinates must agree BIT FOR BIT at every shape, sweep count and split of the sweeps across
+calls.  n = 4 a + r sweeps run as a quads and then a pair (r = 2) or a triple (r = 3); r = 1 takes one quad fewer, a triple and a pair.
+Small blocks take the smallest chunk height (6 rows), so the shapes below cover several chunks and their 4-row overlaps.
+By default a handle takes quads only from 8 M nodes per launch on (where they are faster; tests/test_gpu_benchsize.py
+and test_gpu_fullsize.py run them at that size); TM_FUSE_4=1 asks for them wherever the window fits, which is how the small blocks here
+get them."""
+import numpy as np
+import pytest
+
+from oracle import oracle
+from tests.conftest import mesh_flat
+from turbomesh_amd import configs
+from turbomesh_amd.discrete import Mesh
+from turbomesh_amd.smoothing import smooth, solver
+
+pytestmark = pytest.mark.gpu
+
+SWEEPS = [4, 5, 6, 7, 8, 11]
+HEIGHT = 6   # the smallest chunk height of K2x4 (relax4_rows_for_launch): what a launch of this few workgroups gets
+# nj: one strip (9, 10), 56 / 57 owned columns (57, 58, 59), a second strip (61, 64, 65), exactly 4 strips of a workgroup and a bit more (225, 226, 227);
+# ni: the 9 x 9 minimum and its neighbours, HEIGHT + 3, 2 HEIGHT + 2, many chunks with a short last one (67)
+SHAPES = [(9, 9), (10, 10), (11, 57), (13, 58), (HEIGHT + 3, 59), (2 * HEIGHT + 2, 61), (67, 64), (10, 65), (11, 113), (2 * HEIGHT + 2, 114),
+          (67, 225), (13, 226), (67, 227), (2 * HEIGHT + 2, 10), (67, 9), (9, 227)]
+FALLBACK = [(HEIGHT + 2, 40), (40, 8)]   # below 9 x 9: the handle keeps triples
+
+
+@pytest.fixture(autouse=True)
+def _quads_wherever_supported(monkeypatch):
+    monkeypatch.setenv("TM_FUSE_4", "1")
+
+
+def _opt(single, omega=1.0):
+    return solver.Option.hip(inner=solver.Inner.relax, single_sweep=single, omega=omega)
+
+
+def _single_sweep_states(build, counts, omega=1.0):
+    """the mesh after each of the (ascending) sweep counts, one sweep per pass, and the statistics of the last sweep of each"""
+    mesh = build()
+    out, done = {}, 0
+    with smooth.Smoother(mesh, _opt(True, omega)) as sm:
+        for n in counts:
+            st = sm.iterate(n - done)
+            done = n
+            sm.download()
+            out[n] = (mesh_flat(mesh).copy(), st)
+    return out
+
+
+def _fused(build, chunks, omega=1.0):
+    mesh = build()
+    total = 0
+    with smooth.Smoother(mesh, _opt(False, omega)) as sm:
+        sm.profile(1)
+        for n in chunks:
+            st = sm.iterate(n)
+            total += st["operator_sweeps"]
+        launches = sm.profile_read()[2]
+        sm.download()
+    return mesh_flat(mesh), st, total, launches
+
+
+def _launches(n, quads=True):
+    """kernel passes of the default schedule for n sweeps in one call on a block with fixed walls"""
+    nq = (n // 4 - (1 if n % 4 == 1 else 0)) if (quads and n >= 4) else 0
+    rest = n - 4 * nq
+    return nq + rest // 3 + (rest % 3 + 1) // 2
+
+
+@pytest.mark.parametrize("ni,nj", SHAPES + FALLBACK)
+def test_quads_equal_single_sweeps(ni, nj):
+    build = lambda: configs.single_block(ni, nj, perturb=0.2)
+    ref = _single_sweep_states(build, SWEEPS)
+    assert not np.array_equal(ref[4][0], mesh_flat(build()))   # the sweeps moved the mesh
+    for n in SWEEPS:
+        got, st, total, launches = _fused(build, [n])
+        assert np.array_equal(got, ref[n][0]), (ni, nj, n, float(np.abs(got - ref[n][0]).max()))
+        assert total == n
+        assert launches == _launches(n, quads=(ni, nj) in SHAPES), (n, launches)   # the quads did run (did not, below 9 x 9)
+    got, st, total, _ = _fused(build, [1, 4, 2, 4])
+    assert np.array_equal(got, ref[11][0]) and total == 11
+
+
+@pytest.mark.parametrize("ni,nj", [(13, 58), (67, 227), (2 * HEIGHT + 2, 114)])
+def test_quads_with_damping(ni, nj):
+    build = lambda: configs.single_block(ni, nj, perturb=0.2)
+    ref = _single_sweep_states(build, [8, 11], omega=0.9)
+    for n in (8, 11):
+        got, _, _, _ = _fused(build, [n], omega=0.9)
+        assert np.array_equal(got, ref[n][0]), (ni, nj, n)
+
+
+def _array_mesh(*arrays):
+    m = Mesh()
+    for k, a in enumerate(arrays):
+        m.addBlock(f"b{k}", configs.block_from_array(np.ascontiguousarray(a).copy()))
+    return m
+
+
+def _collapsed():
+    base = configs.single_block(70, 131, perturb=0.2).blocks[0].points.data.copy()
+    base[20:27, 40:90] = base[23, 60]   # 7 x 50 nodes on one point: D = 0 there
+    base[50:53, 3:8] = base[51, 5]
+    return base
+
+
+@pytest.mark.parametrize("name,make", [("collapsed", _collapsed),
+                                       ("tiny_2^-400", lambda: configs.single_block(40, 131, perturb=0.2).blocks[0].points.data * 2.0 ** -400),
+                                       ("tiny_2^-352", lambda: configs.single_block(40, 131, perturb=0.2).blocks[0].points.data * 2.0 ** -352)])
+def test_quads_on_degenerate_and_extreme_cells(name, make):
+    # the slow (exact division) branch of the reciprocal inside the warm-up groups and the steady loop
+    build = lambda: _array_mesh(make())
+    ref = _single_sweep_states(build, [8])[8][0]
+    got, _, _, launches = _fused(build, [8])
+    assert launches == 2
+    assert np.array_equal(got, ref, equal_nan=True), name
+    assert np.array_equal(np.isfinite(got), np.isfinite(ref))
+
+
+def test_quads_batched_launch():
+    # independent slices in one handle (one batched launch per pass): each equals its own single-block run
+    nsl, n = 3, 70
+    mesh = configs.slices(nsl, n, perturb=0.2)
+    with smooth.Smoother(mesh, _opt(False)) as sm:
+        sm.profile(1)
+        st = sm.iterate(9)   # a quad, a triple, a pair
+        assert sm.profile_read()[2] == 3 and st["operator_sweeps"] == 9
+        sm.download()
+    for k in range(nsl):
+        one = configs.slices(1, n, first=k, perturb=0.2)
+        smooth.mesh(one, 9, _opt(True))
+        assert np.array_equal(mesh.blocks[k].points.data, one.blocks[0].points.data), k
+    # two blocks of different shapes, no interface between them
+    a = configs.single_block(67, 114, perturb=0.2).blocks[0].points.data
+    b = configs.single_block(13, 227, perturb=0.2, seed=7).blocks[0].points.data + 3.0
+    both = _array_mesh(a, b)
+    with smooth.Smoother(both, _opt(False)) as sm:
+        sm.iterate(8)
+        sm.download()
+    for k, arr in enumerate((a, b)):
+        one = _array_mesh(arr)
+        smooth.mesh(one, 8, _opt(True))
+        assert np.array_equal(both.blocks[k].points.data, one.blocks[0].points.data), k
+
+
+def test_quads_against_the_oracle_mirror():
+    blk = configs.single_block(70, 131, perturb=0.2)
+    ref = blk.blocks[0].points.data.copy()
+    oracle.time_relax_sweeps(ref, 8, 1.0)
+    with smooth.Smoother(blk, _opt(False)) as sm:
+        sm.iterate(8)
+        sm.download()
+    assert np.array_equal(blk.blocks[0].points.data, ref)
+
+
+@pytest.mark.parametrize("n", [4, 8, 9])
+def test_quad_statistics_and_switch(n, monkeypatch):
+    build = lambda: configs.single_block(67, 227, perturb=0.2)
+    ref, sref = _single_sweep_states(build, [n])[n]
+    got, st, total, launches = _fused(build, [n])
+    assert np.array_equal(got, ref)
+    assert st["operator_sweeps"] == n == sref["operator_sweeps"] and launches == _launches(n)
+    # the displacement sums of the last sweep are reduced in a different (still deterministic) order
+    assert st["last_dx2"] == pytest.approx(sref["last_dx2"], rel=1e-11, abs=1e-300)
+    assert st["last_dy2"] == pytest.approx(sref["last_dy2"], rel=1e-11, abs=1e-300)
+    # TM_FUSE_4=0 is read when the handle is created: triples as before, the same coordinates
+    monkeypatch.setenv("TM_FUSE_4", "0")
+    off, st0, _, launches0 = _fused(build, [n])
+    assert np.array_equal(off, ref) and st0["operator_sweeps"] == n
+    assert launches0 == _launches(n, quads=False)
+    assert st0["last_dx2"] == pytest.approx(sref["last_dx2"], rel=1e-11, abs=1e-300)
+    # unset: a block this small is below the size from which quads pay -- triples, the same coordinates
+    monkeypatch.delenv("TM_FUSE_4")
+    auto, _, _, launches1 = _fused(build, [n])
+    assert np.array_equal(auto, ref) and launches1 == _launches(n, quads=False)

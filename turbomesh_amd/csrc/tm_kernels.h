@@ -134,6 +134,11 @@ int relax3_rows_per_chunk(int ni, int nj);
 void relax3_rows_for_launch(const int* ni, const int* nj, int n, int* rows, bool beside_chain);
 int relax3_block_nwg(int ni, int nj, int rows_per_chunk);
 hipError_t launch_relax3_blocks(const Relax2Block* blocks, const int* rows_per_chunk, int n, int dot, hipStream_t stream);
+// ---- K2x4: FOUR fused sweeps per pass, blocks with dyn == 0 only (ni, nj >= 9: relax4_supported); TM_FUSE4_ROWS forces the chunk height
+bool relax4_supported(int ni, int nj);
+void relax4_rows_for_launch(const int* ni, const int* nj, int n, int* rows);   // n <= APPLY_BATCH_MAX: the blocks of one launch
+int relax4_block_nwg(int ni, int nj, int rows_per_chunk);
+hipError_t launch_relax4_blocks(const Relax2Block* blocks, const int* rows_per_chunk, int n, int dot, hipStream_t stream);
 
 // ---- K4/K5 perimeter rows and the fused level kernel: EdgeRun / EdgeRowsDev / LevelTask / FusedLevelsDev live in tm_edge_types.h
 hipError_t launch_edge_levels3(const FusedLevelsDev& F, const EdgeRowsDev& e1, const EdgeRowsDev& e2, const EdgeRowsDev& e3, const double2* x, double2* m,

@@ -1079,6 +1079,127 @@ __global__ __launch_bounds__(256) void k_relax3_batch(Relax2Batch B) {
         if (q < B.n && static_cast<int>(blockIdx.x) >= B.start[q]) k = q;
     relax3_tile<DOT, U, NT, W1>(B.b[k], B.RI[k], B.nSG[k], B.nRC[k], static_cast<int>(blockIdx.x) - B.start[k]);
 }
+// ------------------------------------------------------------------------------------------
+// K2x4: FOUR fused sweeps per pass, same blocks as K2x3 with Relax2Block::dyn == 0 only (every perimeter row fixed).  One read and one
+// write of the field cost ~95 us at 4096^2 whatever the pass computes; each further sweep carried by the same bytes costs far less
+// than its issue time.  The body is K2x3's with the depth L as a parameter: L window levels, halo H = L lanes
+// per side, 64 - 2L owned columns (L = 4: 56, every stored segment 896 B = whole 128 B lines), chunks overlapping by L rows either
+// side.  Step s takes input row r = i0 - (L-2) + s (rows i0-L, i0-L+1 are preloaded), forms level k's row r - k for k = 1..L and
+// stores row r - L; level k has its three operand rows from step 2 (k-1) on, the evaluations before that are skipped at compile
+// time.  The same relax_row applied once more: bit-identical to L single sweeps (tests/test_gpu_quads.py).
+// ------------------------------------------------------------------------------------------
+constexpr int R4_L = 4;
+constexpr int R4_W = 64 - 2 * R4_L;     // output columns per wave
+template <int L, int DOT, int U, int NT, bool W1, bool INSIDE>
+__device__ __forceinline__ void relaxn_strip(const Relax2Block& a, const Relax2Tile& t, double (&acc)[MAX_PARTIALS]) {
+    static_assert(U == 3 && L >= 3, "three steps per group; the windows rotate by renaming");
+    constexpr int STEADY = (2 * (L - 1) + 2) / 3;   // first group in which every level is live at every step
+    const int ni = a.ni, nj = a.nj;
+    const int cc = INSIDE ? t.c : min(max(t.c, 0), nj - 1);
+    const double2* in_col = a.in + cc;
+    const int last_row = INSIDE ? t.i1 + L - 1 : ni - 1;
+    auto load_in = [&](int row) { return in_col[static_cast<size_t>(INSIDE ? min(row, last_row) : min(max(row, 0), last_row)) * nj]; };
+    const bool perim_col = !INSIDE && ((t.c <= 0) || (t.c >= nj - 1));
+    const int nrows = t.i1 - t.i0;
+    const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.out + static_cast<size_t>(t.i0) * nj, 0, nrows * nj * 16, 0x00020000);
+    const unsigned lane_off = t.out_lane ? static_cast<unsigned>(cc) * 16u : OOB_VOFFSET;
+    const double2 zero = make_double2(0.0, 0.0);
+    const int r0 = t.i0 - (L - 2);   // input row of step 0
+
+    Row3 A[3], S[L - 1][3];
+    double2 pc[U], pn[U];
+    {
+        const double2 a0 = load_in(r0 - 2), a1 = load_in(r0 - 1);
+#pragma unroll
+        for (int u = 0; u < U; ++u) pc[u] = load_in(r0 + u);
+        A[0] = make_row(a0);
+        A[1] = make_row(a1);
+        A[2].c = A[2].e = A[2].h = zero;
+#pragma unroll
+        for (int k = 0; k < L - 1; ++k) S[k][0] = S[k][1] = S[k][2] = A[2];
+    }
+    const int nsteps = nrows + 2 * (L - 1);
+    // (phase: the group's number, STEADY for every later one -- a literal at each call, so the tests below fold away)
+    auto group = [&](const int tb, const int phase) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) pn[u] = load_in(r0 + tb + U + u);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int A0 = u % 3, A1 = (u + 1) % 3, A2 = (u + 2) % 3;   // window slots of rows r-2, r-1, r (and of the same offsets k levels up)
+            const int r = r0 + tb + u;
+            const int s = U * phase + u;   // the step's number while phase < STEADY
+            A[A2] = make_row(pc[u]);
+            double2 d = zero;
+            double2 v = relax_row<W1>(A[A0], A[A1], A[A2], a.omega, d);               // level 1, row r-1
+            if (!INSIDE && (perim_col || r - 1 <= 0 || r - 1 >= ni - 1)) v = A[A1].c;   // fixed: the level below's own value
+            S[0][A2] = make_row(v);
+#pragma unroll
+            for (int k = 2; k < L; ++k) {   // level k, row r-k; a skipped slot keeps the zeros it was filled with and is never read
+                if (phase >= STEADY || s >= 2 * (k - 1)) {
+                    v = relax_row<W1>(S[k - 2][A0], S[k - 2][A1], S[k - 2][A2], a.omega, d);
+                    if (!INSIDE && (perim_col || r - k <= 0 || r - k >= ni - 1)) v = S[k - 2][A1].c;
+                    S[k - 1][A2] = make_row(v);
+                }
+            }
+            double2 dl = zero, o = zero;
+            if (phase >= STEADY || s >= 2 * (L - 1)) o = relax_row<W1>(S[L - 2][A0], S[L - 2][A1], S[L - 2][A2], a.omega, dl);   // row r-L
+            const int i = r - L;
+            const bool row_live = (i >= t.i0) && (i < t.i1);   // wave-uniform
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i32, o), out_rsrc,
+                                                   static_cast<int>(row_live ? lane_off + static_cast<unsigned>((i - t.i0) * nj * 16) : OOB_VOFFSET), 0,
+                                                   (NT & 1) ? 2 : 0);
+            if (DOT == DOT_DELTA) {
+                if (!(t.out_lane && row_live)) dl = zero;   // masked lanes hold garbage (possibly non-finite): select, never multiply
+                accumulate<DOT_DELTA>(acc, S[L - 2][A1].c, o, dl);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) pc[u] = pn[u];
+    };
+    static_assert(STEADY == 2, "two warm-up groups are peeled below");
+    group(0, 0);
+    group(U, 1);   // (steps past nsteps store nothing: row_live)
+    for (int tb = 2 * U; tb < nsteps; tb += U) group(tb, STEADY);
+}
+
+template <int L, int DOT, int U, int NT, bool W1>
+__device__ __forceinline__ void relaxn_tile(const Relax2Block& a, int RI, int nSG, int nRC, int bid) {
+    constexpr int W = 64 - 2 * L;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int total = nSG * nRC;
+    const int q8 = total >> 3, rem = total & 7, xcd = bid & 7, k8 = bid >> 3;
+    const int logical = (xcd < rem) ? xcd * (q8 + 1) + k8 : rem * (q8 + 1) + (xcd - rem) * q8 + k8;
+    const int rc = logical / nSG;
+    const int sg = logical - rc * nSG;
+    const int ni = a.ni, nj = a.nj;
+    Relax2Tile t;
+    t.c0 = (sg * 4 + wave) * W;
+    t.c = t.c0 - L + lane;
+    t.out_lane = (lane >= L) && (lane < 64 - L) && (t.c >= 1) && (t.c <= nj - 2);
+    t.i0 = 1 + rc * RI;
+    t.i1 = min(t.i0 + RI, ni - 1);
+    double acc[MAX_PARTIALS] = {0.0, 0.0, 0.0, 0.0};
+    if (t.c0 <= nj - 2 && t.i0 < t.i1) {   // wave-uniform
+        // strictly inside: all 64 loaded columns within [1, nj-2] and rows i0-L .. i1+L-1 within [1, ni-2]
+        const bool inside = (t.c0 - L >= 1) && (t.c0 - L + 63 <= nj - 2) && (t.i0 - L >= 1) && (t.i1 + L - 1 <= ni - 2);
+        if (inside) relaxn_strip<L, DOT, U, NT, W1, true>(a, t, acc);
+        else relaxn_strip<L, DOT, U, NT, W1, false>(a, t, acc);
+    }
+    if (DOT != DOT_NONE) block_partials<256, dot_columns(DOT)>(acc, a.partials + static_cast<size_t>(logical) * MAX_PARTIALS);
+}
+template <int DOT, int U, int NT, bool W1>
+__global__ __launch_bounds__(256) void k_relax4(Relax2Block a, int RI, int nSG, int nRC) {
+    relaxn_tile<R4_L, DOT, U, NT, W1>(a, RI, nSG, nRC, blockIdx.x);
+}
+template <int DOT, int U, int NT, bool W1>
+__global__ __launch_bounds__(256) void k_relax4_batch(Relax2Batch B) {
+    int k = 0;
+#pragma unroll
+    for (int q = 1; q < APPLY_BATCH_MAX; ++q)
+        if (q < B.n && static_cast<int>(blockIdx.x) >= B.start[q]) k = q;
+    relaxn_tile<R4_L, DOT, U, NT, W1>(B.b[k], B.RI[k], B.nSG[k], B.nRC[k], static_cast<int>(blockIdx.x) - B.start[k]);
+}
 static int g_fuse3_rows = 0;   // experiments (TM_FUSE3_ROWS)
 // Rows per chunk of K2x3 for the blocks of ONE launch (launch_relax3_blocks batches APPLY_BATCH_MAX blocks).
 // The pass is bound by fp64 issue under the power cap, not by bandwidth, so the rows a chunk recomputes for its neighbours
@@ -1126,7 +1247,9 @@ int relax3_block_nwg(int ni, int nj, int RI) {
     const int nstrips = (nj - 1 + R3_W - 1) / R3_W;
     return ((nstrips + 3) / 4) * ((ni - 2 + RI - 1) / RI);
 }
-hipError_t launch_relax3_blocks(const Relax2Block* blocks, const int* rows_per_chunk, int n, int dot, hipStream_t st) {
+// K2x3 (depth 3) or K2x4 (depth 4) on the blocks of a rank, APPLY_BATCH_MAX of them per launch
+static hipError_t launch_fixed_wall_blocks(int depth, const Relax2Block* blocks, const int* rows_per_chunk, int n, int dot, hipStream_t st) {
+    const int W = 64 - 2 * depth;
     for (int first = 0; first < n; first += APPLY_BATCH_MAX) {
         Relax2Batch B;
         B.n = 0;
@@ -1137,7 +1260,7 @@ hipError_t launch_relax3_blocks(const Relax2Block* blocks, const int* rows_per_c
             const int q = B.n++;
             B.b[q] = blocks[k];
             B.RI[q] = rows_per_chunk[k];
-            B.nSG[q] = ((blocks[k].nj - 1 + R3_W - 1) / R3_W + 3) / 4;
+            B.nSG[q] = ((blocks[k].nj - 1 + W - 1) / W + 3) / 4;
             B.nRC[q] = (blocks[k].ni - 2 + B.RI[q] - 1) / B.RI[q];
             B.start[q] = total;
             total += B.nSG[q] * B.nRC[q];
@@ -1159,13 +1282,65 @@ hipError_t launch_relax3_blocks(const Relax2Block* blocks, const int* rows_per_c
         }                                                                                                                    \
     } while (0)
         static const bool force_batch = [] { const char* e = std::getenv("TM_R3_FORCE_BATCH"); return e && std::atoi(e) != 0; }();
-        if (B.n == 1 && !force_batch) TM_R3(k_relax3, B.b[0], B.RI[0], B.nSG[0], B.nRC[0]);
-        else TM_R3(k_relax3_batch, B);
+        const bool lone = B.n == 1 && !force_batch;
+        if (depth == R4_L) {
+            if (lone) TM_R3(k_relax4, B.b[0], B.RI[0], B.nSG[0], B.nRC[0]);
+            else TM_R3(k_relax4_batch, B);
+        } else {
+            if (lone) TM_R3(k_relax3, B.b[0], B.RI[0], B.nSG[0], B.nRC[0]);
+            else TM_R3(k_relax3_batch, B);
+        }
 #undef TM_R3
         const hipError_t rc = hipGetLastError();
         if (rc != hipSuccess) return rc;
     }
     return hipSuccess;
+}
+hipError_t launch_relax3_blocks(const Relax2Block* blocks, const int* rows_per_chunk, int n, int dot, hipStream_t st) {
+    return launch_fixed_wall_blocks(3, blocks, rows_per_chunk, n, dot, st);
+}
+
+// ---- K2x4's launch.  Chunk heights: K2x3's finding carries over -- RI + 6 steps whole groups of three, RI = 2 x odd, i.e. RI = 6 (mod 12);
+// which of them a launch takes follows K2x3's rule (the largest that still puts 0.6 x 3 workgroups on every CU).  Measured
+// (tools/dev/steady_time.py, us per sweep, triples 37.0-37.7 on the same box; the whole table: DESIGN.md section 4): 4096^2: 54 rows
+// 35.4-35.9, 78: 35.8-36.0, 66: 36.0-36.6, 42: 36.2-37.2, 30: 36.9-37.3, 18: 37.7, 90: 38.5; off the rule 60: 37.3-37.6, 72: 37.5-38.1, 58: 38.5.
+// 2048^2: 42 rows 10.0-10.1, 30: 10.3, 54: 12.2 (too few workgroups); 8 x 2048^2 in one launch: 42-54 rows 70.4-70.7, 30: 72.0.
+void relax4_rows_for_launch(const int* ni, const int* nj, int n, int* rows) {
+    static const int forced = [] { const char* e = std::getenv("TM_FUSE4_ROWS"); return e ? std::atoi(e) : 0; }();
+    if (forced > 0) {
+        for (int k = 0; k < n; ++k) rows[k] = std::max(1, std::min(forced, ni[k] - 2));
+        return;
+    }
+    static int slots = 0;
+    if (slots == 0) {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        slots = 3 * cus;
+    }
+    static const int heights[] = {54, 42, 30, 18, 6};
+    const long need = static_cast<long>(slots) * 6;
+    int RI = 6;
+    for (const int h : heights) {
+        long total = 0;
+        for (int k = 0; k < n; ++k) {
+            const int nstrips = (nj[k] - 1 + R4_W - 1) / R4_W, nSG = (nstrips + 3) / 4, interior = ni[k] - 2, r = std::max(1, std::min(h, interior));
+            total += static_cast<long>(nSG) * ((interior + r - 1) / r);
+        }
+        RI = h;
+        if (total * 10 >= need) break;
+    }
+    for (int k = 0; k < n; ++k) rows[k] = std::max(1, std::min(RI, ni[k] - 2));
+}
+// the smallest block whose interior the window's L rows / columns either side of a node can come from: 2 L + 1 nodes a side
+bool relax4_supported(int ni, int nj) { return ni >= 2 * R4_L + 1 && nj >= 2 * R4_L + 1 && nj <= (1 << 20); }
+int relax4_block_nwg(int ni, int nj, int RI) {
+    const int nstrips = (nj - 1 + R4_W - 1) / R4_W;
+    return ((nstrips + 3) / 4) * ((ni - 2 + RI - 1) / RI);
+}
+hipError_t launch_relax4_blocks(const Relax2Block* blocks, const int* rows_per_chunk, int n, int dot, hipStream_t st) {
+    for (int k = 0; k < n; ++k)
+        if (blocks[k].dyn != 0) return hipErrorInvalidValue;   // coupled blocks keep K2x3 and its depth-3 zone
+    return launch_fixed_wall_blocks(R4_L, blocks, rows_per_chunk, n, dot, st);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -567,8 +567,42 @@ uint64_t Smoother::size_launches() {
         }
         nwg_apply3 = off3;
     }
+    // four sweeps per pass (K2x4) where plain triples run: n = 4 a + r sweeps take a quads, then triples / pairs / singles (relax_sweeps)
+    // The fourth sweep saves a quarter of the bytes of a pass and pays 4 % more arithmetic, which comes out ahead only where the pass is
+    // long against its own ramp and tail: measured per launch, quads win from QUAD_MIN_NODES nodes per launch on and
+    // tie or lose below.  TM_FUSE_4=0: never (the schedule of triples, same binary); TM_FUSE_4=1: wherever the window fits (tests, experiments).
+    fuse_quads = fuse_triples;
+    bool quads_forced = false;
+    if (const char* e = std::getenv("TM_FUSE_4")) {
+        fuse_quads = fuse_quads && std::atoi(e) != 0;
+        quads_forced = std::atoi(e) != 0;
+    }
+    nwg_apply4 = 0;
+    if (fuse_quads) {
+        std::vector<int> bi, bj;
+        for (size_t first = 0; first < lp.owned_blocks.size(); first += APPLY_BATCH_MAX) {   // one launch takes APPLY_BATCH_MAX blocks
+            int64_t nodes = 0;
+            for (size_t k = first; k < std::min<size_t>(first + APPLY_BATCH_MAX, lp.owned_blocks.size()); ++k) nodes += topo.ni[lp.owned_blocks[k]] * topo.nj[lp.owned_blocks[k]];
+            if (nodes < QUAD_MIN_NODES && !quads_forced) fuse_quads = false;
+        }
+        for (int64_t b : lp.owned_blocks) {
+            bi.push_back(static_cast<int>(topo.ni[b]));
+            bj.push_back(static_cast<int>(topo.nj[b]));
+            if (!relax4_supported(bi.back(), bj.back())) fuse_quads = false;   // smaller blocks keep triples
+        }
+        poff4.clear();
+        rows4.assign(bi.size(), 1);
+        for (size_t first = 0; first < rows4.size(); first += APPLY_BATCH_MAX)
+            relax4_rows_for_launch(bi.data() + first, bj.data() + first, static_cast<int>(std::min<size_t>(APPLY_BATCH_MAX, rows4.size() - first)), rows4.data() + first);
+        int off4 = 0;
+        for (size_t k = 0; k < rows4.size(); ++k) {
+            poff4.push_back(off4);
+            off4 += relax4_block_nwg(bi[k], bj[k], rows4[k]);
+        }
+        nwg_apply4 = fuse_quads ? off4 : 0;
+    }
     nwg_vec = vec_nwg(n_owned);
-    const int nwg3_all = fuse_triples ? nwg_apply3 : (triples_coupled ? nwg_apply3 + std::max(edge_L[2].nwg, fused_levels.nstrips) : 0);
+    const int nwg3_all = std::max(nwg_apply4, fuse_triples ? nwg_apply3 : (triples_coupled ? nwg_apply3 + std::max(edge_L[2].nwg, fused_levels.nstrips) : 0));
     // Overlapping strips for the two kernels of the two-kernel BiCGStab iteration (single process, no preconditioner -- where fuse2 holds,
     // below): no halo registers -> 234 instead of 276 VGPRs for VK_R, two workgroups per CU without spills.  Where it pays was MEASURED, same
     // box, alternating runs (tools/dev/vk_overlap_sizes.py, us per iteration halo loads / overlapping strips): 128^2 20.1 / 17.9, 512^2 34.3 / 31.8,
@@ -1748,8 +1782,12 @@ void Smoother::warm_transport() {
 }
 
 // Three sweeps in one pass (K2x3, all perimeter rows fixed): X^(k+3) = S(S(S(X^k))), bit-identical to three single sweeps
-void Smoother::relax_triple(bool want_partials) {
+void Smoother::relax_triple(bool want_partials) { relax_fixed_walls(3, want_partials); }
+// Four (K2x4): the same pass one level deeper, on its own grid of 56-column strips
+void Smoother::relax_quad(bool want_partials) { relax_fixed_walls(4, want_partials); }
+void Smoother::relax_fixed_walls(int depth, bool want_partials) {
     const int dot = want_partials ? DOT_DELTA : DOT_NONE;
+    const std::vector<int>& poffd = depth == 4 ? poff4 : poff3;
     std::vector<Relax2Block> blocks(lp.owned_blocks.size());
     for (size_t k = 0; k < lp.owned_blocks.size(); ++k) {
         const int64_t b = lp.owned_blocks[k];
@@ -1765,9 +1803,10 @@ void Smoother::relax_triple(bool want_partials) {
         a.store_nt = relax2_store_nt ? 1 : 0;
         a.border = nullptr;
         a.nborder = 0;
-        a.partials = partials + static_cast<size_t>(poff3[k]) * MAX_PARTIALS;
+        a.partials = partials + static_cast<size_t>(poffd[k]) * MAX_PARTIALS;
     }
-    profiled([&]() { HIPCHK(launch_relax3_blocks(blocks.data(), rows3.data(), static_cast<int>(blocks.size()), dot, stream)); }, true, stream);
+    if (depth == 4) profiled([&]() { HIPCHK(launch_relax4_blocks(blocks.data(), rows4.data(), static_cast<int>(blocks.size()), dot, stream)); }, true, stream);
+    else profiled([&]() { HIPCHK(launch_relax3_blocks(blocks.data(), rows3.data(), static_cast<int>(blocks.size()), dot, stream)); }, true, stream);
     std::swap(X, U);
 }
 
@@ -1980,18 +2019,29 @@ void Smoother::relax_pairs_pipelined(uint64_t npairs, bool want_partials_last) {
 void Smoother::relax_sweeps(uint64_t n, tm_stats& st) {
     int last_nwg = nwg_apply;
     uint64_t k = 0;
-    if ((fuse_triples || triples_coupled) && n >= 3) {   // n = 3 a + 2 b + c, as many triples as possible (n = 4: one triple + one single sweep)
-        const uint64_t ntriples = n / 3;
-        if (fuse_triples) {
-            for (uint64_t q = 0; q < ntriples; ++q) relax_triple(q + 1 == ntriples && n % 3 == 0);
-            last_nwg = nwg_apply3;
-        } else {
-            relax_triples_coupled(ntriples, n % 3 == 0);
-            last_nwg = nwg_apply3 + (levels_fused ? fused_levels.nstrips : edge_L[2].nwg);
-        }
-        k = 3 * ntriples;
+    if (fuse_quads && n >= 4) {
+        // n = 4 a + r: a quads, then r = 2 a pair, r = 3 a triple.  r = 1: one quad fewer and a triple + a pair, not a quad + a single sweep --
+        // per launch at 4096^2 a single sweep costs 91-96 us, a pair 102-107, a triple 110-112, so trading a quad
+        // and a single for a triple and a pair wins as long as a quad takes more than ~123 us; it takes 140-144.
+        const uint64_t nquads = n / 4 - (n % 4 == 1 ? 1 : 0);
+        for (uint64_t q = 0; q < nquads; ++q) relax_quad(q + 1 == nquads && n == 4 * nquads);
+        k = 4 * nquads;
+        if (nquads) last_nwg = nwg_apply4;
         st.operator_sweeps += k;
         outer_done += k;
+    }
+    if ((fuse_triples || triples_coupled) && n - k >= 3) {   // the rest n' = 3 a + 2 b + c, as many triples as possible (n' = 4: one triple + one single sweep)
+        const uint64_t ntriples = (n - k) / 3;
+        if (fuse_triples) {
+            for (uint64_t q = 0; q < ntriples; ++q) relax_triple(q + 1 == ntriples && (n - k) % 3 == 0);
+            last_nwg = nwg_apply3;
+        } else {
+            relax_triples_coupled(ntriples, n % 3 == 0);   // (no quads on coupled blocks: k = 0 here)
+            last_nwg = nwg_apply3 + (levels_fused ? fused_levels.nstrips : edge_L[2].nwg);
+        }
+        k += 3 * ntriples;
+        st.operator_sweeps += 3 * ntriples;
+        outer_done += 3 * ntriples;
     }
     if (fuse_pairs && n - k >= 2) {
         const uint64_t npairs = (n - k) / 2;

@@ -132,6 +132,10 @@ struct Smoother {
     std::vector<int> poff3, rows3;  // ... and for the three-sweep launches (all perimeter rows fixed)
     int nwg_apply3 = 0;
     bool fuse_triples = false;
+    std::vector<int> poff4, rows4;  // ... and for the four-sweep launches (K2x4: where fuse_triples holds and every block is 9 x 9 or larger)
+    int nwg_apply4 = 0;
+    bool fuse_quads = false;        // TM_FUSE_4=0 at creation: the schedule of triples alone, same binary
+    static constexpr int64_t QUAD_MIN_NODES = 8000000;         // nodes per launch from which a quad beats a triple per sweep (measured)
     // Coupled triples (single process): K2x3 with a frozen perimeter stores everything but the nodes within two of a side whose
     // perimeter rows move; three perimeter-row passes evaluate the perimeter and that zone level by level (rows within 4 / 3 / 2 nodes)
     bool triples_coupled = false;
@@ -303,6 +307,8 @@ struct Smoother {
     void relax_pair(bool want_partials);
     std::vector<int> relax3_rows_of_owned_blocks() const;
     void relax_triple(bool want_partials);
+    void relax_quad(bool want_partials);
+    void relax_fixed_walls(int depth, bool want_partials);
     void relax_triples_coupled(uint64_t ntriples, bool want_partials_last);
     void profiled(const std::function<void()>& launch, bool counts = true, hipStream_t on = nullptr);
     void relax2_launch(int subset, bool counts, int dot, hipStream_t on = nullptr, const QueueWait* wait = nullptr);
