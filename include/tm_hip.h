@@ -101,7 +101,19 @@ typedef struct tm_mesh_desc {    /* discrete.zig:166-171 (names omitted) */
 } tm_mesh_desc;
 
 /* wall_control_function.zig:10-20, 56-68 */
-enum { TM_CF_LAPLACE = 0, TM_CF_WHITE = 1 };
+/* Two kinds the reference does not have, for any topology (its stencil, smooth.zig:192-208, takes a per-node P, Q as it is):
+ *   TM_CF_PRESCRIBED          the caller's field: zero after create, set with tm_smoother_set_control_function (handles only:
+ *                             tm_smooth_mesh has no way to pass a field and answers TM_E_ARG)
+ *   TM_CF_THOMAS_MIDDLECOFF   block-local field that keeps the boundary point distribution in the interior.  For an edge polyline
+ *                             e[0..n-1]: d1 = (e[k+1] - e[k-1]) / 2, d2 = e[k+1] - 2 e[k] + e[k-1], f[k] = -(d1.d2) / (d1.d1) for
+ *                             k = 1..n-2 (0 where d1.d1 == 0), f[0] = f[1], f[n-1] = f[n-2]; n < 3: f = 0.  With phi_lo / phi_hi = f of
+ *                             the j = 0 / j = nj-1 edge and psi_lo / psi_hi = f of the i = 0 / i = ni-1 edge:
+ *                             P[i][j] = (1-t) phi_lo[i] + t phi_hi[i], t = j/(nj-1); Q[i][j] = (1-s) psi_lo[j] + s psi_hi[j], s = i/(ni-1),
+ *                             every node of every block.  Evaluated on the device from the resident coordinates at the end of
+ *                             create and of tm_smoother_upload, then FROZEN over the outer iterations;
+ *                             tm_smoother_update_control_function evaluates it again.  Needs no halo: works with rank hooks.
+ * Both run in every inner mode; relaxation sweeps go one per kernel pass (as with White).  ds_target / theta_target are White's. */
+enum { TM_CF_LAPLACE = 0, TM_CF_WHITE = 1, TM_CF_PRESCRIBED = 2, TM_CF_THOMAS_MIDDLECOFF = 3 };
 typedef struct tm_control_fn {
     int32_t kind;
     int32_t _pad;
@@ -329,7 +341,7 @@ int tm_rccl_comm_create(const char* librccl_path, const void* id, int32_t rank, 
 void tm_rccl_comm_destroy(tm_rccl_comm* comm);
 int tm_rccl_hooks(tm_rccl_comm* comm, const tm_mesh_desc* mesh, const int32_t* owner /* [nblocks] */, tm_comm_hooks* hooks);
 /* The same when the options of the handle the hooks are for are known (pass the very structures given to tm_smoother_create): a handle that
- * never runs sweep triples -- the Krylov modes, the White control function, TM_OPT_SINGLE_SWEEP -- then exchanges the depth-2 halo only
+ * never runs sweep triples -- the Krylov modes, any control function but laplace, TM_OPT_SINGLE_SWEEP -- then exchanges the depth-2 halo only
  * (tm_rccl_hooks sizes its tables by the topology alone: depth 3 wherever every block has at least 16 x 16 nodes, whatever the handle does with it).
  * A handle created with the library's own hooks follows the depth their tables were built for. */
 int tm_rccl_hooks_for(tm_rccl_comm* comm, const tm_mesh_desc* mesh, const int32_t* owner, const tm_solver_opt* opt, const tm_control_fn* cf /* NULL = laplace */,
@@ -396,6 +408,14 @@ int tm_smoother_inner(const tm_smoother* s);
 int tm_smoother_inner_counts(const tm_smoother* s, uint64_t* x_iterations, uint64_t* y_iterations);
 /* Current control function (P,Q) per node, 2*dof doubles (wall_control_function.zig:22-54). */
 int tm_smoother_control_function(tm_smoother* s, double* pq);
+/* Replace the resident field; same layout and extent as the getter above (2 doubles per owned node, owned blocks in order).
+ * TM_CF_PRESCRIBED and TM_CF_THOMAS_MIDDLECOFF handles (there it overrides the evaluated field until the next
+ * tm_smoother_update_control_function or tm_smoother_upload); TM_E_UNSUPPORTED on laplace and White handles.  A non-finite
+ * entry: TM_E_ARG, the resident field unchanged.  Everything that depends on the field follows at the next call. */
+int tm_smoother_set_control_function(tm_smoother* s, const double* pq);
+/* Evaluate the Thomas-Middlecoff field again from the coordinates as they are now (TM_CF_THOMAS_MIDDLECOFF handles; the other
+ * three kinds: TM_E_UNSUPPORTED). */
+int tm_smoother_update_control_function(tm_smoother* s);
 
 /* ------------------------------------------------------------------ export (the step right after the path)
  * The reference's structured output hands the writer one plane per coordinate with i fastest: plane[j*ni + i] =

@@ -18,7 +18,7 @@ import sys
 
 from . import input as tm_input
 from . import quality
-from .smoothing import smooth, solver
+from .smoothing import smooth, solver, wall_control_function
 
 
 def main(argv=None):
@@ -31,6 +31,10 @@ def main(argv=None):
     ap.add_argument("--refine", action="store_true",
                     help="refine every inner solve with a double-double residual (up to 3 steps): each Picard iterate is the exact one rounded to fp64; "
                          "with --hip auto, bicgstab, mg_bicgstab, gmres or file, not with relax or reference")
+    ap.add_argument("--control", default="file", choices=["file", "laplace", "thomas-middlecoff"],
+                    help="control function (P, Q): `file` = smoothing.wall_control_function of the input file (the default), `laplace` = none, "
+                         "`thomas-middlecoff` = every block keeps the point distribution of its own edges in its interior (evaluated once from the "
+                         "TFI seed on the device, then frozen)")
     ap.add_argument("--iterations", type=int, help="override smoothing.iterations")
     ap.add_argument("--output", help="override the output file (.xyz / .p3d: multi-block PLOT3D)")
     ap.add_argument("--until", type=float, metavar="TOL",
@@ -58,6 +62,10 @@ def main(argv=None):
         inp.solver = solver.Option.hip(inner=getattr(solver.Inner, args.hip))
     if args.refine:
         inp.solver.refine = True
+    if args.control == "laplace":
+        inp.wall_control_function = wall_control_function.Algorithm.laplace()
+    elif args.control == "thomas-middlecoff":
+        inp.wall_control_function = wall_control_function.Algorithm.thomas_middlecoff()
     if inp.solver.tag != solver.Tag.hip:
         sys.exit(f"error.ExternalSolverNotEnabled: solver `{inp.solver.tag.name}` is served by the Zig program; "
                  "use \"solver\": {\"hip\": {}} in the input file or pass --hip")

@@ -22,7 +22,7 @@ _ERR_NAMES = {-1: "InconsistentSize", -2: "Topology", -3: "Mismatch", -4: "Overf
               -7: "OutOfMemory", -8: "Hip", -9: "Comm"}
 TM_SOLVER_GMRES, TM_SOLVER_BICGSTAB, TM_SOLVER_UMFPACK, TM_SOLVER_PETSC, TM_SOLVER_HIP = 0, 1, 2, 3, 4
 TM_INNER_BICGSTAB, TM_INNER_RELAX, TM_INNER_MG_BICGSTAB, TM_INNER_AUTO, TM_INNER_GMRES, TM_INNER_REFERENCE_GMRES = 0, 1, 2, 3, 4, 5
-TM_CF_LAPLACE, TM_CF_WHITE = 0, 1
+TM_CF_LAPLACE, TM_CF_WHITE, TM_CF_PRESCRIBED, TM_CF_THOMAS_MIDDLECOFF = 0, 1, 2, 3
 TM_OPT_REFINE = 16
 
 
@@ -138,6 +138,7 @@ EXPORTS = [
     "tm_rccl_peer_table_build", "tm_rccl_peer_table_free", "tm_white_math_probe", "tm_stream_probe", "tm_smoother_queue_ordering", "tm_smoother_inner", "tm_csr_ilu0_probe", "tm_rccl_hooks_for", "tm_smoother_assemble_csr", "tm_smoother_apply_reference_order",
     "tm_smoother_inner_counts", "tm_mesh_quality", "tm_mesh_quality_host", "tm_smoother_quality", "tm_smoother_quality_field",
     "tm_csr_residual", "tm_smoother_residual", "tm_smoother_refine_report",
+    "tm_smoother_set_control_function", "tm_smoother_update_control_function",
     "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
 ]
 
@@ -210,6 +211,8 @@ def lib():
         L.tm_smoother_apply_reference_order.argtypes = [C.c_void_p, _dp, _dp]
         L.tm_smoother_row_kinds.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.tm_smoother_control_function.argtypes = [C.c_void_p, _dp]
+        L.tm_smoother_set_control_function.argtypes = [C.c_void_p, _dp]
+        L.tm_smoother_update_control_function.argtypes = [C.c_void_p]
         L.tm_smoother_profile.argtypes = [C.c_void_p, C.c_int]
         L.tm_smoother_profile_read.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.tm_smoother_queue_ordering.argtypes = [C.c_void_p]

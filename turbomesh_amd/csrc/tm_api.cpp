@@ -448,6 +448,24 @@ int tm_smoother_upload(tm_smoother* s, const tm_mesh_desc* mesh) {
             s->impl.white_launch(0);
             s->impl.sync();
         }
+        if (s->impl.thomas_middlecoff()) {   // the field belongs to the coordinates it was evaluated from
+            s->impl.tm_field_launch();
+            s->impl.sync();
+        }
+        return TM_OK;
+    });
+}
+int tm_smoother_set_control_function(tm_smoother* s, const double* pq) {
+    return guarded([&]() {
+        if (!s || !pq) throw TmError(TM_E_ARG, "null argument");
+        s->impl.set_control_function_host(pq);
+        return TM_OK;
+    });
+}
+int tm_smoother_update_control_function(tm_smoother* s) {
+    return guarded([&]() {
+        if (!s) throw TmError(TM_E_ARG, "null handle");
+        s->impl.update_control_function();
         return TM_OK;
     });
 }
@@ -670,6 +688,8 @@ int tm_smoother_queue_ordering(const tm_smoother* s) { return s ? s->impl.queue_
 // ------------------------------------------------------------------ seam 1 (smooth.zig:74-80)
 int tm_smooth_mesh(const tm_mesh_desc* mesh, uint64_t iterations, const tm_solver_opt* opt, const tm_control_fn* cf, tm_stats* stats) {
     tm_smoother* h = nullptr;
+    if (cf && cf->kind == TM_CF_PRESCRIBED)   // a one-shot call has no way to pass the field: the handle API has tm_smoother_set_control_function
+        return guarded([&]() -> int { throw TmError(TM_E_ARG, "tm_smooth_mesh cannot take a prescribed control function: use a handle and tm_smoother_set_control_function"); });
     int rc = tm_smoother_create(mesh, opt, cf, nullptr, nullptr, &h);
     if (rc < 0) return rc;
     tm_stats st;

@@ -325,6 +325,19 @@ struct WhiteArgs {
 };
 hipError_t launch_white(const WhiteArgs& w, int update, hipStream_t stream);
 
+// ---- K10 Thomas-Middlecoff control field (tm_control.hip): (P,Q) of every owned block from its own four edges.  One table entry per
+// owned block; node0 / edge0 = where the block starts in the rank-local vectors / in the scratch of 2 (ni + nj) doubles per block;
+// wg_edges / wg_blend = the block's first workgroup in the two launches (tm_field_*_nwg workgroups each).  X is read along the four
+// edges only, PQ is written for every node of every block in the table.
+struct TmFieldBlock {
+    long long node0, edge0;
+    int ni, nj, wg_edges, wg_blend;
+};
+int tm_field_edges_nwg(int ni, int nj);
+int tm_field_blend_nwg(int ni, int nj);
+hipError_t launch_tm_field(const TmFieldBlock* table /* device */, int nblocks, int nwg_edges, int nwg_blend, const double2* X, double* scratch,
+                           double2* PQ, hipStream_t stream);
+
 // ---- multigrid transfer kernels (one block, one pair of levels).  Coarse node c of a coarsened direction sits on fine node
 // min(2c, n_fine - 1): standard vertex coarsening, with one short last cell when n_fine is even (4096 -> 2049 -> 1025 ...).
 struct MgPair {

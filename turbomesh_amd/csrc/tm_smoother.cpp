@@ -215,7 +215,8 @@ void Smoother::resolve_options(const tm_mesh_desc* mesh, const tm_solver_opt* o,
     if (opt.check_every == 0) opt.check_every = (opt.inner == TM_INNER_MG_BICGSTAB) ? 1 : 8;   // a multigrid-preconditioned iteration costs ~100x a poll
     if (!(opt.omega > 0)) opt.omega = 1.0;
     cf = c ? *c : tm_control_fn{TM_CF_LAPLACE, 0, 0.0, 0.0};
-    if (cf.kind != TM_CF_LAPLACE && cf.kind != TM_CF_WHITE) throw TmError(TM_E_ARG, "unknown control function");
+    if (cf.kind != TM_CF_LAPLACE && cf.kind != TM_CF_WHITE && cf.kind != TM_CF_PRESCRIBED && cf.kind != TM_CF_THOMAS_MIDDLECOFF)
+        throw TmError(TM_E_ARG, "unknown control function");
 }
 
 // topology, the defaults that depend on the size of the system, rows, this rank's local plan, the White layout check
@@ -260,6 +261,7 @@ void Smoother::plan_mesh(const tm_mesh_desc* mesh, const tm_comm_hooks* h, bool 
     if (n_owned == 0) throw TmError(TM_E_ARG, "this rank owns no block");
 
     white = cf.kind == TM_CF_WHITE;
+    has_field = cf.kind != TM_CF_LAPLACE;
     if (white) {   // wall_control_function.zig:72, 204-217: hard-coded to blocks 0,1 and connection 0
         if (topo.nblocks() < 2 || topo.conns.empty()) throw TmError(TM_E_TOPOLOGY, "white control function needs the O4H layout (blocks 0,1 + connection 0)");
         const TopoConn& c0 = topo.conns[0];
@@ -298,7 +300,22 @@ void Smoother::alloc_vectors(const tm_mesh_desc* mesh, bool measure) {
         s = vec();
         t = vec();
     }
-    if (white) PQ = vec();
+    if (has_field) PQ = vec();
+    if (thomas_middlecoff()) {   // K10: one table entry and 2 (ni + nj) doubles of edge functions per owned block
+        std::vector<TmFieldBlock> table(lp.owned_blocks.size());
+        long long edge0 = 0;
+        tmf_nwg_edges = tmf_nwg_blend = 0;
+        for (size_t k = 0; k < lp.owned_blocks.size(); ++k) {
+            const int64_t b = lp.owned_blocks[k];
+            const int bi = static_cast<int>(topo.ni[b]), bj = static_cast<int>(topo.nj[b]);
+            table[k] = TmFieldBlock{static_cast<long long>(lp.local_start[k]), edge0, bi, bj, tmf_nwg_edges, tmf_nwg_blend};
+            edge0 += 2LL * (bi + bj);
+            tmf_nwg_edges += tm_field_edges_nwg(bi, bj);
+            tmf_nwg_blend += tm_field_blend_nwg(bi, bj);
+        }
+        tmf_table = static_cast<TmFieldBlock*>(upload_table(table.data(), sizeof(TmFieldBlock) * table.size()));
+        tmf_scratch = arena.alloc_n<double>(static_cast<uint64_t>(edge0));
+    }
     if (refine()) {   // TM_OPT_REFINE: right-hand side, double-double residual, correction, 1 / a_ii of the assembled system
         ref_b = vec();
         rf_r = vec();
@@ -319,7 +336,7 @@ void Smoother::alloc_vectors(const tm_mesh_desc* mesh, bool measure) {
             const int64_t b = lp.owned_blocks[k];
             const int bi = static_cast<int>(topo.ni[b]), bj = static_cast<int>(topo.nj[b]);
             const double* xy = (mesh && mesh->blocks) ? mesh->blocks[b].xy : nullptr;
-            mg[k].build(arena, bi, bj, white, BlockMG::aspect_of(xy, bi, bj), measure);
+            mg[k].build(arena, bi, bj, has_field, BlockMG::aspect_of(xy, bi, bj), measure);
         }
         // Small and medium blocks: every level of a cycle is a handful of launch-bound kernels, and the cycles of different blocks share nothing
         // -- run them side by side, a stream per block (the reference's examples refined 8 x: 8 blocks, ~190 us of dependent launches each
@@ -342,8 +359,9 @@ void Smoother::alloc_vectors(const tm_mesh_desc* mesh, bool measure) {
 
 // sweep pairs, coupled triples, how K2x2 stores, the LDS cap of the interior pass (and the vectors these schedules need)
 void Smoother::decide_schedule() {
-    // two sweeps per pass (K2x2): Laplace control function only (White updates P,Q between sweeps), every owned block >= 5 x 5
-    fuse_pairs = opt.inner == TM_INNER_RELAX && !white && !(opt.flags & TM_OPT_SINGLE_SWEEP);
+    // two sweeps per pass (K2x2): Laplace control function only (White updates P,Q between sweeps; any field sends the sweeps down the
+    // single-sweep path, the one that takes a.pq), every owned block >= 5 x 5
+    fuse_pairs = opt.inner == TM_INNER_RELAX && !has_field && !(opt.flags & TM_OPT_SINGLE_SWEEP);
     { const char* e = std::getenv("TM_PAIR_SYNC"); pair_sync_events = e && std::strcmp(e, "events") == 0; }
     // (every block of the mesh, not just the owned ones: the ranks of a job must agree on the schedule -- a pair costs one exchange)
     for (int64_t b = 0; b < topo.nblocks(); ++b)
@@ -725,6 +743,7 @@ void Smoother::finish_create(const tm_mesh_desc* mesh) {
     if (PQ) HIPCHK(hipMemsetAsync(PQ, 0, sizeof(double2) * n_local, stream));
     upload(mesh);
     if (white) white_launch(0);   // ControlFunction.init, wall_control_function.zig:27-42
+    if (thomas_middlecoff()) tm_field_launch();   // from the coordinates just uploaded; frozen from here on
     if (refine()) csr_fill_values();       // pattern and value arrays of the assembled system, kept for the handle's lifetime (csr_release)
     if (reference()) reference_create();   // everything the mode needs, now: a mesh that does not fit fails here, not in the middle of a solve
     sync();
@@ -1053,6 +1072,28 @@ void Smoother::white_launch(int update) {
     w.ds_target = cf.ds_target;
     w.theta_target = cf.theta_target;
     HIPCHK(launch_white(w, update, stream));
+}
+
+// K10: the Thomas-Middlecoff field of every owned block from the coordinates as they are now (ghost rows keep their zeros: every row reads
+// the field at its own, owned, node).  In stream order, no synchronisation.
+void Smoother::tm_field_launch() {
+    HIPCHK(launch_tm_field(tmf_table, static_cast<int>(lp.owned_blocks.size()), tmf_nwg_edges, tmf_nwg_blend, X, tmf_scratch, PQ, stream));
+}
+
+void Smoother::update_control_function() {
+    if (!thomas_middlecoff()) throw TmError(TM_E_UNSUPPORTED, "tm_smoother_update_control_function: the handle's control function is not Thomas-Middlecoff");
+    tm_field_launch();
+}
+
+// The caller's field in place of the resident one.  What depends on it is formed from PQ when it is used: the multigrid hierarchy by
+// set_field at the start of every outer iteration, the assembled system by csr_fill_values in front of every use.
+void Smoother::set_control_function_host(const double* pq) {
+    if (cf.kind != TM_CF_PRESCRIBED && !thomas_middlecoff())
+        throw TmError(TM_E_UNSUPPORTED, "tm_smoother_set_control_function needs a prescribed or Thomas-Middlecoff handle");
+    for (int64_t k = 0; k < 2 * n_owned; ++k)
+        if (!std::isfinite(pq[k])) throw TmError(TM_E_ARG, "tm_smoother_set_control_function: entry " + std::to_string(k) + " is not finite");
+    HIPCHK(hipMemcpyAsync(PQ, pq, sizeof(double2) * n_owned, hipMemcpyHostToDevice, stream));
+    sync();   // the caller's array is free when the call returns
 }
 
 // out = M^-1 in: one V-cycle per owned block on the interior rows, identity on the perimeter rows (tm_multigrid.hpp)

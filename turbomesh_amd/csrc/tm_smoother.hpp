@@ -150,6 +150,16 @@ struct Smoother {
     // white control function
     bool white = false;
     ConnShifts white_le{};
+    // a per-node (P,Q) field exists: every kind but laplace.  `white` above = White's O4H algorithm runs on it; the prescribed and the
+    // Thomas-Middlecoff field are frozen over the outer iterations and change only through the three calls below
+    bool has_field = false;
+    bool thomas_middlecoff() const { return cf.kind == TM_CF_THOMAS_MIDDLECOFF; }
+    TmFieldBlock* tmf_table = nullptr;   // K10 (tm_control.hip): block table and edge scratch, carved from the arena (Thomas-Middlecoff handles)
+    double* tmf_scratch = nullptr;
+    int tmf_nwg_edges = 0, tmf_nwg_blend = 0;
+    void tm_field_launch();                            // PQ of every owned block from the resident coordinates (asynchronous)
+    void set_control_function_host(const double* pq);  // tm_smoother_set_control_function
+    void update_control_function();                    // tm_smoother_update_control_function
     uint64_t outer_done = 0;
     // measurement: HIP event pairs around K2 launches
     int profile = 0;                // 0 = off, k > 0 = every k-th launch of the dominant kernel is bracketed

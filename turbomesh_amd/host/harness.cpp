@@ -3,6 +3,7 @@
 //
 //   tm_harness strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]
 //   tm_harness single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]
+//   tm_harness tm <ni> <nj> <iterations>               the Thomas-Middlecoff control field on a clustered rectangle (exit 0: it kept the clustering)
 //   tm_harness csr                                     the linear-solver slot (seam 2) on the reference's 5 x 5 known answer
 //   tm_harness ranks <world> <rank> <idfile> <nblocks> <ni> <nj> <iterations> [relax|bicgstab] [dump.bin]
 //        one process per GPU (start each with HIP_VISIBLE_DEVICES=<its GPU>): the strip's blocks are dealt to the ranks in order, the
@@ -181,9 +182,53 @@ static int runRank(int argc, char** argv) {
     return 0;
 }
 
+// tm_harness tm <ni> <nj> <iterations>: a rectangle whose i lines are tanh-clustered towards both ends and whose j lines towards the lower
+// wall, x = x(i), y = y(j): under the Thomas-Middlecoff field this seed is a fixed point of the discrete equations (P = -x_ii / x_i exactly
+// cancels the second difference), under Laplace it relaxes towards the uniform mesh.  Prints how far the nodes moved under either.
+static int thomasMiddlecoff(std::size_t ni, std::size_t nj, std::size_t iterations) {
+    std::vector<double> x(ni), y(nj);
+    for (std::size_t i = 0; i < ni; ++i) x[i] = 0.5 * (1.0 + std::tanh(2.0 * (2.0 * static_cast<double>(i) / static_cast<double>(ni - 1) - 1.0)) / std::tanh(2.0));
+    for (std::size_t j = 0; j < nj; ++j) y[j] = 1.0 + std::tanh(2.5 * (static_cast<double>(j) / static_cast<double>(nj - 1) - 1.0)) / std::tanh(2.5);
+    auto build = [&]() {
+        std::vector<Vec2d> lo(ni), up(ni), le(nj), ri(nj);
+        for (std::size_t i = 0; i < ni; ++i) lo[i] = Vec2d{{x[i], y[0]}}, up[i] = Vec2d{{x[i], y[nj - 1]}};
+        for (std::size_t j = 0; j < nj; ++j) le[j] = Vec2d{{x[0], y[j]}}, ri[j] = Vec2d{{x[ni - 1], y[j]}};
+        Block2d b = Block2d::init(uniformEdge(lo), uniformEdge(up), uniformEdge(le), uniformEdge(ri));
+        for (std::size_t i = 0; i < ni; ++i)
+            for (std::size_t j = 0; j < nj; ++j) b.points.data[b.points.index(i, j)] = Vec2d{{x[i], y[j]}};
+        discrete::Mesh mesh;
+        mesh.addBlock("block_0", std::move(b));
+        return mesh;
+    };
+    auto moved = [&](const discrete::Mesh& m) {
+        double s = 0.0;
+        for (std::size_t i = 0; i < ni; ++i)
+            for (std::size_t j = 0; j < nj; ++j) {
+                const Vec2d p = m.blocks[0].points.getIndex(i, j);
+                s += (p.data[0] - x[i]) * (p.data[0] - x[i]) + (p.data[1] - y[j]) * (p.data[1] - y[j]);
+            }
+        return std::sqrt(s / static_cast<double>(2 * ni * nj));
+    };
+    smoothing::solver::Option opt;
+    double rms[2], pmax = 0.0, qmax = 0.0;
+    for (int k = 0; k < 2; ++k) {
+        discrete::Mesh mesh = build();
+        smoothing::smooth::Smoother sm(mesh, opt, k == 0 ? smoothing::wall_control_function::Algorithm::thomas_middlecoff() : smoothing::wall_control_function::Algorithm::laplace());
+        if (k == 0)
+            for (const Vec2d& pq : sm.controlFunction()) pmax = std::max(pmax, std::fabs(pq.data[0])), qmax = std::max(qmax, std::fabs(pq.data[1]));
+        sm.iterate(iterations);
+        sm.download();
+        rms[k] = moved(mesh);
+    }
+    std::printf("thomas_middlecoff max|P| %.6f max|Q| %.6f rms_moved %.3e laplace rms_moved %.3e\n", pmax, qmax, rms[0], rms[1]);
+    return rms[0] <= 1e-12 && rms[1] > 1e-2 ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     try {
         if (argc >= 2 && std::strcmp(argv[1], "csr") == 0) return csrKat();
+        if (argc >= 5 && std::strcmp(argv[1], "tm") == 0)
+            return thomasMiddlecoff(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "ranks") == 0) return runRank(argc, argv);
         if (argc < 5) {
             std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n", argv[0], argv[0]);

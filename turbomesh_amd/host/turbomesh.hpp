@@ -238,8 +238,23 @@ struct Option {
 namespace wall_control_function {               // wall_control_function.zig:10-20, 56-68
 struct White { double ds_target; double theta_target = 1.5707963267948966; };
 struct Algorithm {
-    std::optional<White> white;   // nullopt = .laplace
+    std::optional<White> white;   // nullopt = .laplace (or one of the two kinds below)
+    // the two kinds the library adds for any topology (include/tm_hip.h): thomas_middlecoff = block-local field from the block's own edges,
+    // evaluated on the device and frozen; prescribed = the caller's per-node field, one vector of ni*nj (P, Q) pairs per block, which
+    // smooth::Smoother sets after create (smooth::mesh, the one-shot call, cannot take it)
+    bool thomas_middlecoff_ = false;
+    std::optional<std::vector<std::vector<types::Vec2d>>> prescribed_;
     static Algorithm laplace() { return Algorithm{}; }
+    static Algorithm thomas_middlecoff() {
+        Algorithm a;
+        a.thomas_middlecoff_ = true;
+        return a;
+    }
+    static Algorithm prescribed(std::vector<std::vector<types::Vec2d>> fields) {
+        Algorithm a;
+        a.prescribed_ = std::move(fields);
+        return a;
+    }
 };
 }  // namespace wall_control_function
 namespace smooth {
@@ -290,6 +305,8 @@ inline tm_solver_opt toOpt(const solver::Option& o) {
 }
 inline tm_control_fn toControl(const wall_control_function::Algorithm& a) {
     if (a.white) return tm_control_fn{TM_CF_WHITE, 0, a.white->ds_target, a.white->theta_target};
+    if (a.thomas_middlecoff_) return tm_control_fn{TM_CF_THOMAS_MIDDLECOFF, 0, 0.0, 0.0};
+    if (a.prescribed_) return tm_control_fn{TM_CF_PRESCRIBED, 0, 0.0, 0.0};
     return tm_control_fn{TM_CF_LAPLACE, 0, 0.0, 0.0};
 }
 
@@ -320,7 +337,27 @@ class Smoother {
         tm_solver_opt so = toOpt(o);
         tm_control_fn cf = toControl(a);
         check(tm_smoother_create(&d_.desc, &so, &cf, hooks, nullptr, &h_));
+        if (a.prescribed_) {
+            try {
+                std::vector<types::Vec2d> flat;
+                for (const auto& f : *a.prescribed_) flat.insert(flat.end(), f.begin(), f.end());
+                if (flat.size() != tm_smoother_dof(h_)) throw Error(TM_E_SIZE, "prescribed control function: one (P, Q) pair per node of every block");
+                setControlFunction(flat);
+            } catch (...) {
+                tm_smoother_destroy(h_);
+                throw;
+            }
+        }
     }
+    // the resident (P, Q) field, one pair per owned node in block order; set: prescribed and Thomas-Middlecoff handles; update: evaluate the
+    // Thomas-Middlecoff field again from the coordinates resident now
+    std::vector<types::Vec2d> controlFunction() {
+        std::vector<types::Vec2d> pq(tm_smoother_dof(h_));
+        check(tm_smoother_control_function(h_, &pq[0].data[0]));
+        return pq;
+    }
+    void setControlFunction(const std::vector<types::Vec2d>& pq) { check(tm_smoother_set_control_function(h_, &pq[0].data[0])); }
+    void updateControlFunction() { check(tm_smoother_update_control_function(h_)); }
     const tm_mesh_desc& desc() const { return d_.desc; }
     ~Smoother() { tm_smoother_destroy(h_); }
     Smoother(const Smoother&) = delete;

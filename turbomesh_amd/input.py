@@ -80,7 +80,14 @@ class Input:
             opt = _solver.Option(tag=getattr(_solver.Tag, stag), preconditioner=getattr(_solver.Preconditioner, spay.get("preconditioner", "diagonal")))
         wcf = sm.get("wall_control_function", {"laplace": {}})
         (wtag, wpay), = wcf.items()
-        algo = _wcf.Algorithm.laplace() if wtag == "laplace" else _wcf.Algorithm(_wcf.White(wpay["ds_target"], wpay.get("theta_target", 1.5707963267948966)))
+        if wtag == "laplace":
+            algo = _wcf.Algorithm.laplace()
+        elif wtag == "thomas_middlecoff":   # not in the reference's schema: the library's block-local field, no parameters
+            algo = _wcf.Algorithm.thomas_middlecoff()
+        elif wtag == "white":
+            algo = _wcf.Algorithm(_wcf.White(wpay["ds_target"], wpay.get("theta_target", 1.5707963267948966)))
+        else:
+            raise ValueError(f"unknown wall_control_function {wtag}")
         g = j["geometry"]
         return cls(tmpl, sm.get("iterations", 0), opt, algo, g.get("scale", 1.0), g["pitch"], g["profile"], j.get("output"), j.get("gui"))
 

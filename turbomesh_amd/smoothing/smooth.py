@@ -81,6 +81,13 @@ class Smoother:
         self._h = h
         self.dof = int(_capi.lib().tm_smoother_dof(self._h))
         self.inner = _solver.Inner(int(_capi.lib().tm_smoother_inner(self._h)))   # what Inner.auto resolved to
+        fields = getattr(control_function_algorithm, "fields", None)
+        if fields is not None:   # Algorithm.prescribed(fields): the handle starts from a zero field
+            try:
+                self.set_control_function(fields)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None):
@@ -268,6 +275,28 @@ class Smoother:
         out = np.empty((self.dof, 2))
         _capi.check(_capi.lib().tm_smoother_control_function(self._h, _capi.f64ptr(out)))
         return out
+
+    def set_control_function(self, fields):
+        """Replace the resident (P, Q) field (tm_smoother_set_control_function): one (ni, nj, 2) array per block in block order, or
+        the getter's flat (dof, 2) array.  Prescribed and Thomas-Middlecoff handles; on the latter it holds until the next
+        update_control_function() or upload()."""
+        if isinstance(fields, np.ndarray):
+            flat = np.ascontiguousarray(fields, dtype=np.float64)
+        else:
+            blocks = self._mesh.blocks
+            if len(fields) != len(blocks):
+                raise ValueError(f"{len(fields)} fields for {len(blocks)} blocks")
+            for f, b in zip(fields, blocks):
+                if tuple(np.shape(f)) != (b.points.size[0], b.points.size[1], 2):
+                    raise ValueError(f"field of shape {np.shape(f)} for a block of {tuple(b.points.size)} nodes")
+            flat = np.ascontiguousarray(np.concatenate([np.asarray(f, dtype=np.float64).reshape(-1, 2) for f in fields]))
+        if flat.shape != (self.dof, 2):
+            raise ValueError(f"the control function has shape {flat.shape}, the handle {self.dof} nodes")
+        _capi.check(_capi.lib().tm_smoother_set_control_function(self._h, _capi.f64ptr(flat)))
+
+    def update_control_function(self):
+        """Evaluate the Thomas-Middlecoff field again from the coordinates resident now (tm_smoother_update_control_function)."""
+        _capi.check(_capi.lib().tm_smoother_update_control_function(self._h))
 
 
 def plan_rows(mesh_data):
