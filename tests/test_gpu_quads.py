@@ -17,7 +17,7 @@ from turbomesh_amd.smoothing import smooth, solver
 pytestmark = pytest.mark.gpu
 
 SWEEPS = [4, 5, 6, 7, 8, 11]
-HEIGHT = 6   # the smallest chunk height of K2x4 (relax4_rows_for_launch): what a launch of this few workgroups gets
+HEIGHT = 6   # the smallest chunk height of K2x4 (relaxn_rows_for_launch, depth 4): what a launch of this few workgroups gets
 # nj: one strip (9, 10), 56 / 57 owned columns (57, 58, 59), a second strip (61, 64, 65), exactly 4 strips of a workgroup and a bit more (225, 226, 227);
 # ni: the 9 x 9 minimum and its neighbours, HEIGHT + 3, 2 HEIGHT + 2, many chunks with a short last one (67)
 SHAPES = [(9, 9), (10, 10), (11, 57), (13, 58), (HEIGHT + 3, 59), (2 * HEIGHT + 2, 61), (67, 64), (10, 65), (11, 113), (2 * HEIGHT + 2, 114),

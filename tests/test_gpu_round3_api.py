@@ -38,7 +38,11 @@ def test_stream_probe_reports_a_plausible_ceiling():
     assert _capi.lib().tm_stream_probe(16, 10, C.byref(cp), C.byref(tr)) == _capi.TM_E_ARG
 
 
-@pytest.mark.parametrize("shape", [(7, 7), (8, 61), (64, 59), (70, 131), (131, 300), (40, 1000)])
+@pytest.mark.parametrize("shape", [(7, 7), (8, 61), (64, 59), (70, 131), (131, 300), (40, 1000),
+                                   # the seams of the depth-templated pass K2x3 shares with K2x4: the 7-row minimum with exactly one full strip of 58
+                                   # owned columns; one column into a second strip, 8 + 3 rows; two chunks of the smallest height; four strips =
+                                   # a workgroup exactly; one column into a second workgroup; the minimum width with a short last chunk
+                                   (7, 60), (11, 61), (18, 233), (67, 234), (9, 235), (67, 7)])
 def test_three_sweeps_per_pass_equal_single_sweeps(shape, monkeypatch):
     # K2x3 (blocks whose perimeter rows are all fixed) against one sweep per pass, every split of the sweep count into triples, pairs
     # and single sweeps, around the 58-column strip seams and the chunk seams; and with omega != 1 (the general update form)

@@ -127,18 +127,16 @@ struct Relax2Batch {
 hipError_t launch_relax2_blocks(const Relax2Block* blocks, const int* rows_per_chunk, int n, int dot, int subset, hipStream_t stream,
                                 size_t lds_bytes = 0, const QueueWait* wait = nullptr);
 void tune_fuse_rows(int rows);
-// ---- K2x3: THREE fused sweeps per pass of blocks whose perimeter rows are all `fixed` (in -> out; `mid`, `border`, `dyn` unused)
-bool relax3_supported(int ni, int nj);
-int relax3_rows_per_chunk(int ni, int nj);
-// ... chosen for the blocks of one launch together (n <= APPLY_BATCH_MAX; launch_relax3_blocks groups the blocks in this order)
-void relax3_rows_for_launch(const int* ni, const int* nj, int n, int* rows, bool beside_chain);
-int relax3_block_nwg(int ni, int nj, int rows_per_chunk);
-hipError_t launch_relax3_blocks(const Relax2Block* blocks, const int* rows_per_chunk, int n, int dot, hipStream_t stream);
-// ---- K2x4: FOUR fused sweeps per pass, blocks with dyn == 0 only (ni, nj >= 9: relax4_supported); TM_FUSE4_ROWS forces the chunk height
-bool relax4_supported(int ni, int nj);
-void relax4_rows_for_launch(const int* ni, const int* nj, int n, int* rows);   // n <= APPLY_BATCH_MAX: the blocks of one launch
-int relax4_block_nwg(int ni, int nj, int rows_per_chunk);
-hipError_t launch_relax4_blocks(const Relax2Block* blocks, const int* rows_per_chunk, int n, int dot, hipStream_t stream);
+// ---- K2x3 / K2x4: depth = 3 or 4 fused sweeps per pass of blocks whose perimeter rows are all `fixed` (in -> out; `mid`, `border`
+// unused).  One pass, two instantiations; ni, nj >= 2 depth + 1.  Depth 3 also takes coupled blocks: along the sides named in `dyn` it
+// leaves the nodes within two of the side to the perimeter-row chain (Smoother::relax_triples_coupled); depth 4 takes dyn == 0 only
+// (hipErrorInvalidValue otherwise).
+bool relaxn_supported(int depth, int ni, int nj);
+// rows per chunk, chosen for the blocks of one launch together (n <= APPLY_BATCH_MAX; launch_relaxn_blocks groups the blocks in this
+// order); beside_chain (depth 3): the pass runs beside the perimeter-row chain.  TM_FUSE3_ROWS / TM_FUSE4_ROWS force the height.
+void relaxn_rows_for_launch(int depth, const int* ni, const int* nj, int n, int* rows, bool beside_chain);
+int relaxn_block_nwg(int depth, int ni, int nj, int rows_per_chunk);
+hipError_t launch_relaxn_blocks(int depth, const Relax2Block* blocks, const int* rows_per_chunk, int n, int dot, hipStream_t stream);
 
 // ---- K4/K5 perimeter rows and the fused level kernel: EdgeRun / EdgeRowsDev / LevelTask / FusedLevelsDev live in tm_edge_types.h
 hipError_t launch_edge_levels3(const FusedLevelsDev& F, const EdgeRowsDev& e1, const EdgeRowsDev& e2, const EdgeRowsDev& e3, const double2* x, double2* m,

@@ -301,6 +301,16 @@ __device__ __forceinline__ double2 virtual_vec(double2 x, double2 y, double2 z, 
 
 __device__ __forceinline__ double2 load_nt(const double2* src);   // defined with the vector kernels
 
+// The block of a batched launch (ApplyBatch, Relax2Batch) that this workgroup works on: start[k] = first workgroup of block k.
+template <class Batch>
+__device__ __forceinline__ int batch_slot(const Batch& B) {
+    int k = 0;
+#pragma unroll
+    for (int q = 1; q < APPLY_BATCH_MAX; ++q)
+        if (q < B.n && static_cast<int>(blockIdx.x) >= B.start[q]) k = q;
+    return k;
+}
+
 // One workgroup's tile of one block; `bid` = the workgroup's index within that block's tiles (also its partial-sum slot).
 // VK (virtual input vector, formed as the rows are taken into the window; va, vb component-wise):
 //   VK_S: in - va * in2                (s = r - alpha v, never stored)
@@ -596,10 +606,7 @@ __global__ __launch_bounds__(256) void k_apply(ApplyBlock a, int RI, int nSG, in
 // launch-bound, not bandwidth-bound.  start[k] = first workgroup of block k.
 template <int MODE, int DOT, bool FIELD, bool HAS_PQ, int U, bool NT>
 __global__ __launch_bounds__(256) void k_apply_batch(ApplyBatch B) {
-    int k = 0;
-#pragma unroll
-    for (int q = 1; q < APPLY_BATCH_MAX; ++q)
-        if (q < B.n && static_cast<int>(blockIdx.x) >= B.start[q]) k = q;
+    const int k = batch_slot(B);
     apply_tile<MODE, DOT, FIELD, HAS_PQ, U, NT>(B.b[k], B.RI[k], B.nSG[k], B.nRC[k], static_cast<int>(blockIdx.x) - B.start[k]);
 }
 
@@ -934,162 +941,35 @@ __global__ __launch_bounds__(256) void k_relax2_waited(Relax2Block a, int RI, in
 template <int DOT, int U, int NT, bool W1>
 __global__ __launch_bounds__(256) void k_relax2_batch_waited(Relax2Batch B, int subset, QueueWait w) {
     queue_wait_in_kernel(w);
-    int k = 0;
-#pragma unroll
-    for (int q = 1; q < APPLY_BATCH_MAX; ++q)
-        if (q < B.n && static_cast<int>(blockIdx.x) >= B.start[q]) k = q;
+    const int k = batch_slot(B);
     relax2_tile<DOT, U, NT, W1>(B.b[k], B.RI[k], B.nSG[k], B.nRC[k], subset, static_cast<int>(blockIdx.x) - B.start[k]);
 }
 template <int DOT, int U, int NT, bool W1>
 __global__ __launch_bounds__(256) void k_relax2_batch(Relax2Batch B, int subset) {
-    int k = 0;
-#pragma unroll
-    for (int q = 1; q < APPLY_BATCH_MAX; ++q)
-        if (q < B.n && static_cast<int>(blockIdx.x) >= B.start[q]) k = q;
+    const int k = batch_slot(B);
     relax2_tile<DOT, U, NT, W1>(B.b[k], B.RI[k], B.nSG[k], B.nRC[k], subset, static_cast<int>(blockIdx.x) - B.start[k]);
 }
 
 // ------------------------------------------------------------------------------------------
-// K2x3: THREE fused Jacobi sweeps per pass, for blocks whose perimeter rows are all `fixed` (a single block with prescribed
-// walls: BASELINE configs[1], the slices of configs[4]).  K2x2 is within ~10 % of what the part streams for its traffic
-// (tools/ubench/stream.hip) while its fp64 pipes idle a third of the time; a third sweep per pass costs arithmetic only.  With the
-// perimeter constant, the perimeter value of every intermediate field is the input's own value at that node, so no `mid` array,
-// no ring and no perimeter-row kernel take part.  A wave loads the 64 columns c0-H .. c0+63-H and owns the 64-2H output columns
-// c0 .. c0+63-2H (H = 3: 58 columns); row chunks overlap
-// by 3 rows either side.  Same arithmetic as three K2 launches, bit for bit (tests/test_gpu_fused.py, test_gpu_benchsize.py).
+// K2x3 / K2x4: L = 3 or 4 fused Jacobi sweeps per pass, for blocks whose perimeter rows are all `fixed` (a single block with
+// prescribed walls: BASELINE configs[1], the slices of configs[4]); L = 3 also serves coupled blocks (Relax2Block::dyn != 0, below),
+// L = 4 takes dyn == 0 only.  K2x2 is within ~10 % of what the part streams for its traffic (tools/ubench/stream.hip) while its fp64
+// pipes idle a third of the time: one read and one write of the field cost ~95 us at 4096^2 whatever the pass computes, and each
+// further sweep carried by the same bytes costs far less than its issue time.  With the perimeter constant, the
+// perimeter value of every intermediate field is the input's own value at that node, so no `mid` array, no ring and no
+// perimeter-row kernel take part.
+// One body, the depth L a parameter: L window levels, a halo of L lanes per side -- a wave loads the 64 columns c0-L .. c0+63-L and
+// owns the 64 - 2L output columns c0 .. c0+63-2L (L = 3: 58; L = 4: 56, every stored segment 896 B = whole 128 B lines) -- and row
+// chunks overlapping by L rows either side.  (Depth 3 with a halo of 4 lanes, every stored segment whole 64 B sectors: slower, 39.4
+// against 38.4 us per sweep at 4096^2, 12.6 against 11.45 at 2048^2.)  Step s takes input row r = i0 - (L-2) + s (rows i0-L,
+// i0-L+1 are preloaded), forms level k's row r - k for k = 1..L and stores row r - L; level k has its three operand rows from
+// step 2 (k-1) on, the evaluations before that are skipped at compile time.  The same relax_row applied L times: bit-identical to
+// L single sweeps (tests/test_gpu_fused.py, test_gpu_benchsize.py, test_gpu_quads.py).
 // ------------------------------------------------------------------------------------------
 #ifndef TM_R3_WAVES
 #define TM_R3_WAVES 1
 #endif
-constexpr int R3_U = 3;                 // rows per load group
-constexpr int R3_H = 3;                 // halo lanes per side (4 would make every stored segment whole 64 B sectors: slower, 39.4 against 38.4 us per sweep at 4096^2, 12.6 against 11.45 at 2048^2)
-constexpr int R3_W = 64 - 2 * R3_H;     // output columns per wave
-template <int DOT, int U, int NT, bool W1, bool INSIDE>
-__device__ __forceinline__ void relax3_strip(const Relax2Block& a, const Relax2Tile& t, double (&acc)[MAX_PARTIALS]) {
-    const int ni = a.ni, nj = a.nj;
-    const int cc = INSIDE ? t.c : min(max(t.c, 0), nj - 1);
-    const double2* in_col = a.in + cc;
-    const int last_row = INSIDE ? t.i1 + 2 : ni - 1;
-    auto load_in = [&](int row) { return in_col[static_cast<size_t>(INSIDE ? min(row, last_row) : min(max(row, 0), last_row)) * nj]; };
-    const bool perim_col = !INSIDE && ((t.c <= 0) || (t.c >= nj - 1));
-    const int nrows = t.i1 - t.i0;
-    const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.out + static_cast<size_t>(t.i0) * nj, 0, nrows * nj * 16, 0x00020000);
-    // Coupled blocks (Relax2Block::dyn != 0, Smoother::relax_triples_coupled): the pass treats every perimeter value as frozen, which is
-    // wrong along a side whose perimeter rows move -- but three sweeps carry that error only two nodes deep, so the pass simply does
-    // not store the nodes within two of such a side; the perimeter-row kernel evaluates them (and the perimeter) level by level.
-    const bool skip_col = !INSIDE && (((a.dyn & 4) && t.c <= 2) || ((a.dyn & 8) && t.c >= nj - 3));
-    const bool live_lane = t.out_lane && !skip_col;
-    const unsigned lane_off = live_lane ? static_cast<unsigned>(cc) * 16u : OOB_VOFFSET;
-    const double2 zero = make_double2(0.0, 0.0);
-
-    Row3 A[3], S1[3], S2[3];
-    double2 pc[U], pn[U];
-    {   // rows i0-3, i0-2 are in the window before the first step (which takes row i0-1)
-        const double2 a0 = load_in(t.i0 - 3), a1 = load_in(t.i0 - 2);
-#pragma unroll
-        for (int u = 0; u < U; ++u) pc[u] = load_in(t.i0 - 1 + u);
-        A[0] = make_row(a0);
-        A[1] = make_row(a1);
-        A[2].c = A[2].e = A[2].h = zero;
-        S1[0] = S1[1] = S1[2] = A[2];
-        S2[0] = S2[1] = S2[2] = A[2];
-    }
-    // step s takes row r = i0 - 1 + s of the input, forms s1[r-1], s2[r-2], s3[r-3] and stores row r-3; s3 is live from s = 4 on
-    const int nsteps = nrows + 4;
-    // (phase 0: the first group, 1: the second, 2: every later one -- a literal at each call, so the tests below fold away)
-    auto group = [&](const int tb, const int phase) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) pn[u] = load_in(t.i0 - 1 + tb + U + u);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int A0 = u % 3, A1 = (u + 1) % 3, A2 = (u + 2) % 3;   // window slots of rows r-2, r-1, r (and of the same offsets one / two levels up)
-            const int r = t.i0 - 1 + tb + u;
-            A[A2] = make_row(pc[u]);
-            double2 d = zero;
-            double2 s1 = relax_row<W1>(A[A0], A[A1], A[A2], a.omega, d);          // row r-1
-            if (!INSIDE && (perim_col || r - 1 <= 0 || r - 1 >= ni - 1)) s1 = A[A1].c;   // fixed: the input's own value
-            S1[A2] = make_row(s1);
-            // the window fills from the top: the second level has its three rows from step 2 on, the third from step 4 on.  The rows
-            // they would form before that are never used (and, from windows still holding zeros, would take the slow branch of
-            // the reciprocal): skipped -- 6 of the 3 (RI + 4) evaluations of a chunk.
-            const bool do2 = phase > 0 || u >= 2, do3 = phase > 1 || (phase == 1 && u >= 1);
-            double2 s2 = zero;
-            if (do2) {
-                s2 = relax_row<W1>(S1[A0], S1[A1], S1[A2], a.omega, d);       // row r-2
-                if (!INSIDE && (perim_col || r - 2 <= 0 || r - 2 >= ni - 1)) s2 = S1[A1].c;
-            }
-            if (do2) S2[A2] = make_row(s2);   // (else: the slot keeps the zeros it was filled with)
-            double2 d3 = zero;
-            double2 o = zero;
-            if (do3) o = relax_row<W1>(S2[A0], S2[A1], S2[A2], a.omega, d3);   // row r-3
-            const int i = r - 3;
-            const bool row_live = (i >= t.i0) && (i < t.i1) && (INSIDE || !(((a.dyn & 1) && i <= 2) || ((a.dyn & 2) && i >= ni - 3)));   // wave-uniform
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i32, o), out_rsrc,
-                                                   static_cast<int>(row_live ? lane_off + static_cast<unsigned>((i - t.i0) * nj * 16) : OOB_VOFFSET), 0,
-                                                   (NT & 1) ? 2 : 0);
-            if (DOT == DOT_DELTA) {
-                if (!(live_lane && row_live)) d3 = zero;   // masked lanes hold garbage (possibly non-finite): select, never multiply
-                accumulate<DOT_DELTA>(acc, S2[A1].c, o, d3);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) pc[u] = pn[u];
-    };
-    static_assert(U == 3, "the phases below assume three steps per group");
-    group(0, 0);
-    group(U, 1);   // (nsteps >= 5)
-    for (int tb = 2 * U; tb < nsteps; tb += U) group(tb, 2);
-}
-
-template <int DOT, int U, int NT, bool W1>
-__device__ __forceinline__ void relax3_tile(const Relax2Block& a, int RI, int nSG, int nRC, int bid) {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int total = nSG * nRC;
-    const int q8 = total >> 3, rem = total & 7, xcd = bid & 7, k8 = bid >> 3;
-    const int logical = (xcd < rem) ? xcd * (q8 + 1) + k8 : rem * (q8 + 1) + (xcd - rem) * q8 + k8;
-    const int rc = logical / nSG;
-    const int sg = logical - rc * nSG;
-    const int ni = a.ni, nj = a.nj;
-    Relax2Tile t;
-    t.c0 = (sg * 4 + wave) * R3_W;
-    t.c = t.c0 - R3_H + lane;
-    t.out_lane = (lane >= R3_H) && (lane < 64 - R3_H) && (t.c >= 1) && (t.c <= nj - 2);
-    t.i0 = 1 + rc * RI;
-    t.i1 = min(t.i0 + RI, ni - 1);
-    double acc[MAX_PARTIALS] = {0.0, 0.0, 0.0, 0.0};
-    if (t.c0 <= nj - 2 && t.i0 < t.i1) {   // wave-uniform
-        // strictly inside: every column the wave loads within [1, nj-2] and every row it touches within [1, ni-2] -> no fixed value is
-        // ever selected, no index is clamped from below
-        const bool inside = (t.c0 - R3_H >= 1) && (t.c0 - R3_H + 63 <= nj - 2) && (t.i0 - 3 >= 1) && (t.i1 + 2 <= ni - 2);
-        if (inside) relax3_strip<DOT, U, NT, W1, true>(a, t, acc);
-        else relax3_strip<DOT, U, NT, W1, false>(a, t, acc);
-    }
-    if (DOT != DOT_NONE) block_partials<256, dot_columns(DOT)>(acc, a.partials + static_cast<size_t>(logical) * MAX_PARTIALS);
-}
-template <int DOT, int U, int NT, bool W1>
-__global__ __launch_bounds__(256, TM_R3_WAVES) void k_relax3(Relax2Block a, int RI, int nSG, int nRC) {
-    relax3_tile<DOT, U, NT, W1>(a, RI, nSG, nRC, blockIdx.x);
-}
-template <int DOT, int U, int NT, bool W1>
-__global__ __launch_bounds__(256) void k_relax3_batch(Relax2Batch B) {
-    int k = 0;
-#pragma unroll
-    for (int q = 1; q < APPLY_BATCH_MAX; ++q)
-        if (q < B.n && static_cast<int>(blockIdx.x) >= B.start[q]) k = q;
-    relax3_tile<DOT, U, NT, W1>(B.b[k], B.RI[k], B.nSG[k], B.nRC[k], static_cast<int>(blockIdx.x) - B.start[k]);
-}
-// ------------------------------------------------------------------------------------------
-// K2x4: FOUR fused sweeps per pass, same blocks as K2x3 with Relax2Block::dyn == 0 only (every perimeter row fixed).  One read and one
-// write of the field cost ~95 us at 4096^2 whatever the pass computes; each further sweep carried by the same bytes costs far less
-// than its issue time.  The body is K2x3's with the depth L as a parameter: L window levels, halo H = L lanes
-// per side, 64 - 2L owned columns (L = 4: 56, every stored segment 896 B = whole 128 B lines), chunks overlapping by L rows either
-// side.  Step s takes input row r = i0 - (L-2) + s (rows i0-L, i0-L+1 are preloaded), forms level k's row r - k for k = 1..L and
-// stores row r - L; level k has its three operand rows from step 2 (k-1) on, the evaluations before that are skipped at compile
-// time.  The same relax_row applied once more: bit-identical to L single sweeps (tests/test_gpu_quads.py).
-// ------------------------------------------------------------------------------------------
-constexpr int R4_L = 4;
-constexpr int R4_W = 64 - 2 * R4_L;     // output columns per wave
+constexpr int R3_U = 3;   // rows per load group, every depth
 template <int L, int DOT, int U, int NT, bool W1, bool INSIDE>
 __device__ __forceinline__ void relaxn_strip(const Relax2Block& a, const Relax2Tile& t, double (&acc)[MAX_PARTIALS]) {
     static_assert(U == 3 && L >= 3, "three steps per group; the windows rotate by renaming");
@@ -1102,7 +982,14 @@ __device__ __forceinline__ void relaxn_strip(const Relax2Block& a, const Relax2T
     const bool perim_col = !INSIDE && ((t.c <= 0) || (t.c >= nj - 1));
     const int nrows = t.i1 - t.i0;
     const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.out + static_cast<size_t>(t.i0) * nj, 0, nrows * nj * 16, 0x00020000);
-    const unsigned lane_off = t.out_lane ? static_cast<unsigned>(cc) * 16u : OOB_VOFFSET;
+    // Coupled blocks (Relax2Block::dyn != 0, Smoother::relax_triples_coupled): the pass treats every perimeter value as frozen, which is
+    // wrong along a side whose perimeter rows move -- but three sweeps carry that error only two nodes deep, so the pass simply does
+    // not store the nodes within two of such a side; the perimeter-row kernel evaluates them (and the perimeter) level by level.
+    // Depth 3 only: there is no perimeter-row chain for depth 4, whose launch rejects dyn != 0.
+    constexpr bool DYN = L == 3;
+    const bool skip_col = DYN && !INSIDE && (((a.dyn & 4) && t.c <= L - 1) || ((a.dyn & 8) && t.c >= nj - L));
+    const bool live_lane = t.out_lane && !skip_col;
+    const unsigned lane_off = live_lane ? static_cast<unsigned>(cc) * 16u : OOB_VOFFSET;
     const double2 zero = make_double2(0.0, 0.0);
     const int r0 = t.i0 - (L - 2);   // input row of step 0
 
@@ -1144,12 +1031,12 @@ __device__ __forceinline__ void relaxn_strip(const Relax2Block& a, const Relax2T
             double2 dl = zero, o = zero;
             if (phase >= STEADY || s >= 2 * (L - 1)) o = relax_row<W1>(S[L - 2][A0], S[L - 2][A1], S[L - 2][A2], a.omega, dl);   // row r-L
             const int i = r - L;
-            const bool row_live = (i >= t.i0) && (i < t.i1);   // wave-uniform
+            const bool row_live = (i >= t.i0) && (i < t.i1) && (!DYN || INSIDE || !(((a.dyn & 1) && i <= L - 1) || ((a.dyn & 2) && i >= ni - L)));   // wave-uniform
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i32, o), out_rsrc,
                                                    static_cast<int>(row_live ? lane_off + static_cast<unsigned>((i - t.i0) * nj * 16) : OOB_VOFFSET), 0,
                                                    (NT & 1) ? 2 : 0);
             if (DOT == DOT_DELTA) {
-                if (!(t.out_lane && row_live)) dl = zero;   // masked lanes hold garbage (possibly non-finite): select, never multiply
+                if (!(live_lane && row_live)) dl = zero;   // masked lanes hold garbage (possibly non-finite): select, never multiply
                 accumulate<DOT_DELTA>(acc, S[L - 2][A1].c, o, dl);
             }
         }
@@ -1168,7 +1055,7 @@ __device__ __forceinline__ void relaxn_tile(const Relax2Block& a, int RI, int nS
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int total = nSG * nRC;
-    const int q8 = total >> 3, rem = total & 7, xcd = bid & 7, k8 = bid >> 3;
+    const int q8 = total >> 3, rem = total & 7, xcd = bid & 7, k8 = bid >> 3;   // XCD-aware tile order (see apply_tile)
     const int logical = (xcd < rem) ? xcd * (q8 + 1) + k8 : rem * (q8 + 1) + (xcd - rem) * q8 + k8;
     const int rc = logical / nSG;
     const int sg = logical - rc * nSG;
@@ -1188,67 +1075,84 @@ __device__ __forceinline__ void relaxn_tile(const Relax2Block& a, int RI, int nS
     }
     if (DOT != DOT_NONE) block_partials<256, dot_columns(DOT)>(acc, a.partials + static_cast<size_t>(logical) * MAX_PARTIALS);
 }
+// the entry points keep their names: recorded profiles and the traffic tools key on them
+template <int DOT, int U, int NT, bool W1>
+__global__ __launch_bounds__(256, TM_R3_WAVES) void k_relax3(Relax2Block a, int RI, int nSG, int nRC) {
+    relaxn_tile<3, DOT, U, NT, W1>(a, RI, nSG, nRC, blockIdx.x);
+}
+template <int DOT, int U, int NT, bool W1>
+__global__ __launch_bounds__(256) void k_relax3_batch(Relax2Batch B) {
+    const int k = batch_slot(B);
+    relaxn_tile<3, DOT, U, NT, W1>(B.b[k], B.RI[k], B.nSG[k], B.nRC[k], static_cast<int>(blockIdx.x) - B.start[k]);
+}
 template <int DOT, int U, int NT, bool W1>
 __global__ __launch_bounds__(256) void k_relax4(Relax2Block a, int RI, int nSG, int nRC) {
-    relaxn_tile<R4_L, DOT, U, NT, W1>(a, RI, nSG, nRC, blockIdx.x);
+    relaxn_tile<4, DOT, U, NT, W1>(a, RI, nSG, nRC, blockIdx.x);
 }
 template <int DOT, int U, int NT, bool W1>
 __global__ __launch_bounds__(256) void k_relax4_batch(Relax2Batch B) {
-    int k = 0;
-#pragma unroll
-    for (int q = 1; q < APPLY_BATCH_MAX; ++q)
-        if (q < B.n && static_cast<int>(blockIdx.x) >= B.start[q]) k = q;
-    relaxn_tile<R4_L, DOT, U, NT, W1>(B.b[k], B.RI[k], B.nSG[k], B.nRC[k], static_cast<int>(blockIdx.x) - B.start[k]);
+    const int k = batch_slot(B);
+    relaxn_tile<4, DOT, U, NT, W1>(B.b[k], B.RI[k], B.nSG[k], B.nRC[k], static_cast<int>(blockIdx.x) - B.start[k]);
 }
-static int g_fuse3_rows = 0;   // experiments (TM_FUSE3_ROWS)
-// Rows per chunk of K2x3 for the blocks of ONE launch (launch_relax3_blocks batches APPLY_BATCH_MAX blocks).
-// The pass is bound by fp64 issue under the power cap, not by bandwidth, so the rows a chunk recomputes for its neighbours
-// ((3 RI + 6) / 3 RI of the arithmetic) count: tall chunks, as long as the LAUNCH -- all its blocks together -- still puts ~0.6 x
-// 3 workgroups on every CU.  Measured (tools/dev/steady_time.py, us per sweep, two or three boxes each): the height should be
-// 2 (mod 12) -- RI + 4 steps are then whole groups of three, and chunk starts 2 x odd rows apart spread over the memory
-// channels (4096^2: 38 / 50 rows 37.4 / 36.9-38.2 against 36: 39.5, 44: 37.9-39.7, 56: 41.0, 32 at 2048^2: 11.5; odd heights
-// 35 / 39: 40.7 / 41.7).  2048^2: 38 rows 10.25, 26: 10.4 (21 rows, the earlier rule: 11.9); 1448^2: 14 rows 6.7; 1024^2: 8 rows 4.33, 14: 4.67.
-void relax3_rows_for_launch(const int* ni, const int* nj, int n, int* rows, bool beside_chain) {
-    static const int forced = [] { const char* e = std::getenv("TM_FUSE3_ROWS"); return e ? std::atoi(e) : 0; }();
-    if (forced > 0 || g_fuse3_rows > 0) {
-        for (int k = 0; k < n; ++k) rows[k] = std::max(1, std::min(forced > 0 ? forced : g_fuse3_rows, ni[k] - 2));
-        return;
-    }
-    static int slots = 0;
-    if (slots == 0) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        slots = 3 * cus;
-    }
+// ---- the host side of the depth-L pass.  The smallest block whose interior the window's L rows / columns either side of a node can
+// come from: 2 L + 1 nodes a side
+bool relaxn_supported(int depth, int ni, int nj) { return ni >= 2 * depth + 1 && nj >= 2 * depth + 1 && nj <= (1 << 20); }
+int relaxn_block_nwg(int depth, int ni, int nj, int RI) {
+    const int W = 64 - 2 * depth, nstrips = (nj - 1 + W - 1) / W;
+    return ((nstrips + 3) / 4) * ((ni - 2 + RI - 1) / RI);
+}
+// Rows per chunk for the blocks of ONE launch (launch_relaxn_blocks batches APPLY_BATCH_MAX blocks): the tallest of the depth's
+// candidate heights with which the LAUNCH -- all its blocks together -- still puts ~0.6 x 3 workgroups on every CU.
+struct RelaxnHeights {
+    int depth;
+    const char* env;   // forces the height (experiments)
+    int n, h[5];       // tallest first
+};
+static const RelaxnHeights relaxn_heights[] = {
+    // The pass is bound by fp64 issue under the power cap, not by bandwidth, so the rows a chunk recomputes for its neighbours
+    // ((3 RI + 6) / 3 RI of the arithmetic) count: tall chunks, as long as the LAUNCH -- all its blocks together -- still puts ~0.6 x
+    // 3 workgroups on every CU.  Measured (tools/dev/steady_time.py, us per sweep, two or three boxes each): the height should be
+    // 2 (mod 12) -- RI + 4 steps are then whole groups of three, and chunk starts 2 x odd rows apart spread over the memory
+    // channels (4096^2: 38 / 50 rows 37.4 / 36.9-38.2 against 36: 39.5, 44: 37.9-39.7, 56: 41.0, 32 at 2048^2: 11.5; odd heights
+    // 35 / 39: 40.7 / 41.7).  2048^2: 38 rows 10.25, 26: 10.4 (21 rows, the earlier rule: 11.9); 1448^2: 14 rows 6.7; 1024^2: 8 rows 4.33, 14: 4.67.
     // (50 rows: a lone 4096^2 block 36.6 against 37.1 with 38, but 8 x 2048^2 in one launch 75.1 against 73.2-75.3: not offered.)
-    // Beside the perimeter-row chain of coupled blocks (relax_triples_coupled) the chain's short kernels queue for the wave slots
-    // this pass gives back, once per workgroup lifetime: shorter chunks there (a 2048^2 rank: 38 rows 13.6-13.9, 21-26 rows 13.1).
-    static const int heights[] = {38, 26, 14, 8};
-    const long need = static_cast<long>(slots) * (beside_chain ? 9 : 6);
-    int RI = 8;
-    for (const int h : heights) {
-        long total = 0;
-        for (int k = 0; k < n; ++k) {
-            const int nstrips = (nj[k] - 1 + R3_W - 1) / R3_W, nSG = (nstrips + 3) / 4, interior = ni[k] - 2, r = std::max(1, std::min(h, interior));
-            total += static_cast<long>(nSG) * ((interior + r - 1) / r);
+    {3, "TM_FUSE3_ROWS", 4, {38, 26, 14, 8}},
+    // K2x3's finding carries over -- RI + 6 steps whole groups of three, RI = 2 x odd, i.e. RI = 6 (mod 12).  Measured
+    // (tools/dev/steady_time.py, us per sweep, triples 37.0-37.7 on the same box; the whole table: DESIGN.md section 4): 4096^2: 54 rows
+    // 35.4-35.9, 78: 35.8-36.0, 66: 36.0-36.6, 42: 36.2-37.2, 30: 36.9-37.3, 18: 37.7, 90: 38.5; off the rule 60: 37.3-37.6, 72: 37.5-38.1, 58: 38.5.
+    // 2048^2: 42 rows 10.0-10.1, 30: 10.3, 54: 12.2 (too few workgroups); 8 x 2048^2 in one launch: 42-54 rows 70.4-70.7, 30: 72.0.
+    {4, "TM_FUSE4_ROWS", 5, {54, 42, 30, 18, 6}},
+};
+void relaxn_rows_for_launch(int depth, const int* ni, const int* nj, int n, int* rows, bool beside_chain) {
+    const int d = depth == 4 ? 1 : 0;
+    const RelaxnHeights& T = relaxn_heights[d];
+    static const auto env_rows = [](const char* name) { const char* e = std::getenv(name); return e ? std::atoi(e) : 0; };
+    static const int forced[2] = {env_rows(relaxn_heights[0].env), env_rows(relaxn_heights[1].env)};
+    int RI = forced[d];
+    if (RI <= 0) {
+        static int slots = 0;
+        if (slots == 0) {
+            int dev = 0, cus = 0;
+            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+            slots = 3 * cus;
         }
-        RI = h;
-        if (total * 10 >= need) break;
+        // Beside the perimeter-row chain of coupled blocks (relax_triples_coupled, depth 3 only) the chain's short kernels queue for the
+        // wave slots this pass gives back, once per workgroup lifetime: shorter chunks there (a 2048^2 rank: 38 rows 13.6-13.9, 21-26 rows 13.1).
+        const long need = static_cast<long>(slots) * (beside_chain ? 9 : 6);
+        for (int c = 0; c < T.n; ++c) {
+            long total = 0;
+            for (int k = 0; k < n; ++k) total += relaxn_block_nwg(depth, ni[k], nj[k], std::max(1, std::min(T.h[c], ni[k] - 2)));
+            RI = T.h[c];
+            if (total * 10 >= need) break;
+        }
     }
     for (int k = 0; k < n; ++k) rows[k] = std::max(1, std::min(RI, ni[k] - 2));
 }
-int relax3_rows_per_chunk(int ni, int nj) {
-    int r = 0;
-    relax3_rows_for_launch(&ni, &nj, 1, &r, false);
-    return r;
-}
-bool relax3_supported(int ni, int nj) { return ni >= 7 && nj >= 7 && nj <= (1 << 20); }
-int relax3_block_nwg(int ni, int nj, int RI) {
-    const int nstrips = (nj - 1 + R3_W - 1) / R3_W;
-    return ((nstrips + 3) / 4) * ((ni - 2 + RI - 1) / RI);
-}
 // K2x3 (depth 3) or K2x4 (depth 4) on the blocks of a rank, APPLY_BATCH_MAX of them per launch
-static hipError_t launch_fixed_wall_blocks(int depth, const Relax2Block* blocks, const int* rows_per_chunk, int n, int dot, hipStream_t st) {
+hipError_t launch_relaxn_blocks(int depth, const Relax2Block* blocks, const int* rows_per_chunk, int n, int dot, hipStream_t st) {
+    if (depth != 3 && depth != 4) return hipErrorInvalidValue;
+    for (int k = 0; k < n; ++k)
+        if (depth != 3 && blocks[k].dyn != 0) return hipErrorInvalidValue;   // coupled blocks keep K2x3 and its depth-3 zone
     const int W = 64 - 2 * depth;
     for (int first = 0; first < n; first += APPLY_BATCH_MAX) {
         Relax2Batch B;
@@ -1283,7 +1187,7 @@ static hipError_t launch_fixed_wall_blocks(int depth, const Relax2Block* blocks,
     } while (0)
         static const bool force_batch = [] { const char* e = std::getenv("TM_R3_FORCE_BATCH"); return e && std::atoi(e) != 0; }();
         const bool lone = B.n == 1 && !force_batch;
-        if (depth == R4_L) {
+        if (depth == 4) {
             if (lone) TM_R3(k_relax4, B.b[0], B.RI[0], B.nSG[0], B.nRC[0]);
             else TM_R3(k_relax4_batch, B);
         } else {
@@ -1295,52 +1199,6 @@ static hipError_t launch_fixed_wall_blocks(int depth, const Relax2Block* blocks,
         if (rc != hipSuccess) return rc;
     }
     return hipSuccess;
-}
-hipError_t launch_relax3_blocks(const Relax2Block* blocks, const int* rows_per_chunk, int n, int dot, hipStream_t st) {
-    return launch_fixed_wall_blocks(3, blocks, rows_per_chunk, n, dot, st);
-}
-
-// ---- K2x4's launch.  Chunk heights: K2x3's finding carries over -- RI + 6 steps whole groups of three, RI = 2 x odd, i.e. RI = 6 (mod 12);
-// which of them a launch takes follows K2x3's rule (the largest that still puts 0.6 x 3 workgroups on every CU).  Measured
-// (tools/dev/steady_time.py, us per sweep, triples 37.0-37.7 on the same box; the whole table: DESIGN.md section 4): 4096^2: 54 rows
-// 35.4-35.9, 78: 35.8-36.0, 66: 36.0-36.6, 42: 36.2-37.2, 30: 36.9-37.3, 18: 37.7, 90: 38.5; off the rule 60: 37.3-37.6, 72: 37.5-38.1, 58: 38.5.
-// 2048^2: 42 rows 10.0-10.1, 30: 10.3, 54: 12.2 (too few workgroups); 8 x 2048^2 in one launch: 42-54 rows 70.4-70.7, 30: 72.0.
-void relax4_rows_for_launch(const int* ni, const int* nj, int n, int* rows) {
-    static const int forced = [] { const char* e = std::getenv("TM_FUSE4_ROWS"); return e ? std::atoi(e) : 0; }();
-    if (forced > 0) {
-        for (int k = 0; k < n; ++k) rows[k] = std::max(1, std::min(forced, ni[k] - 2));
-        return;
-    }
-    static int slots = 0;
-    if (slots == 0) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        slots = 3 * cus;
-    }
-    static const int heights[] = {54, 42, 30, 18, 6};
-    const long need = static_cast<long>(slots) * 6;
-    int RI = 6;
-    for (const int h : heights) {
-        long total = 0;
-        for (int k = 0; k < n; ++k) {
-            const int nstrips = (nj[k] - 1 + R4_W - 1) / R4_W, nSG = (nstrips + 3) / 4, interior = ni[k] - 2, r = std::max(1, std::min(h, interior));
-            total += static_cast<long>(nSG) * ((interior + r - 1) / r);
-        }
-        RI = h;
-        if (total * 10 >= need) break;
-    }
-    for (int k = 0; k < n; ++k) rows[k] = std::max(1, std::min(RI, ni[k] - 2));
-}
-// the smallest block whose interior the window's L rows / columns either side of a node can come from: 2 L + 1 nodes a side
-bool relax4_supported(int ni, int nj) { return ni >= 2 * R4_L + 1 && nj >= 2 * R4_L + 1 && nj <= (1 << 20); }
-int relax4_block_nwg(int ni, int nj, int RI) {
-    const int nstrips = (nj - 1 + R4_W - 1) / R4_W;
-    return ((nstrips + 3) / 4) * ((ni - 2 + RI - 1) / RI);
-}
-hipError_t launch_relax4_blocks(const Relax2Block* blocks, const int* rows_per_chunk, int n, int dot, hipStream_t st) {
-    for (int k = 0; k < n; ++k)
-        if (blocks[k].dyn != 0) return hipErrorInvalidValue;   // coupled blocks keep K2x3 and its depth-3 zone
-    return launch_fixed_wall_blocks(R4_L, blocks, rows_per_chunk, n, dot, st);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2099,10 +1957,7 @@ __global__ __launch_bounds__(256) void k_apply_edge_batch(ApplyBatch B, int tota
                                                           const double2* __restrict__ xk, const double2* __restrict__ pq,
                                                           const double2* __restrict__ aux, double2* __restrict__ out, double* edge_partials) {
     if (static_cast<int>(blockIdx.x) < total_interior) {   // workgroup-uniform
-        int k = 0;
-#pragma unroll
-        for (int q = 1; q < APPLY_BATCH_MAX; ++q)
-            if (q < B.n && static_cast<int>(blockIdx.x) >= B.start[q]) k = q;
+        const int k = batch_slot(B);
         apply_tile<MODE, DOT, false, HAS_PQ, 3, true>(B.b[k], B.RI[k], B.nSG[k], B.nRC[k], static_cast<int>(blockIdx.x) - B.start[k]);
         return;
     }
@@ -2156,10 +2011,7 @@ __global__ __launch_bounds__(256, MINW) void k_apply_vk(ApplyBatch B, int total_
     const KrylovScalars* S = lazy_scalars<256>(L);
     const VirtualArgs A = virtual_args<VK>(V, S);
     if (total_interior < 0 || static_cast<int>(blockIdx.x) < total_interior) {   // workgroup-uniform
-        int k = 0;
-#pragma unroll
-        for (int q = 1; q < APPLY_BATCH_MAX; ++q)
-            if (q < B.n && static_cast<int>(blockIdx.x) >= B.start[q]) k = q;
+        const int k = batch_slot(B);
         apply_tile<MODE_SCALED, DOT, false, HAS_PQ, 3, true, VK, OV>(B.b[k], B.RI[k], B.nSG[k], B.nRC[k], static_cast<int>(blockIdx.x) - B.start[k], A.va, A.vb, A.vc);
         return;
     }

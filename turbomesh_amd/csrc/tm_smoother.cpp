@@ -379,7 +379,7 @@ void Smoother::decide_schedule() {
         int64_t single_min = 0;
         if (const char* e = std::getenv("TM_TRIPLES_SINGLE_MIN_NODES")) single_min = std::atoll(e);
         triples_coupled = fuse_pairs && any_nf && (peers ? lp.triple_halo : lp.n_owned >= single_min);
-        for (int64_t b : lp.owned_blocks) triples_coupled = triples_coupled && topo.ni[b] >= 16 && topo.nj[b] >= 16 && relax3_supported(static_cast<int>(topo.ni[b]), static_cast<int>(topo.nj[b]));
+        for (int64_t b : lp.owned_blocks) triples_coupled = triples_coupled && topo.ni[b] >= 16 && topo.nj[b] >= 16 && relaxn_supported(3, static_cast<int>(topo.ni[b]), static_cast<int>(topo.nj[b]));
         if (const char* e = std::getenv("TM_TRIPLES_COUPLED")) triples_coupled = triples_coupled && std::atoi(e) != 0;
         if (triples_coupled) M2 = vec();
     }
@@ -566,24 +566,19 @@ uint64_t Smoother::size_launches() {
     // beside the interior workgroups like a rank with neighbours does (relax_pairs_pipelined; nothing is exchanged)
     pipelined_single = fuse_pairs && !(has_hooks && (lp.send_ids.size() > 0 || !lp.ghost_gid.empty())) && edge_nf.nrows > 0 && lp.n_owned >= (1 << 21);
     if (const char* e = std::getenv("TM_SINGLE_PIPELINED")) pipelined_single = pipelined_single && std::atoi(e) != 0;
+    const auto all_blocks_fit = [&](int depth) {   // the window of the depth-L pass (K2x3 / K2x4)
+        for (int64_t b : lp.owned_blocks)
+            if (!relaxn_supported(depth, static_cast<int>(topo.ni[b]), static_cast<int>(topo.nj[b]))) return false;
+        return true;
+    };
     // three sweeps per pass (K2x3): every perimeter row of every owned block `fixed` (nothing for a perimeter-row kernel to do, no
     // neighbour to exchange with) -- a single block with prescribed walls, independent slices
     fuse_triples = fuse_pairs && edge_nf.nrows == 0 && !(has_hooks && (!lp.send_ids.empty() || !lp.ghost_gid.empty()));
     if (const char* e = std::getenv("TM_FUSE_3")) fuse_triples = fuse_triples && std::atoi(e) != 0;
     // ... and the coupled triples: the same K2x3 grid, plus the level-3 perimeter-row pass behind it in the partial sums
     if (fuse_triples || triples_coupled) {
-        poff3.clear();
-        rows3.clear();
-        int off3 = 0;
-        rows3 = relax3_rows_of_owned_blocks();
-        for (size_t k = 0; k < lp.owned_blocks.size(); ++k) {
-            const int64_t b = lp.owned_blocks[k];
-            const int bi = static_cast<int>(topo.ni[b]), bj = static_cast<int>(topo.nj[b]);
-            if (!relax3_supported(bi, bj)) fuse_triples = false;   // (the blocks of coupled triples passed this test in decide_schedule)
-            poff3.push_back(off3);
-            off3 += relax3_block_nwg(bi, bj, rows3[k]);
-        }
-        nwg_apply3 = off3;
+        fuse_triples = fuse_triples && all_blocks_fit(3);   // (the blocks of coupled triples passed this test in decide_schedule)
+        plan3 = plan_fixed_walls(3, triples_coupled);
     }
     // four sweeps per pass (K2x4) where plain triples run: n = 4 a + r sweeps take a quads, then triples / pairs / singles (relax_sweeps)
     // The fourth sweep saves a quarter of the bytes of a pass and pays 4 % more arithmetic, which comes out ahead only where the pass is
@@ -595,32 +590,17 @@ uint64_t Smoother::size_launches() {
         fuse_quads = fuse_quads && std::atoi(e) != 0;
         quads_forced = std::atoi(e) != 0;
     }
-    nwg_apply4 = 0;
     if (fuse_quads) {
-        std::vector<int> bi, bj;
         for (size_t first = 0; first < lp.owned_blocks.size(); first += APPLY_BATCH_MAX) {   // one launch takes APPLY_BATCH_MAX blocks
             int64_t nodes = 0;
             for (size_t k = first; k < std::min<size_t>(first + APPLY_BATCH_MAX, lp.owned_blocks.size()); ++k) nodes += topo.ni[lp.owned_blocks[k]] * topo.nj[lp.owned_blocks[k]];
             if (nodes < QUAD_MIN_NODES && !quads_forced) fuse_quads = false;
         }
-        for (int64_t b : lp.owned_blocks) {
-            bi.push_back(static_cast<int>(topo.ni[b]));
-            bj.push_back(static_cast<int>(topo.nj[b]));
-            if (!relax4_supported(bi.back(), bj.back())) fuse_quads = false;   // smaller blocks keep triples
-        }
-        poff4.clear();
-        rows4.assign(bi.size(), 1);
-        for (size_t first = 0; first < rows4.size(); first += APPLY_BATCH_MAX)
-            relax4_rows_for_launch(bi.data() + first, bj.data() + first, static_cast<int>(std::min<size_t>(APPLY_BATCH_MAX, rows4.size() - first)), rows4.data() + first);
-        int off4 = 0;
-        for (size_t k = 0; k < rows4.size(); ++k) {
-            poff4.push_back(off4);
-            off4 += relax4_block_nwg(bi[k], bj[k], rows4[k]);
-        }
-        nwg_apply4 = fuse_quads ? off4 : 0;
+        fuse_quads = fuse_quads && all_blocks_fit(4);   // smaller blocks keep triples
     }
+    plan4 = fuse_quads ? plan_fixed_walls(4, false) : FixedWallPlan();
     nwg_vec = vec_nwg(n_owned);
-    const int nwg3_all = std::max(nwg_apply4, fuse_triples ? nwg_apply3 : (triples_coupled ? nwg_apply3 + std::max(edge_L[2].nwg, fused_levels.nstrips) : 0));
+    const int nwg3_all = std::max(plan4.nwg, fuse_triples ? plan3.nwg : (triples_coupled ? plan3.nwg + std::max(edge_L[2].nwg, fused_levels.nstrips) : 0));
     // Overlapping strips for the two kernels of the two-kernel BiCGStab iteration (single process, no preconditioner -- where fuse2 holds,
     // below): no halo registers -> 234 instead of 276 VGPRs for VK_R, two workgroups per CU without spills.  Where it pays was MEASURED, same
     // box, alternating runs (tools/dev/vk_overlap_sizes.py, us per iteration halo loads / overlapping strips): 128^2 20.1 / 17.9, 512^2 34.3 / 31.8,
@@ -1728,39 +1708,51 @@ int Smoother::picard_reference(tm_stats& st) {
 // latency-critical chain, the rest beside it.
 void Smoother::relax2_launch(int subset, bool counts, int dot, hipStream_t on, const QueueWait* wait) {
     if (!on) on = stream;
+    const std::vector<Relax2Block> blocks = relax_blocks(X, M, U, true, true, poff2);
+    const size_t lds = (subset == R2_INSIDE) ? inside_lds : 0;
+    profiled([&]() { HIPCHK(launch_relax2_blocks(blocks.data(), rows2.data(), static_cast<int>(blocks.size()), dot, subset, on, lds, wait)); }, counts, on);
+}
+
+std::vector<Relax2Block> Smoother::relax_blocks(const double2* in, double2* mid, double2* out, bool dyn, bool borders, const std::vector<int>& poff) const {
     std::vector<Relax2Block> blocks(lp.owned_blocks.size());
     for (size_t k = 0; k < lp.owned_blocks.size(); ++k) {
         const int64_t b = lp.owned_blocks[k];
         const int64_t ls = lp.local_start[k];
         Relax2Block& a = blocks[k];
-        a.in = X + ls;
-        a.mid = M + ls;
-        a.out = U + ls;
+        a.in = in + ls;
+        a.mid = mid ? mid + ls : nullptr;
+        a.out = out + ls;
         a.ni = static_cast<int>(topo.ni[b]);
         a.nj = static_cast<int>(topo.nj[b]);
         a.omega = opt.omega;
-        a.dyn = dyn_mask[k];
+        a.dyn = dyn ? dyn_mask[k] : 0;
         a.store_nt = relax2_store_nt ? 1 : 0;
-        a.border = border_ids[k];
-        a.nborder = border_n[k];
-        a.partials = partials + static_cast<size_t>(poff2[k]) * MAX_PARTIALS;
+        a.border = borders ? border_ids[k] : nullptr;
+        a.nborder = borders ? border_n[k] : 0;
+        a.partials = partials + static_cast<size_t>(poff[k]) * MAX_PARTIALS;
     }
-    const size_t lds = (subset == R2_INSIDE) ? inside_lds : 0;
-    profiled([&]() { HIPCHK(launch_relax2_blocks(blocks.data(), rows2.data(), static_cast<int>(blocks.size()), dot, subset, on, lds, wait)); }, counts, on);
+    return blocks;
 }
 
-// Rows per chunk of K2x3, chosen per launch: launch_relax3_blocks takes the owned blocks in groups of APPLY_BATCH_MAX
-std::vector<int> Smoother::relax3_rows_of_owned_blocks() const {
-    std::vector<int> rows(lp.owned_blocks.size(), 1), bi, bj;
+// Rows per chunk, partial-row offsets and workgroups of the depth-L pass on the owned blocks.  The heights are chosen per launch:
+// launch_relaxn_blocks takes the blocks in groups of APPLY_BATCH_MAX
+Smoother::FixedWallPlan Smoother::plan_fixed_walls(int depth, bool beside_chain) const {
+    FixedWallPlan p;
+    std::vector<int> bi, bj;
     for (int64_t b : lp.owned_blocks) {
         bi.push_back(static_cast<int>(topo.ni[b]));
         bj.push_back(static_cast<int>(topo.nj[b]));
     }
-    for (size_t first = 0; first < rows.size(); first += APPLY_BATCH_MAX) {
-        const int n = static_cast<int>(std::min<size_t>(APPLY_BATCH_MAX, rows.size() - first));
-        relax3_rows_for_launch(bi.data() + first, bj.data() + first, n, rows.data() + first, triples_coupled);
+    p.rows.assign(bi.size(), 1);
+    for (size_t first = 0; first < bi.size(); first += APPLY_BATCH_MAX) {
+        const int n = static_cast<int>(std::min<size_t>(APPLY_BATCH_MAX, bi.size() - first));
+        relaxn_rows_for_launch(depth, bi.data() + first, bj.data() + first, n, p.rows.data() + first, beside_chain);
     }
-    return rows;
+    for (size_t k = 0; k < bi.size(); ++k) {
+        p.poff.push_back(p.nwg);
+        p.nwg += relaxn_block_nwg(depth, bi[k], bj[k], p.rows[k]);
+    }
+    return p;
 }
 
 // ---- the second queue of a pipelined pass and how it is ordered against the handle's stream (see tm_smoother.hpp)
@@ -1822,32 +1814,13 @@ void Smoother::warm_transport() {
     HIPCHK(hipStreamSynchronize(side));
 }
 
-// Three sweeps in one pass (K2x3, all perimeter rows fixed): X^(k+3) = S(S(S(X^k))), bit-identical to three single sweeps
-void Smoother::relax_triple(bool want_partials) { relax_fixed_walls(3, want_partials); }
-// Four (K2x4): the same pass one level deeper, on its own grid of 56-column strips
-void Smoother::relax_quad(bool want_partials) { relax_fixed_walls(4, want_partials); }
+// depth = 3 or 4 sweeps in one pass (K2x3 / K2x4, all perimeter rows fixed): X^(k+3) = S(S(S(X^k))), bit-identical to that many single
+// sweeps; depth 4 is the same pass one level deeper, on its own grid of 56-column strips
 void Smoother::relax_fixed_walls(int depth, bool want_partials) {
     const int dot = want_partials ? DOT_DELTA : DOT_NONE;
-    const std::vector<int>& poffd = depth == 4 ? poff4 : poff3;
-    std::vector<Relax2Block> blocks(lp.owned_blocks.size());
-    for (size_t k = 0; k < lp.owned_blocks.size(); ++k) {
-        const int64_t b = lp.owned_blocks[k];
-        const int64_t ls = lp.local_start[k];
-        Relax2Block& a = blocks[k];
-        a.in = X + ls;
-        a.mid = nullptr;
-        a.out = U + ls;
-        a.ni = static_cast<int>(topo.ni[b]);
-        a.nj = static_cast<int>(topo.nj[b]);
-        a.omega = opt.omega;
-        a.dyn = 0;
-        a.store_nt = relax2_store_nt ? 1 : 0;
-        a.border = nullptr;
-        a.nborder = 0;
-        a.partials = partials + static_cast<size_t>(poffd[k]) * MAX_PARTIALS;
-    }
-    if (depth == 4) profiled([&]() { HIPCHK(launch_relax4_blocks(blocks.data(), rows4.data(), static_cast<int>(blocks.size()), dot, stream)); }, true, stream);
-    else profiled([&]() { HIPCHK(launch_relax3_blocks(blocks.data(), rows3.data(), static_cast<int>(blocks.size()), dot, stream)); }, true, stream);
+    const FixedWallPlan& plan = depth == 4 ? plan4 : plan3;
+    const std::vector<Relax2Block> blocks = relax_blocks(X, nullptr, U, false, false, plan.poff);
+    profiled([&]() { HIPCHK(launch_relaxn_blocks(depth, blocks.data(), plan.rows.data(), static_cast<int>(blocks.size()), dot, stream)); }, true, stream);
     std::swap(X, U);
 }
 
@@ -1873,25 +1846,9 @@ void Smoother::relax_triples_coupled(uint64_t ntriples, bool want_partials_last)
     if (use_flags) HIPCHK(hipMemsetAsync(sync_flags, 0, sizeof(uint32_t) * 4, stream));
     fence(stream, side, ev_to_side);   // X (and the cleared counters) complete on the handle's stream
     warm_transport();
-    std::vector<Relax2Block> blocks(lp.owned_blocks.size());
     for (uint64_t q = 0; q < ntriples; ++q) {
         const int dot = (q + 1 == ntriples && want_partials_last) ? DOT_DELTA : DOT_NONE;
-        for (size_t k = 0; k < lp.owned_blocks.size(); ++k) {
-            const int64_t b = lp.owned_blocks[k];
-            const int64_t ls = lp.local_start[k];
-            Relax2Block& a = blocks[k];
-            a.in = X + ls;
-            a.mid = nullptr;
-            a.out = U + ls;
-            a.ni = static_cast<int>(topo.ni[b]);
-            a.nj = static_cast<int>(topo.nj[b]);
-            a.omega = opt.omega;
-            a.dyn = dyn_mask[k];
-            a.store_nt = relax2_store_nt ? 1 : 0;
-            a.border = nullptr;
-            a.nborder = 0;
-            a.partials = partials + static_cast<size_t>(poff3[k]) * MAX_PARTIALS;
-        }
+        const std::vector<Relax2Block> blocks = relax_blocks(X, nullptr, U, true, false, plan3.poff);
         // handle's stream: K2x3 of triple q needs the chain of triple q-1 (its level 3 wrote rows of X).  With counters, ONE one-wave
         // kernel per queue and triple does both jobs: starting behind K2x3 of triple q-1 it announces that pass (inside_done = q), then
         // waits for the chain of triple q-1 (chain_done >= q); its twin on the chain's queue announces the chain and waits for the pass.
@@ -1902,7 +1859,7 @@ void Smoother::relax_triples_coupled(uint64_t ntriples, bool want_partials_last)
             if (use_flags) HIPCHK(launch_queue_signal_wait(inside_done, chain_done, static_cast<uint32_t>(q), sync_err, stream));
             else HIPCHK(hipStreamWaitEvent(stream, ev_to_main, 0));
         }
-        profiled([&]() { HIPCHK(launch_relax3_blocks(blocks.data(), rows3.data(), static_cast<int>(blocks.size()), dot, stream)); }, true, stream);
+        profiled([&]() { HIPCHK(launch_relaxn_blocks(3, blocks.data(), plan3.rows.data(), static_cast<int>(blocks.size()), dot, stream)); }, true, stream);
         if (!use_flags) HIPCHK(hipEventRecord(ev_inside[q & 1], stream));
         // chain: the levels of triple q read X: K2x3 of triple q-1 must be complete (its own level 3 precedes them in this queue)
         if (q > 0) {
@@ -1913,11 +1870,11 @@ void Smoother::relax_triples_coupled(uint64_t ntriples, bool want_partials_last)
         exchange_finish(side);
         if (levels_fused) {   // the three level passes in one launch: strips with their own closure of level-1 and level-2 rows (k_edge_levels3)
             HIPCHK(launch_edge_levels3(fused_levels, edge_L[0], edge_L[1], edge_L[2], X, M, M2, U, PQ, opt.omega, dot,
-                                       partials + static_cast<size_t>(nwg_apply3) * MAX_PARTIALS, side));
+                                       partials + static_cast<size_t>(plan3.nwg) * MAX_PARTIALS, side));
         } else {
             HIPCHK(launch_edge_rows(edge_L[0], X, X, PQ, nullptr, M, opt.omega, MODE_RELAX, DOT_NONE, partials, side));
             HIPCHK(launch_edge_rows(edge_L[1], M, M, PQ, nullptr, M2, opt.omega, MODE_RELAX, DOT_NONE, partials, side));
-            HIPCHK(launch_edge_rows(edge_L[2], M2, M2, PQ, nullptr, U, opt.omega, MODE_RELAX, dot, partials + static_cast<size_t>(nwg_apply3) * MAX_PARTIALS, side));
+            HIPCHK(launch_edge_rows(edge_L[2], M2, M2, PQ, nullptr, U, opt.omega, MODE_RELAX, dot, partials + static_cast<size_t>(plan3.nwg) * MAX_PARTIALS, side));
         }
         if (q + 1 < ntriples && !use_flags) HIPCHK(hipEventRecord(ev_to_main, side));
         std::swap(X, U);
@@ -2065,20 +2022,20 @@ void Smoother::relax_sweeps(uint64_t n, tm_stats& st) {
         // per launch at 4096^2 a single sweep costs 91-96 us, a pair 102-107, a triple 110-112, so trading a quad
         // and a single for a triple and a pair wins as long as a quad takes more than ~123 us; it takes 140-144.
         const uint64_t nquads = n / 4 - (n % 4 == 1 ? 1 : 0);
-        for (uint64_t q = 0; q < nquads; ++q) relax_quad(q + 1 == nquads && n == 4 * nquads);
+        for (uint64_t q = 0; q < nquads; ++q) relax_fixed_walls(4, q + 1 == nquads && n == 4 * nquads);
         k = 4 * nquads;
-        if (nquads) last_nwg = nwg_apply4;
+        if (nquads) last_nwg = plan4.nwg;
         st.operator_sweeps += k;
         outer_done += k;
     }
     if ((fuse_triples || triples_coupled) && n - k >= 3) {   // the rest n' = 3 a + 2 b + c, as many triples as possible (n' = 4: one triple + one single sweep)
         const uint64_t ntriples = (n - k) / 3;
         if (fuse_triples) {
-            for (uint64_t q = 0; q < ntriples; ++q) relax_triple(q + 1 == ntriples && (n - k) % 3 == 0);
-            last_nwg = nwg_apply3;
+            for (uint64_t q = 0; q < ntriples; ++q) relax_fixed_walls(3, q + 1 == ntriples && (n - k) % 3 == 0);
+            last_nwg = plan3.nwg;
         } else {
             relax_triples_coupled(ntriples, n % 3 == 0);   // (no quads on coupled blocks: k = 0 here)
-            last_nwg = nwg_apply3 + (levels_fused ? fused_levels.nstrips : edge_L[2].nwg);
+            last_nwg = plan3.nwg + (levels_fused ? fused_levels.nstrips : edge_L[2].nwg);
         }
         k += 3 * ntriples;
         st.operator_sweeps += 3 * ntriples;

@@ -129,12 +129,10 @@ struct Smoother {
     int poff_edge = 0, nwg_apply = 0, nwg_vec = 0;
     std::vector<int> poff2, rows2;  // same for the fused two-sweep launches, and their rows per workgroup
     int poff2_edge = 0, nwg_apply2 = 0;
-    std::vector<int> poff3, rows3;  // ... and for the three-sweep launches (all perimeter rows fixed)
-    int nwg_apply3 = 0;
+    struct FixedWallPlan { std::vector<int> poff, rows; int nwg = 0; };   // ... and for a depth of the fixed-wall pass (K2x3 / K2x4)
+    FixedWallPlan plan3, plan4;     // three sweeps per pass (all perimeter rows fixed, or coupled triples); four (where fuse_quads holds)
     bool fuse_triples = false;
-    std::vector<int> poff4, rows4;  // ... and for the four-sweep launches (K2x4: where fuse_triples holds and every block is 9 x 9 or larger)
-    int nwg_apply4 = 0;
-    bool fuse_quads = false;        // TM_FUSE_4=0 at creation: the schedule of triples alone, same binary
+    bool fuse_quads = false;        // fuse_triples, every block 9 x 9 or larger; TM_FUSE_4=0 at creation: the schedule of triples alone, same binary
     static constexpr int64_t QUAD_MIN_NODES = 8000000;         // nodes per launch from which a quad beats a triple per sweep (measured)
     // Coupled triples (single process): K2x3 with a frozen perimeter stores everything but the nodes within two of a side whose
     // perimeter rows move; three perimeter-row passes evaluate the perimeter and that zone level by level (rows within 4 / 3 / 2 nodes)
@@ -315,9 +313,9 @@ struct Smoother {
     }
     void relax_sweeps(uint64_t n, tm_stats& st);
     void relax_pair(bool want_partials);
-    std::vector<int> relax3_rows_of_owned_blocks() const;
-    void relax_triple(bool want_partials);
-    void relax_quad(bool want_partials);
+    FixedWallPlan plan_fixed_walls(int depth, bool beside_chain) const;
+    // the owned blocks as the fused-sweep kernels take them; mid == nullptr / dyn, borders false: K2x3 / K2x4 use none of them
+    std::vector<Relax2Block> relax_blocks(const double2* in, double2* mid, double2* out, bool dyn, bool borders, const std::vector<int>& poff) const;
     void relax_fixed_walls(int depth, bool want_partials);
     void relax_triples_coupled(uint64_t ntriples, bool want_partials_last);
     void profiled(const std::function<void()>& launch, bool counts = true, hipStream_t on = nullptr);
