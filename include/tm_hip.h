@@ -471,6 +471,62 @@ int tm_smoother_quality(tm_smoother* s, tm_quality* per_block, tm_quality* total
 /* per-cell minimum of o*s of an owned block, i fastest like the export planes: out[j*(ni-1)+i]; NaN for degenerate cells */
 int tm_smoother_quality_field(tm_smoother* s, uint64_t block, double* min_scaled_jacobian /* (ni-1)*(nj-1) */);
 
+/* ------------------------------------------------------------------ 3-D from 2-D cuts
+ * The reference's first open roadmap item is "extension to 3D based on meshed 2d cuts", its second "rotational configurations".  A
+ * layer k of a 3-D block is a fixed linear combination of the same node in the K cuts:
+ *     v[k][i][j] = sum_c A[k][c] * v_c[i][j]
+ * A is an nlayers x ncuts weight matrix that depends only on the span positions.  It is not per node.
+ * Inputs:
+ *   - Cut span coordinates z[0..K-1] are finite and strictly increasing, with 2 <= K <= TM_STACK_MAX_CUTS = 16.
+ *   - Layer coordinates s[0..nk-1] are finite, each in [z[0], z[K-1]], with nk >= 1.  No order is required.
+ *   - Any violation answers TM_E_ARG.  There is no extrapolation.
+ * Weights:
+ *   - If s[k] == z[c] in fp64, the weight row is exactly the unit vector e_c.  A layer at a cut then reproduces the cut, numerically
+ *     equal in both coordinates.
+ *   - Otherwise c is the largest index <= K-2 with z[c] <= s, and h = z[c+1] - z[c].
+ *   - TM_STACK_LINEAR: t = (s - z[c])/h, A[c] = 1 - t, A[c+1] = t.
+ *   - TM_STACK_CUBIC: the natural cubic spline through the cuts, with zero second derivative at both end cuts.  With a = (z[c+1]-s)/h
+ *     and b = (s-z[c])/h: S = a v_c + b v_{c+1} + ((a^3-a) M_c + (b^3-b) M_{c+1}) h^2/6.  The second derivatives M are linear in v, so
+ *     S is a weight row.  At K = 2 it equals linear.
+ *   - Weights are formed on the host in long double and rounded once to fp64.
+ * Mappings:
+ *   - TM_STACK_PLANAR: the output is (x, y, s[k]).  The third coordinate is s[k] itself, stored and not computed.
+ *   - TM_STACK_CYLINDRICAL: the cuts are unrolled cylinders (x, r theta) at radius z[c] > 0.  Any z[c] <= 0 answers TM_E_ARG.  Per cut,
+ *     theta_c = y_c / z[c] with one rounding.  x and theta are interpolated with A.  The output is (x, r sin theta, r cos theta) with
+ *     r = s[k].
+ * Output:
+ *   - Per block and per layer window [k_begin, k_begin + k_count), three planes X, Y, Z in PLOT3D order.
+ *   - Element ((k - k_begin)*nj + j)*ni + i, with i fastest.  This is the same transposition K8 (k_soa_planes) does for 2-D.
+ * Every sum runs over c = 0 .. K-1 in that order, products and sums rounded separately (nothing fused), on the device and on the host. */
+#define TM_STACK_MAX_CUTS 16
+enum { TM_STACK_LINEAR = 0, TM_STACK_CUBIC = 1 };
+enum { TM_STACK_PLANAR = 0, TM_STACK_CYLINDRICAL = 1 };
+typedef struct tm_stack_opt {
+    uint64_t ncuts;
+    const double* span;      /* [ncuts] z */
+    uint64_t nlayers;
+    const double* layers;    /* [nlayers] s */
+    int32_t interpolation;   /* TM_STACK_LINEAR / TM_STACK_CUBIC */
+    int32_t mapping;         /* TM_STACK_PLANAR / TM_STACK_CYLINDRICAL */
+} tm_stack_opt;
+/* the weight matrix, nlayers * ncuts doubles, row = layer.  Host only: no GPU touched */
+int tm_stack_weights(const tm_stack_opt* opt, double* weights);
+/* Block `block` of K meshes given on the host (cuts[c]->blocks[block].xy): uploads the K copies of the block, stacks them on the device,
+ * writes the window's planes to x, y, z (k_count * ni * nj doubles each).  The cuts must agree in block count and in (ni, nj) of `block`:
+ * otherwise TM_E_SIZE.  A window that is empty or reaches past nlayers, a block index past the mesh, a NULL pointer: TM_E_ARG. */
+int tm_stack_block(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt, uint64_t block, uint64_t k_begin, uint64_t k_count,
+                   double* x, double* y, double* z);
+/* the same definition evaluated on the host: no GPU touched, works in a process without a device (as tm_mesh_quality_host).  Planar
+ * results equal the device's bit for bit; cylindrical y, z differ by what the two sine / cosine implementations differ */
+int tm_stack_block_host(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt, uint64_t block, uint64_t k_begin, uint64_t k_count,
+                        double* x, double* y, double* z);
+/* The same kernel on the coordinates RESIDENT in K handles, one handle per cut (a combined K*B-block handle would run White on cut 0
+ * only).  Ordered behind the pending work of every handle; nothing moves to the host but the result; no handle is modified.  `block` must
+ * be owned by every handle, every entry must be a live handle: otherwise TM_E_ARG.  Handles that disagree in block count or in (ni, nj) of
+ * `block`: TM_E_SIZE.  Cuts spread over ranks are not served.  Bit-identical to tm_stack_block on the downloaded coordinates. */
+int tm_stack_smoothers(tm_smoother* const* cuts, const tm_stack_opt* opt, uint64_t block, uint64_t k_begin, uint64_t k_count,
+                       double* x, double* y, double* z);
+
 /* ------------------------------------------------------------------ host-only planning (no GPU needed)
  * The perimeter-row table the device kernels consume, exported as CSR so it can be compared with
  * the reference's assembled rows (smooth.zig:421-921).  Only sizes/topology are read from `mesh`

@@ -8,10 +8,15 @@ by {"hip": {"inner": "auto"}} (what a user would write into the JSON): the plain
 like the reference's examples (T106 / LS89: 7x faster there than the multigrid-preconditioned one), the multigrid-preconditioned
 solve once a block has 100 000 nodes or more (1000 when the blocks are not coupled) and the cells' aspect ratio does not vary strongly inside any block (refined O-grids with
 boundary-layer clustering keep the plain solve).  --hip reference runs the file's own solver AS WRITTEN on the device: GMRES(30) with ILU(0) or the
-diagonal on the assembled system, the reference's tolerances -- the iterates a run of the reference gives (solver.Option.as_written)."""
+diagonal on the assembled system, the reference's tolerances -- the iterates a run of the reference gives (solver.Option.as_written).
+
+--stack CFG2 [CFG3 ...] --span z0,z1,... --layers NK: `config` and the further files are the spanwise cuts of one blade.  Every file runs the
+path above with its own handle; the smoothed cuts are stacked into 3-D blocks on the device (stack.py, include/tm_hip.h "3-D from 2-D cuts")
+and --output becomes a multi-block 3-D PLOT3D file.  Without --stack the program is what it was."""
 from __future__ import annotations
 
 import argparse
+import contextlib
 import logging
 import os
 import sys
@@ -21,34 +26,10 @@ from . import quality
 from .smoothing import smooth, solver, wall_control_function
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(prog="python -m turbomesh_amd", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("config", help="input file in the reference's JSON schema (examples/T106/T106.json)")
-    ap.add_argument("--hip", nargs="?", const="auto", choices=["auto", "bicgstab", "mg_bicgstab", "gmres", "relax", "file", "reference"],
-                    help="use the hip solver with this inner strategy instead of the solver named in the file; `file` = the device counterpart of "
-                         "the solver the file names (gmres -> GMRES(30) on the device, bicgstab -> BiCGStab; ilu0 -> diagonal); `reference` = the file's "
-                         "solver as written: gmres + ilu0 / diagonal on the assembled system with the reference's tolerances")
-    ap.add_argument("--refine", action="store_true",
-                    help="refine every inner solve with a double-double residual (up to 3 steps): each Picard iterate is the exact one rounded to fp64; "
-                         "with --hip auto, bicgstab, mg_bicgstab, gmres or file, not with relax or reference")
-    ap.add_argument("--control", default="file", choices=["file", "laplace", "thomas-middlecoff"],
-                    help="control function (P, Q): `file` = smoothing.wall_control_function of the input file (the default), `laplace` = none, "
-                         "`thomas-middlecoff` = every block keeps the point distribution of its own edges in its interior (evaluated once from the "
-                         "TFI seed on the device, then frozen)")
-    ap.add_argument("--iterations", type=int, help="override smoothing.iterations")
-    ap.add_argument("--output", help="override the output file (.xyz / .p3d: multi-block PLOT3D)")
-    ap.add_argument("--until", type=float, metavar="TOL",
-                    help="iterate until the scaled nonlinear residual is <= TOL (at most `iterations`, default 100) instead of a fixed count")
-    ap.add_argument("--quality", action="store_true",
-                    help="log a mesh quality report (`quality` logger: one line per block and a total) before and after smoothing")
-    ap.add_argument("--fail-on-inverted", action="store_true",
-                    help="exit non-zero when the smoothed mesh has inverted or degenerate cells (implies the quality evaluation)")
-    args = ap.parse_args(argv)
-    if args.refine and args.hip in ("relax", "reference"):
-        ap.error("--refine goes with --hip auto, bicgstab, mg_bicgstab, gmres or file (relax has no inner solve to refine; reference keeps the reference's stop test)")
-    logging.basicConfig(level=logging.INFO, format="%(levelname)s(%(name)s): %(message)s")
-
-    with open(args.config) as f:
+def _run(ap, args, config, keep=None, tag=""):
+    """One input file through the existing path: parse, block, seed, smooth, download.  keep: an ExitStack that takes the handle over
+    (None: it is closed here, as ever); tag: prefix of the quality report's stage names."""
+    with open(config) as f:
         inp = tm_input.Input.parse(f.read())
     if args.hip == "file":
         inp.solver, note = inp.solver.served_by_hip()
@@ -73,15 +54,19 @@ def main(argv=None):
     mesh = inp.template.run(geometry)                                   # blocking (O4H.zig:67-118) + TFI per block
     iterations = inp.iterations if args.iterations is None else args.iterations
     slog = logging.getLogger("smoothing")
-    with smooth.per_iteration_log(slog.isEnabledFor(logging.INFO) and not args.until), smooth.Smoother(mesh, inp.solver, inp.wall_control_function) as sm:
+    with contextlib.ExitStack() as scope:
+        scope.enter_context(smooth.per_iteration_log(slog.isEnabledFor(logging.INFO) and not args.until))
+        sm = smooth.Smoother(mesh, inp.solver, inp.wall_control_function)
+        (keep if keep is not None else scope).enter_context(sm)   # --stack: the handle outlives this call (its coordinates are stacked on the device)
         slog.info("hip solver, inner strategy: %s%s", sm.inner.name, " (chosen from the block sizes and the spread of the cells' aspect ratios)" if inp.solver.inner == solver.Inner.auto else
                   f", preconditioner: {inp.solver.preconditioner.name}" if sm.inner == solver.Inner.reference_gmres else "")
         qlog = logging.getLogger("quality")
         want_quality = args.quality or args.fail_on_inverted
+        after = None
         if want_quality:
             before = sm.quality()
             if args.quality:
-                quality.log_report(qlog, mesh.names, *before, "before")
+                quality.log_report(qlog, mesh.names, *before, tag + "before")
         if args.until:
             reached, stats = sm.iterate_until(args.until, iterations or 100)
             slog.info("scaled residual %.3e after %d iterations (%s)", stats["scaled_residual_rms"], stats["outer_iterations"], "reached" if reached else "NOT reached")
@@ -99,8 +84,111 @@ def main(argv=None):
         if want_quality:
             after = sm.quality()
             if args.quality:
-                quality.log_report(qlog, mesh.names, *after, "after")
+                quality.log_report(qlog, mesh.names, *after, tag + "after")
             stats["quality"] = {"before": before, "after": after}
+    return inp, mesh, sm, stats, after
+
+
+def _span_clustering(ap, text):
+    from . import clustering
+
+    kind, _, rest = text.partition(":")
+    try:
+        vals = [float(v) for v in rest.split(",")] if rest else []
+        if kind == "uniform" and not vals:
+            return clustering.Uniform()
+        if kind == "roberts" and len(vals) == 2:
+            return clustering.Roberts(*vals)
+        if kind == "tanh" and len(vals) == 1:
+            return clustering.SingleHyperbolicClustering(*vals)
+    except ValueError:
+        pass
+    ap.error(f"--span-clustering {text!r}: uniform, roberts:alpha,beta or tanh:delta_s")
+
+
+def _main_stack(ap, args):
+    """config + --stack files: every cut through _run with its own handle (kept alive), then the 3-D file block by block from the
+    coordinates resident in the handles (tm_stack_smoothers)."""
+    from . import output, stack
+
+    output._format_of(args.output)
+    st = stack.Stack(args.span_values, stack.layers_from(args.span_values, args.layers, args.span_clustering_fn), args.stack_interpolation, args.stack_mapping)
+    st.weights()   # a span that is not increasing (or a radius <= 0) is refused before anything is smoothed
+    files = [args.config] + list(args.stack)
+    all_stats, worst = [], None
+    with contextlib.ExitStack() as keep:
+        handles = []
+        for c, config in enumerate(files):
+            _, mesh, sm, stats, after = _run(ap, args, config, keep=keep, tag=f"cut {c} ")
+            handles.append(sm)
+            all_stats.append(stats)
+            if after is not None and not after[1].ok and worst is None:
+                worst = (c, after[1])
+        m3 = st.mesh3d(handles)
+    m3.write(args.output)
+    logging.getLogger("output").info("wrote %s (%d blocks, %d cuts, %d layers, %d nodes)", args.output, len(m3.blocks), len(files), st.nlayers,
+                                     sum(x.size for x, _, _ in m3.blocks))
+    if args.fail_on_inverted and worst is not None:
+        sys.exit(f"mesh quality: cut {worst[0]} has {worst[1].inverted} inverted and {worst[1].degenerate} degenerate cells after smoothing")
+    return {"cuts": all_stats, "blocks": len(m3.blocks), "layers": st.nlayers}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m turbomesh_amd", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("config", help="input file in the reference's JSON schema (examples/T106/T106.json)")
+    ap.add_argument("--hip", nargs="?", const="auto", choices=["auto", "bicgstab", "mg_bicgstab", "gmres", "relax", "file", "reference"],
+                    help="use the hip solver with this inner strategy instead of the solver named in the file; `file` = the device counterpart of "
+                         "the solver the file names (gmres -> GMRES(30) on the device, bicgstab -> BiCGStab; ilu0 -> diagonal); `reference` = the file's "
+                         "solver as written: gmres + ilu0 / diagonal on the assembled system with the reference's tolerances")
+    ap.add_argument("--refine", action="store_true",
+                    help="refine every inner solve with a double-double residual (up to 3 steps): each Picard iterate is the exact one rounded to fp64; "
+                         "with --hip auto, bicgstab, mg_bicgstab, gmres or file, not with relax or reference")
+    ap.add_argument("--control", default="file", choices=["file", "laplace", "thomas-middlecoff"],
+                    help="control function (P, Q): `file` = smoothing.wall_control_function of the input file (the default), `laplace` = none, "
+                         "`thomas-middlecoff` = every block keeps the point distribution of its own edges in its interior (evaluated once from the "
+                         "TFI seed on the device, then frozen)")
+    ap.add_argument("--iterations", type=int, help="override smoothing.iterations")
+    ap.add_argument("--output", help="override the output file (.xyz / .p3d: multi-block PLOT3D)")
+    ap.add_argument("--until", type=float, metavar="TOL",
+                    help="iterate until the scaled nonlinear residual is <= TOL (at most `iterations`, default 100) instead of a fixed count")
+    ap.add_argument("--quality", action="store_true",
+                    help="log a mesh quality report (`quality` logger: one line per block and a total) before and after smoothing")
+    ap.add_argument("--fail-on-inverted", action="store_true",
+                    help="exit non-zero when the smoothed mesh has inverted or degenerate cells (implies the quality evaluation)")
+    ap.add_argument("--stack", nargs="+", metavar="CFG", default=None,
+                    help="further input files: the spanwise cuts after `config`, in span order.  Every file runs the path above with its own "
+                         "handle; the smoothed cuts are then stacked into 3-D blocks on the device and --output becomes a multi-block 3-D PLOT3D file")
+    ap.add_argument("--span", metavar="Z0,Z1,...", help="span coordinate of every cut (radius with --stack-mapping cylindrical), strictly increasing; one per file")
+    ap.add_argument("--layers", type=int, metavar="NK", help="number of layers of the 3-D blocks, first and last at the end cuts")
+    ap.add_argument("--span-clustering", default="uniform", metavar="uniform|roberts:a,b|tanh:d",
+                    help="distribution of the layers over the span (clustering.zig: Uniform, Roberts alpha,beta, SingleHyperbolicClustering delta_s)")
+    ap.add_argument("--stack-interpolation", default="cubic", choices=["linear", "cubic"], help="between the cuts: linear, or the natural cubic spline")
+    ap.add_argument("--stack-mapping", default="planar", choices=["planar", "cylindrical"],
+                    help="planar: (x, y, s); cylindrical: the cuts are unrolled cylinders (x, r theta) at radius span, output (x, r sin theta, r cos theta)")
+    args = ap.parse_args(argv)
+    if args.stack is None and (args.span or args.layers is not None):
+        ap.error("--span and --layers go with --stack")
+    if args.stack is not None:
+        if not args.span or args.layers is None:
+            ap.error("--stack needs --span z0,z1,... and --layers NK")
+        try:
+            args.span_values = [float(v) for v in args.span.split(",")]
+        except ValueError:
+            ap.error(f"--span {args.span!r}: comma-separated numbers")
+        if len(args.span_values) != 1 + len(args.stack):
+            ap.error(f"--span has {len(args.span_values)} values for {1 + len(args.stack)} files (config + --stack)")
+        if args.layers < 1:
+            ap.error("--layers: at least 1")
+        args.span_clustering_fn = _span_clustering(ap, args.span_clustering)
+        if not args.output:
+            ap.error("--stack needs --output (the 3-D file)")
+    if args.refine and args.hip in ("relax", "reference"):
+        ap.error("--refine goes with --hip auto, bicgstab, mg_bicgstab, gmres or file (relax has no inner solve to refine; reference keeps the reference's stop test)")
+    logging.basicConfig(level=logging.INFO, format="%(levelname)s(%(name)s): %(message)s")
+
+    if args.stack is not None:
+        return _main_stack(ap, args)
+    inp, mesh, _, stats, after = _run(ap, args, args.config)
     out = args.output or inp.output
     if out:
         mesh.write(out)

@@ -24,6 +24,9 @@ TM_SOLVER_GMRES, TM_SOLVER_BICGSTAB, TM_SOLVER_UMFPACK, TM_SOLVER_PETSC, TM_SOLV
 TM_INNER_BICGSTAB, TM_INNER_RELAX, TM_INNER_MG_BICGSTAB, TM_INNER_AUTO, TM_INNER_GMRES, TM_INNER_REFERENCE_GMRES = 0, 1, 2, 3, 4, 5
 TM_CF_LAPLACE, TM_CF_WHITE, TM_CF_PRESCRIBED, TM_CF_THOMAS_MIDDLECOFF = 0, 1, 2, 3
 TM_OPT_REFINE = 16
+TM_STACK_MAX_CUTS = 16
+TM_STACK_LINEAR, TM_STACK_CUBIC = 0, 1
+TM_STACK_PLANAR, TM_STACK_CYLINDRICAL = 0, 1
 
 
 class TmError(RuntimeError):
@@ -128,6 +131,11 @@ class tm_quality(C.Structure):
                 ("hist", C.c_uint64 * 10)]
 
 
+class tm_stack_opt(C.Structure):
+    _fields_ = [("ncuts", C.c_uint64), ("span", C.POINTER(C.c_double)), ("nlayers", C.c_uint64), ("layers", C.POINTER(C.c_double)),
+                ("interpolation", C.c_int32), ("mapping", C.c_int32)]
+
+
 # every symbol include/tm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "tm_last_error", "tm_abi_version", "tm_set_log", "tm_csr_solve", "tm_tfi_block", "tm_tfi_linear2d", "tm_smooth_mesh", "tm_smoother_create",
@@ -139,6 +147,7 @@ EXPORTS = [
     "tm_smoother_inner_counts", "tm_mesh_quality", "tm_mesh_quality_host", "tm_smoother_quality", "tm_smoother_quality_field",
     "tm_csr_residual", "tm_smoother_residual", "tm_smoother_refine_report",
     "tm_smoother_set_control_function", "tm_smoother_update_control_function",
+    "tm_stack_weights", "tm_stack_block", "tm_stack_block_host", "tm_stack_smoothers",
     "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
 ]
 
@@ -228,6 +237,10 @@ def lib():
         L.tm_mesh_quality_host.argtypes = [C.POINTER(tm_mesh_desc), C.POINTER(tm_quality), C.POINTER(tm_quality)]
         L.tm_smoother_quality.argtypes = [C.c_void_p, C.POINTER(tm_quality), C.POINTER(tm_quality)]
         L.tm_smoother_quality_field.argtypes = [C.c_void_p, C.c_uint64, _dp]
+        L.tm_stack_weights.argtypes = [C.POINTER(tm_stack_opt), _dp]
+        L.tm_stack_block.argtypes = [C.POINTER(C.POINTER(tm_mesh_desc)), C.POINTER(tm_stack_opt), C.c_uint64, C.c_uint64, C.c_uint64, _dp, _dp, _dp]
+        L.tm_stack_block_host.argtypes = L.tm_stack_block.argtypes
+        L.tm_stack_smoothers.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt), C.c_uint64, C.c_uint64, C.c_uint64, _dp, _dp, _dp]
         L.tm_rccl_unique_id.argtypes = [C.c_char_p, C.c_void_p]
         L.tm_rccl_comm_create.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.tm_rccl_comm_destroy.argtypes = [C.c_void_p]

@@ -12,6 +12,19 @@ using namespace tmh;
 #include "tm_ilu.hpp"
 #include "tm_refine.hpp"
 #include "tm_quality_dev.hpp"
+#include "tm_stack.hpp"
+
+#include <mutex>
+#include <set>
+
+// the handles tm_smoother_create has handed out and tm_smoother_destroy has not taken back: what lets a call that takes a LIST of handles
+// (tm_stack_smoothers) refuse a destroyed one without touching its memory
+static std::mutex g_live_mutex;
+static std::set<const tm_smoother*> g_live_handles;
+bool tmh::smoother_is_live(const tm_smoother* s) {
+    std::lock_guard<std::mutex> lock(g_live_mutex);
+    return g_live_handles.count(s) != 0;
+}
 
 static void require_gfx950() {
     static int checked = 0;
@@ -386,6 +399,10 @@ int tm_smoother_create(const tm_mesh_desc* mesh, const tm_solver_opt* opt, const
         auto h = std::make_unique<tm_smoother>();
         h->impl.create(mesh, opt, cf, hooks, stream, false);
         *out = h.release();
+        {
+            std::lock_guard<std::mutex> lock(g_live_mutex);
+            g_live_handles.insert(*out);
+        }
         return TM_OK;
     });
 }
@@ -400,6 +417,10 @@ int tm_smoother_workspace_bytes(const tm_mesh_desc* mesh, const tm_solver_opt* o
     });
 }
 void tm_smoother_destroy(tm_smoother* s) {
+    {
+        std::lock_guard<std::mutex> lock(g_live_mutex);
+        g_live_handles.erase(s);
+    }
     delete s;   // ~Smoother releases the pinned buffers, events, side stream and scratch
 }
 int tm_smoother_iterate(tm_smoother* s, uint64_t iterations, tm_stats* stats) {

@@ -1,0 +1,33 @@
+// Spanwise stacking of 2-D cuts into 3-D blocks (include/tm_hip.h, "3-D from 2-D cuts"): what the host part (tm_stack_host.cpp:
+// validation, weights, the CPU evaluation) and the device part (tm_stack.hip: K11 and its entry points) share.
+#pragma once
+#include "../../include/tm_hip.h"
+
+#include <cstdint>
+#include <vector>
+
+struct tm_smoother;
+
+namespace tmh {
+
+// validated options of one call: the weight rows of the window and what the mapping needs
+struct StackPlan {
+    int ncuts = 0;
+    int mapping = TM_STACK_PLANAR;
+    uint64_t nlayers = 0;
+    std::vector<double> span;      // z[ncuts]
+    std::vector<double> weights;   // nlayers * ncuts, row = layer
+    std::vector<double> layers;    // s[nlayers]
+};
+
+// throws TmError(TM_E_ARG) on any violation of the definition
+StackPlan stack_plan(const tm_stack_opt* opt);
+// TM_E_ARG unless [k_begin, k_begin + k_count) is a non-empty window of the plan's layers
+void stack_check_window(const StackPlan& plan, uint64_t k_begin, uint64_t k_count);
+// block `block` of the K descriptions: TM_E_ARG / TM_E_SIZE as the header says; returns (ni, nj)
+void stack_check_cuts(const tm_mesh_desc* const* cuts, int ncuts, uint64_t block, uint64_t* ni, uint64_t* nj);
+
+// live handles of the process (tm_api.cpp: entered by tm_smoother_create, removed by tm_smoother_destroy)
+bool smoother_is_live(const tm_smoother* s);
+
+}  // namespace tmh

@@ -4,6 +4,8 @@
 //   tm_harness strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]
 //   tm_harness single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]
 //   tm_harness tm <ni> <nj> <iterations>               the Thomas-Middlecoff control field on a clustered rectangle (exit 0: it kept the clustering)
+//   tm_harness stack <ni> <nj> <ncuts> <nlayers>       config-5 cuts (amplitude 0.05 + 0.001 c), five relaxation sweeps per handle, stacked on the
+//                                                      device by the natural cubic spline: a checksum per layer (exit 0: layers at cuts equal the cuts)
 //   tm_harness csr                                     the linear-solver slot (seam 2) on the reference's 5 x 5 known answer
 //   tm_harness ranks <world> <rank> <idfile> <nblocks> <ni> <nj> <iterations> [relax|bicgstab] [dump.bin]
 //        one process per GPU (start each with HIP_VISIBLE_DEVICES=<its GPU>): the strip's blocks are dealt to the ranks in order, the
@@ -18,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <thread>
 
 using namespace core;
@@ -74,8 +77,8 @@ static discrete::Mesh buildStrip(std::size_t nblocks, std::size_t ni, std::size_
     return mesh;
 }
 
-static discrete::Mesh buildSingle(std::size_t ni, std::size_t nj) {
-    const double A = 0.1, two_pi = 2 * M_PI;
+static discrete::Mesh buildSingle(std::size_t ni, std::size_t nj, double A = 0.1) {
+    const double two_pi = 2 * M_PI;
     const auto s = clustering::create(clustering::Uniform{}, ni);
     const auto t = clustering::create(clustering::Uniform{}, nj);
     std::vector<Vec2d> lo(ni), up(ni), le(nj), ri(nj);
@@ -224,14 +227,62 @@ static int thomasMiddlecoff(std::size_t ni, std::size_t nj, std::size_t iteratio
     return rms[0] <= 1e-12 && rms[1] > 1e-2 ? 0 : 1;
 }
 
+// tm_harness stack <ni> <nj> <ncuts> <nlayers>: the spanwise cuts of SURVEY 8d config 5 (the config-2 block with amplitude
+// 0.05 + 0.001 c), one handle per cut, five relaxation sweeps each; the cuts sit at span 0, 1, .. K-1, the layers are uniform over it.
+// The 3-D block comes from the coordinates resident in the handles (stack::stack_block -> tm_stack_smoothers).
+static int stackCuts(std::size_t ni, std::size_t nj, std::size_t ncuts, std::size_t nlayers) {
+    if (ncuts < 2 || nlayers < 1) throw Error(TM_E_ARG, "stack <ni> <nj> <ncuts> <nlayers>: at least two cuts and one layer");
+    smoothing::solver::Option opt;
+    opt.inner = TM_INNER_RELAX;
+    std::vector<discrete::Mesh> meshes;
+    meshes.reserve(ncuts);
+    for (std::size_t c = 0; c < ncuts; ++c) meshes.push_back(buildSingle(ni, nj, 0.05 + 0.001 * static_cast<double>(c)));
+    std::vector<std::unique_ptr<smoothing::smooth::Smoother>> handles;
+    std::vector<smoothing::smooth::Smoother*> cuts;
+    for (std::size_t c = 0; c < ncuts; ++c) {
+        handles.push_back(std::make_unique<smoothing::smooth::Smoother>(meshes[c], opt, smoothing::wall_control_function::Algorithm::laplace()));
+        handles.back()->iterate(5);
+        cuts.push_back(handles.back().get());
+    }
+    stack::Option so;
+    for (std::size_t c = 0; c < ncuts; ++c) so.span.push_back(static_cast<double>(c));
+    const double z1 = so.span.back();
+    for (std::size_t k = 0; k < nlayers; ++k) so.layers.push_back(nlayers == 1 ? 0.0 : (k + 1 == nlayers ? z1 : z1 * (static_cast<double>(k) / static_cast<double>(nlayers - 1))));
+    const stack::Block3d b = stack::stack_block(cuts, so, 0, 0, nlayers);
+    for (auto& h : handles) h->download();
+    const std::size_t n = ni * nj;
+    std::size_t compared = 0;
+    bool equal = true;
+    for (std::size_t k = 0; k < nlayers; ++k) {
+        double sx = 0, sy = 0;
+        for (std::size_t q = 0; q < n; ++q) sx += b.x[k * n + q], sy += b.y[k * n + q];
+        std::printf("stack: layer %zu s %.17g sum_x %.17g sum_y %.17g z %.17g\n", k, so.layers[k], sx, sy, b.z[k * n]);
+        for (std::size_t c = 0; c < ncuts; ++c) {
+            if (so.layers[k] != so.span[c]) continue;
+            ++compared;
+            for (std::size_t i = 0; i < ni; ++i)
+                for (std::size_t j = 0; j < nj; ++j) {
+                    const Vec2d p = meshes[c].blocks[0].points.getIndex(i, j);
+                    const std::size_t o = (k * nj + j) * ni + i;
+                    if (!(b.x[o] == p.data[0] && b.y[o] == p.data[1] && b.z[o] == so.span[c])) equal = false;
+                }
+        }
+    }
+    const bool ok = equal && compared >= (nlayers >= 2 ? 2u : 1u);
+    std::printf("stack: layers at cuts equal the cuts: %s\n", ok ? "yes" : "no");
+    return ok ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     try {
+        if (argc >= 6 && std::strcmp(argv[1], "stack") == 0)
+            return stackCuts(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "csr") == 0) return csrKat();
         if (argc >= 5 && std::strcmp(argv[1], "tm") == 0)
             return thomasMiddlecoff(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "ranks") == 0) return runRank(argc, argv);
         if (argc < 5) {
-            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n", argv[0], argv[0]);
+            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n", argv[0], argv[0], argv[0]);
             return 2;
         }
         int a = 2;

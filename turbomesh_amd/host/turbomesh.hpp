@@ -18,6 +18,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <limits>
+#include <memory>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -359,6 +360,7 @@ class Smoother {
     void setControlFunction(const std::vector<types::Vec2d>& pq) { check(tm_smoother_set_control_function(h_, &pq[0].data[0])); }
     void updateControlFunction() { check(tm_smoother_update_control_function(h_)); }
     const tm_mesh_desc& desc() const { return d_.desc; }
+    tm_smoother* handle() const { return h_; }   // for the calls that take a list of handles (stack::stack_block)
     ~Smoother() { tm_smoother_destroy(h_); }
     Smoother(const Smoother&) = delete;
     Smoother& operator=(const Smoother&) = delete;
@@ -421,6 +423,64 @@ class Smoother {
 };
 }  // namespace smooth
 }  // namespace smoothing
+
+// 3-D from 2-D cuts (tm_hip.h): layer k of a 3-D block = sum_c A[k][c] * cut c, weights from the span positions alone
+namespace stack {
+struct Option {
+    std::vector<double> span;     // z of every cut, strictly increasing (the radius with the cylindrical mapping)
+    std::vector<double> layers;   // s of every layer, inside [z_0, z_{K-1}]
+    int32_t interpolation = TM_STACK_CUBIC;
+    int32_t mapping = TM_STACK_PLANAR;
+    tm_stack_opt c_struct() const { return tm_stack_opt{span.size(), span.data(), layers.size(), layers.data(), interpolation, mapping}; }
+};
+struct Block3d {                  // planes in PLOT3D order: element (k*nj + j)*ni + i
+    std::size_t ni = 0, nj = 0, nk = 0;
+    std::vector<double> x, y, z;
+};
+inline std::vector<double> weights(const Option& o) {
+    std::vector<double> w(o.span.size() * o.layers.size() + 1);
+    const tm_stack_opt so = o.c_struct();
+    check(tm_stack_weights(&so, w.data()));
+    w.resize(o.span.size() * o.layers.size());
+    return w;
+}
+// layers [k_begin, k_begin + k_count) of `block` from the coordinates RESIDENT in one handle per cut (tm_stack_smoothers)
+inline Block3d stack_block(const std::vector<smoothing::smooth::Smoother*>& cuts, const Option& o, std::size_t block, std::size_t k_begin, std::size_t k_count) {
+    if (cuts.empty() || cuts.size() != o.span.size()) throw Error(TM_E_ARG, "one handle per span position");
+    std::vector<tm_smoother*> h;
+    for (const auto* c : cuts) h.push_back(c ? c->handle() : nullptr);
+    const tm_mesh_desc& d = cuts[0]->desc();
+    if (block >= d.nblocks) throw Error(TM_E_ARG, "block index past the mesh");
+    Block3d b;
+    b.ni = d.blocks[block].ni, b.nj = d.blocks[block].nj, b.nk = k_count;
+    const std::size_t n = b.ni * b.nj * k_count;
+    b.x.resize(n + 1), b.y.resize(n + 1), b.z.resize(n + 1);
+    const tm_stack_opt so = o.c_struct();
+    check(tm_stack_smoothers(h.data(), &so, block, k_begin, k_count, b.x.data(), b.y.data(), b.z.data()));
+    b.x.resize(n), b.y.resize(n), b.z.resize(n);
+    return b;
+}
+// the same from host coordinates, uploaded per call (tm_stack_block) or, host = true, evaluated on the CPU (tm_stack_block_host)
+inline Block3d stack_block(const std::vector<discrete::Mesh*>& cuts, const Option& o, std::size_t block, std::size_t k_begin, std::size_t k_count, bool host = false) {
+    if (cuts.empty() || cuts.size() != o.span.size()) throw Error(TM_E_ARG, "one mesh per span position");
+    std::vector<std::unique_ptr<smoothing::smooth::Desc>> descs;
+    std::vector<const tm_mesh_desc*> d;
+    for (auto* m : cuts) {
+        if (!m) throw Error(TM_E_ARG, "null mesh");
+        descs.push_back(std::make_unique<smoothing::smooth::Desc>(*m));
+        d.push_back(&descs.back()->desc);
+    }
+    if (block >= cuts[0]->blocks.size()) throw Error(TM_E_ARG, "block index past the mesh");
+    Block3d b;
+    b.ni = cuts[0]->blocks[block].points.size[0], b.nj = cuts[0]->blocks[block].points.size[1], b.nk = k_count;
+    const std::size_t n = b.ni * b.nj * k_count;
+    b.x.resize(n + 1), b.y.resize(n + 1), b.z.resize(n + 1);
+    const tm_stack_opt so = o.c_struct();
+    check((host ? tm_stack_block_host : tm_stack_block)(d.data(), &so, block, k_begin, k_count, b.x.data(), b.y.data(), b.z.data()));
+    b.x.resize(n), b.y.resize(n), b.z.resize(n);
+    return b;
+}
+}  // namespace stack
 
 namespace discrete {
 inline Quality Mesh::quality(bool host) {

@@ -71,6 +71,35 @@ def read_plot3d(filename):
     return out
 
 
+def write_plot3d_3d(filename, sizes, planes):
+    """Multi-block 3-D PLOT3D grid file, little-endian, no record markers:
+        int32 nblocks | nblocks x (int32 ni, nj, nk) | per block: X[ni*nj*nk], Y, Z (float64, i fastest, then j, then k).
+    sizes: [(ni, nj, nk)]; planes: per block (X, Y, Z), each any array of ni*nj*nk elements in that order -- what
+    `stack.Stack.block` returns as (nk, nj, ni) arrays.  Pure file writing (no device)."""
+    with open(filename, "wb") as f:
+        np.array([len(sizes)], dtype="<i4").tofile(f)
+        np.array(sizes, dtype="<i4").reshape(-1, 3).tofile(f)
+        for (ni, nj, nk), xyz in zip(sizes, planes):
+            assert len(xyz) == 3
+            for p in xyz:
+                p = np.asarray(p)
+                assert p.size == ni * nj * nk
+                np.ascontiguousarray(p, dtype="<f8").tofile(f)
+
+
+def read_plot3d_3d(filename):
+    """-> [(ni, nj, nk, X, Y, Z)], the coordinates as (nk, nj, ni) arrays (the order of the file)."""
+    with open(filename, "rb") as f:
+        nb = int(np.fromfile(f, dtype="<i4", count=1)[0])
+        sizes = np.fromfile(f, dtype="<i4", count=3 * nb).reshape(nb, 3)
+        out = []
+        for ni, nj, nk in sizes:
+            n = int(ni) * int(nj) * int(nk)
+            xyz = [np.fromfile(f, dtype="<f8", count=n).reshape(nk, nj, ni) for _ in range(3)]
+            out.append((int(ni), int(nj), int(nk), *xyz))
+    return out
+
+
 def _format_of(filename):
     ext = os.path.splitext(filename)[1].lower()
     if ext == ".cgns":
