@@ -615,42 +615,19 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
             ilu->factor(n, A.p, A.i, A.vx, two ? A.vy : nullptr, nnz, d_dvec.as<double2>(), st);
         }
 
-        double* part_buf[3] = {d_part.as<double>(), d_part.as<double>() + (lazy ? 1 : 0) * MAX_PARTIALS * static_cast<size_t>(npart),
-                               d_part.as<double>() + (lazy ? 2 : 0) * MAX_PARTIALS * static_cast<size_t>(npart)};
-        int part_rot = 0;
-        double* partials = part_buf[0];
-        double* red = d_red.as<double>();
-        KrylovScalars* S_buf[2] = {d_S.as<KrylovScalars>(), d_S.as<KrylovScalars>() + 1};
-        KrylovScalars* S = S_buf[0];
-        HIPCHK(hipMemsetAsync(S_buf[0], 0, sizeof(KrylovScalars) * 2, st));
-        LazyStep pending[2];
-        int npending = 0;
-        auto flush_pending = [&]() {   // pending steps applied by launches of their own (before the host reads the scalars)
-            for (int q = 0; q < npending; ++q) HIPCHK(launch_finalize_scalar(pending[q].partials, pending[q].nwg, red, S, pending[q].step, st));
-            npending = 0;
-        };
-        auto reduce_update = [&](int nrows, int step) {   // the partial rows just written feed scalar step `step`
-            if (!lazy) {
-                HIPCHK(launch_finalize_scalar(partials, nrows, red, S, step, st));
-                return;
-            }
-            if (npending == 2) flush_pending();
-            pending[npending++] = LazyStep{step, partials, nrows};
-            part_rot = (part_rot + 1) % 3;
-            partials = part_buf[part_rot];   // the next producer writes elsewhere: this buffer is read by the consumer's workgroups
-        };
-        auto scalars_for = [&]() {   // for a kernel that reads the scalars: it applies the pending steps itself and publishes the result
-            LazyScalars L;
-            L.S_in = S;
-            if (npending == 0) return L;
-            KrylovScalars* other = (S == S_buf[0]) ? S_buf[1] : S_buf[0];
-            L.S_out = other;
-            L.nsteps = npending;
-            for (int q = 0; q < npending; ++q) L.st[q] = pending[q];
-            npending = 0;
-            S = other;
-            return L;
-        };
+        LazyScalarQueue lsq;   // (tm_krylov.hpp; no all-reduce: one process)
+        lsq.lazy = lazy;
+        lsq.stream = st;
+        for (int k = 0; k < 3; ++k) lsq.part_buf[k] = d_part.as<double>() + (lazy ? k : 0) * MAX_PARTIALS * static_cast<size_t>(npart);
+        lsq.partials = lsq.part_buf[0];
+        lsq.red = d_red.as<double>();
+        lsq.S_buf[0] = d_S.as<KrylovScalars>();
+        lsq.S_buf[1] = lsq.S_buf[0] + 1;
+        lsq.S = lsq.S_buf[0];
+        HIPCHK(hipMemsetAsync(lsq.S_buf[0], 0, sizeof(KrylovScalars) * 2, st));
+        double*& partials = lsq.partials;
+        double* const red = lsq.red;
+        KrylovScalars*& S = lsq.S;
         double2 *r = d_r.as<double2>(), *r_hat = d_rh.as<double2>(), *p = d_pv.as<double2>(), *v = d_v.as<double2>(),
                 *s = d_s.as<double2>(), *t = d_t.as<double2>();
         // one solve of A u = bvec from the guess in u, stop test relative to ||D^-1 bvec||: the call's own solve and, with TM_OPT_REFINE, the
@@ -678,7 +655,7 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
             GmresScalars* G = d_G.as<GmresScalars>();
             HIPCHK(hipMemsetAsync(G, 0, sizeof(GmresScalars), st));
             HIPCHK(hipMemsetAsync(V, 0, vb * (GMRES_M + 1), st));
-            auto Vk = [&](int k) { return V + static_cast<size_t>(k) * n; };
+            const GmresSpace g{G, V, n, W, n, partials, red, st};
             auto norm2_of = [&](const double2* v) {
                 hipLaunchKernelGGL(k_csr_norm2, dim3(nwg), dim3(256), 0, st, n, v, partials);
                 HIPCHK(hipGetLastError());
@@ -699,6 +676,11 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
                 HIPCHK(hipStreamSynchronize(st));
                 return h_G.done[0] == 1 && h_G.done[1] == 1;
             };
+            auto apply_op = [&](const double2* vj, double2* w) {
+                hipLaunchKernelGGL((k_csr_apply<false, DOT_NONE>), dim3(nwg), dim3(256), 0, st, A, vj, nullptr, nullptr, w, partials);   // D^-1 A v_j
+                HIPCHK(hipGetLastError());
+                if (use_ilu) ilu->apply(w, w, st);
+            };
             uint64_t it_total = 0;
             bool converged = false, first = true;
             double rr0[2] = {0.0, 0.0};
@@ -712,46 +694,15 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
                     HIPCHK(launch_finalize(partials, nwg, red, st));
                 }
                 HIPCHK(launch_gm_begin(G, red, st));
-                const bool all_done = poll();
+                converged = poll();
                 if (first) {
                     rr0[0] = h_G.rr0[0];
                     rr0[1] = h_G.rr0[1];
                     first = false;
                 }
-                if (all_done) {
-                    converged = true;
-                    break;
-                }
-                HIPCHK(launch_gm_divide(Vk(0), W, G, n, st));
-                bool cycle_done = false;
-                for (int j = 0; j < GMRES_M && it_total < opt.max_inner; ++j) {
-                    hipLaunchKernelGGL((k_csr_apply<false, DOT_NONE>), dim3(nwg), dim3(256), 0, st, A, Vk(j), nullptr, nullptr, W, partials);   // D^-1 A v_j
-                    HIPCHK(hipGetLastError());
-                    if (use_ilu) ilu->apply(W, W, st);
-                    HIPCHK(launch_gm_mgs(W, nullptr, Vk(0), nullptr, G, 0, n, partials, st));
-                    HIPCHK(launch_finalize(partials, nwg_vec, red, st));
-                    for (int i = 1; i <= j; ++i) {
-                        HIPCHK(launch_gm_mgs(W, Vk(i - 1), Vk(i), red, G, i - 1, n, partials, st));
-                        HIPCHK(launch_finalize(partials, nwg_vec, red, st));
-                    }
-                    HIPCHK(launch_gm_mgs(W, Vk(j), nullptr, red, G, j, n, partials, st));
-                    HIPCHK(launch_finalize(partials, nwg_vec, red, st));
-                    HIPCHK(launch_gm_column(G, red, st));
-                    HIPCHK(launch_gm_divide(Vk(j + 1), W, G, n, st));
-                    it_total += 1;
-                    if ((j + 1) % static_cast<int>(opt.check_every) == 0 || j + 1 == GMRES_M || it_total == opt.max_inner) {
-                        if (poll()) {
-                            cycle_done = true;
-                            break;
-                        }
-                    }
-                }
-                HIPCHK(launch_gm_backsub(G, st));
-                HIPCHK(launch_gm_update(u, V, n, G, n, st));
-                if (cycle_done) {
-                    converged = true;
-                    break;
-                }
+                if (converged) break;
+                converged = gmres_cycle(g, u, apply_op, [&] { HIPCHK(launch_finalize(partials, nwg_vec, red, st)); }, poll, opt.check_every, it_total, opt.max_inner);
+                if (converged) break;
             }
             out.converged = converged;
             out.iterations = it_total;
@@ -763,23 +714,29 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
 
         KrylovScalars h_S;
         auto read_S = [&]() {
-            flush_pending();
+            lsq.flush();
             HIPCHK(hipMemcpyAsync(&h_S, S, sizeof(KrylovScalars), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
         };
         uint64_t it_total = 0;
         int restarts = 0;
-        bool converged = false, stalled = false;
+        bool converged = false;
         double rr0[2] = {0.0, 0.0};
-        // stagnation watch, as in Smoother::poll_done: a recurrence residual that fails to halve over max(4000, 4 sqrt(n)) iterations ends
-        // the solve (not converged, a warning) instead of running to the iteration cap
-        double stall_best[2] = {0.0, 0.0};
-        uint64_t stall_since = 0;
-        const uint64_t stall_window = std::max<uint64_t>(4000, static_cast<uint64_t>(4.0 * std::sqrt(static_cast<double>(n))));
+        StallWatch stall;   // runs without ILU(0) only
+        stall.window = StallWatch::window_for(static_cast<double>(n));
+        // with ILU(0): the preconditioned recurrence, the substitutions where the handle's mg_bicgstab has its multigrid cycle
+        const BicgVectors w{r, p, v, s, t, use_ilu ? d_ph.as<double2>() : p, use_ilu ? d_sh.as<double2>() : s, r_hat, n, nwg_vec};
+        auto precond = [&](const double2* in, double2* out) { ilu->apply(in, out, st); };
+        auto apply_op = [&](const double2* in, double2* out, int dot, const double2* aux, int step) {
+            const auto kernel = dot == DOT_AUX ? k_csr_apply<false, DOT_AUX> : (dot == DOT_AUX2 ? k_csr_apply<false, DOT_AUX2> : k_csr_apply<false, DOT_IN>);
+            hipLaunchKernelGGL(kernel, dim3(nwg), dim3(256), 0, st, A, in, nullptr, aux, out, partials);
+            HIPCHK(hipGetLastError());
+            lsq.reduce_update(nwg, step);
+        };
         while (true) {
             hipLaunchKernelGGL((k_csr_apply<true, DOT_OUT2>), dim3(nwg), dim3(256), 0, st, A, u, bvec, nullptr, r, partials);
             HIPCHK(hipGetLastError());
-            flush_pending();
+            lsq.flush();
             HIPCHK(launch_finalize_scalar(partials, nwg, red, S, STEP_INIT, st));
             HIPCHK(hipMemcpyAsync(r_hat, r, vb, hipMemcpyDeviceToDevice, st));
             HIPCHK(hipMemsetAsync(p, 0, vb, st));
@@ -795,43 +752,8 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
             }
             bool breakdown = false;
             while (it_total < opt.max_inner) {
-                if (use_ilu) {   // the preconditioned recurrence, as Smoother::picard_bicgstab with the multigrid cycle in this place
-                    double2 *p_hat = d_ph.as<double2>(), *s_hat = d_sh.as<double2>();
-                    HIPCHK(launch_p_update(scalars_for(), r, p, v, n, nwg_vec, st));
-                    ilu->apply(p, p_hat, st);
-                    hipLaunchKernelGGL((k_csr_apply<false, DOT_AUX>), dim3(nwg), dim3(256), 0, st, A, p_hat, nullptr, r_hat, v, partials);
-                    HIPCHK(hipGetLastError());
-                    reduce_update(nwg, STEP_SIGMA);
-                    HIPCHK(launch_s_update(scalars_for(), r, v, s, n, nwg_vec, partials, st));
-                    reduce_update(nwg_vec, STEP_SS);
-                    ilu->apply(s, s_hat, st);
-                    hipLaunchKernelGGL((k_csr_apply<false, DOT_AUX2>), dim3(nwg), dim3(256), 0, st, A, s_hat, nullptr, s, t, partials);   // t.s, t.t with the unpreconditioned s
-                    HIPCHK(hipGetLastError());
-                    reduce_update(nwg, STEP_TSTT);
-                    HIPCHK(launch_xr_update(scalars_for(), u, p_hat, s_hat, s, t, r, r_hat, n, nwg_vec, partials, st));
-                    reduce_update(nwg_vec, STEP_RHO);
-                    it_total += 1;
-                    if (it_total % opt.check_every == 0 || it_total == opt.max_inner) {
-                        read_S();
-                        if (h_S.done[0] && h_S.done[1]) {
-                            converged = h_S.done[0] == 1 && h_S.done[1] == 1;
-                            breakdown = !converged;
-                            break;
-                        }
-                    }
-                    continue;
-                }
-                HIPCHK(launch_p_update(scalars_for(), r, p, v, n, nwg_vec, st));
-                hipLaunchKernelGGL((k_csr_apply<false, DOT_AUX>), dim3(nwg), dim3(256), 0, st, A, p, nullptr, r_hat, v, partials);
-                HIPCHK(hipGetLastError());
-                reduce_update(nwg, STEP_SIGMA);
-                HIPCHK(launch_s_update(scalars_for(), r, v, s, n, nwg_vec, partials, st));
-                reduce_update(nwg_vec, STEP_SS);
-                hipLaunchKernelGGL((k_csr_apply<false, DOT_IN>), dim3(nwg), dim3(256), 0, st, A, s, nullptr, nullptr, t, partials);
-                HIPCHK(hipGetLastError());
-                reduce_update(nwg, STEP_TSTT);
-                HIPCHK(launch_xr_update(scalars_for(), u, p, s, s, t, r, r_hat, n, nwg_vec, partials, st));
-                reduce_update(nwg_vec, STEP_RHO);
+                bicgstab_direction(lsq, w, precond, apply_op);
+                bicgstab_correction(lsq, w, u, precond, apply_op);
                 it_total += 1;
                 if (it_total % opt.check_every == 0 || it_total == opt.max_inner) {
                     read_S();
@@ -840,23 +762,13 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
                         breakdown = !converged;
                         break;
                     }
-                    bool progress = false;
-                    for (int c = 0; c < 2; ++c)
-                        if (!h_S.done[c] && (!(stall_best[c] > 0.0) || h_S.rr[c] < 0.25 * stall_best[c])) {
-                            stall_best[c] = h_S.rr[c];
-                            progress = true;
-                        }
-                    if (progress) stall_since = it_total;
-                    else if (it_total - stall_since > stall_window) {
-                        stalled = true;
-                        break;
-                    }
+                    if (!use_ilu && stall.observe(h_S, it_total)) break;
                 }
             }
-            if (converged || !breakdown || stalled || restarts >= 8 || it_total >= opt.max_inner) break;
+            if (converged || !breakdown || stall.stalled || restarts >= 8 || it_total >= opt.max_inner) break;
             restarts += 1;   // rho or omega vanished: restart from the current iterate (the reference only warns, BiCGStab.zig:368-369)
         }
-        npending = 0;   // scalar steps still pending belong to an iteration nobody reads
+        lsq.drop();   // scalar steps still pending belong to an iteration nobody reads
         out.converged = converged;
         out.iterations = it_total;
         out.sweeps = 1 + static_cast<uint64_t>(restarts) + 2 * it_total;
@@ -884,12 +796,12 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
             for (int q = 0; q < REFINE_MAX_STEPS; ++q) {
                 HIPCHK(launch_csr_residual_dd(n, A.p, A.i, A.vx, A.vy, u, d_b.as<double2>(), d_rr.as<double2>(), st));
                 HIPCHK(hipMemsetAsync(d_d.p, 0, vb, st));
-                HIPCHK(hipMemsetAsync(S_buf[0], 0, sizeof(KrylovScalars) * 2, st));
+                HIPCHK(hipMemsetAsync(lsq.S_buf[0], 0, sizeof(KrylovScalars) * 2, st));
                 const SolveOut c = solve(d_rr.as<double2>(), d_d.as<double2>(), rtol_c);
                 it_corr += c.iterations;
                 sweeps += c.sweeps + 1;
-                HIPCHK(launch_refine_update(n, u, d_d.as<double2>(), part_buf[0], st));
-                HIPCHK(launch_finalize(part_buf[0], nwg, red, st));
+                HIPCHK(launch_refine_update(n, u, d_d.as<double2>(), lsq.part_buf[0], st));
+                HIPCHK(launch_finalize(lsq.part_buf[0], nwg, red, st));
                 HIPCHK(hipMemcpyAsync(h_red, red, sizeof(double) * MAX_PARTIALS, hipMemcpyDeviceToHost, st));
                 HIPCHK(hipStreamSynchronize(st));
                 steps += 1;

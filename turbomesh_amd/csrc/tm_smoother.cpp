@@ -623,7 +623,7 @@ uint64_t Smoother::size_launches() {
     // 0.28 / 0.41 M nodes: 46.2 -> 42.8 / 62.6 -> 59.4 us per iteration, same iterates bit for bit; more than 512 partial rows do NOT pay:
     // 2048 of them in every workgroup's prologue made T106 x 8 115 instead of 95 us)
     if (vk_able && std::max(nwg_apply, nwg_apply_ov) <= 512) nwg_vec = std::min(nwg_vec, 512);
-    lazy = !has_hooks && opt.inner != TM_INNER_RELAX && std::max(std::max(nwg_apply, nwg_apply_ov), nwg_vec) <= 512 && !(opt.flags & TM_OPT_EAGER_SCALARS);
+    lsq.lazy = !has_hooks && opt.inner != TM_INNER_RELAX && std::max(std::max(nwg_apply, nwg_apply_ov), nwg_vec) <= 512 && !(opt.flags & TM_OPT_EAGER_SCALARS);
     const int nwg_refine = refine() ? csr_nwg(n_owned) : 0;   // the CSR kernels of a refinement step: 256 rows per workgroup
     const uint64_t npart = static_cast<uint64_t>(std::max(std::max(std::max(std::max(std::max(nwg_apply, nwg_apply_ov), nwg_apply2), nwg3_all), nwg_vec), nwg_refine)) * MAX_PARTIALS;
     // second apply of an iteration with the s-update folded in: single process (nothing of s has to travel) and no preconditioner
@@ -674,16 +674,18 @@ void Smoother::alloc_reductions(uint64_t npart) {
     partials_guard = false;
     if (const char* e = std::getenv("TM_PARTIALS_GUARD")) partials_guard = std::atoi(e) != 0;
     const uint64_t nguard = partials_guard ? GUARD_DOUBLES : 0;
-    for (int k = 0; k < (lazy ? 3 : 1); ++k) part_buf[k] = arena.alloc_n<double>(npart + nguard);
-    partials = part_buf[0];
+    lsq.stream = stream;
+    if (has_hooks) lsq.all_reduce = [this](int nwg) { reduce(nwg); };
+    for (int k = 0; k < (lsq.lazy ? 3 : 1); ++k) lsq.part_buf[k] = arena.alloc_n<double>(npart + nguard);
+    partials = lsq.part_buf[0];
     red = arena.alloc_n<double>(MAX_PARTIALS + nguard);
     if (partials_guard) {
-        for (int k = 0; k < 3; ++k) guard[k] = part_buf[k] ? part_buf[k] + npart : nullptr;
+        for (int k = 0; k < 3; ++k) guard[k] = lsq.part_buf[k] ? lsq.part_buf[k] + npart : nullptr;
         guard[3] = red ? red + MAX_PARTIALS : nullptr;
     }
-    S_buf[0] = arena.alloc_n<KrylovScalars>(1);
-    S_buf[1] = lazy ? arena.alloc_n<KrylovScalars>(1) : S_buf[0];
-    S = S_buf[0];
+    lsq.S_buf[0] = arena.alloc_n<KrylovScalars>(1);
+    lsq.S_buf[1] = lsq.lazy ? arena.alloc_n<KrylovScalars>(1) : lsq.S_buf[0];
+    S = lsq.S_buf[0];
     sync_flags = arena.alloc_n<uint32_t>(64);   // [0] border passes done, [1] interior passes done, [2] a wait timed out
 
     // ---- halo exchange
@@ -697,7 +699,7 @@ void Smoother::alloc_reductions(uint64_t npart) {
 // what only a handle that runs needs (the sizing call stops in front of it): pinned buffers, cleared device state, the first upload
 void Smoother::finish_create(const tm_mesh_desc* mesh) {
     HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h_S), sizeof(KrylovScalars), hipHostMallocDefault));
-    pipelined_poll = lazy;   // small single-process meshes (see poll_done)
+    pipelined_poll = lsq.lazy;   // small single-process meshes (see poll_done)
     if (const char* e = std::getenv("TM_PIPELINED_POLL")) pipelined_poll = pipelined_poll && std::atoi(e) != 0;
     if (pipelined_poll)
         for (int k = 0; k < 2; ++k) {
@@ -711,8 +713,8 @@ void Smoother::finish_create(const tm_mesh_desc* mesh) {
         HIPCHK(hipMemsetAsync(gm_V, 0, sizeof(double2) * static_cast<size_t>(n_local) * (GMRES_M + 1), stream));
         HIPCHK(hipMemsetAsync(r, 0, sizeof(double2) * n_local, stream));
     }
-    HIPCHK(hipMemsetAsync(S_buf[0], 0, sizeof(KrylovScalars), stream));
-    if (S_buf[1] != S_buf[0]) HIPCHK(hipMemsetAsync(S_buf[1], 0, sizeof(KrylovScalars), stream));
+    HIPCHK(hipMemsetAsync(lsq.S_buf[0], 0, sizeof(KrylovScalars), stream));
+    if (lsq.S_buf[1] != lsq.S_buf[0]) HIPCHK(hipMemsetAsync(lsq.S_buf[1], 0, sizeof(KrylovScalars), stream));
     HIPCHK(hipMemsetAsync(sync_flags, 0, sizeof(uint32_t) * 64, stream));
     for (double* g : guard)
         if (g) HIPCHK(hipMemsetAsync(g, GUARD_BYTE, sizeof(double) * GUARD_DOUBLES, stream));
@@ -842,44 +844,6 @@ void Smoother::reduce(int nwg) {
     }
 }
 
-void Smoother::reduce_update(int nwg, int step, double rtol, double atol) {
-    if (has_hooks) {   // the sums of all ranks are needed before the scalars can move
-        reduce(nwg);
-        HIPCHK(launch_scalar_update(S, red, step, stream, rtol, atol));
-        return;
-    }
-    if (lazy && step != STEP_TOL) {   // no launch: the step waits for the kernel that needs its result (scalars_for)
-        if (npending == 2) flush_pending();
-        pending[npending++] = LazyStep{step, partials, nwg};
-        part_rot = (part_rot + 1) % 3;
-        partials = part_buf[part_rot];   // the next producer writes elsewhere: this buffer is read by the consumer's workgroups
-        return;
-    }
-    flush_pending();
-    HIPCHK(launch_finalize_scalar(partials, nwg, red, S, step, stream, rtol, atol));
-}
-
-// pending steps applied by their own launches (before the host reads the scalars, or a step that cannot wait)
-void Smoother::flush_pending() {
-    for (int q = 0; q < npending; ++q) HIPCHK(launch_finalize_scalar(pending[q].partials, pending[q].nwg, red, S, pending[q].step, stream));
-    npending = 0;
-}
-
-// the scalars for a kernel that reads them: with pending steps, the kernel applies them itself and publishes the result to the
-// other scalar block, which is the current one from then on
-LazyScalars Smoother::scalars_for() {
-    LazyScalars L;
-    L.S_in = S;
-    if (npending == 0) return L;
-    KrylovScalars* other = (S == S_buf[0]) ? S_buf[1] : S_buf[0];
-    L.S_out = other;
-    L.nsteps = npending;
-    for (int q = 0; q < npending; ++q) L.st[q] = pending[q];
-    npending = 0;
-    S = other;
-    return L;
-}
-
 // runs `launch`; with profiling on, bracketed by a hipEvent pair on the handle's stream
 void Smoother::profiled(const std::function<void()>& launch, bool counts, hipStream_t on) {
     if (!on) on = stream;
@@ -968,7 +932,7 @@ void Smoother::apply(const double2* in, double2* out, int mode, int dot, const d
                                                        partials + static_cast<size_t>(poff_edge) * MAX_PARTIALS, stream);
         if (rc == hipSuccess) {
             if (dot != DOT_NONE && dot != DOT_DELTA) {
-                if (step >= 0) reduce_update(nwg_apply, step);
+                if (step >= 0) lsq.reduce_update(nwg_apply, step);
                 else reduce(nwg_apply);
             }
             return;
@@ -982,7 +946,7 @@ void Smoother::apply(const double2* in, double2* out, int mode, int dot, const d
     // a relaxation sweep evaluates only the perimeter rows that are not `fixed` (see prefill_fixed)
     HIPCHK(launch_edge_rows(mode == MODE_RELAX ? edge_nf : edge, in, xk, PQ, aux, out, omega, mode, dot, partials + static_cast<size_t>(poff_edge) * MAX_PARTIALS, stream));
     if (dot != DOT_NONE && dot != DOT_DELTA) {   // relax sweeps leave the per-workgroup partials; summed when read
-        if (step >= 0) reduce_update(nwg_apply, step);
+        if (step >= 0) lsq.reduce_update(nwg_apply, step);
         else reduce(nwg_apply);
     }
 }
@@ -1029,8 +993,8 @@ void Smoother::apply_virtual(int kind, const double2* in, const double2* in2, co
     V.rout = rout;
     V.uio = uio;
     HIPCHK(launch_apply_virtual(blocks.data(), static_cast<int>(blocks.size()), edge, V, X, PQ, out,
-                                partials + static_cast<size_t>(ov ? poff_edge_ov : poff_edge) * MAX_PARTIALS, scalars_for(), stream, ov));
-    reduce_update(ov ? nwg_apply_ov : nwg_apply, kind == VK_P ? STEP_SIGMA : (kind == VK_S ? STEP_SS_TSTT : (kind == VK_R ? STEP_A2 : STEP_B2)));
+                                partials + static_cast<size_t>(ov ? poff_edge_ov : poff_edge) * MAX_PARTIALS, lsq.scalars_for(), stream, ov));
+    lsq.reduce_update(ov ? nwg_apply_ov : nwg_apply, kind == VK_P ? STEP_SIGMA : (kind == VK_S ? STEP_SS_TSTT : (kind == VK_R ? STEP_A2 : STEP_B2)));
 }
 
 void Smoother::white_launch(int update) {
@@ -1153,28 +1117,11 @@ void Smoother::precondition_probe_host(const double* f, double* z, double* f_aft
 // (scalar_update_body), so its U and r no longer move and `done` never reverts.  `poll_iters` = the iteration count of the poll
 // that saw the end (what a blocking poll would have reported).
 int Smoother::poll_done(uint64_t it, bool final) {
-    // Stagnation watch: the default tolerance of the diagonal-only solve lies below the TRUE residual fp64 can reach (it is met
-    // by the recurrence residual drifting down, which does keep removing low-frequency error: DESIGN.md section 5); should the recurrence
-    // residual of an active component ever fail to halve over max(4000, 4 sqrt(dof)) iterations, the solve is over -- reported as not
-    // converged (a warning), without a restart, instead of running to the iteration cap.
-    auto verdict = [&](const KrylovScalars* h, uint64_t at) {
+    auto verdict = [&](const KrylovScalars* h, uint64_t at) {   // (a stalled solve ends like a breakdown: StallWatch, tm_krylov.hpp)
         if (h->done[0] && h->done[1]) return (h->done[0] == 1 && h->done[1] == 1) ? 1 : 2;
-        bool progress = false;
-        for (int c = 0; c < 2; ++c) {
-            if (h->done[c]) continue;
-            if (!(stall_best[c] > 0.0) || h->rr[c] < 0.25 * stall_best[c]) {   // ||r||^2 down by 4 = the norm halved
-                stall_best[c] = h->rr[c];
-                progress = true;
-            }
-        }
-        if (progress) stall_since = at;
-        else if (at > stall_since && at - stall_since > stall_window) {
-            stalled = true;
-            return 2;
-        }
-        return 0;
+        return stall.observe(*h, at) ? 2 : 0;
     };
-    flush_pending();
+    lsq.flush();
     if (!pipelined_poll) {
         HIPCHK(hipMemcpyAsync(h_S, S, sizeof(KrylovScalars), hipMemcpyDeviceToHost, stream));
         sync();
@@ -1204,31 +1151,38 @@ int Smoother::poll_done(uint64_t it, bool final) {
 // ------------------------------------------------------------------ Picard + BiCGStab
 // One outer iteration: returns 1 if the inner solve did not converge.
 int Smoother::picard_bicgstab(tm_stats& st) {
-    if (white && outer_done > 0) white_launch(1);   // system.fill(n): control_function.update for n > 0 (smooth.zig:1107-1110)
-    exchange(X);
-    exchange_finish();
+    begin_outer();
     if (use_mg)   // level hierarchy of the newly frozen field
         for (size_t k = 0; k < lp.owned_blocks.size(); ++k) mg[k].set_field(X + lp.local_start[k], PQ ? PQ + lp.local_start[k] : nullptr, stream);
     // warm start: the solution vector starts from the current coordinates (BiCGStab.zig:136-153; later
     // outer iterations continue from the copied-back solution, which is the same field) -- copied behind the stop test below
     // tolerance from ||D^-1 b||
     HIPCHK(launch_edge_rhs(edge, X, PQ, nullptr, 1, partials, stream));
-    reduce_update(edge.nwg, STEP_TOL, (opt.flags & TM_OPT_RTOL_INITIAL) ? -opt.rtol : opt.rtol, opt.atol);
+    lsq.reduce_update(edge.nwg, STEP_TOL, (opt.flags & TM_OPT_RTOL_INITIAL) ? -opt.rtol : opt.rtol, opt.atol);
 
     int restarts = 0;
     uint64_t it_total = 0;
-    bool converged = false;
+    bool converged = false, breakdown = false;
     poll_iters = 0;
-    stall_best[0] = stall_best[1] = 0.0;
-    stall_since = 0;
-    stalled = false;
-    stall_window = std::max<uint64_t>(4000, static_cast<uint64_t>(4.0 * std::sqrt(static_cast<double>(dof_global))));
+    stall.reset();
+    stall.window = StallWatch::window_for(static_cast<double>(dof_global));
+    auto precond = [&](const double2* in, double2* out) { precondition(in, out); };
+    auto apply_op = [&](const double2* in, double2* out, int dot, const double2* aux, int step) { apply(in, out, MODE_SCALED, dot, aux, X, 0.0, step); };
+    auto iteration_done = [&]() {   // counts the iteration just enqueued and polls when one is due; true = the solve (or this start of it) is over
+        st.operator_sweeps += 2;
+        it_total += 1;
+        if (it_total % opt.check_every != 0 && it_total != opt.max_inner) return false;
+        const int verdict = poll_done(it_total, it_total == opt.max_inner);
+        converged = verdict == 1;
+        breakdown = verdict == 2;
+        return verdict != 0;
+    };
     while (true) {
         // r = D^-1 (b - A U) ; r_hat = r ; p = v = 0   (first pass: U is X)
         apply(restarts == 0 ? X : U, r, MODE_RESID, DOT_OUT2, nullptr, X, 0.0, fuse2 ? STEP_INIT2 : STEP_INIT);
         st.operator_sweeps += 1;
         if (restarts == 0) {   // scaled nonlinear residual of this outer iteration
-            flush_pending();
+            lsq.flush();
             HIPCHK(hipMemcpyAsync(h_S, S, sizeof(KrylovScalars), hipMemcpyDeviceToHost, stream));
             sync();
             st.scaled_residual_rms = std::sqrt((h_S->rr0[0] + h_S->rr0[1]) / (2.0 * static_cast<double>(dof_global)));
@@ -1247,7 +1201,7 @@ int Smoother::picard_bicgstab(tm_stats& st) {
             HIPCHK(hipMemsetAsync(v, 0, sizeof(double2) * n_local, stream));
         }
         if (fuse2) HIPCHK(hipMemsetAsync(t, 0, sizeof(double2) * n_local, stream));   // the first pass multiplies it by omega = 0
-        bool breakdown = false;
+        breakdown = false;
         poll_open = false;
         while (it_total < opt.max_inner) {
             if (fuse2) {
@@ -1262,16 +1216,7 @@ int Smoother::picard_bicgstab(tm_stats& st) {
                 std::swap(p, p_alt);
                 std::swap(v, v_alt);
                 apply_virtual(VK_S2, r, v, nullptr, nullptr, t);
-                st.operator_sweeps += 2;
-                it_total += 1;
-                if (it_total % opt.check_every == 0 || it_total == opt.max_inner) {
-                    const int verdict = poll_done(it_total, it_total == opt.max_inner);
-                    if (verdict) {
-                        converged = verdict == 1;
-                        breakdown = !converged;
-                        break;
-                    }
-                }
+                if (iteration_done()) break;
                 continue;
             }
             if (fuse_p) {
@@ -1281,65 +1226,43 @@ int Smoother::picard_bicgstab(tm_stats& st) {
                 std::swap(p, p_alt);
                 std::swap(v, v_alt);
             } else {
-                HIPCHK(launch_p_update(scalars_for(), r, p, v, n_owned, nwg_vec, stream));
-                if (use_mg) {   // right preconditioning (BiCGStab.zig:314-316, 340-342 with M = one V-cycle)
-                    precondition(p, p_hat);
-                    apply(p_hat, v, MODE_SCALED, DOT_AUX, r_hat, X, 0.0, STEP_SIGMA);
-                } else {
-                    apply(p, v, MODE_SCALED, DOT_AUX, r_hat, X, 0.0, STEP_SIGMA);
-                }
+                bicgstab_direction(lsq, bicg_vectors(), precond, apply_op);   // (with M = one V-cycle where the mode has it)
             }
             if (fuse_s) {
                 // s = r - alpha v is never stored: the second apply forms it as the rows enter its window (interior rows and
                 // perimeter rows), with ||s||^2 beside t.s and t.t in one reduction; k_xr_update_vs forms it again
                 apply_virtual(VK_S, r, v, nullptr, nullptr, t);
-                HIPCHK(launch_xr_update_vs(scalars_for(), U, p, v, t, r, r_hat, n_owned, nwg_vec, partials, stream));
-                reduce_update(nwg_vec, STEP_RHO);
-                st.operator_sweeps += 2;
-                it_total += 1;
-                if (it_total % opt.check_every == 0 || it_total == opt.max_inner) {
-                    const int verdict = poll_done(it_total, it_total == opt.max_inner);
-                    if (verdict) {
-                        converged = verdict == 1;
-                        breakdown = !converged;
-                        break;
-                    }
-                }
-                continue;
-            }
-            HIPCHK(launch_s_update(scalars_for(), r, v, s, n_owned, nwg_vec, partials, stream));
-            reduce_update(nwg_vec, STEP_SS);
-            if (use_mg) {
-                precondition(s, s_hat);
-                apply(s_hat, t, MODE_SCALED, DOT_AUX2, s, X, 0.0, STEP_TSTT);   // t.s and t.t with the UNpreconditioned s
+                HIPCHK(launch_xr_update_vs(lsq.scalars_for(), U, p, v, t, r, r_hat, n_owned, nwg_vec, partials, stream));
+                lsq.reduce_update(nwg_vec, STEP_RHO);
             } else {
-                apply(s, t, MODE_SCALED, DOT_IN, nullptr, X, 0.0, STEP_TSTT);
+                bicgstab_correction(lsq, bicg_vectors(), U, precond, apply_op);
             }
-            HIPCHK(launch_xr_update(scalars_for(), U, use_mg ? p_hat : p, use_mg ? s_hat : s, s, t, r, r_hat, n_owned, nwg_vec, partials, stream));
-            reduce_update(nwg_vec, STEP_RHO);
-            st.operator_sweeps += 2;
-            it_total += 1;
-            if (it_total % opt.check_every == 0 || it_total == opt.max_inner) {
-                const int verdict = poll_done(it_total, it_total == opt.max_inner);
-                if (verdict) {
-                    converged = verdict == 1;
-                    breakdown = !converged;
-                    break;
-                }
-            }
+            if (iteration_done()) break;
         }
         if (fuse2) {   // the last iteration's x / r update is still pending (zero scalars once a component has finished)
-            flush_pending();
-            HIPCHK(launch_xr_update_vs(scalars_for(), U, p, v, t, r, r_hat, n_owned, nwg_vec, partials, stream));   // its partial sums are not used
+            lsq.flush();
+            HIPCHK(launch_xr_update_vs(lsq.scalars_for(), U, p, v, t, r, r_hat, n_owned, nwg_vec, partials, stream));   // its partial sums are not used
         }
-        if (converged || !breakdown || stalled || restarts >= 8 || it_total >= opt.max_inner) break;
+        if (converged || !breakdown || stall.stalled || restarts >= 8 || it_total >= opt.max_inner) break;
         restarts += 1;   // breakdown (rho or omega vanished): restart from the current iterate
     }
     st.inner_iterations += (converged && poll_iters) ? poll_iters : it_total;
-    flush_pending();
+    lsq.flush();
     if (refine()) refine_solution();
+    finish_outer(st);
+    return converged ? 0 : 1;
+}
 
-    // residual + copy-back (smooth.zig:112-153); X becomes the new frozen field
+// The start of every outer iteration: system.fill(n) runs control_function.update for n > 0 (smooth.zig:1107-1110); the ghost rows of X
+void Smoother::begin_outer() {
+    if (white && outer_done > 0) white_launch(1);
+    if (reference()) return;   // single-process handles only: no ghost rows
+    exchange(X);
+    exchange_finish();
+}
+
+// ... and its end: residual + copy-back (smooth.zig:112-153); X becomes the new frozen field
+void Smoother::finish_outer(tm_stats& st) {
     HIPCHK(launch_residual_copyback(X, U, n_owned, nwg_vec, partials, stream));
     reduce(nwg_vec);
     HIPCHK(hipMemcpyAsync(h_red, red, sizeof(double) * MAX_PARTIALS, hipMemcpyDeviceToHost, stream));
@@ -1348,7 +1271,12 @@ int Smoother::picard_bicgstab(tm_stats& st) {
     st.last_dy2 = h_red[1];
     st.last_residual = (h_red[0] + h_red[1]) * (h_red[0] + h_red[1]);   // smooth.zig:136
     outer_done += 1;
-    return converged ? 0 : 1;
+}
+
+bool Smoother::gmres_poll() {
+    HIPCHK(hipMemcpyAsync(h_gm, gm_S, sizeof(GmresScalars), hipMemcpyDeviceToHost, stream));
+    sync();
+    return h_gm->done[0] == 1 && h_gm->done[1] == 1;
 }
 
 // Picard outer iteration with GMRES(30) as the inner solver (GMRES.zig:300-423 restated on the device, csrc/tm_gmres.hip): left
@@ -1356,82 +1284,36 @@ int Smoother::picard_bicgstab(tm_stats& st) {
 // rotations and the triangular solve by one-thread kernels on device-resident state, both components together.  Returns like
 // picard_bicgstab: 0 converged, 1 not converged (a warning, GMRES.zig:422), 2 stop_tol already met.
 int Smoother::picard_gmres(tm_stats& st) {
-    if (white && outer_done > 0) white_launch(1);   // system.fill(n): control_function.update for n > 0 (smooth.zig:1107-1110)
-    exchange(X);
-    exchange_finish();
+    begin_outer();
     HIPCHK(launch_edge_rhs(edge, X, PQ, nullptr, 1, partials, stream));   // ||D^-1 b||^2 -> the tolerance
     reduce(edge.nwg);
     HIPCHK(launch_gm_tol(gm_S, red, (opt.flags & TM_OPT_RTOL_INITIAL) ? -opt.rtol : opt.rtol, opt.atol, stream));
-    double2* const W = r;
-    const int64_t ld = n_local;
-    auto V = [&](int k) { return gm_V + static_cast<int64_t>(k) * ld; };
-    auto poll = [&]() {   // the flags of both components, after everything enqueued so far
-        HIPCHK(hipMemcpyAsync(h_gm, gm_S, sizeof(GmresScalars), hipMemcpyDeviceToHost, stream));
-        sync();
-        return h_gm->done[0] == 1 && h_gm->done[1] == 1;
+    const GmresSpace g = gmres_space();
+    auto apply_op = [&](const double2* vj, double2* w) {   // w = A v_j, z = D^-1 w (GMRES.zig:335-336)
+        apply(vj, w, MODE_SCALED, DOT_NONE, nullptr, X, 0.0, -1);
+        st.operator_sweeps += 1;
     };
     uint64_t it_total = 0;
     bool converged = false, first = true;
     while (it_total < opt.max_inner) {
         // z = D^-1 (b - A x), beta = ||z|| (GMRES.zig:312-319); the warm start is the current field (GMRES.zig:136-153 seeds x_new from the mesh)
-        apply(first ? X : U, W, MODE_RESID, DOT_OUT2, nullptr, X, 0.0, -1);
+        apply(first ? X : U, g.W, MODE_RESID, DOT_OUT2, nullptr, X, 0.0, -1);
         st.operator_sweeps += 1;
         HIPCHK(launch_gm_begin(gm_S, red, stream));
-        const bool all_done = poll();
+        converged = gmres_poll();
         if (first) {
             st.scaled_residual_rms = std::sqrt((h_gm->rr0[0] + h_gm->rr0[1]) / (2.0 * static_cast<double>(dof_global)));
             if (stop_tol > 0.0 && st.scaled_residual_rms <= stop_tol) return 2;
             HIPCHK(hipMemcpyAsync(U, X, sizeof(double2) * n_local, hipMemcpyDeviceToDevice, stream));
             first = false;
         }
-        if (all_done) {
-            converged = true;
-            break;
-        }
-        HIPCHK(launch_gm_divide(V(0), W, gm_S, n_owned, stream));   // v0 = z / beta
-        bool cycle_done = false;
-        for (int j = 0; j < GMRES_M && it_total < opt.max_inner; ++j) {
-            apply(V(j), W, MODE_SCALED, DOT_NONE, nullptr, X, 0.0, -1);   // w = A v_j, z = D^-1 w (GMRES.zig:335-336)
-            st.operator_sweeps += 1;
-            // modified Gram-Schmidt (GMRES.zig:338-345): h_ij = z . v_i, z -= h_ij v_i, i = 0 .. j -- the subtraction of step i - 1 and
-            // the inner product of step i in one pass each; then h_{j+1,j} = ||z|| behind the last subtraction
-            HIPCHK(launch_gm_mgs(W, nullptr, V(0), nullptr, gm_S, 0, n_owned, partials, stream));
-            reduce(nwg_vec);
-            for (int i = 1; i <= j; ++i) {
-                HIPCHK(launch_gm_mgs(W, V(i - 1), V(i), red, gm_S, i - 1, n_owned, partials, stream));
-                reduce(nwg_vec);
-            }
-            HIPCHK(launch_gm_mgs(W, V(j), nullptr, red, gm_S, j, n_owned, partials, stream));
-            reduce(nwg_vec);
-            HIPCHK(launch_gm_column(gm_S, red, stream));                      // rotations, g, |g_{j+1}|, flags (GMRES.zig:347-386)
-            if (j + 1 < GMRES_M + 1) HIPCHK(launch_gm_divide(V(j + 1), W, gm_S, n_owned, stream));   // v_{j+1} = z / h_next unless h_next <= 1e-30
-            it_total += 1;
-            if ((j + 1) % static_cast<int>(opt.check_every) == 0 || j + 1 == GMRES_M || it_total == opt.max_inner) {
-                if (poll()) {
-                    cycle_done = true;
-                    break;
-                }
-            }
-        }
-        HIPCHK(launch_gm_backsub(gm_S, stream));                              // GMRES.zig:394-409
-        HIPCHK(launch_gm_update(U, gm_V, ld, gm_S, n_owned, stream));          // x += V y, GMRES.zig:411-417
-        if (cycle_done) {
-            converged = true;
-            break;
-        }
+        if (converged) break;
+        converged = gmres_cycle(g, U, apply_op, [&] { reduce(nwg_vec); }, [&] { return gmres_poll(); }, opt.check_every, it_total, opt.max_inner);
+        if (converged) break;
     }
     st.inner_iterations += it_total;
     if (refine()) refine_solution();
-
-    // residual + copy-back (smooth.zig:112-153); X becomes the new frozen field
-    HIPCHK(launch_residual_copyback(X, U, n_owned, nwg_vec, partials, stream));
-    reduce(nwg_vec);
-    HIPCHK(hipMemcpyAsync(h_red, red, sizeof(double) * MAX_PARTIALS, hipMemcpyDeviceToHost, stream));
-    sync();
-    st.last_dx2 = h_red[0];
-    st.last_dy2 = h_red[1];
-    st.last_residual = (h_red[0] + h_red[1]) * (h_red[0] + h_red[1]);   // smooth.zig:136
-    outer_done += 1;
+    finish_outer(st);
     return converged ? 0 : 1;
 }
 
@@ -1479,33 +1361,19 @@ uint64_t Smoother::correct_bicgstab(const double2* rhs, double2* d) {
     HIPCHK(hipMemsetAsync(p, 0, sizeof(double2) * n_local, stream));
     HIPCHK(hipMemsetAsync(v, 0, sizeof(double2) * n_local, stream));
     HIPCHK(launch_csr_norm2(n, rhs, partials, stream));
-    reduce_update(csr_nwg(n), STEP_TOL, refine_rtol, opt.atol);   // tol = max(atol, rtol ||rhs||) ...
-    reduce_update(csr_nwg(n), STEP_INIT);                      // ... and ||r0||^2 from the same sums
-    flush_pending();   // (a launch of its own: a lazy step would have every workgroup of the next kernel sum these 256-row partials)
+    lsq.reduce_update(csr_nwg(n), STEP_TOL, refine_rtol, opt.atol);   // tol = max(atol, rtol ||rhs||) ...
+    lsq.reduce_update(csr_nwg(n), STEP_INIT);                      // ... and ||r0||^2 from the same sums
+    lsq.flush();   // (a launch of its own: a lazy step would have every workgroup of the next kernel sum these 256-row partials)
     poll_iters = 0;
     poll_open = false;
-    stall_best[0] = stall_best[1] = 0.0;
-    stall_since = 0;
-    stalled = false;
+    stall.reset();
+    const BicgVectors w = bicg_vectors();
+    auto precond = [&](const double2* in, double2* out) { precondition(in, out); };
+    auto apply_op = [&](const double2* in, double2* out, int dot, const double2* aux, int step) { apply(in, out, MODE_SCALED, dot, aux, X, 0.0, step); };
     uint64_t it = 0;
     while (it < opt.max_inner) {
-        HIPCHK(launch_p_update(scalars_for(), r, p, v, n_owned, nwg_vec, stream));
-        if (use_mg) {
-            precondition(p, p_hat);
-            apply(p_hat, v, MODE_SCALED, DOT_AUX, r_hat, X, 0.0, STEP_SIGMA);
-        } else {
-            apply(p, v, MODE_SCALED, DOT_AUX, r_hat, X, 0.0, STEP_SIGMA);
-        }
-        HIPCHK(launch_s_update(scalars_for(), r, v, s, n_owned, nwg_vec, partials, stream));
-        reduce_update(nwg_vec, STEP_SS);
-        if (use_mg) {
-            precondition(s, s_hat);
-            apply(s_hat, t, MODE_SCALED, DOT_AUX2, s, X, 0.0, STEP_TSTT);
-        } else {
-            apply(s, t, MODE_SCALED, DOT_IN, nullptr, X, 0.0, STEP_TSTT);
-        }
-        HIPCHK(launch_xr_update(scalars_for(), d, use_mg ? p_hat : p, use_mg ? s_hat : s, s, t, r, r_hat, n_owned, nwg_vec, partials, stream));
-        reduce_update(nwg_vec, STEP_RHO);
+        bicgstab_direction(lsq, w, precond, apply_op);
+        bicgstab_correction(lsq, w, d, precond, apply_op);
         it += 1;
         if (it % opt.check_every == 0 || it == opt.max_inner) {
             const int verdict = poll_done(it, it == opt.max_inner);
@@ -1515,21 +1383,16 @@ uint64_t Smoother::correct_bicgstab(const double2* rhs, double2* d) {
             }
         }
     }
-    flush_pending();
+    lsq.flush();
     return it;
 }
 
 // the same by GMRES(30) as picard_gmres runs it: left-preconditioned with the diagonal, the restart residual rhs - D^-1 A d
 uint64_t Smoother::correct_gmres(const double2* rhs, double2* d) {
     const int n = static_cast<int>(n_owned);
-    double2* const W = r;
-    const int64_t ld = n_local;
-    auto V = [&](int k) { return gm_V + static_cast<int64_t>(k) * ld; };
-    auto poll = [&]() {
-        HIPCHK(hipMemcpyAsync(h_gm, gm_S, sizeof(GmresScalars), hipMemcpyDeviceToHost, stream));
-        sync();
-        return h_gm->done[0] == 1 && h_gm->done[1] == 1;
-    };
+    const GmresSpace g = gmres_space();
+    double2* const W = g.W;
+    auto apply_op = [&](const double2* vj, double2* w) { apply(vj, w, MODE_SCALED, DOT_NONE, nullptr, X, 0.0, -1); };   // (a correction counts no sweeps)
     HIPCHK(launch_csr_norm2(n, rhs, partials, stream));
     reduce(csr_nwg(n));
     HIPCHK(launch_gm_tol(gm_S, red, refine_rtol, opt.atol, stream));
@@ -1546,32 +1409,8 @@ uint64_t Smoother::correct_gmres(const double2* rhs, double2* d) {
         HIPCHK(launch_csr_norm2(n, W, partials, stream));
         reduce(csr_nwg(n));
         HIPCHK(launch_gm_begin(gm_S, red, stream));
-        if (poll()) break;
-        HIPCHK(launch_gm_divide(V(0), W, gm_S, n_owned, stream));
-        bool cycle_done = false;
-        for (int j = 0; j < GMRES_M && it < opt.max_inner; ++j) {
-            apply(V(j), W, MODE_SCALED, DOT_NONE, nullptr, X, 0.0, -1);
-            HIPCHK(launch_gm_mgs(W, nullptr, V(0), nullptr, gm_S, 0, n_owned, partials, stream));
-            reduce(nwg_vec);
-            for (int i = 1; i <= j; ++i) {
-                HIPCHK(launch_gm_mgs(W, V(i - 1), V(i), red, gm_S, i - 1, n_owned, partials, stream));
-                reduce(nwg_vec);
-            }
-            HIPCHK(launch_gm_mgs(W, V(j), nullptr, red, gm_S, j, n_owned, partials, stream));
-            reduce(nwg_vec);
-            HIPCHK(launch_gm_column(gm_S, red, stream));
-            HIPCHK(launch_gm_divide(V(j + 1), W, gm_S, n_owned, stream));
-            it += 1;
-            if ((j + 1) % static_cast<int>(opt.check_every) == 0 || j + 1 == GMRES_M || it == opt.max_inner) {
-                if (poll()) {
-                    cycle_done = true;
-                    break;
-                }
-            }
-        }
-        HIPCHK(launch_gm_backsub(gm_S, stream));
-        HIPCHK(launch_gm_update(d, gm_V, ld, gm_S, n_owned, stream));
-        if (cycle_done) break;
+        if (gmres_poll()) break;
+        if (gmres_cycle(g, d, apply_op, [&] { reduce(nwg_vec); }, [&] { return gmres_poll(); }, opt.check_every, it, opt.max_inner)) break;
     }
     return it;
 }
@@ -1599,13 +1438,14 @@ void Smoother::reference_create() {
 // (sticky, k_gm_begin) while the other goes on, so each sees the cycles and columns the reference's separate solves give it.  What differs
 // from the reference is the summation order of the dot products and norms.  Returns like picard_gmres.
 int Smoother::picard_reference(tm_stats& st) {
-    if (white && outer_done > 0) white_launch(1);   // system.fill(n): control_function.update for n > 0 (smooth.zig:1107-1110)
+    begin_outer();
     const int n = static_cast<int>(n_owned);
     const int nwg = csr_nwg(n);
     csr_fill_values();
     HIPCHK(hipMemsetAsync(ref_b, 0, sizeof(double2) * n_local, stream));   // interior rows have b = 0
     HIPCHK(launch_edge_rhs(edge, X, PQ, ref_b, 0, nullptr, stream));
-    double2* const W = r;
+    const GmresSpace g = gmres_space();
+    double2* const W = g.W;
     double* const part = ref->part.as<double>();
     double2* const dinv = ref->dinv.as<double2>();
     // stats.scaled_residual_rms keeps its meaning: D^-1 (b - A x) of this iteration's system at its start
@@ -1620,16 +1460,14 @@ int Smoother::picard_reference(tm_stats& st) {
     HIPCHK(launch_csr_norm2(n, ref_b, part, stream));   // tol = max(atol, rtol ||b||), GMRES.zig:305-306
     HIPCHK(launch_finalize(part, nwg, red, stream));
     HIPCHK(launch_gm_tol(gm_S, red, opt.rtol, opt.atol, stream, 1));
-    const int64_t ld = n_local;
-    auto V = [&](int k) { return gm_V + static_cast<int64_t>(k) * ld; };
     auto precondition_W = [&]() {   // z = M^-1 r, in place
         if (ref->ilu) ref->ilu->apply(W, W, stream, false);
         else HIPCHK(launch_csr_diag_precond(n, dinv, W, W, stream));
     };
-    auto poll = [&]() {
-        HIPCHK(hipMemcpyAsync(h_gm, gm_S, sizeof(GmresScalars), hipMemcpyDeviceToHost, stream));
-        sync();
-        return h_gm->done[0] == 1 && h_gm->done[1] == 1;
+    auto apply_op = [&](const double2* vj, double2* w) {
+        HIPCHK(launch_csr_product(n_owned, csr.p, csr.i, csr.vx, csr.vy, vj, w, stream));   // w = A v_j
+        precondition_W();                                                                   // z = M^-1 w (GMRES.zig:339-340)
+        st.operator_sweeps += 1;
     };
     uint64_t it_total = 0;
     bool converged = false, first = true;
@@ -1641,45 +1479,14 @@ int Smoother::picard_reference(tm_stats& st) {
         HIPCHK(launch_csr_norm2(n, W, part, stream));
         HIPCHK(launch_finalize(part, nwg, red, stream));
         HIPCHK(launch_gm_begin(gm_S, red, stream));   // beta = ||z||; if (beta <= tol) return
-        const bool all_done = poll();
+        converged = gmres_poll();
         if (first) {
             HIPCHK(hipMemcpyAsync(U, X, sizeof(double2) * n_local, hipMemcpyDeviceToDevice, stream));
             first = false;
         }
-        if (all_done) {
-            converged = true;
-            break;
-        }
-        HIPCHK(launch_gm_divide(V(0), W, gm_S, n_owned, stream));   // v0 = z / beta
-        bool cycle_done = false;
-        for (int j = 0; j < GMRES_M && it_total < opt.max_inner; ++j) {
-            HIPCHK(launch_csr_product(n_owned, csr.p, csr.i, csr.vx, csr.vy, V(j), W, stream));   // w = A v_j
-            precondition_W();                                                                     // z = M^-1 w (GMRES.zig:339-340)
-            st.operator_sweeps += 1;
-            HIPCHK(launch_gm_mgs(W, nullptr, V(0), nullptr, gm_S, 0, n_owned, partials, stream));
-            reduce(nwg_vec);
-            for (int i = 1; i <= j; ++i) {
-                HIPCHK(launch_gm_mgs(W, V(i - 1), V(i), red, gm_S, i - 1, n_owned, partials, stream));
-                reduce(nwg_vec);
-            }
-            HIPCHK(launch_gm_mgs(W, V(j), nullptr, red, gm_S, j, n_owned, partials, stream));
-            reduce(nwg_vec);
-            HIPCHK(launch_gm_column(gm_S, red, stream));
-            HIPCHK(launch_gm_divide(V(j + 1), W, gm_S, n_owned, stream));
-            it_total += 1;
-            if ((j + 1) % static_cast<int>(opt.check_every) == 0 || j + 1 == GMRES_M || it_total == opt.max_inner) {
-                if (poll()) {
-                    cycle_done = true;
-                    break;
-                }
-            }
-        }
-        HIPCHK(launch_gm_backsub(gm_S, stream));
-        HIPCHK(launch_gm_update(U, gm_V, ld, gm_S, n_owned, stream));
-        if (cycle_done) {
-            converged = true;
-            break;
-        }
+        if (converged) break;
+        converged = gmres_cycle(g, U, apply_op, [&] { reduce(nwg_vec); }, [&] { return gmres_poll(); }, opt.check_every, it_total, opt.max_inner);
+        if (converged) break;
     }
     // the counts of the two solves (solver.zig:69-78): a component's columns, wherever the other one stopped
     HIPCHK(hipMemcpyAsync(h_gm, gm_S, sizeof(GmresScalars), hipMemcpyDeviceToHost, stream));
@@ -1687,16 +1494,7 @@ int Smoother::picard_reference(tm_stats& st) {
     inner_counts[0] = static_cast<uint64_t>(h_gm->iters[0]);
     inner_counts[1] = static_cast<uint64_t>(h_gm->iters[1]);
     st.inner_iterations += inner_counts[0] + inner_counts[1];
-
-    // residual + copy-back (smooth.zig:112-153); X becomes the new frozen field
-    HIPCHK(launch_residual_copyback(X, U, n_owned, nwg_vec, partials, stream));
-    reduce(nwg_vec);
-    HIPCHK(hipMemcpyAsync(h_red, red, sizeof(double) * MAX_PARTIALS, hipMemcpyDeviceToHost, stream));
-    sync();
-    st.last_dx2 = h_red[0];
-    st.last_dy2 = h_red[1];
-    st.last_residual = (h_red[0] + h_red[1]) * (h_red[0] + h_red[1]);   // smooth.zig:136
-    outer_done += 1;
+    finish_outer(st);
     return converged ? 0 : 1;
 }
 

@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include "tm_edge_tables.hpp"
 #include "tm_kernels.h"
+#include "tm_krylov.hpp"
 #include "tm_multigrid.hpp"
 #include "tm_plan.hpp"
 #include <cmath>
@@ -104,10 +105,11 @@ struct Smoother {
     std::vector<const int32_t*> border_ids;   // per owned block: device list of the K2x2 border tiles
     std::vector<int> border_n;
     void prefill_fixed();   // perimeter of X -> perimeter of U and M
-    // reductions
-    double* partials = nullptr;
-    double* red = nullptr;
-    KrylovScalars* S = nullptr;
+    // reductions: the partial-sum buffers, their sums and the Krylov scalar block live in the lazy scalar queue (tm_krylov.hpp)
+    LazyScalarQueue lsq;
+    double*& partials = lsq.partials;
+    double*& red = lsq.red;
+    KrylovScalars*& S = lsq.S;
     KrylovScalars* h_S = nullptr;   // pinned
     // pipelined convergence poll (poll_done): two pinned copies of the scalar block in flight alternately
     bool pipelined_poll = false, poll_open = false;
@@ -116,9 +118,7 @@ struct Smoother {
     uint64_t poll_it[2] = {0, 0}, poll_iters = 0;
     int poll_slot = 0;
     int poll_done(uint64_t it, bool final);
-    double stall_best[2] = {0.0, 0.0};   // stagnation watch of the inner solve (poll_done): best ||r||^2 per component, iteration of the last halving
-    uint64_t stall_since = 0, stall_window = 4000;
-    bool stalled = false;
+    StallWatch stall;   // stagnation watch of the inner solve (poll_done)
     double* h_red = nullptr;        // pinned
     // the two-kernel Krylov iteration of a large mesh runs its kernels on overlapping 62-column strips (apply_tile<.., OV>): their own
     // partial-row layout (more strips per block than the 64-column tiling)
@@ -234,8 +234,6 @@ struct Smoother {
     // step >= 0: the Krylov scalar update that consumes the fused dot products follows the reduction (one launch without hooks)
     void apply(const double2* in, double2* out, int mode, int dot, const double2* aux, const double2* xk, double omega, int step = -1);
     void reduce(int nwg);   // partials -> red (+ all-reduce)
-    void reduce_update(int nwg, int step, double rtol = 0.0, double atol = 0.0);   // reduce + Krylov scalar update
-    // lazy scalar steps (small single-process meshes): see LazyScalars in tm_kernels.h
     int apply_rows = 0;             // K2 rows per chunk of this handle (0 = per-block rule)
     bool fuse_s = false;            // k_apply_vk<VK_S> / k_xr_update_vs instead of k_s_update + apply + k_xr_update
     bool fuse_p = false;            // k_apply_vk<VK_P> instead of k_p_update + apply; p and v alternate with p_alt, v_alt
@@ -243,20 +241,12 @@ struct Smoother {
     double2 *p_alt = nullptr, *v_alt = nullptr, *r_alt = nullptr;
     void apply_virtual(int kind, const double2* in, const double2* in2, const double2* in3, double2* pout, double2* out, const double2* in4 = nullptr,
                        double2* rout = nullptr, double2* uio = nullptr);
-    bool lazy = false;
-    double* part_buf[3] = {nullptr, nullptr, nullptr};
-    // TM_PARTIALS_GUARD (see alloc_reductions): a guard region behind part_buf[0..2] and behind red, compared by check_guards
+    // TM_PARTIALS_GUARD (see alloc_reductions): a guard region behind lsq.part_buf[0..2] and behind red, compared by check_guards
     static constexpr uint64_t GUARD_DOUBLES = 2048 * MAX_PARTIALS;
     static constexpr int GUARD_BYTE = 0xA5;
     bool partials_guard = false;
     double* guard[4] = {nullptr, nullptr, nullptr, nullptr};
     void check_guards();
-    int part_rot = 0;
-    KrylovScalars* S_buf[2] = {nullptr, nullptr};
-    LazyStep pending[2];
-    int npending = 0;
-    void flush_pending();
-    LazyScalars scalars_for();
     void white_launch(int update);
     void sync();
     void ensure_tmp();
@@ -301,6 +291,11 @@ struct Smoother {
     int picard_bicgstab(tm_stats& st);
     int picard_gmres(tm_stats& st);
     int picard_reference(tm_stats& st);
+    void begin_outer();                 // what every picard_* starts with: the control function's update, the exchange of X
+    void finish_outer(tm_stats& st);    // ... and ends with: residual and copy-back, X becomes the new frozen field
+    BicgVectors bicg_vectors() { return {r, p, v, s, t, use_mg ? p_hat : p, use_mg ? s_hat : s, r_hat, n_owned, nwg_vec}; }
+    GmresSpace gmres_space() { return {gm_S, gm_V, n_local, r, n_owned, partials, red, stream}; }
+    bool gmres_poll();                  // the flags of both components, after everything enqueued so far
     void refine_solution();
     uint64_t correct_bicgstab(const double2* rhs, double2* d);
     uint64_t correct_gmres(const double2* rhs, double2* d);
