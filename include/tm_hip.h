@@ -527,6 +527,70 @@ int tm_stack_block_host(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt
 int tm_stack_smoothers(tm_smoother* const* cuts, const tm_stack_opt* opt, uint64_t block, uint64_t k_begin, uint64_t k_count,
                        double* x, double* y, double* z);
 
+/* ------------------------------------------------------------------ 3-D quality of stacked blocks
+ * Is the stacked mesh usable?  The 2-D report above sees each cut alone; cuts that are clean in 2-D can still enclose negative hexahedra
+ * between layers (twist, lean, a spline overshooting between unevenly spaced cuts, a cylindrical wrap of cuts of different pitch, layers
+ * given out of order).  A stacked block with nk layers, in the order the caller gave them, has cells (i, j, k), 0 <= i < ni-1,
+ * 0 <= j < nj-1, 0 <= k < nk-1.  Corner (a, b, c), each in {0, 1}, is node (i+a, j+b, k+c); x0 .. x7 below number the corners a + 2b + 4c.
+ * All arithmetic IEEE fp64, nothing fused, divisions and square roots correctly rounded, sums in the order written.
+ *   nodes        exactly what tm_stack_block returns for the layer: the same weight table, the same sum over the cuts c = 0 .. K-1, the
+ *                same theta_c = y_c / z[c] and sincos of the cylindrical mapping.  The device report sees bit for bit what K11 writes.
+ *   edge         d = upper node - lower node; l2 = d.x*d.x + d.y*d.y + d.z*d.z (left to right), l = sqrt(l2).  One value per edge,
+ *                whichever cell asks ((q-p)^2 == (p-q)^2 bit for bit).
+ *   corner       u, v, w: the edges leaving the corner along i, j, k, multiplied by (1-2a), (1-2b), (1-2c), so that all eight corners
+ *                measure the same handedness (that product IS the edge's d: subtraction is antisymmetric, negation exact).
+ *                J = u.x*(v.y*w.z - v.z*w.y) + u.y*(v.z*w.x - v.x*w.z) + u.z*(v.x*w.y - v.y*w.x);  s = J / ((lu*lv)*lw)
+ *   cell volume  the exact volume of the trilinear hexahedron, det[p,q,r] = p.(q x r) expanded as J:
+ *                12 V = (det[(x7-x1)+(x6-x0), x7-x2, x3-x0] + det[x6-x0, (x7-x2)+(x5-x0), x7-x4]) + det[x7-x1, x5-x0, (x7-x4)+(x3-x0)]
+ *                and V = that sum / 12.  (The "long diagonal" 1/6 formula is not exact for warped faces and is not used.)
+ *   orientation  o = sign(sum V) over the block's cells; 0 when |sum V| <= cells * 2^-53 * sum |V|, and then everything is reported as
+ *                for +1 (the 2-D rule)
+ *   classes      degenerate: a corner with (lu*lv)*lw == 0 or non-finite, or a non-finite J;  else inverted: min over corners of
+ *                o*J <= 0;  else valid
+ *   min_scaled_jacobian   min of o*s over the corners of non-degenerate cells, (worst_block, worst_i, worst_j, worst_k) its cell, ties
+ *                to the lowest (block, k, j, i); NaN and 0, 0, 0, 0 when every cell is degenerate
+ *   hist[k]      valid cells by their min o*s, the bins of the 2-D report; sum hist == cells - inverted - degenerate
+ *   max_aspect   max over non-degenerate cells of max(Li, Lj, Lk) / min(Li, Lj, Lk), L* the sum of the cell's four edges of that
+ *                direction added in corner order: Li = ((|x0x1| + |x2x3|) + |x4x5|) + |x6x7|, Lj = ((|x0x2| + |x1x3|) + |x4x6|) + |x5x7|,
+ *                Lk = ((|x0x4| + |x1x5|) + |x2x6|) + |x3x7|
+ *   max_growth_k max of max(l0, l1) / min(l0, l1) over pairs of consecutive k-edges along every spanwise grid line, pairs with a
+ *                zero-length edge skipped; 1.0 when nk < 3.  Growth along i and j inside a layer stays the 2-D report's subject
+ *                (tm_smoother_quality on the cuts); growth across block connections is not reported
+ *   volumes      min_volume / max_volume: o*V over non-degenerate cells; total_volume = o * sum V
+ * tm_quality3d_total: counts and hist summed, extremes combined, total_volume summed, the worst cell the one with the smallest value,
+ * orientation the blocks' common one or 0; records with cells == 0 are left out.  Host only. */
+typedef struct tm_quality3d {            /* 192 bytes */
+    uint64_t cells, inverted, degenerate;
+    int32_t  orientation, _pad;
+    double   min_scaled_jacobian;
+    uint64_t worst_block, worst_i, worst_j, worst_k;
+    double   max_aspect, max_growth_k;
+    double   min_volume, max_volume, total_volume;
+    uint64_t hist[10];
+} tm_quality3d;
+
+/* Any 3-D block in PLOT3D order (planes x, y, z of nk*nj*ni doubles, i fastest: what tm_stack_block returned, or a file read back).
+ * No GPU touched.  `block` only labels the record.  field, when given, receives the per-cell min of o*s (NaN for degenerate cells),
+ * element (k*(nj-1) + j)*(ni-1) + i.  ni, nj or nk < 2: TM_E_SIZE.  NULL x, y, z or out: TM_E_ARG. */
+int tm_quality3d_planes_host(const double* x, const double* y, const double* z, uint64_t ni, uint64_t nj, uint64_t nk,
+                             uint64_t block, tm_quality3d* out, double* field /* may be NULL: (nk-1)*(nj-1)*(ni-1), i fastest */);
+/* Block `block` of the stack of K meshes given on the host, all layers of `opt`, evaluated on the device (kernel K12) straight from
+ * the K cuts: the 3-D block is never stored.  Every field equals tm_quality3d_planes_host of the planes tm_stack_block returns, bit
+ * for bit, but total_volume (a sum: equal within cells * 2^-53 * sum |V|).  Errors as tm_stack_block; in addition nlayers < 2 or a
+ * block with ni < 2 or nj < 2 (no cells): TM_E_SIZE. */
+int tm_stack_quality(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt, uint64_t block, tm_quality3d* out);
+/* tm_stack_block_host followed by tm_quality3d_planes_host, two layers held at a time; no GPU touched */
+int tm_stack_quality_host(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt, uint64_t block, tm_quality3d* out);
+/* The same kernel on the coordinates RESIDENT in K handles.  Ordered behind the pending work of every handle exactly as
+ * tm_stack_smoothers is; modifies no handle; nothing but the record crosses to the host.  Errors as tm_stack_smoothers, plus the
+ * TM_E_SIZE cases above.  Bit-identical to tm_stack_quality on the downloaded coordinates. */
+int tm_stack_smoothers_quality(tm_smoother* const* cuts, const tm_stack_opt* opt, uint64_t block, tm_quality3d* out);
+/* per-cell min of o*s (NaN for degenerate cells) of the cell layers [k_begin, k_begin + k_count), element
+ * ((k-k_begin)*(nj-1) + j)*(ni-1) + i; runs the report first to learn o.  A window that is empty or reaches past nlayers-1: TM_E_ARG. */
+int tm_stack_smoothers_quality_field(tm_smoother* const* cuts, const tm_stack_opt* opt, uint64_t block,
+                                     uint64_t k_begin, uint64_t k_count /* cell layers */, double* min_scaled_jacobian);
+int tm_quality3d_total(const tm_quality3d* per_block, uint64_t n, tm_quality3d* total);
+
 /* ------------------------------------------------------------------ host-only planning (no GPU needed)
  * The perimeter-row table the device kernels consume, exported as CSR so it can be compared with
  * the reference's assembled rows (smooth.zig:421-921).  Only sizes/topology are read from `mesh`

@@ -12,7 +12,8 @@ diagonal on the assembled system, the reference's tolerances -- the iterates a r
 
 --stack CFG2 [CFG3 ...] --span z0,z1,... --layers NK: `config` and the further files are the spanwise cuts of one blade.  Every file runs the
 path above with its own handle; the smoothed cuts are stacked into 3-D blocks on the device (stack.py, include/tm_hip.h "3-D from 2-D cuts")
-and --output becomes a multi-block 3-D PLOT3D file.  Without --stack the program is what it was."""
+and --output becomes a multi-block 3-D PLOT3D file; --stack-quality / --fail-on-inverted-3d report on the hexahedra of that mesh
+(include/tm_hip.h "3-D quality of stacked blocks").  Without --stack the program is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -125,12 +126,22 @@ def _main_stack(ap, args):
             if after is not None and not after[1].ok and worst is None:
                 worst = (c, after[1])
         m3 = st.mesh3d(handles)
+        q3 = st.quality(handles) if (args.stack_quality or args.fail_on_inverted_3d) else None   # from the resident cuts: no 3-D block is formed
     m3.write(args.output)
     logging.getLogger("output").info("wrote %s (%d blocks, %d cuts, %d layers, %d nodes)", args.output, len(m3.blocks), len(files), st.nlayers,
                                      sum(x.size for x, _, _ in m3.blocks))
+    if q3 is not None and args.stack_quality:
+        quality.log_report_3d(logging.getLogger("quality"), m3.names, *q3)
     if args.fail_on_inverted and worst is not None:
         sys.exit(f"mesh quality: cut {worst[0]} has {worst[1].inverted} inverted and {worst[1].degenerate} degenerate cells after smoothing")
-    return {"cuts": all_stats, "blocks": len(m3.blocks), "layers": st.nlayers}
+    if args.fail_on_inverted_3d and not q3[1].ok:
+        b, bad = next((b, q) for b, q in enumerate(q3[0]) if not q.ok)
+        sys.exit(f"mesh quality: the stacked mesh has {q3[1].inverted} inverted and {q3[1].degenerate} degenerate hexahedra "
+                 f"(block {b}: {bad.inverted} inverted, {bad.degenerate} degenerate, worst cell i {bad.worst_i}, j {bad.worst_j}, k {bad.worst_k})")
+    out = {"cuts": all_stats, "blocks": len(m3.blocks), "layers": st.nlayers}
+    if q3 is not None:
+        out["quality3d"] = {"per_block": q3[0], "total": q3[1]}
+    return out
 
 
 def main(argv=None):
@@ -165,9 +176,17 @@ def main(argv=None):
     ap.add_argument("--stack-interpolation", default="cubic", choices=["linear", "cubic"], help="between the cuts: linear, or the natural cubic spline")
     ap.add_argument("--stack-mapping", default="planar", choices=["planar", "cylindrical"],
                     help="planar: (x, y, s); cylindrical: the cuts are unrolled cylinders (x, r theta) at radius span, output (x, r sin theta, r cos theta)")
+    ap.add_argument("--stack-quality", action="store_true",
+                    help="with --stack: log the 3-D quality report of the stacked blocks (`quality` logger: one line per block and a total) -- "
+                         "negative and degenerate hexahedra across layers, which --quality (every cut alone) cannot see")
+    ap.add_argument("--fail-on-inverted-3d", action="store_true",
+                    help="with --stack: exit non-zero, after the file is written, when the stacked mesh has inverted or degenerate hexahedra "
+                         "(implies the 3-D quality evaluation)")
     args = ap.parse_args(argv)
     if args.stack is None and (args.span or args.layers is not None):
         ap.error("--span and --layers go with --stack")
+    if args.stack is None and (args.stack_quality or args.fail_on_inverted_3d):
+        ap.error("--stack-quality and --fail-on-inverted-3d go with --stack")
     if args.stack is not None:
         if not args.span or args.layers is None:
             ap.error("--stack needs --span z0,z1,... and --layers NK")

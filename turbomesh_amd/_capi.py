@@ -131,6 +131,13 @@ class tm_quality(C.Structure):
                 ("hist", C.c_uint64 * 10)]
 
 
+class tm_quality3d(C.Structure):
+    _fields_ = [("cells", C.c_uint64), ("inverted", C.c_uint64), ("degenerate", C.c_uint64), ("orientation", C.c_int32), ("_pad", C.c_int32),
+                ("min_scaled_jacobian", C.c_double), ("worst_block", C.c_uint64), ("worst_i", C.c_uint64), ("worst_j", C.c_uint64),
+                ("worst_k", C.c_uint64), ("max_aspect", C.c_double), ("max_growth_k", C.c_double), ("min_volume", C.c_double),
+                ("max_volume", C.c_double), ("total_volume", C.c_double), ("hist", C.c_uint64 * 10)]
+
+
 class tm_stack_opt(C.Structure):
     _fields_ = [("ncuts", C.c_uint64), ("span", C.POINTER(C.c_double)), ("nlayers", C.c_uint64), ("layers", C.POINTER(C.c_double)),
                 ("interpolation", C.c_int32), ("mapping", C.c_int32)]
@@ -148,6 +155,8 @@ EXPORTS = [
     "tm_csr_residual", "tm_smoother_residual", "tm_smoother_refine_report",
     "tm_smoother_set_control_function", "tm_smoother_update_control_function",
     "tm_stack_weights", "tm_stack_block", "tm_stack_block_host", "tm_stack_smoothers",
+    "tm_quality3d_planes_host", "tm_stack_quality", "tm_stack_quality_host", "tm_stack_smoothers_quality", "tm_stack_smoothers_quality_field",
+    "tm_quality3d_total",
     "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
 ]
 
@@ -241,7 +250,13 @@ def lib():
         L.tm_stack_block.argtypes = [C.POINTER(C.POINTER(tm_mesh_desc)), C.POINTER(tm_stack_opt), C.c_uint64, C.c_uint64, C.c_uint64, _dp, _dp, _dp]
         L.tm_stack_block_host.argtypes = L.tm_stack_block.argtypes
         L.tm_stack_smoothers.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt), C.c_uint64, C.c_uint64, C.c_uint64, _dp, _dp, _dp]
-        L.tm_rccl_unique_id.argtypes = [C.c_char_p, C.c_void_p]
+        L.tm_quality3d_planes_host.argtypes = [_dp, _dp, _dp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(tm_quality3d), _dp]
+        L.tm_stack_quality.argtypes = [C.POINTER(C.POINTER(tm_mesh_desc)), C.POINTER(tm_stack_opt), C.c_uint64, C.POINTER(tm_quality3d)]
+        L.tm_stack_quality_host.argtypes = L.tm_stack_quality.argtypes
+        L.tm_stack_smoothers_quality.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt), C.c_uint64, C.POINTER(tm_quality3d)]
+        L.tm_stack_smoothers_quality_field.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt), C.c_uint64, C.c_uint64, C.c_uint64, _dp]
+        L.tm_quality3d_total.argtypes = [C.POINTER(tm_quality3d), C.c_uint64, C.POINTER(tm_quality3d)]
+        L.tm_rccl_unique_id.argtypes =[C.c_char_p, C.c_void_p]
         L.tm_rccl_comm_create.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.tm_rccl_comm_destroy.argtypes = [C.c_void_p]
         L.tm_rccl_comm_destroy.restype = None

@@ -12,19 +12,12 @@
 //
 // Traffic per node: 16 K bytes read, 24 k_count bytes written, each byte once: plain coalesced loads and stores, the three output
 // streams dominate.  Compiler's resource usage (cross-compile, -Rpass-analysis=kernel-resource-usage): see DESIGN.md section 4, K11.
-#include "tm_stack.hpp"
-#include "tm_api_util.hpp"
-#include "tm_smoother.hpp"
+#include "tm_stack_dev.hpp"
 
 #include <algorithm>
 #include <cstring>
 
 namespace tmh {
-
-struct StackCuts {
-    const double2* xy[TM_STACK_MAX_CUTS];   // the block in each cut, node (i,j) at i*nj + j
-    double radius[TM_STACK_MAX_CUTS];       // z[c] (cylindrical mapping)
-};
 
 constexpr int STACK_TILE = 32, STACK_THREADS = STACK_TILE * STACK_TILE;
 
@@ -101,36 +94,12 @@ static hipError_t launch_stack_planes(int K, const StackCuts& cuts, int mapping,
     return hipGetLastError();
 }
 
-namespace {
-struct StackBuf {   // RAII device buffer
-    void* p = nullptr;
-    explicit StackBuf(size_t bytes, const char* what) {
-        if (hipMalloc(&p, bytes ? bytes : 256) != hipSuccess) throw TmError(TM_E_MEMORY, std::string("hipMalloc failed (") + what + ")");
-    }
-    ~StackBuf() { (void)hipFree(p); }
-    StackBuf(const StackBuf&) = delete;
-    StackBuf& operator=(const StackBuf&) = delete;
-    template <class T>
-    T* as() { return static_cast<T*>(p); }
-};
-struct StackEvent {
-    hipEvent_t e = nullptr;
-    StackEvent() { HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
-    ~StackEvent() { (void)hipEventDestroy(e); }
-    StackEvent(const StackEvent&) = delete;
-    StackEvent& operator=(const StackEvent&) = delete;
-};
-}  // namespace
-
 // The window's table to the device, the kernel on `st`, the three planes back to the host; returns when they have arrived.
 static void stack_run(const StackPlan& p, StackCuts& cuts, uint64_t k_begin, uint64_t k_count, uint64_t ni, uint64_t nj, double* x, double* y, double* z,
                       hipStream_t st) {
     const int K = p.ncuts;
     if (k_count >= (uint64_t{1} << 31)) throw TmError(TM_E_SIZE, "layer window out of range");
-    for (int c = 0; c < TM_STACK_MAX_CUTS; ++c) {
-        cuts.radius[c] = c < K ? p.span[c] : 1.0;
-        if (c >= K) cuts.xy[c] = nullptr;
-    }
+    stack_fill_radii(p, cuts);
     std::vector<double> table(static_cast<size_t>(k_count) * (K + 1));
     for (uint64_t k = 0; k < k_count; ++k) {
         std::memcpy(&table[k * (K + 1)], &p.weights[(k_begin + k) * K], sizeof(double) * K);
@@ -147,13 +116,34 @@ static void stack_run(const StackPlan& p, StackCuts& cuts, uint64_t k_begin, uin
     HIPCHK(hipStreamSynchronize(st));   // `table` and the device buffers live until here
 }
 
-static void require_gfx950_stack() {
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, dev));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        throw TmError(TM_E_HIP, std::string("libtm_hip is built for gfx950 (MI355X) only, found ") + prop.gcnArchName);
+void stack_resident_cuts(tm_smoother* const* cuts, const StackPlan& p, uint64_t block, StackCuts& dc, uint64_t* ni, uint64_t* nj) {
+    for (int c = 0; c < p.ncuts; ++c)
+        if (!cuts[c] || !smoother_is_live(cuts[c])) throw TmError(TM_E_ARG, "a cut is not a live handle");
+    const Smoother& s0 = cuts[0]->impl;
+    for (int c = 1; c < p.ncuts; ++c)
+        if (cuts[c]->impl.topo.nblocks() != s0.topo.nblocks()) throw TmError(TM_E_SIZE, "InconsistentSize: the handles differ in block count");
+    if (block >= static_cast<uint64_t>(s0.topo.nblocks())) throw TmError(TM_E_ARG, "block index past the mesh");
+    const int64_t b = static_cast<int64_t>(block);
+    for (int c = 0; c < p.ncuts; ++c) {
+        const Smoother& s = cuts[c]->impl;
+        if (s.topo.ni[b] != s0.topo.ni[b] || s.topo.nj[b] != s0.topo.nj[b]) throw TmError(TM_E_SIZE, "InconsistentSize: the handles differ in the size of the block");
+        const auto it = std::lower_bound(s.lp.owned_blocks.begin(), s.lp.owned_blocks.end(), b);
+        if (it == s.lp.owned_blocks.end() || *it != b) throw TmError(TM_E_ARG, "block is not owned by every handle");
+        dc.xy[c] = s.X + s.lp.local_start[it - s.lp.owned_blocks.begin()];
+    }
+    *ni = static_cast<uint64_t>(s0.topo.ni[b]);
+    *nj = static_cast<uint64_t>(s0.topo.nj[b]);
+}
+
+hipStream_t stack_order_behind(tm_smoother* const* cuts, int ncuts, std::vector<std::unique_ptr<StackEvent>>& events) {
+    const hipStream_t st = cuts[0]->impl.stream;
+    for (int c = 1; c < ncuts; ++c) {
+        if (cuts[c]->impl.stream == st) continue;
+        events.push_back(std::make_unique<StackEvent>());
+        HIPCHK(hipEventRecord(events.back()->e, cuts[c]->impl.stream));
+        HIPCHK(hipStreamWaitEvent(st, events.back()->e, 0));
+    }
+    return st;
 }
 
 }  // namespace tmh
@@ -187,32 +177,11 @@ extern "C" int tm_stack_smoothers(tm_smoother* const* cuts, const tm_stack_opt* 
         if (!cuts || !x || !y || !z) throw TmError(TM_E_ARG, "null argument");
         const StackPlan p = stack_plan(opt);
         stack_check_window(p, k_begin, k_count);
-        for (int c = 0; c < p.ncuts; ++c)
-            if (!cuts[c] || !smoother_is_live(cuts[c])) throw TmError(TM_E_ARG, "a cut is not a live handle");
-        const Smoother& s0 = cuts[0]->impl;
-        for (int c = 1; c < p.ncuts; ++c)
-            if (cuts[c]->impl.topo.nblocks() != s0.topo.nblocks()) throw TmError(TM_E_SIZE, "InconsistentSize: the handles differ in block count");
-        if (block >= static_cast<uint64_t>(s0.topo.nblocks())) throw TmError(TM_E_ARG, "block index past the mesh");
-        const int64_t b = static_cast<int64_t>(block);
         StackCuts dc{};
-        for (int c = 0; c < p.ncuts; ++c) {
-            const Smoother& s = cuts[c]->impl;
-            if (s.topo.ni[b] != s0.topo.ni[b] || s.topo.nj[b] != s0.topo.nj[b]) throw TmError(TM_E_SIZE, "InconsistentSize: the handles differ in the size of the block");
-            const auto it = std::lower_bound(s.lp.owned_blocks.begin(), s.lp.owned_blocks.end(), b);
-            if (it == s.lp.owned_blocks.end() || *it != b) throw TmError(TM_E_ARG, "block is not owned by every handle");
-            dc.xy[c] = s.X + s.lp.local_start[it - s.lp.owned_blocks.begin()];
-        }
-        const uint64_t ni = static_cast<uint64_t>(s0.topo.ni[b]), nj = static_cast<uint64_t>(s0.topo.nj[b]);
-        // behind the pending work of every handle: the kernel runs on the first handle's stream, which waits for an event recorded on each
-        // of the other streams (the same stream twice is harmless)
-        const hipStream_t st = s0.stream;
+        uint64_t ni = 0, nj = 0;
+        stack_resident_cuts(cuts, p, block, dc, &ni, &nj);
         std::vector<std::unique_ptr<StackEvent>> events;
-        for (int c = 1; c < p.ncuts; ++c) {
-            if (cuts[c]->impl.stream == st) continue;
-            events.push_back(std::make_unique<StackEvent>());
-            HIPCHK(hipEventRecord(events.back()->e, cuts[c]->impl.stream));
-            HIPCHK(hipStreamWaitEvent(st, events.back()->e, 0));
-        }
+        const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
         stack_run(p, dc, k_begin, k_count, ni, nj, x, y, z, st);   // synchronises st: the other handles' coordinates have been read when it returns
         return TM_OK;
     });

@@ -27,6 +27,12 @@ void stack_check_window(const StackPlan& plan, uint64_t k_begin, uint64_t k_coun
 // block `block` of the K descriptions: TM_E_ARG / TM_E_SIZE as the header says; returns (ni, nj)
 void stack_check_cuts(const tm_mesh_desc* const* cuts, int ncuts, uint64_t block, uint64_t* ni, uint64_t* nj);
 
+// layer k of the plan from the K cuts v[c] (node (i,j) at i*nj + j, interleaved x y): one plane each of x, y, z, element j*ni + i.
+// The definition as a plain loop, summed over c = 0 .. K-1 like the kernel (tm_stack_block_host, tm_stack_quality_host)
+void stack_layer_host(const StackPlan& plan, const double* const* v, uint64_t k, uint64_t ni, uint64_t nj, double* x, double* y, double* z);
+// what the 3-D quality calls ask on top of the stacking calls: TM_E_SIZE unless the stack has cells
+void stack_check_cells(const StackPlan& plan, uint64_t ni, uint64_t nj);
+
 // live handles of the process (tm_api.cpp: entered by tm_smoother_create, removed by tm_smoother_destroy)
 bool smoother_is_live(const tm_smoother* s);
 

@@ -124,6 +124,25 @@ void stack_check_cuts(const tm_mesh_desc* const* cuts, int ncuts, uint64_t block
     *nj = b0.nj;
 }
 
+void stack_layer_host(const StackPlan& p, const double* const* v, uint64_t k, uint64_t ni, uint64_t nj, double* x, double* y, double* z) {
+    const int K = p.ncuts;
+    const bool cyl = p.mapping == TM_STACK_CYLINDRICAL;
+    const double* w = &p.weights[static_cast<size_t>(k) * K];
+    const double s = p.layers[k];
+    for (uint64_t j = 0; j < nj; ++j)
+        for (uint64_t i = 0; i < ni; ++i) {
+            const size_t n = static_cast<size_t>(i) * nj + j, o = static_cast<size_t>(j) * ni + i;
+            double ax = w[0] * v[0][2 * n], ay = w[0] * (cyl ? v[0][2 * n + 1] / p.span[0] : v[0][2 * n + 1]);
+            for (int c = 1; c < K; ++c) {
+                ax = ax + w[c] * v[c][2 * n];
+                ay = ay + w[c] * (cyl ? v[c][2 * n + 1] / p.span[c] : v[c][2 * n + 1]);
+            }
+            x[o] = ax;
+            y[o] = cyl ? s * std::sin(ay) : ay;
+            z[o] = cyl ? s * std::cos(ay) : s;
+        }
+}
+
 }  // namespace tmh
 
 using namespace tmh;
@@ -145,26 +164,10 @@ extern "C" int tm_stack_block_host(const tm_mesh_desc* const* cuts, const tm_sta
         stack_check_window(p, k_begin, k_count);
         uint64_t ni = 0, nj = 0;
         stack_check_cuts(cuts, p.ncuts, block, &ni, &nj);
-        const int K = p.ncuts;
-        const bool cyl = p.mapping == TM_STACK_CYLINDRICAL;
         const double* v[TM_STACK_MAX_CUTS];
-        for (int c = 0; c < K; ++c) v[c] = cuts[c]->blocks[block].xy;
-        for (uint64_t k = 0; k < k_count; ++k) {
-            const double* w = &p.weights[static_cast<size_t>(k_begin + k) * K];
-            const double s = p.layers[k_begin + k];
-            for (uint64_t j = 0; j < nj; ++j)
-                for (uint64_t i = 0; i < ni; ++i) {
-                    const size_t n = static_cast<size_t>(i) * nj + j, o = (static_cast<size_t>(k) * nj + j) * ni + i;
-                    double ax = w[0] * v[0][2 * n], ay = w[0] * (cyl ? v[0][2 * n + 1] / p.span[0] : v[0][2 * n + 1]);
-                    for (int c = 1; c < K; ++c) {
-                        ax = ax + w[c] * v[c][2 * n];
-                        ay = ay + w[c] * (cyl ? v[c][2 * n + 1] / p.span[c] : v[c][2 * n + 1]);
-                    }
-                    x[o] = ax;
-                    y[o] = cyl ? s * std::sin(ay) : ay;
-                    z[o] = cyl ? s * std::cos(ay) : s;
-                }
-        }
+        for (int c = 0; c < p.ncuts; ++c) v[c] = cuts[c]->blocks[block].xy;
+        const size_t plane = static_cast<size_t>(ni) * nj;
+        for (uint64_t k = 0; k < k_count; ++k) stack_layer_host(p, v, k_begin + k, ni, nj, x + k * plane, y + k * plane, z + k * plane);
         return TM_OK;
     });
 }

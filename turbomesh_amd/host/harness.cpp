@@ -6,6 +6,7 @@
 //   tm_harness tm <ni> <nj> <iterations>               the Thomas-Middlecoff control field on a clustered rectangle (exit 0: it kept the clustering)
 //   tm_harness stack <ni> <nj> <ncuts> <nlayers>       config-5 cuts (amplitude 0.05 + 0.001 c), five relaxation sweeps per handle, stacked on the
 //                                                      device by the natural cubic spline: a checksum per layer (exit 0: layers at cuts equal the cuts)
+//   tm_harness stack-quality <ni> <nj> <ncuts> <nlayers>   the same cuts: the 3-D quality record of the stacked block (kernel K12; exit 0: equal to the CPU's)
 //   tm_harness csr                                     the linear-solver slot (seam 2) on the reference's 5 x 5 known answer
 //   tm_harness ranks <world> <rank> <idfile> <nblocks> <ni> <nj> <iterations> [relax|bicgstab] [dump.bin]
 //        one process per GPU (start each with HIP_VISIBLE_DEVICES=<its GPU>): the strip's blocks are dealt to the ranks in order, the
@@ -17,6 +18,7 @@
 #include "turbomesh.hpp"
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -273,8 +275,48 @@ static int stackCuts(std::size_t ni, std::size_t nj, std::size_t ncuts, std::siz
     return ok ? 0 : 1;
 }
 
+// tm_harness stack-quality <ni> <nj> <ncuts> <nlayers>: the cuts of `stack`; the 3-D quality record of the stacked block from the
+// coordinates resident in the handles (stack::quality -> tm_stack_smoothers_quality), compared with the CPU's report of the planes
+// tm_stack_smoothers returns for the same handles (every field but the summed total_volume bit for bit).
+static int stackQuality(std::size_t ni, std::size_t nj, std::size_t ncuts, std::size_t nlayers) {
+    if (ncuts < 2 || nlayers < 2) throw Error(TM_E_ARG, "stack-quality <ni> <nj> <ncuts> <nlayers>: at least two cuts and two layers");
+    smoothing::solver::Option opt;
+    opt.inner = TM_INNER_RELAX;
+    std::vector<discrete::Mesh> meshes;
+    meshes.reserve(ncuts);
+    for (std::size_t c = 0; c < ncuts; ++c) meshes.push_back(buildSingle(ni, nj, 0.05 + 0.001 * static_cast<double>(c)));
+    std::vector<std::unique_ptr<smoothing::smooth::Smoother>> handles;
+    std::vector<smoothing::smooth::Smoother*> cuts;
+    for (std::size_t c = 0; c < ncuts; ++c) {
+        handles.push_back(std::make_unique<smoothing::smooth::Smoother>(meshes[c], opt, smoothing::wall_control_function::Algorithm::laplace()));
+        handles.back()->iterate(5);
+        cuts.push_back(handles.back().get());
+    }
+    stack::Option so;
+    for (std::size_t c = 0; c < ncuts; ++c) so.span.push_back(static_cast<double>(c));
+    const double z1 = so.span.back();
+    for (std::size_t k = 0; k < nlayers; ++k) so.layers.push_back(k + 1 == nlayers ? z1 : z1 * (static_cast<double>(k) / static_cast<double>(nlayers - 1)));
+    const tm_quality3d q = stack::quality(cuts, so, 0);
+    const tm_quality3d h = stack::quality(stack::stack_block(cuts, so, 0, 0, nlayers));
+    std::printf("stack-quality: hexahedra %llu inverted %llu degenerate %llu orientation %d\n", static_cast<unsigned long long>(q.cells),
+                static_cast<unsigned long long>(q.inverted), static_cast<unsigned long long>(q.degenerate), q.orientation);
+    std::printf("stack-quality: min scaled jacobian %.17g at (i %llu, j %llu, k %llu) max aspect %.17g max growth k %.17g\n", q.min_scaled_jacobian,
+                static_cast<unsigned long long>(q.worst_i), static_cast<unsigned long long>(q.worst_j), static_cast<unsigned long long>(q.worst_k), q.max_aspect, q.max_growth_k);
+    std::printf("stack-quality: volume min %.17g max %.17g total %.17g\n", q.min_volume, q.max_volume, q.total_volume);
+    std::printf("stack-quality: hist");
+    for (int k = 0; k < 10; ++k) std::printf(" %llu", static_cast<unsigned long long>(q.hist[k]));
+    std::printf("\n");
+    tm_quality3d a = q, b = h;
+    a.total_volume = b.total_volume = 0.0;
+    const bool same = std::memcmp(&a, &b, sizeof(a)) == 0 && std::fabs(q.total_volume - h.total_volume) <= static_cast<double>(q.cells) * 0x1p-53 * std::fabs(h.total_volume);
+    std::printf("stack-quality: device equals host: %s\n", same ? "yes" : "no");
+    return same ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     try {
+        if (argc >= 6 && std::strcmp(argv[1], "stack-quality") == 0)
+            return stackQuality(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10));
         if (argc >= 6 && std::strcmp(argv[1], "stack") == 0)
             return stackCuts(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "csr") == 0) return csrKat();
@@ -282,7 +324,7 @@ int main(int argc, char** argv) {
             return thomasMiddlecoff(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "ranks") == 0) return runRank(argc, argv);
         if (argc < 5) {
-            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n", argv[0], argv[0], argv[0]);
+            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n", argv[0], argv[0], argv[0], argv[0]);
             return 2;
         }
         int a = 2;

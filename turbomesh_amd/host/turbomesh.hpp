@@ -480,6 +480,23 @@ inline Block3d stack_block(const std::vector<discrete::Mesh*>& cuts, const Optio
     b.x.resize(n), b.y.resize(n), b.z.resize(n);
     return b;
 }
+// 3-D quality of stacked blocks (tm_hip.h): the hexahedra of `block` of the stack, evaluated on the device straight from the coordinates
+// RESIDENT in one handle per cut (tm_stack_smoothers_quality: the 3-D block is never stored)
+inline tm_quality3d quality(const std::vector<smoothing::smooth::Smoother*>& cuts, const Option& o, std::size_t block) {
+    if (cuts.empty() || cuts.size() != o.span.size()) throw Error(TM_E_ARG, "one handle per span position");
+    std::vector<tm_smoother*> h;
+    for (const auto* c : cuts) h.push_back(c ? c->handle() : nullptr);
+    const tm_stack_opt so = o.c_struct();
+    tm_quality3d q;
+    check(tm_stack_smoothers_quality(h.data(), &so, block, &q));
+    return q;
+}
+// the same of any 3-D block held on the host, evaluated on the CPU (tm_quality3d_planes_host)
+inline tm_quality3d quality(const Block3d& b, std::size_t block = 0) {
+    tm_quality3d q;
+    check(tm_quality3d_planes_host(b.x.data(), b.y.data(), b.z.data(), b.ni, b.nj, b.nk, block, &q, nullptr));
+    return q;
+}
 }  // namespace stack
 
 namespace discrete {

@@ -53,6 +53,62 @@ class Quality:
                 f"max growth i {self.max_growth_i:.3f} j {self.max_growth_j:.3f}")
 
 
+@dataclass
+class Quality3d:
+    """tm_quality3d as a record: the hexahedra of a stacked block (include/tm_hip.h, "3-D quality of stacked blocks")."""
+
+    cells: int
+    inverted: int
+    degenerate: int
+    orientation: int           # +1 / -1: handedness of the block (sign of the summed cell volumes); 0: none, or blocks differ (total)
+    min_scaled_jacobian: float
+    worst_block: int
+    worst_i: int
+    worst_j: int
+    worst_k: int
+    max_aspect: float
+    max_growth_k: float
+    min_volume: float
+    max_volume: float
+    total_volume: float
+    hist: Tuple[int, ...]      # valid cells by min scaled Jacobian, bins [k/10, (k+1)/10)
+
+    @classmethod
+    def from_struct(cls, q: "_capi.tm_quality3d") -> "Quality3d":
+        return cls(int(q.cells), int(q.inverted), int(q.degenerate), int(q.orientation), float(q.min_scaled_jacobian), int(q.worst_block),
+                   int(q.worst_i), int(q.worst_j), int(q.worst_k), float(q.max_aspect), float(q.max_growth_k), float(q.min_volume),
+                   float(q.max_volume), float(q.total_volume), tuple(int(h) for h in q.hist))
+
+    @property
+    def ok(self) -> bool:
+        return self.inverted == 0 and self.degenerate == 0
+
+    def line(self, name: str) -> str:
+        """One log line: name, cells, inverted, degenerate, min scaled Jacobian with its cell, max aspect, spanwise growth, volumes."""
+        return (f"{name}: hexahedra {self.cells} inverted {self.inverted} degenerate {self.degenerate} "
+                f"min scaled jacobian {self.min_scaled_jacobian:.4f} at (block {self.worst_block}, i {self.worst_i}, j {self.worst_j}, k {self.worst_k}) "
+                f"max aspect {self.max_aspect:.1f} max growth k {self.max_growth_k:.3f} "
+                f"volume {self.min_volume:.3e}..{self.max_volume:.3e} total {self.total_volume:.6e}")
+
+
+def total_3d(per_block: List[Quality3d]) -> Quality3d:
+    """tm_quality3d_total of the blocks' records (host only)."""
+    arr = (_capi.tm_quality3d * max(1, len(per_block)))()
+    for k, q in enumerate(per_block):
+        arr[k] = _capi.tm_quality3d(q.cells, q.inverted, q.degenerate, q.orientation, 0, q.min_scaled_jacobian, q.worst_block, q.worst_i, q.worst_j,
+                                    q.worst_k, q.max_aspect, q.max_growth_k, q.min_volume, q.max_volume, q.total_volume, (C.c_uint64 * 10)(*q.hist))
+    total = _capi.tm_quality3d()
+    _capi.check(_capi.lib().tm_quality3d_total(arr, len(per_block), C.byref(total)))
+    return Quality3d.from_struct(total)
+
+
+def log_report_3d(logger, names, per_block, total, stage="stack"):
+    """One line per block and a total, on `logger` at INFO; every line starts with `stage`."""
+    for name, q in zip(names, per_block):
+        logger.info("%s", q.line(f"{stage} {name}"))
+    logger.info("%s", total.line(f"{stage} total"))
+
+
 def records(per_block, total) -> Tuple[List[Quality], Quality]:
     return [Quality.from_struct(q) for q in per_block], Quality.from_struct(total)
 

@@ -40,6 +40,24 @@ def layers_from(span, nk, clustering=None):
     return s
 
 
+def quality_of_planes(X, Y, Z, block=0, field=False):
+    """quality.Quality3d of any 3-D block given as (nk, nj, ni) arrays (PLOT3D order: what Stack.block returned, or a file read with
+    output.read_plot3d_3d), evaluated on the CPU (tm_quality3d_planes_host: no GPU needed).  field=True: (record, per-cell min of the
+    oriented scaled Jacobian as a (nk-1, nj-1, ni-1) array)."""
+    from . import quality as _quality
+
+    X, Y, Z = (np.ascontiguousarray(a, dtype=np.float64) for a in (X, Y, Z))
+    if X.ndim != 3 or Y.shape != X.shape or Z.shape != X.shape:
+        raise ValueError("X, Y, Z: three (nk, nj, ni) arrays of one shape")
+    nk, nj, ni = X.shape
+    q = _capi.tm_quality3d()
+    f = np.empty((max(0, nk - 1), max(0, nj - 1), max(0, ni - 1)), dtype=np.float64) if field else None
+    _capi.check(_capi.lib().tm_quality3d_planes_host(_capi.f64ptr(X), _capi.f64ptr(Y), _capi.f64ptr(Z), ni, nj, nk, block, C.byref(q),
+                                                     _capi.f64ptr(f) if field else None))
+    rec = _quality.Quality3d.from_struct(q)
+    return (rec, f) if field else rec
+
+
 @dataclass
 class Mesh3d:
     """Blocks of a stacked mesh: per block the X, Y, Z coordinates as (nk, nj, ni) arrays (PLOT3D order, i fastest)."""
@@ -114,6 +132,48 @@ class Stack:
             fn = L.tm_stack_block_host if host else L.tm_stack_block
             _capi.check(fn(arr, C.byref(self._opt), b, k_begin, k_count, *ptrs))
         return tuple(out)
+
+    def quality(self, cuts, host=False):
+        """(per_block, total): the 3-D quality report of every stacked block (quality.Quality3d) and their total -- negative and degenerate
+        hexahedra ACROSS layers, which the 2-D report of the cuts cannot see.  Evaluated on the device straight from the cuts (kernel K12:
+        the 3-D block is never stored); cuts as in block(): Mesh (tm_stack_quality; host=True: tm_stack_quality_host, no GPU) or Smoother
+        (tm_stack_smoothers_quality, the resident coordinates)."""
+        from . import quality as _quality
+
+        self._check_count(cuts)
+        resident = all(hasattr(c, "_h") for c in cuts)
+        meshes = [c._mesh for c in cuts] if resident else cuts
+        L = _capi.lib()
+        per_block = []
+        if resident:
+            if host:
+                raise ValueError("host=True evaluates host coordinates: pass the meshes, not the handles")
+            handles = (C.c_void_p * len(cuts))(*[c._h for c in cuts])
+        else:
+            descs = [_capi.MeshDesc(m) for m in meshes]
+            arr = (C.POINTER(_capi.tm_mesh_desc) * len(descs))(*[C.pointer(d.desc) for d in descs])
+        for b in range(len(meshes[0].blocks)):
+            q = _capi.tm_quality3d()
+            if resident:
+                _capi.check(L.tm_stack_smoothers_quality(handles, C.byref(self._opt), b, C.byref(q)))
+            else:
+                _capi.check((L.tm_stack_quality_host if host else L.tm_stack_quality)(arr, C.byref(self._opt), b, C.byref(q)))
+            per_block.append(_quality.Quality3d.from_struct(q))
+        return per_block, _quality.total_3d(per_block)
+
+    def quality_field(self, cuts, b, k_begin=0, k_count=None):
+        """Per-cell minimum of the oriented scaled Jacobian of block b, cell layers [k_begin, k_begin + k_count), as a (k_count, nj-1, ni-1)
+        array (NaN for degenerate cells).  cuts: one smooth.Smoother per cut (tm_stack_smoothers_quality_field)."""
+        self._check_count(cuts)
+        if not all(hasattr(c, "_h") for c in cuts):
+            raise ValueError("quality_field reads the coordinates resident in handles: pass one Smoother per cut")
+        if k_count is None:
+            k_count = self.nlayers - 1 - k_begin
+        ni, nj = cuts[0]._mesh.blocks[b].points.size
+        out = np.empty((max(0, k_count), max(0, nj - 1), max(0, ni - 1)), dtype=np.float64)
+        handles = (C.c_void_p * len(cuts))(*[c._h for c in cuts])
+        _capi.check(_capi.lib().tm_stack_smoothers_quality_field(handles, C.byref(self._opt), b, k_begin, k_count, _capi.f64ptr(out)))
+        return out
 
     def mesh3d(self, cuts, host=False) -> Mesh3d:
         """Every block of the cuts, all layers."""
