@@ -591,6 +591,84 @@ int tm_stack_smoothers_quality_field(tm_smoother* const* cuts, const tm_stack_op
                                      uint64_t k_begin, uint64_t k_count /* cell layers */, double* min_scaled_jacobian);
 int tm_quality3d_total(const tm_quality3d* per_block, uint64_t n, tm_quality3d* total);
 
+/* ------------------------------------------------------------------ high-order elements
+ * The reference's roadmap lists "high order meshes -- equidistant / other distributions".  Curved elements of order p come from a smoothed
+ * block by agglomeration: every p x p group of cells is one element with (p+1)^2 nodes, equidistant in index space because they are the
+ * fine mesh itself; any other node distribution is the element's degree-p tensor-product interpolant evaluated at the wanted parametric
+ * points, and the elements are judged by the Jacobian of that same polynomial.
+ * Order and elements:
+ *   - 1 <= p <= TM_HO_MAX_ORDER = 8.  A block of ni x nj nodes qualifies iff (ni-1) % p == 0 and (nj-1) % p == 0 (and ni, nj >= 2); it
+ *     then has Ei = (ni-1)/p by Ej = (nj-1)/p elements.  Anything else: TM_E_SIZE.
+ *   - Element (e, f) owns the source nodes X[e*p + m][f*p + n], m, n = 0 .. p, which sit at the parametric positions u = m, v = n on [0, p].
+ * Target nodes t_0 = 0 < t_1 < ... < t_p = 1 by `distribution`:
+ *   - TM_HO_EQUIDISTANT: u_a = a exactly; T is the identity by definition (it is not derived from a/p).
+ *   - TM_HO_GAUSS_LOBATTO: t_a = (1 + x_a)/2, x_a the ascending roots of (1 - x^2) P'_p(x), found on the host in long double by Newton
+ *     iteration, rounded once to fp64, the end nodes exactly 0 and 1.
+ *   - TM_HO_PRESCRIBED: the caller's nodes[0..p]: finite, strictly increasing, nodes[0] == 0, nodes[p] == 1; anything else TM_E_ARG.
+ * Tables, formed on the host in long double from u_a = p * t_a (t_a the fp64 node), every entry rounded once to fp64:
+ *   T[a][m] = prod_{n != m} (u_a - n)/(m - n);   D[a][m] = sum_{k != m} 1/(m-k) * prod_{n != m,k} (u_a - n)/(m - n)   (d/du of the former at u_a)
+ *   Rows 0 and p of T are exact unit vectors, and so is any row whose u_a is an exact integer.
+ * Elevated nodes and derivatives.  All arithmetic IEEE fp64, nothing fused, both components alike.  For (A, B) in {(T,T), (D,T), (T,D)}:
+ *   W[m][b] = B[b][0]*X[m][0], then + B[b][n]*X[m][n] for n = 1 .. p in that order;
+ *   R[a][b] = A[a][0]*W[0][b], then + A[a][m]*W[m][b] for m = 1 .. p.
+ *   (T,T): the elevated node Y[e*p+a][f*p+b];  (D,T): its derivative d/du;  (T,D): its derivative d/dv.
+ *   A node on an element edge depends only on the source nodes of that grid line, and both neighbouring elements compute it by the same
+ *   expression, so the result is again an ni x nj structured array.  A node shared between elements is written by the element above it
+ *   (local index 0), the last node of a grid line by the last element.  Corner nodes are the source nodes, except that -0 may become +0.
+ *   With TM_HO_EQUIDISTANT, or p = 1, the (T,T) contraction is skipped and the nodes are copied: the planes equal tm_export_soa's bit for
+ *   bit.  Across block connections nothing is reconciled: the two sides sum in their own index order and agree to rounding.
+ * Element record:
+ *   J[a][b] = x_u*y_v - x_v*y_u at the element's own (p+1)^2 nodes (one-sided on element edges)
+ *   orientation  o: the rule of tm_quality applied to the mesh of element corners -- sign of the sum of a = 0.5*((C.x-A.x)*(D.y-B.y) -
+ *                (D.x-B.x)*(C.y-A.y)) over the elements, 0 (reported as +1) when |sum a| <= elements * 2^-53 * sum |a|
+ *   per element  Jmin, Jmax of o*J over its nodes; invalid if Jmin <= 0 or any J is non-finite; otherwise its scaled Jacobian
+ *                sj = Jmin/Jmax, the usual curved-element measure.  It is SAMPLED AT THE NODES: a positive sj is necessary for a valid
+ *                (injective) element, not sufficient -- the Jacobian of a degree-p map is a polynomial of degree 2p-1 per direction and
+ *                can dip below zero between the nodes.
+ *   min_scaled_jacobian  min of sj over valid elements, (worst_block, worst_e, worst_f) its element, ties to the lowest (block, e, f);
+ *                NaN and 0, 0, 0 when no element is valid
+ *   min_jacobian / max_jacobian   the extremes of o*J over valid elements (NaN when there is none)
+ *   hist[k]      valid elements by sj, the bins of tm_quality; sum hist == elements - invalid
+ * The record has no summed field: every field is equal between device and host bit for bit (the orientation is decided from a sum and is
+ * the same unless that sum lies within rounding of the zero tolerance).
+ * tm_ho_quality_total: counts and hist summed, extremes combined, the worst element the one with the smallest value, orientation and
+ * order the blocks' common one or 0; records with elements == 0 are left out.  Host only.
+ * Not served: order elevation in span for stacked blocks; re-projection of wall nodes onto the blade spline (the interpolant of the
+ * on-spline nodes is used as it is); reconciling interface nodes across blocks; Gmsh and HOPR output. */
+#define TM_HO_MAX_ORDER 8
+enum { TM_HO_EQUIDISTANT = 0, TM_HO_GAUSS_LOBATTO = 1, TM_HO_PRESCRIBED = 2 };
+typedef struct tm_ho_opt {               /* 16 bytes */
+    int32_t order, distribution;
+    const double* nodes;                 /* TM_HO_PRESCRIBED: [order + 1]; ignored otherwise */
+} tm_ho_opt;
+typedef struct tm_ho_quality {           /* 152 bytes */
+    uint64_t elements, invalid;
+    int32_t  orientation, order;
+    double   min_scaled_jacobian;
+    uint64_t worst_block, worst_e, worst_f;
+    double   min_jacobian, max_jacobian;
+    uint64_t hist[10];
+} tm_ho_quality;
+
+/* nodes [p+1], T and D [(p+1)*(p+1)], row = target node a; any output may be NULL.  Host only: no GPU touched */
+int tm_ho_tables(const tm_ho_opt* opt, double* nodes, double* T, double* D);
+/* TM_OK, or TM_E_SIZE with tm_last_error naming the first offender: a block whose ni-1 or nj-1 is not a multiple of p, then a
+ * connection range whose start or end is not a multiple of p (element edges would not meet across the interface).  Host only */
+int tm_ho_check(const tm_mesh_desc* mesh, const tm_ho_opt* opt);
+/* Block `block` of a mesh given on the host, elevated on the device (kernel K13).  x, y: planes of ni*nj doubles with i fastest,
+ * x[j*ni + i], the layout of tm_export_soa; both may be NULL for a report alone.  q may be NULL.  sj, when given, receives Ei*Ej values
+ * as sj[f*Ei + e], NaN for invalid elements.  A block index past the mesh, a block without coordinates, x without y: TM_E_ARG. */
+int tm_ho_elevate(const tm_mesh_desc* mesh, const tm_ho_opt* opt, uint64_t block, double* x, double* y, tm_ho_quality* q, double* sj);
+/* the same definition evaluated on the host: no GPU touched, works in a process without a device.  Planes, sj and every field of the
+ * record equal the device's bit for bit */
+int tm_ho_elevate_host(const tm_mesh_desc* mesh, const tm_ho_opt* opt, uint64_t block, double* x, double* y, tm_ho_quality* q, double* sj);
+/* The same kernel on the coordinates resident in the handle, behind its pending work on its stream; modifies neither the coordinates
+ * nor any solver state.  The buffers (two planes, one pair per element, a few KB of partial records) are allocated on first use with the
+ * HIP allocator, outside a caller-provided workspace, and freed by tm_smoother_destroy.  A block the handle does not own, a dead or
+ * NULL handle: TM_E_ARG.  A block that fails the size rule: TM_E_SIZE.  Bit-identical to tm_ho_elevate on the downloaded coordinates. */
+int tm_smoother_elevate(tm_smoother* s, const tm_ho_opt* opt, uint64_t block, double* x, double* y, tm_ho_quality* q, double* sj);
+int tm_ho_quality_total(const tm_ho_quality* per_block, uint64_t n, tm_ho_quality* total);
+
 /* ------------------------------------------------------------------ host-only planning (no GPU needed)
  * The perimeter-row table the device kernels consume, exported as CSR so it can be compared with
  * the reference's assembled rows (smooth.zig:421-921).  Only sizes/topology are read from `mesh`

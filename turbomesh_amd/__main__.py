@@ -13,7 +13,13 @@ diagonal on the assembled system, the reference's tolerances -- the iterates a r
 --stack CFG2 [CFG3 ...] --span z0,z1,... --layers NK: `config` and the further files are the spanwise cuts of one blade.  Every file runs the
 path above with its own handle; the smoothed cuts are stacked into 3-D blocks on the device (stack.py, include/tm_hip.h "3-D from 2-D cuts")
 and --output becomes a multi-block 3-D PLOT3D file; --stack-quality / --fail-on-inverted-3d report on the hexahedra of that mesh
-(include/tm_hip.h "3-D quality of stacked blocks").  Without --stack the program is what it was."""
+(include/tm_hip.h "3-D quality of stacked blocks").  Without --stack the program is what it was.
+
+--order P [--nodes equidistant|gauss-lobatto]: the smoothed blocks become curved elements of order P (highorder.py, include/tm_hip.h
+"high-order elements"): the cell counts of every block and the interface ranges must be multiples of P, which is checked before
+anything is smoothed; the elements are formed on the device from the coordinates resident in the handle, their report is logged per block
+and for the mesh, and --output takes the elevated nodes (.vtk: Lagrange quadrilaterals, equidistant nodes only; .xyz / .p3d: PLOT3D).
+Without --order nothing changes."""
 from __future__ import annotations
 
 import argparse
@@ -53,6 +59,15 @@ def _run(ap, args, config, keep=None, tag=""):
                  "use \"solver\": {\"hip\": {}} in the input file or pass --hip")
     geometry = inp.geometry(os.getcwd())   # profile files are named relative to the working directory, as in the reference
     mesh = inp.template.run(geometry)                                   # blocking (O4H.zig:67-118) + TFI per block
+    elevation = None
+    if getattr(args, "order", None) is not None:
+        from . import _capi, highorder
+
+        elevation = highorder.Elevation(args.order, args.nodes)
+        try:
+            elevation.check(mesh)   # before anything is smoothed
+        except _capi.TmError as e:
+            sys.exit(f"high-order elements of order {args.order}: {e}")
     iterations = inp.iterations if args.iterations is None else args.iterations
     slog = logging.getLogger("smoothing")
     with contextlib.ExitStack() as scope:
@@ -87,6 +102,10 @@ def _run(ap, args, config, keep=None, tag=""):
             if args.quality:
                 quality.log_report(qlog, mesh.names, *after, tag + "after")
             stats["quality"] = {"before": before, "after": after}
+        if elevation is not None:
+            hom = elevation.mesh(sm)   # from the resident coordinates
+            quality.log_report_ho(qlog, hom.names, hom.per_block, hom.total, tag + "elevate")
+            stats["highorder"] = hom
     return inp, mesh, sm, stats, after
 
 
@@ -166,6 +185,14 @@ def main(argv=None):
                     help="log a mesh quality report (`quality` logger: one line per block and a total) before and after smoothing")
     ap.add_argument("--fail-on-inverted", action="store_true",
                     help="exit non-zero when the smoothed mesh has inverted or degenerate cells (implies the quality evaluation)")
+    ap.add_argument("--order", type=int, metavar="P",
+                    help="curved elements of order P (1 .. 8) from the smoothed blocks: every P x P group of cells is one element; the cell counts "
+                         "of every block and the interface ranges must be multiples of P (checked before smoothing).  --output then takes the "
+                         "elevated nodes: .vtk (Lagrange quadrilaterals, --nodes equidistant) or PLOT3D")
+    ap.add_argument("--nodes", default=None, choices=["equidistant", "gauss-lobatto"],
+                    help="with --order: node distribution inside the elements (default: gauss-lobatto; equidistant for a .vtk output)")
+    ap.add_argument("--fail-on-invalid-elements", action="store_true",
+                    help="with --order: exit non-zero, after the file is written, when elements with a non-positive Jacobian at a node remain")
     ap.add_argument("--stack", nargs="+", metavar="CFG", default=None,
                     help="further input files: the spanwise cuts after `config`, in span order.  Every file runs the path above with its own "
                          "handle; the smoothed cuts are then stacked into 3-D blocks on the device and --output becomes a multi-block 3-D PLOT3D file")
@@ -187,6 +214,18 @@ def main(argv=None):
         ap.error("--span and --layers go with --stack")
     if args.stack is None and (args.stack_quality or args.fail_on_inverted_3d):
         ap.error("--stack-quality and --fail-on-inverted-3d go with --stack")
+    if args.order is None and (args.nodes or args.fail_on_invalid_elements):
+        ap.error("--nodes and --fail-on-invalid-elements go with --order")
+    if args.order is not None:
+        if args.stack is not None:
+            ap.error("--order elevates 2-D blocks: it does not go with --stack")
+        if not 1 <= args.order <= 8:
+            ap.error("--order: 1 .. 8")
+        vtk = bool(args.output) and args.output.lower().endswith(".vtk")
+        if args.nodes is None:
+            args.nodes = "equidistant" if vtk else "gauss-lobatto"
+        if vtk and args.nodes != "equidistant":
+            ap.error("a .vtk output holds Lagrange cells, which assume equidistant nodes: --nodes equidistant, or a PLOT3D output")
     if args.stack is not None:
         if not args.span or args.layers is None:
             ap.error("--stack needs --span z0,z1,... and --layers NK")
@@ -209,9 +248,17 @@ def main(argv=None):
         return _main_stack(ap, args)
     inp, mesh, _, stats, after = _run(ap, args, args.config)
     out = args.output or inp.output
-    if out:
+    hom = stats.get("highorder")
+    if out and hom is not None:
+        hom.write(out)
+        logging.getLogger("output").info("wrote %s (%d blocks, %d elements of order %d, %s nodes)", out, len(hom.blocks), hom.total.elements, hom.order, hom.distribution)
+    elif out:
         mesh.write(out)
         logging.getLogger("output").info("wrote %s (%d blocks, %d nodes)", out, len(mesh.blocks), sum(b.points.data.shape[0] * b.points.data.shape[1] for b in mesh.blocks))
+    if args.fail_on_invalid_elements and not hom.total.ok:
+        bad = next(q for q in hom.per_block if not q.ok)
+        sys.exit(f"high-order elements: {hom.total.invalid} invalid elements of order {hom.order} after smoothing "
+                 f"(first in block {hom.per_block.index(bad)}: {bad.invalid} of {bad.elements})")
     if args.fail_on_inverted and not after[1].ok:
         sys.exit(f"mesh quality: {after[1].inverted} inverted and {after[1].degenerate} degenerate cells after smoothing "
                  f"(worst: block {after[1].worst_block}, i {after[1].worst_i}, j {after[1].worst_j})")

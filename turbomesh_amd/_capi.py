@@ -27,6 +27,8 @@ TM_OPT_REFINE = 16
 TM_STACK_MAX_CUTS = 16
 TM_STACK_LINEAR, TM_STACK_CUBIC = 0, 1
 TM_STACK_PLANAR, TM_STACK_CYLINDRICAL = 0, 1
+TM_HO_MAX_ORDER = 8
+TM_HO_EQUIDISTANT, TM_HO_GAUSS_LOBATTO, TM_HO_PRESCRIBED = 0, 1, 2
 
 
 class TmError(RuntimeError):
@@ -143,6 +145,16 @@ class tm_stack_opt(C.Structure):
                 ("interpolation", C.c_int32), ("mapping", C.c_int32)]
 
 
+class tm_ho_opt(C.Structure):
+    _fields_ = [("order", C.c_int32), ("distribution", C.c_int32), ("nodes", C.POINTER(C.c_double))]
+
+
+class tm_ho_quality(C.Structure):
+    _fields_ = [("elements", C.c_uint64), ("invalid", C.c_uint64), ("orientation", C.c_int32), ("order", C.c_int32),
+                ("min_scaled_jacobian", C.c_double), ("worst_block", C.c_uint64), ("worst_e", C.c_uint64), ("worst_f", C.c_uint64),
+                ("min_jacobian", C.c_double), ("max_jacobian", C.c_double), ("hist", C.c_uint64 * 10)]
+
+
 # every symbol include/tm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "tm_last_error", "tm_abi_version", "tm_set_log", "tm_csr_solve", "tm_tfi_block", "tm_tfi_linear2d", "tm_smooth_mesh", "tm_smoother_create",
@@ -157,6 +169,7 @@ EXPORTS = [
     "tm_stack_weights", "tm_stack_block", "tm_stack_block_host", "tm_stack_smoothers",
     "tm_quality3d_planes_host", "tm_stack_quality", "tm_stack_quality_host", "tm_stack_smoothers_quality", "tm_stack_smoothers_quality_field",
     "tm_quality3d_total",
+    "tm_ho_tables", "tm_ho_check", "tm_ho_elevate", "tm_ho_elevate_host", "tm_smoother_elevate", "tm_ho_quality_total",
     "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
 ]
 
@@ -256,6 +269,12 @@ def lib():
         L.tm_stack_smoothers_quality.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt), C.c_uint64, C.POINTER(tm_quality3d)]
         L.tm_stack_smoothers_quality_field.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt), C.c_uint64, C.c_uint64, C.c_uint64, _dp]
         L.tm_quality3d_total.argtypes = [C.POINTER(tm_quality3d), C.c_uint64, C.POINTER(tm_quality3d)]
+        L.tm_ho_tables.argtypes = [C.POINTER(tm_ho_opt), _dp, _dp, _dp]
+        L.tm_ho_check.argtypes = [C.POINTER(tm_mesh_desc), C.POINTER(tm_ho_opt)]
+        L.tm_ho_elevate.argtypes = [C.POINTER(tm_mesh_desc), C.POINTER(tm_ho_opt), C.c_uint64, _dp, _dp, C.POINTER(tm_ho_quality), _dp]
+        L.tm_ho_elevate_host.argtypes = L.tm_ho_elevate.argtypes
+        L.tm_smoother_elevate.argtypes = [C.c_void_p, C.POINTER(tm_ho_opt), C.c_uint64, _dp, _dp, C.POINTER(tm_ho_quality), _dp]
+        L.tm_ho_quality_total.argtypes = [C.POINTER(tm_ho_quality), C.c_uint64, C.POINTER(tm_ho_quality)]
         L.tm_rccl_unique_id.argtypes =[C.c_char_p, C.c_void_p]
         L.tm_rccl_comm_create.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.tm_rccl_comm_destroy.argtypes = [C.c_void_p]

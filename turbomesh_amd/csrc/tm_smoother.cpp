@@ -12,6 +12,7 @@
 #include "tm_ilu.hpp"
 #include "tm_refine.hpp"
 #include "tm_quality_dev.hpp"
+#include "tm_highorder_dev.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -130,6 +131,7 @@ Smoother::~Smoother() {
     }
     if (export_buf) (void)hipFree(export_buf);
     delete qdev;
+    delete hodev;
     delete ref;
     ref = nullptr;
     csr_free();

@@ -47,6 +47,7 @@ class DeviceArena {
 };
 
 struct QualityDev;
+struct HoDev;
 
 struct Smoother {
     Smoother() = default;
@@ -204,6 +205,9 @@ struct Smoother {
     QualityDev* qdev = nullptr;
     void quality_host(tm_quality* per_block, tm_quality* total);
     void quality_field_host(int64_t block, double* out);
+    // high-order elevation of an owned block from the resident coordinates (tm_highorder.hip): reads X only; buffers as for the quality report
+    HoDev* hodev = nullptr;
+    void elevate_host(const tm_ho_opt* opt, int64_t block, double* x, double* y, tm_ho_quality* q, double* sj);
 
     // building blocks
     void exchange(double2* vec, hipStream_t on = nullptr);   // start (and, without a split hook, finish) the halo exchange of `vec`; on = the handle's stream unless given

@@ -1,0 +1,144 @@
+"""High-order curved elements from smoothed blocks (include/tm_hip.h, "high-order elements"; the reference's roadmap item "high order
+meshes -- equidistant / other distributions").
+
+Every p x p group of cells of a block whose cell counts are multiples of p is one element of order p with (p+1)^2 nodes.  Its nodes are
+the fine mesh itself (equidistant) or the element's degree-p tensor-product interpolant evaluated at another node distribution
+(Gauss-Lobatto, or prescribed); the elements are judged by the Jacobian of that same polynomial at their nodes.
+
+    el = Elevation(4)                          # Gauss-Lobatto nodes
+    el.check(mesh)                             # TmError(InconsistentSize) naming the first block / connection off the element grid
+    X, Y, q, sj = el.block(smoother, b)        # planes (nj, ni), quality.HoQuality, scaled Jacobian per element (Ej, Ei)
+    Elevation(2, "equidistant").mesh(smoother).write("blade.vtk")
+
+Evaluated on the MI355X (kernel K13); `host=True` evaluates the same definition on the CPU (a Mesh only), bit for bit."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass, field
+from typing import List, Tuple
+
+import numpy as np
+
+from . import _capi
+from . import quality as _quality
+
+DISTRIBUTION = {"equidistant": _capi.TM_HO_EQUIDISTANT, "gauss_lobatto": _capi.TM_HO_GAUSS_LOBATTO, "prescribed": _capi.TM_HO_PRESCRIBED}
+VTK_LAGRANGE_QUADRILATERAL = 70
+
+
+def lagrange_quad_order(p):
+    """Local nodes (a, b) of an element of order p in the order of VTK's Lagrange quadrilateral (vtkLagrangeQuadrilateral::
+    PointIndexFromIJK): the corners (0,0), (p,0), (p,p), (0,p); the edges b = 0 (a ascending), a = p (b ascending), b = p (a ascending),
+    a = 0 (b ascending); the interior with a fastest."""
+    order = [(0, 0), (p, 0), (p, p), (0, p)]
+    order += [(a, 0) for a in range(1, p)]
+    order += [(p, b) for b in range(1, p)]
+    order += [(a, p) for a in range(1, p)]
+    order += [(0, b) for b in range(1, p)]
+    order += [(a, b) for b in range(1, p) for a in range(1, p)]
+    return order
+
+
+@dataclass
+class HighOrderMesh:
+    """The elevated blocks of a mesh: per block the X, Y planes as (nj, ni) arrays (i fastest, the order of the export planes), the
+    per-block and total quality.HoQuality and the scaled Jacobian per element as (Ej, Ei) arrays."""
+
+    order: int
+    distribution: str
+    names: List[str] = field(default_factory=list)
+    blocks: List[Tuple[np.ndarray, np.ndarray]] = field(default_factory=list)
+    per_block: List["_quality.HoQuality"] = field(default_factory=list)
+    scaled_jacobian: List[np.ndarray] = field(default_factory=list)
+    total: "_quality.HoQuality | None" = None
+
+    def sizes(self):
+        return [(x.shape[1], x.shape[0]) for x, _ in self.blocks]
+
+    def elements(self):
+        """Per block (Ei, Ej)."""
+        return [((ni - 1) // self.order, (nj - 1) // self.order) for ni, nj in self.sizes()]
+
+    def write(self, filename):
+        """`*.vtk`: a legacy ASCII VTK unstructured grid with one VTK_LAGRANGE_QUADRILATERAL (type 70) per element -- points per block
+        in plane order, blocks concatenated (interface nodes are not merged), coordinates as %.17g; VTK's Lagrange cells assume
+        equidistant nodes, so any other distribution raises ValueError.  Any other name: multi-block 2-D PLOT3D of the elevated nodes
+        (output.write_plot3d)."""
+        from . import output
+
+        if str(filename).lower().endswith(".vtk"):
+            if self.distribution != "equidistant":
+                raise ValueError(f"VTK Lagrange cells assume equidistant nodes: a {self.distribution} elevation goes to PLOT3D")
+            output.write_vtk_lagrange(filename, self.order, self.blocks)
+            return
+        output._format_of(filename)
+        output.write_plot3d(filename, self.sizes(), [(x.reshape(-1), y.reshape(-1)) for x, y in self.blocks])
+
+
+class Elevation:
+    """tm_ho_opt + the calls that take it."""
+
+    def __init__(self, order, distribution="gauss_lobatto", nodes=None):
+        distribution = distribution.replace("-", "_")
+        if distribution not in DISTRIBUTION:
+            raise ValueError(f"distribution {distribution!r}: one of {sorted(DISTRIBUTION)}")
+        if nodes is not None and distribution != "prescribed":
+            raise ValueError("nodes go with distribution='prescribed'")
+        if distribution == "prescribed" and nodes is None:
+            raise ValueError("distribution='prescribed' needs nodes")
+        self.order = int(order)
+        self.distribution = distribution
+        self.nodes = None if nodes is None else np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1)
+        if self.nodes is not None and self.nodes.size != self.order + 1:
+            raise ValueError(f"{self.nodes.size} nodes for order {self.order}: order + 1 are needed")
+        self._opt = _capi.tm_ho_opt(self.order, DISTRIBUTION[distribution], _capi.f64ptr(self.nodes) if self.nodes is not None else None)
+
+    def tables(self):
+        """(nodes[p+1], T[p+1, p+1], D[p+1, p+1]), row = target node (tm_ho_tables: host only)."""
+        n1 = max(1, self.order + 1)
+        t, T, D = np.empty(n1), np.empty((n1, n1)), np.empty((n1, n1))
+        _capi.check(_capi.lib().tm_ho_tables(C.byref(self._opt), _capi.f64ptr(t), _capi.f64ptr(T), _capi.f64ptr(D)))
+        return t, T, D
+
+    def check(self, mesh):
+        """TmError (InconsistentSize) naming the first block or connection range that does not lie on the element grid (tm_ho_check)."""
+        md = _capi.MeshDesc(mesh, with_coordinates=False)
+        _capi.check(_capi.lib().tm_ho_check(md.ref(), C.byref(self._opt)))
+
+    def block(self, mesh_or_smoother, b, host=False, planes=True):
+        """(X, Y, HoQuality, sj) of block b: the elevated nodes as (nj, ni) arrays (None, None with planes=False: the report alone), the
+        block's record and the scaled Jacobian per element as an (Ej, Ei) array, NaN for invalid elements.  A discrete.Mesh is uploaded
+        per call (tm_ho_elevate; host=True: tm_ho_elevate_host, no GPU); a smooth.Smoother gives the coordinates resident in its handle
+        (tm_smoother_elevate)."""
+        resident = hasattr(mesh_or_smoother, "_h")
+        mesh = mesh_or_smoother._mesh if resident else mesh_or_smoother
+        if resident and host:
+            raise ValueError("host=True evaluates host coordinates: pass the mesh, not the handle")
+        ni, nj = mesh.blocks[b].points.size
+        p = max(1, self.order)
+        X = np.empty((nj, ni), dtype=np.float64) if planes else None
+        Y = np.empty((nj, ni), dtype=np.float64) if planes else None
+        sj = np.empty((max(0, (nj - 1) // p), max(0, (ni - 1) // p)), dtype=np.float64)
+        q = _capi.tm_ho_quality()
+        args = (C.byref(self._opt), b, _capi.f64ptr(X) if planes else None, _capi.f64ptr(Y) if planes else None, C.byref(q), _capi.f64ptr(sj))
+        L = _capi.lib()
+        if resident:
+            _capi.check(L.tm_smoother_elevate(mesh_or_smoother._h, *args))
+        else:
+            md = _capi.MeshDesc(mesh)
+            _capi.check((L.tm_ho_elevate_host if host else L.tm_ho_elevate)(md.ref(), *args))
+        return X, Y, _quality.HoQuality.from_struct(q), sj
+
+    def mesh(self, mesh_or_smoother, host=False) -> HighOrderMesh:
+        """Every block, with the per-block and total quality."""
+        first = mesh_or_smoother._mesh if hasattr(mesh_or_smoother, "_h") else mesh_or_smoother
+        self.check(first)
+        m = HighOrderMesh(self.order, self.distribution)
+        for b, name in enumerate(first.names):
+            X, Y, q, sj = self.block(mesh_or_smoother, b, host=host)
+            m.names.append(name)
+            m.blocks.append((X, Y))
+            m.per_block.append(q)
+            m.scaled_jacobian.append(sj)
+        m.total = _quality.total_ho(m.per_block)
+        return m

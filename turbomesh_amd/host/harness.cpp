@@ -6,6 +6,7 @@
 //   tm_harness tm <ni> <nj> <iterations>               the Thomas-Middlecoff control field on a clustered rectangle (exit 0: it kept the clustering)
 //   tm_harness stack <ni> <nj> <ncuts> <nlayers>       config-5 cuts (amplitude 0.05 + 0.001 c), five relaxation sweeps per handle, stacked on the
 //                                                      device by the natural cubic spline: a checksum per layer (exit 0: layers at cuts equal the cuts)
+//   tm_harness elevate <ni> <nj> <order>   curved elements of that order from a smoothed block (kernel K13; exit 0: corners unchanged, equal to the CPU's)
 //   tm_harness stack-quality <ni> <nj> <ncuts> <nlayers>   the same cuts: the 3-D quality record of the stacked block (kernel K12; exit 0: equal to the CPU's)
 //   tm_harness csr                                     the linear-solver slot (seam 2) on the reference's 5 x 5 known answer
 //   tm_harness ranks <world> <rank> <idfile> <nblocks> <ni> <nj> <iterations> [relax|bicgstab] [dump.bin]
@@ -313,8 +314,45 @@ static int stackQuality(std::size_t ni, std::size_t nj, std::size_t ncuts, std::
     return same ? 0 : 1;
 }
 
+// tm_harness elevate <ni> <nj> <order>: the config-2 block, five relaxation sweeps; Gauss-Lobatto elements of `order` from the
+// coordinates resident in the handle (highorder::elevate -> tm_smoother_elevate), compared with the CPU's evaluation of the
+// downloaded coordinates (planes, scaled Jacobians and the record bit for bit); element corners must be the smoothed nodes.
+static int elevateBlock(std::size_t ni, std::size_t nj, int order) {
+    smoothing::solver::Option opt;
+    opt.inner = TM_INNER_RELAX;
+    discrete::Mesh mesh = buildSingle(ni, nj);
+    highorder::Option ho;
+    ho.order = order;
+    highorder::check(mesh, ho);
+    smoothing::smooth::Smoother sm(mesh, opt, smoothing::wall_control_function::Algorithm::laplace());
+    sm.iterate(5);
+    const highorder::Elevated dev = highorder::elevate(sm, ho, 0);
+    sm.download();
+    const highorder::Elevated host = highorder::elevate(mesh, ho, 0, true);
+    const tm_ho_quality& q = dev.quality;
+    std::printf("elevate: elements %llu invalid %llu min sj %.17g at (e %llu, f %llu) jacobian %.17g .. %.17g orientation %d order %d\n",
+                static_cast<unsigned long long>(q.elements), static_cast<unsigned long long>(q.invalid), q.min_scaled_jacobian,
+                static_cast<unsigned long long>(q.worst_e), static_cast<unsigned long long>(q.worst_f), q.min_jacobian, q.max_jacobian, q.orientation, q.order);
+    bool corners = true;
+    const std::size_t p = static_cast<std::size_t>(order);
+    for (std::size_t i = 0; i < ni; i += p)
+        for (std::size_t j = 0; j < nj; j += p) {
+            const Vec2d v = mesh.blocks[0].points.getIndex(i, j);
+            if (!(dev.x[j * ni + i] == v.data[0] && dev.y[j * ni + i] == v.data[1])) corners = false;
+        }
+    std::printf("elevate: corners unchanged: %s\n", corners ? "yes" : "no");
+    const auto same_bits = [](const std::vector<double>& a, const std::vector<double>& b) {
+        return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), sizeof(double) * a.size()) == 0);
+    };
+    const bool same = same_bits(dev.x, host.x) && same_bits(dev.y, host.y) && same_bits(dev.sj, host.sj) && std::memcmp(&dev.quality, &host.quality, sizeof(tm_ho_quality)) == 0;
+    std::printf("elevate: device equals host: %s\n", same ? "yes" : "no");
+    return corners && same ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     try {
+        if (argc >= 5 && std::strcmp(argv[1], "elevate") == 0)
+            return elevateBlock(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), static_cast<int>(std::strtol(argv[4], nullptr, 10)));
         if (argc >= 6 && std::strcmp(argv[1], "stack-quality") == 0)
             return stackQuality(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10));
         if (argc >= 6 && std::strcmp(argv[1], "stack") == 0)
@@ -324,7 +362,7 @@ int main(int argc, char** argv) {
             return thomasMiddlecoff(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "ranks") == 0) return runRank(argc, argv);
         if (argc < 5) {
-            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n", argv[0], argv[0], argv[0], argv[0]);
+            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n", argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 2;
         }
         int a = 2;

@@ -499,6 +499,57 @@ inline tm_quality3d quality(const Block3d& b, std::size_t block = 0) {
 }
 }  // namespace stack
 
+// high-order elements (tm_hip.h): every p x p group of cells of a block is one curved element of order p; its nodes at the wanted
+// distribution and its Jacobian come from the element's degree-p tensor-product interpolant
+namespace highorder {
+struct Option {
+    int32_t order = 2;
+    int32_t distribution = TM_HO_GAUSS_LOBATTO;
+    std::vector<double> nodes;    // TM_HO_PRESCRIBED: order + 1 values, 0 first, 1 last, strictly increasing
+    tm_ho_opt c_struct() const { return tm_ho_opt{order, distribution, nodes.empty() ? nullptr : nodes.data()}; }
+};
+struct Elevated {                 // planes with i fastest: element j*ni + i; sj[f*Ei + e], NaN for invalid elements
+    std::size_t ni = 0, nj = 0, Ei = 0, Ej = 0;
+    std::vector<double> x, y, sj;
+    tm_ho_quality quality{};
+};
+namespace detail {
+inline Elevated sized(std::size_t ni, std::size_t nj, const Option& o) {
+    if (o.order < 1 || o.order > TM_HO_MAX_ORDER) throw Error(TM_E_ARG, "the order must be 1 .. TM_HO_MAX_ORDER");
+    Elevated r;
+    r.ni = ni, r.nj = nj, r.Ei = (ni - 1) / static_cast<std::size_t>(o.order), r.Ej = (nj - 1) / static_cast<std::size_t>(o.order);
+    r.x.resize(ni * nj + 1), r.y.resize(ni * nj + 1), r.sj.resize(r.Ei * r.Ej + 1);
+    return r;
+}
+inline void trim(Elevated& r) { r.x.resize(r.ni * r.nj), r.y.resize(r.ni * r.nj), r.sj.resize(r.Ei * r.Ej); }
+}  // namespace detail
+inline void check(discrete::Mesh& mesh, const Option& o) {
+    smoothing::smooth::Desc d(mesh);
+    const tm_ho_opt ho = o.c_struct();
+    core::check(tm_ho_check(&d.desc, &ho));
+}
+// `block` from the coordinates RESIDENT in the handle (tm_smoother_elevate, kernel K13)
+inline Elevated elevate(const smoothing::smooth::Smoother& s, const Option& o, std::size_t block) {
+    const tm_mesh_desc& d = s.desc();
+    if (block >= d.nblocks) throw Error(TM_E_ARG, "block index past the mesh");
+    Elevated r = detail::sized(d.blocks[block].ni, d.blocks[block].nj, o);
+    const tm_ho_opt ho = o.c_struct();
+    core::check(tm_smoother_elevate(s.handle(), &ho, block, r.x.data(), r.y.data(), &r.quality, r.sj.data()));
+    detail::trim(r);
+    return r;
+}
+// the same from host coordinates, uploaded per call (tm_ho_elevate) or, host = true, evaluated on the CPU (tm_ho_elevate_host)
+inline Elevated elevate(discrete::Mesh& mesh, const Option& o, std::size_t block, bool host = false) {
+    if (block >= mesh.blocks.size()) throw Error(TM_E_ARG, "block index past the mesh");
+    smoothing::smooth::Desc d(mesh);
+    Elevated r = detail::sized(mesh.blocks[block].points.size[0], mesh.blocks[block].points.size[1], o);
+    const tm_ho_opt ho = o.c_struct();
+    core::check((host ? tm_ho_elevate_host : tm_ho_elevate)(&d.desc, &ho, block, r.x.data(), r.y.data(), &r.quality, r.sj.data()));
+    detail::trim(r);
+    return r;
+}
+}  // namespace highorder
+
 namespace discrete {
 inline Quality Mesh::quality(bool host) {
     smoothing::smooth::Desc d(*this);

@@ -100,6 +100,73 @@ def read_plot3d_3d(filename):
     return out
 
 
+def write_vtk_lagrange(filename, order, blocks):
+    """Legacy ASCII VTK unstructured grid of curved quadrilaterals: one VTK_LAGRANGE_QUADRILATERAL (type 70) of `order` per element.
+    blocks: per block the (X, Y) planes as (nj, ni) arrays whose ni-1 and nj-1 are multiples of `order` (highorder.HighOrderMesh.blocks).
+    Points: per block in plane order (i fastest), blocks concatenated, %.17g (reads back bit for bit), z = 0.  Local node (a, b) of
+    element (e, f) is point (f*order + b)*ni + e*order + a of its block, listed in the order of highorder.lagrange_quad_order.
+    Pure file writing (no device)."""
+    from .highorder import VTK_LAGRANGE_QUADRILATERAL, lagrange_quad_order
+
+    p = int(order)
+    local = lagrange_quad_order(p)
+    la = np.array([a for a, _ in local], dtype=np.int64)
+    lb = np.array([b for _, b in local], dtype=np.int64)
+    cells, offset, npoints = [], 0, 0
+    for X, _ in blocks:
+        nj, ni = X.shape
+        if (ni - 1) % p or (nj - 1) % p:
+            raise ValueError(f"a block of {ni} x {nj} nodes has no elements of order {p}")
+        Ei, Ej = (ni - 1) // p, (nj - 1) // p
+        f, e = np.meshgrid(np.arange(Ej, dtype=np.int64), np.arange(Ei, dtype=np.int64), indexing="ij")   # elements with e fastest
+        ids = offset + (f.reshape(-1, 1) * p + lb) * ni + e.reshape(-1, 1) * p + la
+        cells.append(ids)
+        offset += ni * nj
+    npoints = offset
+    cells = np.concatenate(cells) if cells else np.empty((0, len(local)), dtype=np.int64)
+    with open(filename, "w") as fh:
+        fh.write(f"# vtk DataFile Version 4.2\ncurved quadrilaterals of order {p}\nASCII\nDATASET UNSTRUCTURED_GRID\n")
+        fh.write(f"POINTS {npoints} double\n")
+        for X, Y in blocks:
+            fh.write("".join("%.17g %.17g 0\n" % (x, y) for x, y in zip(X.reshape(-1).tolist(), Y.reshape(-1).tolist())))
+        fh.write(f"CELLS {len(cells)} {len(cells) * (len(local) + 1)}\n")
+        head = str(len(local))
+        fh.write("".join(head + " " + " ".join(map(str, row)) + "\n" for row in cells.tolist()))
+        fh.write(f"CELL_TYPES {len(cells)}\n")
+        fh.write(f"{VTK_LAGRANGE_QUADRILATERAL}\n" * len(cells))
+
+
+def read_vtk_lagrange(filename):
+    """-> (points (n, 3) float64, cells (ncells, nodes per cell) int64, cell_types (ncells,) int64) of a file written by
+    write_vtk_lagrange (legacy ASCII, every cell with the same number of nodes)."""
+    with open(filename) as fh:
+        tok = fh.read().split("\n", 4)
+    if len(tok) < 5 or not tok[0].startswith("# vtk DataFile") or tok[2].strip() != "ASCII" or tok[3].split() != ["DATASET", "UNSTRUCTURED_GRID"]:
+        raise ValueError(f"{filename}: not a legacy ASCII VTK unstructured grid")
+    w = tok[4].split()
+    k = 0
+    if w[k] != "POINTS" or w[k + 2] != "double":
+        raise ValueError(f"{filename}: POINTS <n> double expected")
+    n = int(w[k + 1])
+    k += 3
+    points = np.array([float(v) for v in w[k:k + 3 * n]], dtype=np.float64).reshape(n, 3)
+    k += 3 * n
+    if w[k] != "CELLS":
+        raise ValueError(f"{filename}: CELLS expected")
+    nc, size = int(w[k + 1]), int(w[k + 2])
+    k += 3
+    flat = np.array([int(v) for v in w[k:k + size]], dtype=np.int64)
+    k += size
+    per = size // nc - 1 if nc else 0
+    rows = flat.reshape(nc, per + 1) if nc else flat.reshape(0, 1)
+    if nc and not np.all(rows[:, 0] == per):
+        raise ValueError(f"{filename}: cells of different sizes")
+    if w[k] != "CELL_TYPES" or int(w[k + 1]) != nc:
+        raise ValueError(f"{filename}: CELL_TYPES expected")
+    types = np.array([int(v) for v in w[k + 2:k + 2 + nc]], dtype=np.int64)
+    return points, rows[:, 1:].copy(), types
+
+
 def _format_of(filename):
     ext = os.path.splitext(filename)[1].lower()
     if ext == ".cgns":

@@ -142,6 +142,11 @@ class Smoother:
         _capi.check(_capi.lib().tm_smoother_quality_field(self._h, block, _capi.f64ptr(plane)))
         return plane.reshape(nj - 1, ni - 1).T
 
+    def elevate(self, elevation, block: int):
+        """(X, Y, HoQuality, sj) of an owned block's curved elements from the coordinates resident in the handle (tm_smoother_elevate):
+        `elevation` is a highorder.Elevation; see Elevation.block."""
+        return elevation.block(self, block)
+
     def write_quality(self, filename):
         """The per-cell planes of every block as a PLOT3D function file (one variable, sizes (ni-1, nj-1))."""
         from .. import output
