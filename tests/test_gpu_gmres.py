@@ -61,14 +61,12 @@ def test_gmres_and_bicgstab_reach_the_same_iterates_and_fixed_point():
     assert reached and _rms(mesh_flat(c), mesh_flat(d)) <= 1e-10
 
 
-def test_device_recurrence_against_the_faithful_cpu_gmres_on_one_frozen_system():
-    # one frozen system (the first Picard solve of a perturbed block), tolerance on the scaled residual: the oracle's restatement of
-    # GMRES.zig with the diagonal preconditioner solves D^-1 A x = D^-1 b when the system is row-equilibrated first -- done here through
-    # scipy on the oracle-assembled CSR -- and must take the same number of Arnoldi steps as the device, give or take the rounding at
-    # the stop test, and land on the same solution
+def frozen_system_against_the_cpu_gmres(ni, nj, prepare=None):
+    """One frozen system (the first Picard solve of a perturbed ni x nj block) on the device and by the CPU GMRES(30) below; `prepare(sm)` runs
+    on the handle before it iterates (tests/test_gpu_chunk_heights.py switches profiling on there).  Asserts what the test below states."""
     import scipy.sparse as sp
 
-    mesh = configs.single_block(41, 37, perturb=0.25)
+    mesh = configs.single_block(ni, nj, perturb=0.25)
     om = OracleMesh(mesh)
     s = oracle.System(om)
     s.fill(0)
@@ -76,8 +74,10 @@ def test_device_recurrence_against_the_faithful_cpu_gmres_on_one_frozen_system()
     d = A.diagonal()
     As = sp.diags(1.0 / d) @ A
     rtol = 1e-12
-    x_dev = configs.single_block(41, 37, perturb=0.25)
+    x_dev = configs.single_block(ni, nj, perturb=0.25)
     with smooth.Smoother(x_dev, solver.Option.hip(inner=solver.Inner.gmres, rtol=rtol, check_every=1)) as sm:
+        if prepare is not None:
+            prepare(sm)
         st = sm.iterate(1)
         sm.download()
     for c, b in enumerate((s.rhs_x, s.rhs_y)):
@@ -90,6 +90,14 @@ def test_device_recurrence_against_the_faithful_cpu_gmres_on_one_frozen_system()
         assert np.abs(got - x).max() <= 1e-9 * max(1.0, np.abs(x).max()), c
         assert np.linalg.norm(bs - As @ got) <= 10 * rtol * np.linalg.norm(bs)
     assert st["not_converged"] == 0 and st["inner_iterations"] > 30     # at least one restart happened
+
+
+def test_device_recurrence_against_the_faithful_cpu_gmres_on_one_frozen_system():
+    # one frozen system (the first Picard solve of a perturbed block), tolerance on the scaled residual: the oracle's restatement of
+    # GMRES.zig with the diagonal preconditioner solves D^-1 A x = D^-1 b when the system is row-equilibrated first -- done here through
+    # scipy on the oracle-assembled CSR -- and must take the same number of Arnoldi steps as the device, give or take the rounding at
+    # the stop test, and land on the same solution
+    frozen_system_against_the_cpu_gmres(41, 37)
 
 
 def _gmres30(A, b, x, tol, m=30, cap=20000):

@@ -196,13 +196,34 @@ def _run(case, env_name, env, monkeypatch, full=False):
     return z
 
 
-LONE = [(5, 5), (6, 6), (9, 8), (33, 33), (34, 61), (66, 122), (5, 70), (300, 4), "stretched", "plate_le_white"]
+# (1545, 9), (7700, 5): tall thin blocks whose fine levels take 6- and 18-row chunks by the per-block rule of K2 (more than 512 chunks of
+# 3 .. 15 rows), so `unfused` sends them through MODE_MG_FIRST2 / MODE_MG_RESID / MODE_MG_SMOOTH of the six-row-group k_apply; every other
+# lone block here fits 512 workgroups at 3 rows
+LONE = [(5, 5), (6, 6), (9, 8), (33, 33), (34, 61), (66, 122), (5, 70), (300, 4), "stretched", "plate_le_white", (1545, 9), (7700, 5)]
 
 
 @pytest.mark.parametrize("case", LONE, ids=str)
 @pytest.mark.parametrize("env_name,env", [("default", {}), ("unfused", UNFUSED)])
 def test_vcycle_against_the_reference_cycle(case, env_name, env, monkeypatch):
     _run(case, env_name, env, monkeypatch)
+
+
+@pytest.mark.parametrize("case", [(1545, 9), (7700, 5)], ids=str)
+def test_vcycle_of_tall_blocks_is_the_same_bit_for_bit_one_sweep_per_pass(case, monkeypatch):
+    # The 16 d bar above cannot see a last bit.  The one-sweep-per-pass cycle (the MODE_MG_* levels of k_apply, here with six-row groups on
+    # the fine level) performs the operation sequence of the default cycle (k_mg_pair, the prolongation folded in) node by node -- tests/
+    # test_gpu_multigrid.py pins that on whole solves at 3-row chunks -- so one application of the preconditioner gives the same bits.
+    out = []
+    for env in ({}, UNFUSED):
+        for k in UNFUSED:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        mesh, _, _ = _build(case)
+        with smooth.Smoother(mesh, solver.Option.hip(**MG)) as sm:
+            out.append(sm.precondition_probe(_rand((sm.dof, 2), 31)))
+    assert np.isfinite(out[0]).all() and np.abs(out[0]).max() > 0
+    assert np.array_equal(out[0], out[1]), float(np.abs(out[0] - out[1]).max())
 
 
 def test_vcycle_with_the_prolongation_folded_on_every_level(monkeypatch):
