@@ -624,7 +624,7 @@ int tm_quality3d_total(const tm_quality3d* per_block, uint64_t n, tm_quality3d* 
  *   per element  Jmin, Jmax of o*J over its nodes; invalid if Jmin <= 0 or any J is non-finite; otherwise its scaled Jacobian
  *                sj = Jmin/Jmax, the usual curved-element measure.  It is SAMPLED AT THE NODES: a positive sj is necessary for a valid
  *                (injective) element, not sufficient -- the Jacobian of a degree-p map is a polynomial of degree 2p-1 per direction and
- *                can dip below zero between the nodes.
+ *                can dip below zero between the nodes.  The sufficient test is tm_ho_certify (next section).
  *   min_scaled_jacobian  min of sj over valid elements, (worst_block, worst_e, worst_f) its element, ties to the lowest (block, e, f);
  *                NaN and 0, 0, 0 when no element is valid
  *   min_jacobian / max_jacobian   the extremes of o*J over valid elements (NaN when there is none)
@@ -634,7 +634,7 @@ int tm_quality3d_total(const tm_quality3d* per_block, uint64_t n, tm_quality3d* 
  * tm_ho_quality_total: counts and hist summed, extremes combined, the worst element the one with the smallest value, orientation and
  * order the blocks' common one or 0; records with elements == 0 are left out.  Host only.
  * Not served: order elevation in span for stacked blocks; re-projection of wall nodes onto the blade spline (the interpolant of the
- * on-spline nodes is used as it is); reconciling interface nodes across blocks; Gmsh and HOPR output. */
+ * on-spline nodes is used as it is); reconciling interface nodes across blocks; Gmsh and HOPR output; repairing invalid elements. */
 #define TM_HO_MAX_ORDER 8
 enum { TM_HO_EQUIDISTANT = 0, TM_HO_GAUSS_LOBATTO = 1, TM_HO_PRESCRIBED = 2 };
 typedef struct tm_ho_opt {               /* 16 bytes */
@@ -668,6 +668,72 @@ int tm_ho_elevate_host(const tm_mesh_desc* mesh, const tm_ho_opt* opt, uint64_t 
  * NULL handle: TM_E_ARG.  A block that fails the size rule: TM_E_SIZE.  Bit-identical to tm_ho_elevate on the downloaded coordinates. */
 int tm_smoother_elevate(tm_smoother* s, const tm_ho_opt* opt, uint64_t block, double* x, double* y, tm_ho_quality* q, double* sj);
 int tm_ho_quality_total(const tm_ho_quality* per_block, uint64_t n, tm_ho_quality* total);
+
+/* ------------------------------------------------------------------ high-order elements: certificate (Bezier bounds of the Jacobian)
+ * The record above samples J at the nodes.  The certificate bounds J on the WHOLE element: J of the degree-p interpolant of the source
+ * nodes X[e*p+m][f*p+n] (u, v = 0 .. p) is a polynomial of degree 2p-1 per direction, and its Bernstein coefficients enclose it.  That
+ * polynomial is the same for every node distribution, so the certificate depends on the order alone: `distribution` and `nodes` are
+ * validated as in tm_ho_elevate and otherwise ignored.  All arithmetic IEEE fp64, nothing fused.
+ * Tables, on the host in long double (from exact integers), every entry rounded once:
+ *   M[i][m]  the Bernstein coefficient i of the Lagrange polynomial of node m/p, (p+1) x (p+1); rows 0 and p are exact unit vectors
+ *   wu[k][i] = C(p-1,i) C(p,k-i) / C(2p-1,k)  (0 <= k-i <= p, else 0),  wv[l][j] = C(p,j) C(p-1,l-j) / C(2p-1,l)  (0 <= l-j <= p-1, else 0)
+ * Control points: d[m][n] = X[e*p+m][f*p+n] - X[e*p][f*p] (the element's first corner: J does not see a translation, and the rounding
+ *   of everything after is then relative to the element's extent, not to its distance from the origin), then per component
+ *   W[m][j] = M[j][0]*d[m][0], then + M[j][n]*d[m][n] for n = 1 .. p;   C[i][j] = M[i][0]*W[0][j], then + M[i][m]*W[m][j] for m = 1 .. p.
+ * Derivative coefficients on u, v in [0, p] (K13's units, no factor):
+ *   xu[i][j] = C[i+1][j] - C[i][j] (i < p),  xv[i][j] = C[i][j+1] - C[i][j] (j < p), likewise yu, yv.
+ * Coefficients of J, k, l = 0 .. 2p-1:
+ *   B[k][l] = sum_i wu[k][i] * ( sum_j wv[l][j] * (xu[i][j]*yv[k-i][l-j] - yu[i][j]*xv[k-i][l-j]) ),
+ *   i ascending over max(0,k-p) .. min(p-1,k), j ascending over max(0,l-p+1) .. min(p,l), both sums started from 0.
+ *   The four corner coefficients are J at the element's corners; min B <= J <= max B on the patch.
+ * Subdivision: a patch is split at its midpoint in u (along k), then each half in v (along l), by de Casteljau with 0.5*(a + b); the
+ *   corners of the patches of level L are values of J at multiples of p/2^L.
+ * Orientation o: K13's (0 counts as +1); the call runs K13's report on the block first to learn it and the nodal verdicts.
+ * Guard: g = (G(p) * 2^-53) * R, R = (max|xu| + max|xv|) * (max|yu| + max|yv|) over the element's derivative coefficients -- that is
+ *   S = max|xu|*max|yv| + max|xv|*max|yu| PLUS the cross products max|xu|*max|yu| + max|xv|*max|yv|.  The conversion rounds relative to the
+ *   element's extent in both directions, so the error of a coefficient scales with R; on a thin cell at an angle to the axes (a boundary
+ *   layer) R exceeds S by the aspect ratio, and S alone does not bound the error there.
+ *   G(p) = 2 p (4p+14) L^2 + 18p + 4 with L = ||M||_inf the largest absolute row sum (fp64, rounded once): g bounds the rounding error of
+ *   a coefficient at any level up to TM_HO_CERT_MAX_DEPTH, with no condition on the element's shape (DESIGN.md, section 4, K14 derives it).
+ * Status of an element, breadth first for L = 0 .. max_depth (0 <= max_depth <= TM_HO_CERT_MAX_DEPTH = 4):
+ *   a patch is INVALID if a corner has o*B <= 0 or any coefficient is non-finite (at level 0 also if K13's nodal record calls the
+ *   element invalid), else PROVEN if min(o*B) > g, else undecided.  The first level with an invalid patch makes the element
+ *   TM_HO_INVALID; otherwise the first level without an undecided patch makes it TM_HO_PROVEN; otherwise the undecided patches are split
+ *   and the next level is judged; TM_HO_UNDECIDED if level max_depth still has one.  depth: that level.
+ *   lo = min over the leaf patches (the proven patches of the levels above `depth`, every patch of level `depth`) of min(o*B), minus g;
+ *   hi = the max likewise, plus g:  lo <= o*J <= hi on the whole element.  For a proven element lo/hi is a certified lower bound of
+ *   the scaled Jacobian min J / max J that K13 samples.
+ * Record: counts; hidden_invalid = invalid here but valid in K13's nodal record; decided_at[L] = proven and invalid elements decided
+ *   at level L; min_scaled_bound = min of lo/hi over proven elements with its element (ties to the lowest (block, e, f); NaN, 0, 0, 0
+ *   when none is proven); the lowest (e, f) that is not proven, has_unproven = 0 and zeros when all are.  No summed floating-point
+ *   field: device and host agree bit for bit in every field, in status and in bounds.
+ * tm_ho_certificate_total: counts summed, min_scaled_bound and the first unproven element from the lowest block, orientation, order
+ *   and max_depth the blocks' common one or 0 (-1 for max_depth); records with elements == 0 are left out.  Host only.
+ * Not served: repairing the elements the certificate rejects; adaptive (non-uniform) subdivision. */
+#define TM_HO_CERT_MAX_DEPTH 4
+enum { TM_HO_PROVEN = 0, TM_HO_INVALID = 1, TM_HO_UNDECIDED = 2 };
+typedef struct tm_ho_certificate {      /* 152 bytes */
+    uint64_t elements, proven, invalid, undecided, hidden_invalid;
+    int32_t  orientation, order, max_depth, has_unproven;
+    uint64_t decided_at[5];
+    double   min_scaled_bound;
+    uint64_t worst_block, worst_e, worst_f;
+    uint64_t first_unproven_block, first_unproven_e, first_unproven_f;
+} tm_ho_certificate;
+/* M [(p+1)*(p+1)], wu [2p*p], wv [2p*(p+1)], G(p) and ||M||_inf; any output may be NULL.  Host only */
+int tm_ho_certify_tables(const tm_ho_opt* opt, double* M, double* wu, double* wv, double* G, double* norm);
+/* Block `block` of a mesh given on the host, certified on the device (K13's report, then kernel K14).  status, when given, receives
+ * Ei*Ej bytes as status[f*Ei + e]; bounds 2*Ei*Ej doubles, bounds[2*(f*Ei + e)] = (lo, hi); cert may be NULL.  Errors as tm_ho_elevate;
+ * a max_depth outside 0 .. TM_HO_CERT_MAX_DEPTH: TM_E_ARG. */
+int tm_ho_certify(const tm_mesh_desc* mesh, const tm_ho_opt* opt, int32_t max_depth, uint64_t block, tm_ho_certificate* cert, uint8_t* status, double* bounds);
+/* the same definition on the host: no GPU touched; every output equals the device's bit for bit */
+int tm_ho_certify_host(const tm_mesh_desc* mesh, const tm_ho_opt* opt, int32_t max_depth, uint64_t block, tm_ho_certificate* cert, uint8_t* status, double* bounds);
+/* The same kernels on the coordinates resident in the handle, behind its pending work on its stream; modifies neither the coordinates
+ * nor any solver state; buffers as tm_smoother_elevate.  Errors as tm_smoother_elevate.  Bit-identical to tm_ho_certify on the download. */
+int tm_smoother_certify(tm_smoother* s, const tm_ho_opt* opt, int32_t max_depth, uint64_t block, tm_ho_certificate* cert, uint8_t* status, double* bounds);
+/* The (2p)^2 coefficients of element (e, f) as B[k*2p + l], NOT multiplied by o.  An element past the block: TM_E_ARG.  Host only */
+int tm_ho_jacobian_bezier_host(const tm_mesh_desc* mesh, const tm_ho_opt* opt, uint64_t block, uint64_t e, uint64_t f, double* B);
+int tm_ho_certificate_total(const tm_ho_certificate* per_block, uint64_t n, tm_ho_certificate* total);
 
 /* ------------------------------------------------------------------ host-only planning (no GPU needed)
  * The perimeter-row table the device kernels consume, exported as CSR so it can be compared with

@@ -19,7 +19,11 @@ and --output becomes a multi-block 3-D PLOT3D file; --stack-quality / --fail-on-
 "high-order elements"): the cell counts of every block and the interface ranges must be multiples of P, which is checked before
 anything is smoothed; the elements are formed on the device from the coordinates resident in the handle, their report is logged per block
 and for the mesh, and --output takes the elevated nodes (.vtk: Lagrange quadrilaterals, equidistant nodes only; .xyz / .p3d: PLOT3D).
-Without --order nothing changes."""
+--certify [DEPTH] with --order: the elements are also judged on their WHOLE area by the Bernstein coefficients of their Jacobian, with up
+to DEPTH (default 3, at most 4) subdivisions (include/tm_hip.h "high-order elements: certificate"): proven, invalid or undecided per
+element, logged per block and for the mesh next to the nodal report; --fail-on-invalid-elements then also counts the elements that
+are folded between their nodes, and --fail-on-unproven-elements exits non-zero when any element is not proven.
+Without --order nothing changes; without --certify neither does --order."""
 from __future__ import annotations
 
 import argparse
@@ -106,6 +110,10 @@ def _run(ap, args, config, keep=None, tag=""):
             hom = elevation.mesh(sm)   # from the resident coordinates
             quality.log_report_ho(qlog, hom.names, hom.per_block, hom.total, tag + "elevate")
             stats["highorder"] = hom
+            if getattr(args, "certify", None) is not None:
+                total, per_block, _, _ = elevation.certify(sm, max_depth=args.certify)   # from the resident coordinates
+                quality.log_report_ho_certificate(qlog, hom.names, per_block, total, tag + "certify")
+                stats["certificate"] = {"per_block": per_block, "total": total}
     return inp, mesh, sm, stats, after
 
 
@@ -193,6 +201,12 @@ def main(argv=None):
                     help="with --order: node distribution inside the elements (default: gauss-lobatto; equidistant for a .vtk output)")
     ap.add_argument("--fail-on-invalid-elements", action="store_true",
                     help="with --order: exit non-zero, after the file is written, when elements with a non-positive Jacobian at a node remain")
+    ap.add_argument("--certify", nargs="?", type=int, const=3, default=None, metavar="DEPTH",
+                    help="with --order: certify every element on its whole area by the Bernstein coefficients of its Jacobian with up to DEPTH "
+                         "(0 .. 4, default 3) subdivisions; logged per block and for the mesh; --fail-on-invalid-elements then counts the "
+                         "elements folded between their nodes too")
+    ap.add_argument("--fail-on-unproven-elements", action="store_true",
+                    help="with --certify: exit non-zero, after the file is written, when any element is not proven valid (invalid or undecided)")
     ap.add_argument("--stack", nargs="+", metavar="CFG", default=None,
                     help="further input files: the spanwise cuts after `config`, in span order.  Every file runs the path above with its own "
                          "handle; the smoothed cuts are then stacked into 3-D blocks on the device and --output becomes a multi-block 3-D PLOT3D file")
@@ -216,6 +230,13 @@ def main(argv=None):
         ap.error("--stack-quality and --fail-on-inverted-3d go with --stack")
     if args.order is None and (args.nodes or args.fail_on_invalid_elements):
         ap.error("--nodes and --fail-on-invalid-elements go with --order")
+    if args.certify is None and args.fail_on_unproven_elements:
+        ap.error("--fail-on-unproven-elements goes with --certify")
+    if args.certify is not None:
+        if args.order is None:
+            ap.error("--certify goes with --order")
+        if not 0 <= args.certify <= 4:
+            ap.error("--certify: 0 .. 4")
     if args.order is not None:
         if args.stack is not None:
             ap.error("--order elevates 2-D blocks: it does not go with --stack")
@@ -255,10 +276,18 @@ def main(argv=None):
     elif out:
         mesh.write(out)
         logging.getLogger("output").info("wrote %s (%d blocks, %d nodes)", out, len(mesh.blocks), sum(b.points.data.shape[0] * b.points.data.shape[1] for b in mesh.blocks))
+    cert = stats.get("certificate")
+    if args.fail_on_invalid_elements and hom.total.ok and cert is not None and cert["total"].hidden_invalid:
+        sys.exit(f"high-order elements: {cert['total'].hidden_invalid} elements of order {hom.order} are valid at their nodes and folded between them "
+                 f"({cert['total'].invalid} invalid by the certificate)")
     if args.fail_on_invalid_elements and not hom.total.ok:
         bad = next(q for q in hom.per_block if not q.ok)
         sys.exit(f"high-order elements: {hom.total.invalid} invalid elements of order {hom.order} after smoothing "
                  f"(first in block {hom.per_block.index(bad)}: {bad.invalid} of {bad.elements})")
+    if args.fail_on_unproven_elements and not cert["total"].ok:
+        t = cert["total"]
+        sys.exit(f"high-order elements: {t.elements - t.proven} of {t.elements} elements of order {hom.order} are not proven valid ({t.invalid} invalid, "
+                 f"{t.undecided} undecided at depth {t.max_depth}; first: block {t.first_unproven_block}, e {t.first_unproven_e}, f {t.first_unproven_f})")
     if args.fail_on_inverted and not after[1].ok:
         sys.exit(f"mesh quality: {after[1].inverted} inverted and {after[1].degenerate} degenerate cells after smoothing "
                  f"(worst: block {after[1].worst_block}, i {after[1].worst_i}, j {after[1].worst_j})")

@@ -29,6 +29,8 @@ TM_STACK_LINEAR, TM_STACK_CUBIC = 0, 1
 TM_STACK_PLANAR, TM_STACK_CYLINDRICAL = 0, 1
 TM_HO_MAX_ORDER = 8
 TM_HO_EQUIDISTANT, TM_HO_GAUSS_LOBATTO, TM_HO_PRESCRIBED = 0, 1, 2
+TM_HO_CERT_MAX_DEPTH = 4
+TM_HO_PROVEN, TM_HO_INVALID, TM_HO_UNDECIDED = 0, 1, 2
 
 
 class TmError(RuntimeError):
@@ -155,6 +157,13 @@ class tm_ho_quality(C.Structure):
                 ("min_jacobian", C.c_double), ("max_jacobian", C.c_double), ("hist", C.c_uint64 * 10)]
 
 
+class tm_ho_certificate(C.Structure):   # 152 bytes
+    _fields_ = [("elements", C.c_uint64), ("proven", C.c_uint64), ("invalid", C.c_uint64), ("undecided", C.c_uint64), ("hidden_invalid", C.c_uint64),
+                ("orientation", C.c_int32), ("order", C.c_int32), ("max_depth", C.c_int32), ("has_unproven", C.c_int32),
+                ("decided_at", C.c_uint64 * 5), ("min_scaled_bound", C.c_double), ("worst_block", C.c_uint64), ("worst_e", C.c_uint64),
+                ("worst_f", C.c_uint64), ("first_unproven_block", C.c_uint64), ("first_unproven_e", C.c_uint64), ("first_unproven_f", C.c_uint64)]
+
+
 # every symbol include/tm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "tm_last_error", "tm_abi_version", "tm_set_log", "tm_csr_solve", "tm_tfi_block", "tm_tfi_linear2d", "tm_smooth_mesh", "tm_smoother_create",
@@ -170,6 +179,7 @@ EXPORTS = [
     "tm_quality3d_planes_host", "tm_stack_quality", "tm_stack_quality_host", "tm_stack_smoothers_quality", "tm_stack_smoothers_quality_field",
     "tm_quality3d_total",
     "tm_ho_tables", "tm_ho_check", "tm_ho_elevate", "tm_ho_elevate_host", "tm_smoother_elevate", "tm_ho_quality_total",
+    "tm_ho_certify_tables", "tm_ho_certify", "tm_ho_certify_host", "tm_smoother_certify", "tm_ho_jacobian_bezier_host", "tm_ho_certificate_total",
     "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
 ]
 
@@ -275,6 +285,12 @@ def lib():
         L.tm_ho_elevate_host.argtypes = L.tm_ho_elevate.argtypes
         L.tm_smoother_elevate.argtypes = [C.c_void_p, C.POINTER(tm_ho_opt), C.c_uint64, _dp, _dp, C.POINTER(tm_ho_quality), _dp]
         L.tm_ho_quality_total.argtypes = [C.POINTER(tm_ho_quality), C.c_uint64, C.POINTER(tm_ho_quality)]
+        L.tm_ho_certify_tables.argtypes = [C.POINTER(tm_ho_opt), _dp, _dp, _dp, _dp, _dp]
+        L.tm_ho_certify.argtypes = [C.POINTER(tm_mesh_desc), C.POINTER(tm_ho_opt), C.c_int32, C.c_uint64, C.POINTER(tm_ho_certificate), C.POINTER(C.c_uint8), _dp]
+        L.tm_ho_certify_host.argtypes = L.tm_ho_certify.argtypes
+        L.tm_smoother_certify.argtypes = [C.c_void_p, C.POINTER(tm_ho_opt), C.c_int32, C.c_uint64, C.POINTER(tm_ho_certificate), C.POINTER(C.c_uint8), _dp]
+        L.tm_ho_jacobian_bezier_host.argtypes = [C.POINTER(tm_mesh_desc), C.POINTER(tm_ho_opt), C.c_uint64, C.c_uint64, C.c_uint64, _dp]
+        L.tm_ho_certificate_total.argtypes = [C.POINTER(tm_ho_certificate), C.c_uint64, C.POINTER(tm_ho_certificate)]
         L.tm_rccl_unique_id.argtypes =[C.c_char_p, C.c_void_p]
         L.tm_rccl_comm_create.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.tm_rccl_comm_destroy.argtypes = [C.c_void_p]

@@ -13,6 +13,7 @@
 #include "tm_refine.hpp"
 #include "tm_quality_dev.hpp"
 #include "tm_highorder_dev.hpp"
+#include "tm_highorder_cert_dev.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -132,6 +133,7 @@ Smoother::~Smoother() {
     if (export_buf) (void)hipFree(export_buf);
     delete qdev;
     delete hodev;
+    delete hcdev;
     delete ref;
     ref = nullptr;
     csr_free();

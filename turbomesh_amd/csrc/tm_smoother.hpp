@@ -48,6 +48,7 @@ class DeviceArena {
 
 struct QualityDev;
 struct HoDev;
+struct HcDev;
 
 struct Smoother {
     Smoother() = default;
@@ -208,6 +209,9 @@ struct Smoother {
     // high-order elevation of an owned block from the resident coordinates (tm_highorder.hip): reads X only; buffers as for the quality report
     HoDev* hodev = nullptr;
     void elevate_host(const tm_ho_opt* opt, int64_t block, double* x, double* y, tm_ho_quality* q, double* sj);
+    // certificate of an owned block's elements from the resident coordinates (tm_highorder_cert.hip): K13's report through hodev, then K14
+    HcDev* hcdev = nullptr;
+    void certify_host(const tm_ho_opt* opt, int max_depth, int64_t block, tm_ho_certificate* cert, uint8_t* status, double* bounds);
 
     // building blocks
     void exchange(double2* vec, hipStream_t on = nullptr);   // start (and, without a split hook, finish) the halo exchange of `vec`; on = the handle's stream unless given

@@ -10,7 +10,9 @@ the fine mesh itself (equidistant) or the element's degree-p tensor-product inte
     X, Y, q, sj = el.block(smoother, b)        # planes (nj, ni), quality.HoQuality, scaled Jacobian per element (Ej, Ei)
     Elevation(2, "equidistant").mesh(smoother).write("blade.vtk")
 
-Evaluated on the MI355X (kernel K13); `host=True` evaluates the same definition on the CPU (a Mesh only), bit for bit."""
+    cert, status, bounds = el.certify(smoother, b)   # quality.HoCertificate, (Ej, Ei) uint8 status, (Ej, Ei, 2) bounds of o*J
+
+Evaluated on the MI355X (kernels K13, K14); `host=True` evaluates the same definition on the CPU (a Mesh only), bit for bit."""
 from __future__ import annotations
 
 import ctypes as C
@@ -128,6 +130,52 @@ class Elevation:
             md = _capi.MeshDesc(mesh)
             _capi.check((L.tm_ho_elevate_host if host else L.tm_ho_elevate)(md.ref(), *args))
         return X, Y, _quality.HoQuality.from_struct(q), sj
+
+    def certify_tables(self):
+        """(M[p+1, p+1], wu[2p, p], wv[2p, p+1], G, norm): the Lagrange -> Bernstein matrix, the product weights, the guard factor G(p)
+        and ||M||_inf (tm_ho_certify_tables: host only)."""
+        p = max(1, self.order)
+        M, wu, wv = np.empty((p + 1, p + 1)), np.empty((2 * p, p)), np.empty((2 * p, p + 1))
+        G, norm = C.c_double(), C.c_double()
+        _capi.check(_capi.lib().tm_ho_certify_tables(C.byref(self._opt), _capi.f64ptr(M), _capi.f64ptr(wu), _capi.f64ptr(wv), C.byref(G), C.byref(norm)))
+        return M, wu, wv, G.value, norm.value
+
+    def jacobian_bezier(self, mesh, b, e, f):
+        """The (2p, 2p) Bernstein coefficients of the Jacobian of element (e, f) of block b (tm_ho_jacobian_bezier_host: host only)."""
+        p = max(1, self.order)
+        B = np.empty((2 * p, 2 * p))
+        md = _capi.MeshDesc(mesh)
+        _capi.check(_capi.lib().tm_ho_jacobian_bezier_host(md.ref(), C.byref(self._opt), b, e, f, _capi.f64ptr(B)))
+        return B
+
+    def certify(self, mesh_or_smoother, b=None, host=False, max_depth=3):
+        """The certificate of block b -- (HoCertificate, status, bounds): status an (Ej, Ei) uint8 array of TM_HO_PROVEN / TM_HO_INVALID /
+        TM_HO_UNDECIDED, bounds an (Ej, Ei, 2) array of (lo, hi) with lo <= o*J <= hi on the whole element.  b=None: every block --
+        (total HoCertificate, [HoCertificate per block], [status], [bounds]).  A discrete.Mesh is uploaded per call (tm_ho_certify;
+        host=True: tm_ho_certify_host, no GPU); a smooth.Smoother gives the coordinates resident in its handle (tm_smoother_certify)."""
+        resident = hasattr(mesh_or_smoother, "_h")
+        mesh = mesh_or_smoother._mesh if resident else mesh_or_smoother
+        if resident and host:
+            raise ValueError("host=True evaluates host coordinates: pass the mesh, not the handle")
+        if b is None:
+            self.check(mesh)
+            out = [self.certify(mesh_or_smoother, k, host=host, max_depth=max_depth) for k in range(len(mesh.blocks))]
+            per_block = [o[0] for o in out]
+            return _quality.total_ho_certificate(per_block), per_block, [o[1] for o in out], [o[2] for o in out]
+        ni, nj = mesh.blocks[b].points.size
+        p = max(1, self.order)
+        Ei, Ej = max(0, (ni - 1) // p), max(0, (nj - 1) // p)
+        status = np.empty((Ej, Ei), dtype=np.uint8)
+        bounds = np.empty((Ej, Ei, 2), dtype=np.float64)
+        c = _capi.tm_ho_certificate()
+        args = (C.byref(self._opt), int(max_depth), b, C.byref(c), status.ctypes.data_as(C.POINTER(C.c_uint8)), _capi.f64ptr(bounds))
+        L = _capi.lib()
+        if resident:
+            _capi.check(L.tm_smoother_certify(mesh_or_smoother._h, *args))
+        else:
+            md = _capi.MeshDesc(mesh)
+            _capi.check((L.tm_ho_certify_host if host else L.tm_ho_certify)(md.ref(), *args))
+        return _quality.HoCertificate.from_struct(c), status, bounds
 
     def mesh(self, mesh_or_smoother, host=False) -> HighOrderMesh:
         """Every block, with the per-block and total quality."""

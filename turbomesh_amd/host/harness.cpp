@@ -6,6 +6,7 @@
 //   tm_harness tm <ni> <nj> <iterations>               the Thomas-Middlecoff control field on a clustered rectangle (exit 0: it kept the clustering)
 //   tm_harness stack <ni> <nj> <ncuts> <nlayers>       config-5 cuts (amplitude 0.05 + 0.001 c), five relaxation sweeps per handle, stacked on the
 //                                                      device by the natural cubic spline: a checksum per layer (exit 0: layers at cuts equal the cuts)
+//   tm_harness certify <ni> <nj> <order>   Bezier certificate of those elements (kernel K14; exit 0: equal to the CPU's, counts add up)
 //   tm_harness elevate <ni> <nj> <order>   curved elements of that order from a smoothed block (kernel K13; exit 0: corners unchanged, equal to the CPU's)
 //   tm_harness stack-quality <ni> <nj> <ncuts> <nlayers>   the same cuts: the 3-D quality record of the stacked block (kernel K12; exit 0: equal to the CPU's)
 //   tm_harness csr                                     the linear-solver slot (seam 2) on the reference's 5 x 5 known answer
@@ -349,8 +350,39 @@ static int elevateBlock(std::size_t ni, std::size_t nj, int order) {
     return corners && same ? 0 : 1;
 }
 
+// tm_harness certify <ni> <nj> <order>: the block of `elevate`, five relaxation sweeps; the certificate of its elements from the
+// coordinates resident in the handle (highorder::certify -> tm_smoother_certify), compared with the CPU's evaluation of the downloaded
+// coordinates (record, status and bounds bit for bit).
+static int certifyBlock(std::size_t ni, std::size_t nj, int order) {
+    smoothing::solver::Option opt;
+    opt.inner = TM_INNER_RELAX;
+    discrete::Mesh mesh = buildSingle(ni, nj);
+    highorder::Option ho;
+    ho.order = order;
+    highorder::check(mesh, ho);
+    smoothing::smooth::Smoother sm(mesh, opt, smoothing::wall_control_function::Algorithm::laplace());
+    sm.iterate(5);
+    const highorder::Certified dev = highorder::certify(sm, ho, 0);
+    sm.download();
+    const highorder::Certified host = highorder::certify(mesh, ho, 0, 3, true);
+    const tm_ho_certificate& c = dev.certificate;
+    std::printf("certify: elements %llu proven %llu invalid %llu undecided %llu hidden invalid %llu min scaled bound %.17g at (e %llu, f %llu) orientation %d order %d depth %d\n",
+                static_cast<unsigned long long>(c.elements), static_cast<unsigned long long>(c.proven), static_cast<unsigned long long>(c.invalid),
+                static_cast<unsigned long long>(c.undecided), static_cast<unsigned long long>(c.hidden_invalid), c.min_scaled_bound,
+                static_cast<unsigned long long>(c.worst_e), static_cast<unsigned long long>(c.worst_f), c.orientation, c.order, c.max_depth);
+    const bool adds = c.proven + c.invalid + c.undecided == c.elements && c.elements == dev.Ei * dev.Ej;
+    std::printf("certify: counts add up: %s\n", adds ? "yes" : "no");
+    const bool same = dev.status == host.status && dev.bounds.size() == host.bounds.size() &&
+                      (dev.bounds.empty() || std::memcmp(dev.bounds.data(), host.bounds.data(), sizeof(double) * dev.bounds.size()) == 0) &&
+                      std::memcmp(&dev.certificate, &host.certificate, sizeof(tm_ho_certificate)) == 0;
+    std::printf("certify: device equals host: %s\n", same ? "yes" : "no");
+    return adds && same ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     try {
+        if (argc >= 5 && std::strcmp(argv[1], "certify") == 0)
+            return certifyBlock(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), static_cast<int>(std::strtol(argv[4], nullptr, 10)));
         if (argc >= 5 && std::strcmp(argv[1], "elevate") == 0)
             return elevateBlock(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), static_cast<int>(std::strtol(argv[4], nullptr, 10)));
         if (argc >= 6 && std::strcmp(argv[1], "stack-quality") == 0)
@@ -362,7 +394,7 @@ int main(int argc, char** argv) {
             return thomasMiddlecoff(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "ranks") == 0) return runRank(argc, argv);
         if (argc < 5) {
-            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n", argv[0], argv[0], argv[0], argv[0], argv[0]);
+            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 2;
         }
         int a = 2;

@@ -548,6 +548,44 @@ inline Elevated elevate(discrete::Mesh& mesh, const Option& o, std::size_t block
     detail::trim(r);
     return r;
 }
+// The certificate of `block`: every element judged on its whole area by the Bernstein coefficients of its Jacobian (tm_hip.h,
+// "high-order elements: certificate").  status[f*Ei + e] is TM_HO_PROVEN / TM_HO_INVALID / TM_HO_UNDECIDED, bounds[2*(f*Ei + e)] = (lo, hi)
+struct Certified {
+    std::size_t Ei = 0, Ej = 0;
+    std::vector<uint8_t> status;
+    std::vector<double> bounds;
+    tm_ho_certificate certificate{};
+};
+namespace detail {
+inline Certified certified(std::size_t ni, std::size_t nj, const Option& o) {
+    if (o.order < 1 || o.order > TM_HO_MAX_ORDER) throw Error(TM_E_ARG, "the order must be 1 .. TM_HO_MAX_ORDER");
+    Certified r;
+    r.Ei = (ni - 1) / static_cast<std::size_t>(o.order), r.Ej = (nj - 1) / static_cast<std::size_t>(o.order);
+    r.status.resize(r.Ei * r.Ej + 1), r.bounds.resize(2 * r.Ei * r.Ej + 2);
+    return r;
+}
+inline void trim(Certified& r) { r.status.resize(r.Ei * r.Ej), r.bounds.resize(2 * r.Ei * r.Ej); }
+}  // namespace detail
+// from the coordinates RESIDENT in the handle (tm_smoother_certify: K13's report, then kernel K14)
+inline Certified certify(const smoothing::smooth::Smoother& s, const Option& o, std::size_t block, int max_depth = 3) {
+    const tm_mesh_desc& d = s.desc();
+    if (block >= d.nblocks) throw Error(TM_E_ARG, "block index past the mesh");
+    Certified r = detail::certified(d.blocks[block].ni, d.blocks[block].nj, o);
+    const tm_ho_opt ho = o.c_struct();
+    core::check(tm_smoother_certify(s.handle(), &ho, max_depth, block, &r.certificate, r.status.data(), r.bounds.data()));
+    detail::trim(r);
+    return r;
+}
+// the same from host coordinates, uploaded per call (tm_ho_certify) or, host = true, evaluated on the CPU (tm_ho_certify_host)
+inline Certified certify(discrete::Mesh& mesh, const Option& o, std::size_t block, int max_depth = 3, bool host = false) {
+    if (block >= mesh.blocks.size()) throw Error(TM_E_ARG, "block index past the mesh");
+    smoothing::smooth::Desc d(mesh);
+    Certified r = detail::certified(mesh.blocks[block].points.size[0], mesh.blocks[block].points.size[1], o);
+    const tm_ho_opt ho = o.c_struct();
+    core::check((host ? tm_ho_certify_host : tm_ho_certify)(&d.desc, &ho, max_depth, block, &r.certificate, r.status.data(), r.bounds.data()));
+    detail::trim(r);
+    return r;
+}
 }  // namespace highorder
 
 namespace discrete {

@@ -147,6 +147,11 @@ class Smoother:
         `elevation` is a highorder.Elevation; see Elevation.block."""
         return elevation.block(self, block)
 
+    def certify(self, elevation, block: int = None, max_depth: int = 3):
+        """The Bezier certificate of an owned block's curved elements (all blocks: block=None) from the coordinates resident in the
+        handle (tm_smoother_certify); see Elevation.certify."""
+        return elevation.certify(self, block, max_depth=max_depth)
+
     def write_quality(self, filename):
         """The per-cell planes of every block as a PLOT3D function file (one variable, sizes (ni-1, nj-1))."""
         from .. import output
