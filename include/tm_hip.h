@@ -500,14 +500,14 @@ int tm_smoother_quality_field(tm_smoother* s, uint64_t block, double* min_scaled
  * Every sum runs over c = 0 .. K-1 in that order, products and sums rounded separately (nothing fused), on the device and on the host. */
 #define TM_STACK_MAX_CUTS 16
 enum { TM_STACK_LINEAR = 0, TM_STACK_CUBIC = 1 };
-enum { TM_STACK_PLANAR = 0, TM_STACK_CYLINDRICAL = 1 };
+enum { TM_STACK_PLANAR = 0, TM_STACK_CYLINDRICAL = 1, TM_STACK_REVOLUTION = 2 /* needs tm_stack_surfaces: see below */ };
 typedef struct tm_stack_opt {
     uint64_t ncuts;
     const double* span;      /* [ncuts] z */
     uint64_t nlayers;
     const double* layers;    /* [nlayers] s */
     int32_t interpolation;   /* TM_STACK_LINEAR / TM_STACK_CUBIC */
-    int32_t mapping;         /* TM_STACK_PLANAR / TM_STACK_CYLINDRICAL */
+    int32_t mapping;         /* TM_STACK_PLANAR / TM_STACK_CYLINDRICAL (TM_STACK_REVOLUTION: the *_surf calls only) */
 } tm_stack_opt;
 /* the weight matrix, nlayers * ncuts doubles, row = layer.  Host only: no GPU touched */
 int tm_stack_weights(const tm_stack_opt* opt, double* weights);
@@ -526,6 +526,68 @@ int tm_stack_block_host(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt
  * `block`: TM_E_SIZE.  Cuts spread over ranks are not served.  Bit-identical to tm_stack_block on the downloaded coordinates. */
 int tm_stack_smoothers(tm_smoother* const* cuts, const tm_stack_opt* opt, uint64_t block, uint64_t k_begin, uint64_t k_count,
                        double* x, double* y, double* z);
+
+/* ------------------------------------------------------------------ cuts on stream surfaces of revolution
+ * No real machine has cylindrical end walls: hub and shroud of an axial turbine are contoured, a mixed-flow or radial stage turns from
+ * axial to radial.  The 2-D cut of such a machine is meshed in the unrolled plane (m', theta) of a stream surface of revolution, which is
+ * described by a meridional curve x(m), r(m).  The reference's roadmap lists this as open ("possible extension to radial
+ * configurations", beside "rotational configurations").  TM_STACK_REVOLUTION = 2 generalises the cylinder to an arbitrary surface of
+ * revolution per cut.  It needs per-cut meridional tables, which tm_stack_opt has no room for: they travel in a second record,
+ * tm_stack_surfaces.
+ *   - Any violation of what the record's comments say answers TM_E_ARG.
+ *   - The entry points above answer TM_E_ARG for mapping 2, because they have no tables.  The ones below answer TM_E_ARG for any other
+ *     mapping.
+ * Cuts.  The 2-D coordinates of cut c are (u, v).
+ *   - u is the parameter of the cut's meridional curve.  For an angle-preserving cut u = rref_c * integral dm / r.
+ *   - v = rref_c * theta.
+ *   - The library does not enforce conformality.  It maps what it is given.
+ *   - A cylinder of radius R is x = u, r = R, rref = R.  That is the cylindrical mapping above.
+ * Tables.  On interval n of cut c, with h = u[n+1] - u[n], both x and r are the cubic a + t(b + t(c + t d)) in t = u - u[n]:
+ *   - a = v[n] exactly, the knot value itself;
+ *   - b = (v[n+1] - v[n])/h - h(2M[n] + M[n+1])/6;
+ *   - c = M[n]/2;
+ *   - d = (M[n+1] - M[n])/(6h).
+ *   M is the vector of second derivatives of the natural cubic spline through the knots, with M[0] = M[N-1] = 0.  For TM_SURF_LINEAR, or
+ *   for N = 2, M is 0, so c and d are exact zeros.  Everything is formed on the host in long double and rounded once to fp64.
+ *   tm_stack_surface_tables is host only, touches no GPU, and returns the coefficients: sum_c (N_c - 1) * 8 doubles, cut after cut,
+ *   interval after interval, within an interval in the order ax bx cx dx ar br cr dr.
+ * Evaluation per node and cut.  All arithmetic is IEEE fp64.  Nothing is fused.  The device and the host compute the same way.
+ *   - n is the largest index <= N-2 with u[n] <= u_node, and n = 0 when u_node < u[0].  Outside the table the end interval's polynomial
+ *     is continued.  This is extrapolation, and it is counted (see below).
+ *   - t = u_node - u[n], with one rounding.
+ *   - x_c = a + t*(b + t*(c + t*d)), innermost first, every operation rounded.  r_c is formed the same way.
+ *   - theta_c = v_node / rref[c], with one rounding.
+ *   - A node on a knot u[n], n <= N-2, gives t = 0 and returns the knot value bit for bit.
+ * Layer k.
+ *   - X = sum_c A[k][c] x_c,  R = sum_c A[k][c] r_c,  Theta = sum_c A[k][c] theta_c.
+ *   - The sums run over c = 0 .. K-1 in that order, products and sums rounded separately, as above.
+ *   - The output is (X, R sin Theta, R cos Theta).
+ *   - A is the weight matrix of span, layers and interpolation (tm_stack_weights).  s[k] itself is not used by this mapping.
+ *   - r_c(u) <= 0 is not checked per node.
+ * Extrapolated nodes.  The three stacking calls take uint64_t* outside, which may be NULL.  They write outside[c], the number of nodes of
+ * the block whose u lies outside [u[0], u[N_c-1]] of table c.  The count is independent of the layer window.  On the device it is formed
+ * with integer atomics only, so it is deterministic.
+ * Error codes, the ordering behind the handles' pending work, the "no handle is modified" rule and the window rules are exactly those of
+ * the calls they extend.  The 3-D quality counterparts see bit for bit what the stacking kernel writes, as for the other two mappings. */
+#define TM_STACK_MAX_KNOTS 256
+enum { TM_SURF_LINEAR = 0, TM_SURF_CUBIC = 1 };
+typedef struct tm_stack_surfaces {
+    uint64_t ncuts;              /* == opt->ncuts, else TM_E_ARG */
+    const uint64_t* nknots;      /* [ncuts], 2 .. TM_STACK_MAX_KNOTS each; may differ between cuts */
+    const double* const* u;      /* [ncuts][nknots[c]]  finite, strictly increasing */
+    const double* const* x;      /* [ncuts][nknots[c]]  finite */
+    const double* const* r;      /* [ncuts][nknots[c]]  finite, > 0 */
+    const double* rref;          /* [ncuts] finite, > 0; NULL: rref[c] = span[c] (then every span[c] must be > 0) */
+    int32_t interpolation, _pad; /* TM_SURF_LINEAR / TM_SURF_CUBIC: of x(u) and r(u) along the curve */
+} tm_stack_surfaces;
+int tm_stack_surface_tables(const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, double* coeff);
+/* tm_stack_block, tm_stack_block_host and tm_stack_smoothers with the tables (kernel K11 with the surface stage K15) */
+int tm_stack_block_surf(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, uint64_t block,
+                        uint64_t k_begin, uint64_t k_count, double* x, double* y, double* z, uint64_t* outside /* [ncuts] or NULL */);
+int tm_stack_block_surf_host(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, uint64_t block,
+                             uint64_t k_begin, uint64_t k_count, double* x, double* y, double* z, uint64_t* outside);
+int tm_stack_smoothers_surf(tm_smoother* const* cuts, const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, uint64_t block,
+                            uint64_t k_begin, uint64_t k_count, double* x, double* y, double* z, uint64_t* outside);
 
 /* ------------------------------------------------------------------ 3-D quality of stacked blocks
  * Is the stacked mesh usable?  The 2-D report above sees each cut alone; cuts that are clean in 2-D can still enclose negative hexahedra
@@ -589,6 +651,16 @@ int tm_stack_smoothers_quality(tm_smoother* const* cuts, const tm_stack_opt* opt
  * ((k-k_begin)*(nj-1) + j)*(ni-1) + i; runs the report first to learn o.  A window that is empty or reaches past nlayers-1: TM_E_ARG. */
 int tm_stack_smoothers_quality_field(tm_smoother* const* cuts, const tm_stack_opt* opt, uint64_t block,
                                      uint64_t k_begin, uint64_t k_count /* cell layers */, double* min_scaled_jacobian);
+/* The four calls above for TM_STACK_REVOLUTION ("cuts on stream surfaces of revolution"): the nodes are exactly what
+ * tm_stack_block_surf returns, evaluated once per node and cut before the march (K12 with the surface stage K15). */
+int tm_stack_quality_surf(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, uint64_t block,
+                          tm_quality3d* out);
+int tm_stack_quality_surf_host(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, uint64_t block,
+                               tm_quality3d* out);
+int tm_stack_smoothers_quality_surf(tm_smoother* const* cuts, const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, uint64_t block,
+                                    tm_quality3d* out);
+int tm_stack_smoothers_quality_field_surf(tm_smoother* const* cuts, const tm_stack_opt* opt, const tm_stack_surfaces* surfaces,
+                                          uint64_t block, uint64_t k_begin, uint64_t k_count /* cell layers */, double* min_scaled_jacobian);
 int tm_quality3d_total(const tm_quality3d* per_block, uint64_t n, tm_quality3d* total);
 
 /* ------------------------------------------------------------------ high-order elements

@@ -13,7 +13,9 @@ diagonal on the assembled system, the reference's tolerances -- the iterates a r
 --stack CFG2 [CFG3 ...] --span z0,z1,... --layers NK: `config` and the further files are the spanwise cuts of one blade.  Every file runs the
 path above with its own handle; the smoothed cuts are stacked into 3-D blocks on the device (stack.py, include/tm_hip.h "3-D from 2-D cuts")
 and --output becomes a multi-block 3-D PLOT3D file; --stack-quality / --fail-on-inverted-3d report on the hexahedra of that mesh
-(include/tm_hip.h "3-D quality of stacked blocks").  Without --stack the program is what it was.
+(include/tm_hip.h "3-D quality of stacked blocks").  --stack-mapping revolution --meridional F0 F1 ... places cuts meshed in the unrolled
+plane of stream surfaces of revolution (contoured end walls, mixed-flow and radial stages) on their surfaces, one table `u x r` per cut
+(include/tm_hip.h "cuts on stream surfaces of revolution").  Without --stack the program is what it was.
 
 --order P [--nodes equidistant|gauss-lobatto]: the smoothed blocks become curved elements of order P (highorder.py, include/tm_hip.h
 "high-order elements"): the cell counts of every block and the interface ranges must be multiples of P, which is checked before
@@ -140,8 +142,17 @@ def _main_stack(ap, args):
     from . import output, stack
 
     output._format_of(args.output)
-    st = stack.Stack(args.span_values, stack.layers_from(args.span_values, args.layers, args.span_clustering_fn), args.stack_interpolation, args.stack_mapping)
+    surfaces = None
+    if args.stack_mapping == "revolution":
+        try:
+            surfaces = stack.Surfaces.read(args.meridional, args.reference_radius_values, args.meridional_interpolation)
+        except (OSError, ValueError) as e:
+            ap.error(f"--meridional: {e}")
+    st = stack.Stack(args.span_values, stack.layers_from(args.span_values, args.layers, args.span_clustering_fn), args.stack_interpolation, args.stack_mapping,
+                     surfaces=surfaces)
     st.weights()   # a span that is not increasing (or a radius <= 0) is refused before anything is smoothed
+    if surfaces is not None:
+        st.surface_tables()   # and so are meridional tables the definition does not admit
     files = [args.config] + list(args.stack)
     all_stats, worst = [], None
     with contextlib.ExitStack() as keep:
@@ -152,7 +163,18 @@ def _main_stack(ap, args):
             all_stats.append(stats)
             if after is not None and not after[1].ok and worst is None:
                 worst = (c, after[1])
-        m3 = st.mesh3d(handles)
+        if surfaces is None:
+            m3 = st.mesh3d(handles)
+        else:   # the same blocks, with the count of extrapolated nodes per cut
+            m3 = stack.Mesh3d()
+            for b, name in enumerate(handles[0]._mesh.names):
+                *planes, outside = st.block(handles, b, return_outside=True)
+                m3.names.append(name)
+                m3.blocks.append(tuple(planes))
+                for c, n in enumerate(outside):
+                    if n:
+                        logging.getLogger("stack").warning("block %d (%s), cut %d: %d nodes lie outside the meridional table %s and are extrapolated", b, name, c,
+                                                           int(n), args.meridional[c])
         q3 = st.quality(handles) if (args.stack_quality or args.fail_on_inverted_3d) else None   # from the resident cuts: no 3-D block is formed
     m3.write(args.output)
     logging.getLogger("output").info("wrote %s (%d blocks, %d cuts, %d layers, %d nodes)", args.output, len(m3.blocks), len(files), st.nlayers,
@@ -215,8 +237,13 @@ def main(argv=None):
     ap.add_argument("--span-clustering", default="uniform", metavar="uniform|roberts:a,b|tanh:d",
                     help="distribution of the layers over the span (clustering.zig: Uniform, Roberts alpha,beta, SingleHyperbolicClustering delta_s)")
     ap.add_argument("--stack-interpolation", default="cubic", choices=["linear", "cubic"], help="between the cuts: linear, or the natural cubic spline")
-    ap.add_argument("--stack-mapping", default="planar", choices=["planar", "cylindrical"],
-                    help="planar: (x, y, s); cylindrical: the cuts are unrolled cylinders (x, r theta) at radius span, output (x, r sin theta, r cos theta)")
+    ap.add_argument("--stack-mapping", default="planar", choices=["planar", "cylindrical", "revolution"],
+                    help="planar: (x, y, s); cylindrical: the cuts are unrolled cylinders (x, r theta) at radius span, output (x, r sin theta, r cos theta); "
+                         "revolution: the cuts are unrolled stream surfaces of revolution (u, rref theta) with the meridional curves of --meridional")
+    ap.add_argument("--meridional", nargs="+", metavar="FILE", default=None,
+                    help="with --stack-mapping revolution: one text file per cut, rows `u x r` (# comments), the meridional curve x(u), r(u) of its surface")
+    ap.add_argument("--meridional-interpolation", default=None, choices=["linear", "cubic"], help="of x(u) and r(u) between the rows of a table (default cubic)")
+    ap.add_argument("--reference-radius", metavar="R0,R1,...", default=None, help="reference radius of every cut, v = rref theta (default: --span)")
     ap.add_argument("--stack-quality", action="store_true",
                     help="with --stack: log the 3-D quality report of the stacked blocks (`quality` logger: one line per block and a total) -- "
                          "negative and degenerate hexahedra across layers, which --quality (every cut alone) cannot see")
@@ -226,6 +253,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.stack is None and (args.span or args.layers is not None):
         ap.error("--span and --layers go with --stack")
+    if args.stack is None and (args.meridional or args.reference_radius or args.meridional_interpolation):
+        ap.error("--meridional, --meridional-interpolation and --reference-radius go with --stack")
     if args.stack is None and (args.stack_quality or args.fail_on_inverted_3d):
         ap.error("--stack-quality and --fail-on-inverted-3d go with --stack")
     if args.order is None and (args.nodes or args.fail_on_invalid_elements):
@@ -261,6 +290,25 @@ def main(argv=None):
         args.span_clustering_fn = _span_clustering(ap, args.span_clustering)
         if not args.output:
             ap.error("--stack needs --output (the 3-D file)")
+        args.reference_radius_values = None
+        if args.stack_mapping == "revolution":
+            if not args.meridional:
+                ap.error("--stack-mapping revolution needs --meridional F0 F1 ... (one table per cut)")
+            if len(args.meridional) != len(args.span_values):
+                ap.error(f"--meridional has {len(args.meridional)} files for {len(args.span_values)} cuts (config + --stack)")
+            if args.reference_radius:
+                try:
+                    args.reference_radius_values = [float(v) for v in args.reference_radius.split(",")]
+                except ValueError:
+                    ap.error(f"--reference-radius {args.reference_radius!r}: comma-separated numbers")
+                if len(args.reference_radius_values) != len(args.span_values):
+                    ap.error(f"--reference-radius has {len(args.reference_radius_values)} values for {len(args.span_values)} cuts")
+            args.meridional_interpolation = args.meridional_interpolation or "cubic"
+        else:
+            for flag, given in (("--meridional", args.meridional), ("--reference-radius", args.reference_radius),
+                                ("--meridional-interpolation", args.meridional_interpolation)):
+                if given:
+                    ap.error(f"{flag} goes with --stack-mapping revolution")
     if args.refine and args.hip in ("relax", "reference"):
         ap.error("--refine goes with --hip auto, bicgstab, mg_bicgstab, gmres or file (relax has no inner solve to refine; reference keeps the reference's stop test)")
     logging.basicConfig(level=logging.INFO, format="%(levelname)s(%(name)s): %(message)s")

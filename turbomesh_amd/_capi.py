@@ -26,7 +26,9 @@ TM_CF_LAPLACE, TM_CF_WHITE, TM_CF_PRESCRIBED, TM_CF_THOMAS_MIDDLECOFF = 0, 1, 2,
 TM_OPT_REFINE = 16
 TM_STACK_MAX_CUTS = 16
 TM_STACK_LINEAR, TM_STACK_CUBIC = 0, 1
-TM_STACK_PLANAR, TM_STACK_CYLINDRICAL = 0, 1
+TM_STACK_PLANAR, TM_STACK_CYLINDRICAL, TM_STACK_REVOLUTION = 0, 1, 2
+TM_STACK_MAX_KNOTS = 256
+TM_SURF_LINEAR, TM_SURF_CUBIC = 0, 1
 TM_HO_MAX_ORDER = 8
 TM_HO_EQUIDISTANT, TM_HO_GAUSS_LOBATTO, TM_HO_PRESCRIBED = 0, 1, 2
 TM_HO_CERT_MAX_DEPTH = 4
@@ -147,6 +149,12 @@ class tm_stack_opt(C.Structure):
                 ("interpolation", C.c_int32), ("mapping", C.c_int32)]
 
 
+class tm_stack_surfaces(C.Structure):
+    _fields_ = [("ncuts", C.c_uint64), ("nknots", C.POINTER(C.c_uint64)), ("u", C.POINTER(C.POINTER(C.c_double))),
+                ("x", C.POINTER(C.POINTER(C.c_double))), ("r", C.POINTER(C.POINTER(C.c_double))), ("rref", C.POINTER(C.c_double)),
+                ("interpolation", C.c_int32), ("_pad", C.c_int32)]
+
+
 class tm_ho_opt(C.Structure):
     _fields_ = [("order", C.c_int32), ("distribution", C.c_int32), ("nodes", C.POINTER(C.c_double))]
 
@@ -178,6 +186,8 @@ EXPORTS = [
     "tm_stack_weights", "tm_stack_block", "tm_stack_block_host", "tm_stack_smoothers",
     "tm_quality3d_planes_host", "tm_stack_quality", "tm_stack_quality_host", "tm_stack_smoothers_quality", "tm_stack_smoothers_quality_field",
     "tm_quality3d_total",
+    "tm_stack_surface_tables", "tm_stack_block_surf", "tm_stack_block_surf_host", "tm_stack_smoothers_surf",
+    "tm_stack_quality_surf", "tm_stack_quality_surf_host", "tm_stack_smoothers_quality_surf", "tm_stack_smoothers_quality_field_surf",
     "tm_ho_tables", "tm_ho_check", "tm_ho_elevate", "tm_ho_elevate_host", "tm_smoother_elevate", "tm_ho_quality_total",
     "tm_ho_certify_tables", "tm_ho_certify", "tm_ho_certify_host", "tm_smoother_certify", "tm_ho_jacobian_bezier_host", "tm_ho_certificate_total",
     "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
@@ -279,6 +289,15 @@ def lib():
         L.tm_stack_smoothers_quality.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt), C.c_uint64, C.POINTER(tm_quality3d)]
         L.tm_stack_smoothers_quality_field.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt), C.c_uint64, C.c_uint64, C.c_uint64, _dp]
         L.tm_quality3d_total.argtypes = [C.POINTER(tm_quality3d), C.c_uint64, C.POINTER(tm_quality3d)]
+        _sfp, _u64p = C.POINTER(tm_stack_surfaces), C.POINTER(C.c_uint64)
+        L.tm_stack_surface_tables.argtypes = [C.POINTER(tm_stack_opt), _sfp, _dp]
+        L.tm_stack_block_surf.argtypes = [C.POINTER(C.POINTER(tm_mesh_desc)), C.POINTER(tm_stack_opt), _sfp, C.c_uint64, C.c_uint64, C.c_uint64, _dp, _dp, _dp, _u64p]
+        L.tm_stack_block_surf_host.argtypes = L.tm_stack_block_surf.argtypes
+        L.tm_stack_smoothers_surf.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt), _sfp, C.c_uint64, C.c_uint64, C.c_uint64, _dp, _dp, _dp, _u64p]
+        L.tm_stack_quality_surf.argtypes = [C.POINTER(C.POINTER(tm_mesh_desc)), C.POINTER(tm_stack_opt), _sfp, C.c_uint64, C.POINTER(tm_quality3d)]
+        L.tm_stack_quality_surf_host.argtypes = L.tm_stack_quality_surf.argtypes
+        L.tm_stack_smoothers_quality_surf.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt), _sfp, C.c_uint64, C.POINTER(tm_quality3d)]
+        L.tm_stack_smoothers_quality_field_surf.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt), _sfp, C.c_uint64, C.c_uint64, C.c_uint64, _dp]
         L.tm_ho_tables.argtypes = [C.POINTER(tm_ho_opt), _dp, _dp, _dp]
         L.tm_ho_check.argtypes = [C.POINTER(tm_mesh_desc), C.POINTER(tm_ho_opt)]
         L.tm_ho_elevate.argtypes = [C.POINTER(tm_mesh_desc), C.POINTER(tm_ho_opt), C.c_uint64, _dp, _dp, C.POINTER(tm_ho_quality), _dp]

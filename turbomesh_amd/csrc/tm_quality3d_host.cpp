@@ -151,6 +151,32 @@ extern "C" int tm_stack_quality_host(const tm_mesh_desc* const* cuts, const tm_s
     });
 }
 
+extern "C" int tm_stack_quality_surf_host(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, uint64_t block,
+                                          tm_quality3d* out) {
+    return guarded([&]() {
+        if (!out) throw TmError(TM_E_ARG, "null argument");
+        SurfPlan sf;
+        const StackPlan p = stack_plan_surf(opt, surfaces, sf);
+        uint64_t ni = 0, nj = 0;
+        stack_check_cuts(cuts, p.ncuts, block, &ni, &nj);
+        stack_check_cells(p, ni, nj);
+        const double* v[TM_STACK_MAX_CUTS];
+        for (int c = 0; c < p.ncuts; ++c) v[c] = cuts[c]->blocks[block].xy;
+        std::vector<double> xc, rc, thc;
+        stack_surf_nodes_host(p, sf, v, ni, nj, xc, rc, thc, nullptr);
+        const size_t plane = static_cast<size_t>(ni) * nj;
+        std::vector<double> buf(6 * plane);   // two layers of x, y, z, alternating
+        Quality3dStream s(ni, nj, p.nlayers, nullptr);
+        for (uint64_t k = 0; k < p.nlayers; ++k) {
+            double* l = buf.data() + (k & 1) * 3 * plane;
+            stack_layer_surf_host(p, xc, rc, thc, k, ni, nj, l, l + plane, l + 2 * plane);
+            s.layer(l, l + plane, l + 2 * plane);
+        }
+        s.finish(block, out);
+        return TM_OK;
+    });
+}
+
 extern "C" int tm_quality3d_total(const tm_quality3d* per_block, uint64_t n, tm_quality3d* total) {
     return guarded([&]() {
         if (!per_block || !total) throw TmError(TM_E_ARG, "null argument");

@@ -22,13 +22,26 @@ namespace tmh {
 constexpr int STACK_TILE = 32, STACK_THREADS = STACK_TILE * STACK_TILE;
 
 // table: per layer of the window K weights followed by s[k] (row pitch K + 1)
+//
+// K15 (MAP == TM_STACK_REVOLUTION; include/tm_hip.h, "cuts on stream surfaces of revolution").  As cut c passes through the tile, the
+// first N_c threads also stage its knots in LDS (two buffers alternating like the tiles: the same one barrier per cut covers both); right
+// behind the transposed read every thread locates its node's u among them (surf_locate: fixed steps, no branch on the data), gathers the
+// interval's 64 B of coefficients from the table (16 KB per cut at the most: L2) and evaluates x_c and r_c by Horner (tm_stack_surface.hpp,
+// shared with the host); theta_c = v / rref_c.  The thread then holds three values per cut, (x_c, theta_c) in v[c] and r_c in rc[c], and
+// the layer loop sums three rows.  Nodes outside a table: ballot and popcount per wave and cut, LDS counters, one global integer atomic
+// per workgroup and cut.  Lanes past the block run along (they hold node (0,0)) and are masked out of the counts and the stores.
 template <int K, int MAP>
-__global__ __launch_bounds__(STACK_THREADS) void k_stack_planes(StackCuts cuts, const double* __restrict__ table, int nk, int ni, int nj, double* __restrict__ X,
-                                                                double* __restrict__ Y, double* __restrict__ Z) {
+__global__ __launch_bounds__(STACK_THREADS) void k_stack_planes(StackCuts cuts, StackSurf surf, const double* __restrict__ table, int nk, int ni, int nj,
+                                                                double* __restrict__ X, double* __restrict__ Y, double* __restrict__ Z,
+                                                                unsigned long long* __restrict__ outside) {
+    constexpr bool REV = MAP == TM_STACK_REVOLUTION;
     __shared__ double2 tile[2][STACK_TILE][STACK_TILE + 1];   // +1: the transposed read walks a column
+    __shared__ double sh_u[REV ? 2 : 1][REV ? TM_STACK_MAX_KNOTS : 1];
+    __shared__ unsigned sh_out[REV ? K : 1];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int i0 = blockIdx.y * STACK_TILE, j0 = blockIdx.x * STACK_TILE;
     double2 v[K];
+    double rc[REV ? K : 1];
     {
         const int i = i0 + ty, j = j0 + tx;
         const bool in = i < ni && j < nj;
@@ -36,14 +49,32 @@ __global__ __launch_bounds__(STACK_THREADS) void k_stack_planes(StackCuts cuts, 
 #pragma unroll
         for (int c = 0; c < K; ++c) v[c] = cuts.xy[c][o];
     }
+    const int i = i0 + tx, j = j0 + ty;
+    const bool valid = i < ni && j < nj;
+    if (REV && static_cast<int>(threadIdx.x) < K) sh_out[threadIdx.x] = 0;   // ordered before the first atomic by the first cut's barrier
 #pragma unroll
     for (int c = 0; c < K; ++c) {
         tile[c & 1][ty][tx] = v[c];
+        if (REV) stack_surf_stage(sh_u[c & 1], surf, c, static_cast<int>(threadIdx.x));
         __syncthreads();   // tile[c & 1] is written again two cuts later: every thread has passed the next barrier, i.e. read it, by then
         v[c] = tile[c & 1][tx][ty];
+        if (REV) {
+            double xs, rs;
+            const bool out = stack_surf_node(sh_u[c & 1], surf, c, v[c].x, &xs, &rs);
+            v[c].x = xs;
+            rc[c] = rs;
+            v[c].y = v[c].y / cuts.radius[c];
+            if (outside) {
+                const unsigned long long m = __ballot(out && valid);
+                if ((threadIdx.x & 63) == 0 && m) atomicAdd(&sh_out[c], static_cast<unsigned>(__popcll(m)));
+            }
+        }
     }
-    const int i = i0 + tx, j = j0 + ty;
-    if (i >= ni || j >= nj) return;   // no barrier below
+    if (REV && outside) {
+        __syncthreads();
+        if (static_cast<int>(threadIdx.x) < K && sh_out[threadIdx.x]) atomicAdd(&outside[threadIdx.x], static_cast<unsigned long long>(sh_out[threadIdx.x]));
+    }
+    if (!valid) return;   // no barrier below
     if (MAP == TM_STACK_CYLINDRICAL) {
 #pragma unroll
         for (int c = 0; c < K; ++c) v[c].y = v[c].y / cuts.radius[c];
@@ -52,15 +83,16 @@ __global__ __launch_bounds__(STACK_THREADS) void k_stack_planes(StackCuts cuts, 
     size_t o = static_cast<size_t>(j) * ni + i;
     for (int k = 0; k < nk; ++k, o += plane) {
         const double* __restrict__ w = table + static_cast<size_t>(k) * (K + 1);   // wave-uniform
-        double ax = w[0] * v[0].x, ay = w[0] * v[0].y;
+        double ax = w[0] * v[0].x, ay = w[0] * v[0].y, ar = REV ? w[0] * rc[0] : 0.0;
 #pragma unroll
         for (int c = 1; c < K; ++c) {
             ax = ax + w[c] * v[c].x;
             ay = ay + w[c] * v[c].y;
+            if (REV) ar = ar + w[c] * rc[c];
         }
-        const double s = w[K];
+        const double s = REV ? ar : w[K];
         X[o] = ax;
-        if (MAP == TM_STACK_CYLINDRICAL) {
+        if (MAP == TM_STACK_CYLINDRICAL || REV) {
             double sn, cs;
             sincos(ay, &sn, &cs);
             Y[o] = s * sn;
@@ -73,19 +105,22 @@ __global__ __launch_bounds__(STACK_THREADS) void k_stack_planes(StackCuts cuts, 
 }
 
 template <int K>
-static void stack_launch_k(const StackCuts& cuts, int mapping, const double* table, int nk, int ni, int nj, double* X, double* Y, double* Z, hipStream_t st) {
+static void stack_launch_k(const StackCuts& cuts, const StackSurf& surf, int mapping, const double* table, int nk, int ni, int nj, double* X, double* Y, double* Z,
+                           unsigned long long* outside, hipStream_t st) {
     const dim3 grid((nj + STACK_TILE - 1) / STACK_TILE, (ni + STACK_TILE - 1) / STACK_TILE), block(STACK_THREADS);
-    if (mapping == TM_STACK_CYLINDRICAL)
-        hipLaunchKernelGGL((k_stack_planes<K, TM_STACK_CYLINDRICAL>), grid, block, 0, st, cuts, table, nk, ni, nj, X, Y, Z);
+    if (mapping == TM_STACK_REVOLUTION)
+        hipLaunchKernelGGL((k_stack_planes<K, TM_STACK_REVOLUTION>), grid, block, 0, st, cuts, surf, table, nk, ni, nj, X, Y, Z, outside);
+    else if (mapping == TM_STACK_CYLINDRICAL)
+        hipLaunchKernelGGL((k_stack_planes<K, TM_STACK_CYLINDRICAL>), grid, block, 0, st, cuts, surf, table, nk, ni, nj, X, Y, Z, outside);
     else
-        hipLaunchKernelGGL((k_stack_planes<K, TM_STACK_PLANAR>), grid, block, 0, st, cuts, table, nk, ni, nj, X, Y, Z);
+        hipLaunchKernelGGL((k_stack_planes<K, TM_STACK_PLANAR>), grid, block, 0, st, cuts, surf, table, nk, ni, nj, X, Y, Z, outside);
 }
 
-static hipError_t launch_stack_planes(int K, const StackCuts& cuts, int mapping, const double* table, int nk, int ni, int nj, double* X, double* Y, double* Z,
-                                      hipStream_t st) {
+static hipError_t launch_stack_planes(int K, const StackCuts& cuts, const StackSurf& surf, int mapping, const double* table, int nk, int ni, int nj, double* X,
+                                      double* Y, double* Z, unsigned long long* outside, hipStream_t st) {
     switch (K) {
 #define TM_STACK_CASE(n) \
-    case n: stack_launch_k<n>(cuts, mapping, table, nk, ni, nj, X, Y, Z, st); break;
+    case n: stack_launch_k<n>(cuts, surf, mapping, table, nk, ni, nj, X, Y, Z, outside, st); break;
         TM_STACK_CASE(2) TM_STACK_CASE(3) TM_STACK_CASE(4) TM_STACK_CASE(5) TM_STACK_CASE(6) TM_STACK_CASE(7) TM_STACK_CASE(8) TM_STACK_CASE(9)
         TM_STACK_CASE(10) TM_STACK_CASE(11) TM_STACK_CASE(12) TM_STACK_CASE(13) TM_STACK_CASE(14) TM_STACK_CASE(15) TM_STACK_CASE(16)
 #undef TM_STACK_CASE
@@ -95,11 +130,20 @@ static hipError_t launch_stack_planes(int K, const StackCuts& cuts, int mapping,
 }
 
 // The window's table to the device, the kernel on `st`, the three planes back to the host; returns when they have arrived.
+// `sf` (TM_STACK_REVOLUTION): the meridional tables go up on `st` like the weight table; outside[c], when asked for, comes back with the planes.
 static void stack_run(const StackPlan& p, StackCuts& cuts, uint64_t k_begin, uint64_t k_count, uint64_t ni, uint64_t nj, double* x, double* y, double* z,
-                      hipStream_t st) {
+                      hipStream_t st, const SurfPlan* sf = nullptr, uint64_t* outside = nullptr) {
     const int K = p.ncuts;
     if (k_count >= (uint64_t{1} << 31)) throw TmError(TM_E_SIZE, "layer window out of range");
     stack_fill_radii(p, cuts);
+    StackSurfDev sd;
+    std::unique_ptr<StackBuf> d_outside;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are copied out as they are");
+    if (sf) stack_surf_upload(p, *sf, cuts, sd, st);
+    if (sf && outside) {
+        d_outside = std::make_unique<StackBuf>(sizeof(unsigned long long) * TM_STACK_MAX_CUTS, "stack outside counts");
+        HIPCHK(hipMemsetAsync(d_outside->p, 0, sizeof(unsigned long long) * TM_STACK_MAX_CUTS, st));
+    }
     std::vector<double> table(static_cast<size_t>(k_count) * (K + 1));
     for (uint64_t k = 0; k < k_count; ++k) {
         std::memcpy(&table[k * (K + 1)], &p.weights[(k_begin + k) * K], sizeof(double) * K);
@@ -109,11 +153,29 @@ static void stack_run(const StackPlan& p, StackCuts& cuts, uint64_t k_begin, uin
     StackBuf d_table(sizeof(double) * table.size(), "stack weights"), d_out(sizeof(double) * 3 * n, "stack planes");
     HIPCHK(hipMemcpyAsync(d_table.p, table.data(), sizeof(double) * table.size(), hipMemcpyHostToDevice, st));
     double* out = d_out.as<double>();
-    HIPCHK(launch_stack_planes(K, cuts, p.mapping, d_table.as<double>(), static_cast<int>(k_count), static_cast<int>(ni), static_cast<int>(nj), out, out + n, out + 2 * n, st));
+    HIPCHK(launch_stack_planes(K, cuts, sd.surf, p.mapping, d_table.as<double>(), static_cast<int>(k_count), static_cast<int>(ni), static_cast<int>(nj), out, out + n,
+                               out + 2 * n, d_outside ? d_outside->as<unsigned long long>() : nullptr, st));
+    if (d_outside) HIPCHK(hipMemcpyAsync(outside, d_outside->p, sizeof(uint64_t) * K, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(x, out, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(y, out + n, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(z, out + 2 * n, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));   // `table` and the device buffers live until here
+}
+
+void stack_surf_upload(const StackPlan& p, const SurfPlan& sf, StackCuts& cuts, StackSurfDev& d, hipStream_t st) {
+    const size_t nknots = (sf.knots.size() + 3) / 4 * 4;   // the coefficients start on a 32 B boundary: they are read as double4
+    d.host.assign(nknots + sf.coef.size(), 0.0);
+    std::copy(sf.knots.begin(), sf.knots.end(), d.host.begin());
+    std::copy(sf.coef.begin(), sf.coef.end(), d.host.begin() + nknots);
+    d.dev = std::make_unique<StackBuf>(sizeof(double) * d.host.size(), "stack meridional tables");
+    HIPCHK(hipMemcpyAsync(d.dev->p, d.host.data(), sizeof(double) * d.host.size(), hipMemcpyHostToDevice, st));
+    d.surf.knots = d.dev->as<double>();
+    d.surf.coef = d.dev->as<double>() + nknots;
+    for (int c = 0; c < TM_STACK_MAX_CUTS; ++c) {
+        d.surf.first[c] = c < p.ncuts ? sf.first[c] : 0;
+        d.surf.nknots[c] = c < p.ncuts ? sf.nknots[c] : 2;
+        if (c < p.ncuts) cuts.radius[c] = sf.rref[c];
+    }
 }
 
 void stack_resident_cuts(tm_smoother* const* cuts, const StackPlan& p, uint64_t block, StackCuts& dc, uint64_t* ni, uint64_t* nj) {
@@ -183,6 +245,45 @@ extern "C" int tm_stack_smoothers(tm_smoother* const* cuts, const tm_stack_opt* 
         std::vector<std::unique_ptr<StackEvent>> events;
         const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
         stack_run(p, dc, k_begin, k_count, ni, nj, x, y, z, st);   // synchronises st: the other handles' coordinates have been read when it returns
+        return TM_OK;
+    });
+}
+
+extern "C" int tm_stack_block_surf(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, uint64_t block, uint64_t k_begin,
+                                   uint64_t k_count, double* x, double* y, double* z, uint64_t* outside) {
+    return guarded([&]() {
+        if (!x || !y || !z) throw TmError(TM_E_ARG, "null argument");
+        SurfPlan sf;
+        const StackPlan p = stack_plan_surf(opt, surfaces, sf);
+        stack_check_window(p, k_begin, k_count);
+        uint64_t ni = 0, nj = 0;
+        stack_check_cuts(cuts, p.ncuts, block, &ni, &nj);
+        require_gfx950_stack();
+        const size_t n = static_cast<size_t>(ni) * nj;
+        StackBuf in(sizeof(double2) * n * p.ncuts, "stack cuts");
+        StackCuts dc{};
+        for (int c = 0; c < p.ncuts; ++c) {
+            dc.xy[c] = in.as<double2>() + n * c;
+            HIPCHK(hipMemcpy(in.as<double2>() + n * c, cuts[c]->blocks[block].xy, sizeof(double2) * n, hipMemcpyHostToDevice));
+        }
+        stack_run(p, dc, k_begin, k_count, ni, nj, x, y, z, nullptr, &sf, outside);
+        return TM_OK;
+    });
+}
+
+extern "C" int tm_stack_smoothers_surf(tm_smoother* const* cuts, const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, uint64_t block, uint64_t k_begin,
+                                       uint64_t k_count, double* x, double* y, double* z, uint64_t* outside) {
+    return guarded([&]() {
+        if (!cuts || !x || !y || !z) throw TmError(TM_E_ARG, "null argument");
+        SurfPlan sf;
+        const StackPlan p = stack_plan_surf(opt, surfaces, sf);
+        stack_check_window(p, k_begin, k_count);
+        StackCuts dc{};
+        uint64_t ni = 0, nj = 0;
+        stack_resident_cuts(cuts, p, block, dc, &ni, &nj);
+        std::vector<std::unique_ptr<StackEvent>> events;
+        const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
+        stack_run(p, dc, k_begin, k_count, ni, nj, x, y, z, st, &sf, outside);   // synchronises st
         return TM_OK;
     });
 }

@@ -20,8 +20,25 @@ struct StackPlan {
     std::vector<double> layers;    // s[nlayers]
 };
 
-// throws TmError(TM_E_ARG) on any violation of the definition
+// throws TmError(TM_E_ARG) on any violation of the definition (TM_STACK_REVOLUTION included: these calls have no tables)
 StackPlan stack_plan(const tm_stack_opt* opt);
+
+// validated meridional tables of a TM_STACK_REVOLUTION call ("cuts on stream surfaces of revolution")
+struct SurfPlan {
+    std::vector<int> nknots;     // N_c
+    std::vector<int> first;      // index of cut c's first knot in `knots`; its first coefficient is (first[c] - c) * 8 into `coef`
+    std::vector<double> knots;   // u, cut after cut
+    std::vector<double> coef;    // ax bx cx dx ar br cr dr per interval, cut after cut (what tm_stack_surface_tables returns)
+    std::vector<double> rref;    // [ncuts]
+};
+// the plan of a *_surf call: TM_E_ARG unless opt->mapping == TM_STACK_REVOLUTION and the tables are as the header says
+StackPlan stack_plan_surf(const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, SurfPlan& surf);
+// x_c, r_c, theta_c of every node of the block (node (i,j) at i*nj + j), cut c at c*ni*nj; outside[c] when given
+void stack_surf_nodes_host(const StackPlan& plan, const SurfPlan& surf, const double* const* v, uint64_t ni, uint64_t nj, std::vector<double>& x,
+                           std::vector<double>& r, std::vector<double>& th, uint64_t* outside);
+// layer k from them: the planes X, R sin Theta, R cos Theta, element j*ni + i
+void stack_layer_surf_host(const StackPlan& plan, const std::vector<double>& xc, const std::vector<double>& rc, const std::vector<double>& thc, uint64_t k,
+                           uint64_t ni, uint64_t nj, double* x, double* y, double* z);
 // TM_E_ARG unless [k_begin, k_begin + k_count) is a non-empty window of the plan's layers
 void stack_check_window(const StackPlan& plan, uint64_t k_begin, uint64_t k_count);
 // block `block` of the K descriptions: TM_E_ARG / TM_E_SIZE as the header says; returns (ni, nj)

@@ -2,6 +2,7 @@
 // buffers and events, the gfx950 check, and the K handles of a call resolved to device pointers behind their pending work.
 #pragma once
 #include "tm_stack.hpp"
+#include "tm_stack_surface.hpp"
 #include "tm_api_util.hpp"
 #include "tm_smoother.hpp"
 
@@ -16,6 +17,15 @@ namespace tmh {
 struct StackCuts {
     const double2* xy[TM_STACK_MAX_CUTS];   // the block in each cut, node (i,j) at i*nj + j
     double radius[TM_STACK_MAX_CUTS];       // z[c] (cylindrical mapping)
+};
+
+// the meridional tables of a TM_STACK_REVOLUTION call on the device (K15); null pointers with the other mappings.  The reference radii
+// travel in StackCuts::radius.
+struct StackSurf {
+    const double* knots;   // u, cut after cut
+    const double* coef;    // 8 per interval, cut after cut
+    int first[TM_STACK_MAX_CUTS];    // index of cut c's first knot; its first coefficient is (first[c] - c) * 8
+    int nknots[TM_STACK_MAX_CUTS];   // 2 .. TM_STACK_MAX_KNOTS
 };
 
 struct StackBuf {   // RAII device buffer
@@ -44,6 +54,37 @@ inline void stack_fill_radii(const StackPlan& p, StackCuts& cuts) {
         if (c >= p.ncuts) cuts.xy[c] = nullptr;
     }
 }
+
+// K15, one cut.  Staging: every thread t < TM_STACK_MAX_KNOTS of the workgroup writes one entry of `sh_u`, knot t of the cut up to
+// N-2 and +inf behind it (surf_locate_padded); the caller's barrier follows.
+__device__ __forceinline__ void stack_surf_stage(double* sh_u, const StackSurf& surf, int c, int t) {
+    if (t < TM_STACK_MAX_KNOTS) sh_u[t] = t < surf.nknots[c] - 1 ? surf.knots[surf.first[c] + t] : __builtin_huge_val();
+}
+// Search and evaluation on the lane's node: the knots from LDS, the table's last knot under a wave-uniform address, the 64 bytes of the
+// interval's coefficients gathered from the table (L2).  Returns whether u lies outside the table.
+__device__ __forceinline__ bool stack_surf_node(const double* sh_u, const StackSurf& surf, int c, double un, double* x, double* r) {
+    const int N = surf.nknots[c];
+    const int n = surf_locate_padded(sh_u, surf_first_step(N), un);   // <= N-2: inside the cut's table
+    const double4* __restrict__ q = reinterpret_cast<const double4*>(surf.coef + (static_cast<size_t>(surf.first[c] - c) + n) * SURF_COEF);
+    const double4 qx = q[0], qr = q[1];
+    const double cf[SURF_COEF] = {qx.x, qx.y, qx.z, qx.w, qr.x, qr.y, qr.z, qr.w};
+    double xs, rs;
+    surf_eval(cf, un - sh_u[n], &xs, &rs);
+    // the two values are wanted HERE: left to itself the scheduler carries the 16 registers of coefficients of every cut past the next
+    // barrier and evaluates late, which costs 12 registers per cut
+    asm volatile("" : "+v"(xs), "+v"(rs));
+    *x = xs;
+    *r = rs;
+    return surf_outside(sh_u[0], surf.knots[surf.first[c] + N - 1], un);
+}
+
+// The tables of `sf` into one device buffer on `st` (`host` must live until st has been synchronised); reference radii into cuts.radius.
+struct StackSurfDev {
+    std::vector<double> host;
+    std::unique_ptr<struct StackBuf> dev;
+    StackSurf surf{};
+};
+void stack_surf_upload(const StackPlan& p, const SurfPlan& sf, StackCuts& cuts, StackSurfDev& d, hipStream_t st);
 
 inline void require_gfx950_stack() {
     int dev = 0;

@@ -39,8 +39,11 @@ __device__ __forceinline__ unsigned long long sq_shfl(unsigned long long v, int 
 // [k0, k1).  partials: one record per workgroup, or null when only the field is wanted; field: per-cell min of o*s, element
 // ((k - k0)*(nj-1) + j)*(ni-1) + i, or null.
 template <int K, int MAP>
-__global__ __launch_bounds__(SQ_THREADS) void k_stack_quality(StackCuts cuts, const double* __restrict__ table, int k0, int k1, int ni, int nj,
+__global__ __launch_bounds__(SQ_THREADS) void k_stack_quality(StackCuts cuts, StackSurf surf, const double* __restrict__ table, int k0, int k1, int ni, int nj,
                                                               Q3Acc* __restrict__ partials, double* __restrict__ field, int orientation) {
+    constexpr bool REV = MAP == TM_STACK_REVOLUTION;
+    static_assert(TM_STACK_MAX_KNOTS <= SQ_THREADS, "one thread stages one knot");
+    __shared__ double sh_u[REV ? 2 : 1][REV ? TM_STACK_MAX_KNOTS : 1];
     __shared__ double sh[2][6][SQ_THREADS];   // per buffer: x, y, z, then the lengths of the node's i-, j- and k-edge; one column per thread
     __shared__ unsigned sh_hist[20];
     __shared__ Q3Acc sh_acc[SQ_WAVES];
@@ -64,6 +67,21 @@ __global__ __launch_bounds__(SQ_THREADS) void k_stack_quality(StackCuts cuts, co
 #pragma unroll
         for (int c = 0; c < K; ++c) v[c].y = v[c].y / cuts.radius[c];
     }
+    // K15 (tm_stack.hip): cut after cut the knots pass through LDS, two buffers alternating, one barrier per cut; the node then holds
+    // (x_c, theta_c) in v[c] and r_c in rc[c], formed by K11's very expressions
+    double rc[REV ? K : 1];
+    if (REV) {
+#pragma unroll
+        for (int c = 0; c < K; ++c) {
+            stack_surf_stage(sh_u[c & 1], surf, c, t);
+            __syncthreads();
+            double xs, rs;
+            stack_surf_node(sh_u[c & 1], surf, c, v[c].x, &xs, &rs);
+            v[c].x = xs;
+            rc[c] = rs;
+            v[c].y = v[c].y / cuts.radius[c];
+        }
+    }
 
     Q3Acc acc;
     q3_init(acc);
@@ -76,16 +94,17 @@ __global__ __launch_bounds__(SQ_THREADS) void k_stack_quality(StackCuts cuts, co
     for (int k = k0; k <= k1; ++k) {
         const double* __restrict__ w = table + static_cast<size_t>(k) * (K + 1);   // wave-uniform
         // K11's expression, operation for operation
-        double ax = w[0] * v[0].x, ay = w[0] * v[0].y;
+        double ax = w[0] * v[0].x, ay = w[0] * v[0].y, ar = REV ? w[0] * rc[0] : 0.0;
 #pragma unroll
         for (int c = 1; c < K; ++c) {
             ax = ax + w[c] * v[c].x;
             ay = ay + w[c] * v[c].y;
+            if (REV) ar = ar + w[c] * rc[c];
         }
-        const double s = w[K];
+        const double s = REV ? ar : w[K];
         Q3Point c00;
         c00.x = ax;
-        if (MAP == TM_STACK_CYLINDRICAL) {
+        if (MAP == TM_STACK_CYLINDRICAL || REV) {
             double sn, cs;
             sincos(ay, &sn, &cs);
             c00.y = s * sn;
@@ -187,20 +206,22 @@ __global__ __launch_bounds__(64) void k_stack_quality_finalize(const Q3Acc* __re
 static dim3 stack_quality_grid(int ni, int nj) { return dim3((nj - 1 + SQ_OWN - 1) / SQ_OWN, (ni - 1 + SQ_OWN - 1) / SQ_OWN); }
 
 template <int K>
-static void stack_quality_launch_k(const StackCuts& cuts, int mapping, const double* table, int k0, int k1, int ni, int nj, Q3Acc* partials, double* field,
-                                   int orientation, hipStream_t st) {
+static void stack_quality_launch_k(const StackCuts& cuts, const StackSurf& surf, int mapping, const double* table, int k0, int k1, int ni, int nj, Q3Acc* partials,
+                                   double* field, int orientation, hipStream_t st) {
     const dim3 grid = stack_quality_grid(ni, nj), block(SQ_THREADS);
-    if (mapping == TM_STACK_CYLINDRICAL)
-        hipLaunchKernelGGL((k_stack_quality<K, TM_STACK_CYLINDRICAL>), grid, block, 0, st, cuts, table, k0, k1, ni, nj, partials, field, orientation);
+    if (mapping == TM_STACK_REVOLUTION)
+        hipLaunchKernelGGL((k_stack_quality<K, TM_STACK_REVOLUTION>), grid, block, 0, st, cuts, surf, table, k0, k1, ni, nj, partials, field, orientation);
+    else if (mapping == TM_STACK_CYLINDRICAL)
+        hipLaunchKernelGGL((k_stack_quality<K, TM_STACK_CYLINDRICAL>), grid, block, 0, st, cuts, surf, table, k0, k1, ni, nj, partials, field, orientation);
     else
-        hipLaunchKernelGGL((k_stack_quality<K, TM_STACK_PLANAR>), grid, block, 0, st, cuts, table, k0, k1, ni, nj, partials, field, orientation);
+        hipLaunchKernelGGL((k_stack_quality<K, TM_STACK_PLANAR>), grid, block, 0, st, cuts, surf, table, k0, k1, ni, nj, partials, field, orientation);
 }
 
-static hipError_t launch_stack_quality(int K, const StackCuts& cuts, int mapping, const double* table, int k0, int k1, int ni, int nj, Q3Acc* partials,
+static hipError_t launch_stack_quality(int K, const StackCuts& cuts, const StackSurf& surf, int mapping, const double* table, int k0, int k1, int ni, int nj, Q3Acc* partials,
                                        double* field, int orientation, hipStream_t st) {
     switch (K) {
 #define TM_STACK_CASE(n) \
-    case n: stack_quality_launch_k<n>(cuts, mapping, table, k0, k1, ni, nj, partials, field, orientation, st); break;
+    case n: stack_quality_launch_k<n>(cuts, surf, mapping, table, k0, k1, ni, nj, partials, field, orientation, st); break;
         TM_STACK_CASE(2) TM_STACK_CASE(3) TM_STACK_CASE(4) TM_STACK_CASE(5) TM_STACK_CASE(6) TM_STACK_CASE(7) TM_STACK_CASE(8) TM_STACK_CASE(9)
         TM_STACK_CASE(10) TM_STACK_CASE(11) TM_STACK_CASE(12) TM_STACK_CASE(13) TM_STACK_CASE(14) TM_STACK_CASE(15) TM_STACK_CASE(16)
 #undef TM_STACK_CASE
@@ -225,15 +246,19 @@ static void stack_quality_check_sizes(const StackPlan& p, uint64_t ni, uint64_t 
 }
 
 // The report of the whole stack: table up, K12 and its finalize on `st`, the record back; returns when it has arrived.
-static void stack_quality_run(const StackPlan& p, StackCuts& cuts, uint64_t block, uint64_t ni, uint64_t nj, tm_quality3d* out, hipStream_t st) {
+// `sf` (TM_STACK_REVOLUTION): the meridional tables go up on `st` like the weight table.
+static void stack_quality_run(const StackPlan& p, StackCuts& cuts, uint64_t block, uint64_t ni, uint64_t nj, tm_quality3d* out, hipStream_t st,
+                              const SurfPlan* sf = nullptr) {
     const int K = p.ncuts;
     stack_fill_radii(p, cuts);
+    StackSurfDev sd;
+    if (sf) stack_surf_upload(p, *sf, cuts, sd, st);
     const dim3 grid = stack_quality_grid(static_cast<int>(ni), static_cast<int>(nj));
     const size_t nrec = static_cast<size_t>(grid.x) * grid.y;   // the records buffer is sized from the very grid that writes it
     std::vector<double> table(static_cast<size_t>(p.nlayers) * (K + 1));
     StackBuf d_table(sizeof(double) * table.size(), "stack weights"), d_rec(sizeof(Q3Acc) * nrec, "stack quality records"), d_out(sizeof(tm_quality3d), "stack quality result");
     stack_quality_table(p, table, d_table, st);
-    HIPCHK(launch_stack_quality(K, cuts, p.mapping, d_table.as<double>(), 0, static_cast<int>(p.nlayers) - 1, static_cast<int>(ni), static_cast<int>(nj), d_rec.as<Q3Acc>(),
+    HIPCHK(launch_stack_quality(K, cuts, sd.surf, p.mapping, d_table.as<double>(), 0, static_cast<int>(p.nlayers) - 1, static_cast<int>(ni), static_cast<int>(nj), d_rec.as<Q3Acc>(),
                                 nullptr, 0, st));
     hipLaunchKernelGGL(k_stack_quality_finalize, dim3(1), dim3(64), 0, st, d_rec.as<Q3Acc>(), static_cast<long long>(nrec), block, ni, nj, p.nlayers, d_out.as<tm_quality3d>());
     HIPCHK(hipGetLastError());
@@ -243,14 +268,16 @@ static void stack_quality_run(const StackPlan& p, StackCuts& cuts, uint64_t bloc
 
 // per-cell min of o*s of the cell layers [k_begin, k_begin + k_count)
 static void stack_quality_field_run(const StackPlan& p, StackCuts& cuts, uint64_t ni, uint64_t nj, uint64_t k_begin, uint64_t k_count, int orientation,
-                                    double* host_field, hipStream_t st) {
+                                    double* host_field, hipStream_t st, const SurfPlan* sf = nullptr) {
     const int K = p.ncuts;
     stack_fill_radii(p, cuts);
+    StackSurfDev sd;
+    if (sf) stack_surf_upload(p, *sf, cuts, sd, st);
     const size_t cells = static_cast<size_t>(k_count) * (ni - 1) * (nj - 1);
     std::vector<double> table(static_cast<size_t>(p.nlayers) * (K + 1));
     StackBuf d_table(sizeof(double) * table.size(), "stack weights"), d_field(sizeof(double) * cells, "stack quality cells");
     stack_quality_table(p, table, d_table, st);
-    HIPCHK(launch_stack_quality(K, cuts, p.mapping, d_table.as<double>(), static_cast<int>(k_begin), static_cast<int>(k_begin + k_count), static_cast<int>(ni),
+    HIPCHK(launch_stack_quality(K, cuts, sd.surf, p.mapping, d_table.as<double>(), static_cast<int>(k_begin), static_cast<int>(k_begin + k_count), static_cast<int>(ni),
                                 static_cast<int>(nj), nullptr, d_field.as<double>(), orientation, st));
     HIPCHK(hipMemcpyAsync(host_field, d_field.p, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -310,6 +337,65 @@ extern "C" int tm_stack_smoothers_quality_field(tm_smoother* const* cuts, const 
         tm_quality3d q;
         stack_quality_run(p, dc, block, ni, nj, &q, st);   // the orientation first
         stack_quality_field_run(p, dc, ni, nj, k_begin, k_count, q.orientation, min_scaled_jacobian, st);
+        return TM_OK;
+    });
+}
+
+extern "C" int tm_stack_quality_surf(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, uint64_t block,
+                                     tm_quality3d* out) {
+    return guarded([&]() {
+        if (!out) throw TmError(TM_E_ARG, "null argument");
+        SurfPlan sf;
+        const StackPlan p = stack_plan_surf(opt, surfaces, sf);
+        uint64_t ni = 0, nj = 0;
+        stack_check_cuts(cuts, p.ncuts, block, &ni, &nj);
+        stack_quality_check_sizes(p, ni, nj);
+        require_gfx950_stack();
+        const size_t n = static_cast<size_t>(ni) * nj;
+        StackBuf in(sizeof(double2) * n * p.ncuts, "stack cuts");
+        StackCuts dc{};
+        for (int c = 0; c < p.ncuts; ++c) {
+            dc.xy[c] = in.as<double2>() + n * c;
+            HIPCHK(hipMemcpy(in.as<double2>() + n * c, cuts[c]->blocks[block].xy, sizeof(double2) * n, hipMemcpyHostToDevice));
+        }
+        stack_quality_run(p, dc, block, ni, nj, out, nullptr, &sf);
+        return TM_OK;
+    });
+}
+
+extern "C" int tm_stack_smoothers_quality_surf(tm_smoother* const* cuts, const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, uint64_t block,
+                                               tm_quality3d* out) {
+    return guarded([&]() {
+        if (!cuts || !out) throw TmError(TM_E_ARG, "null argument");
+        SurfPlan sf;
+        const StackPlan p = stack_plan_surf(opt, surfaces, sf);
+        StackCuts dc{};
+        uint64_t ni = 0, nj = 0;
+        stack_resident_cuts(cuts, p, block, dc, &ni, &nj);
+        stack_quality_check_sizes(p, ni, nj);
+        std::vector<std::unique_ptr<StackEvent>> events;
+        const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
+        stack_quality_run(p, dc, block, ni, nj, out, st, &sf);   // synchronises st
+        return TM_OK;
+    });
+}
+
+extern "C" int tm_stack_smoothers_quality_field_surf(tm_smoother* const* cuts, const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, uint64_t block,
+                                                     uint64_t k_begin, uint64_t k_count, double* min_scaled_jacobian) {
+    return guarded([&]() {
+        if (!cuts || !min_scaled_jacobian) throw TmError(TM_E_ARG, "null argument");
+        SurfPlan sf;
+        const StackPlan p = stack_plan_surf(opt, surfaces, sf);
+        StackCuts dc{};
+        uint64_t ni = 0, nj = 0;
+        stack_resident_cuts(cuts, p, block, dc, &ni, &nj);
+        stack_quality_check_sizes(p, ni, nj);
+        if (k_count < 1 || k_begin >= p.nlayers - 1 || k_count > p.nlayers - 1 - k_begin) throw TmError(TM_E_ARG, "the window of cell layers is empty or reaches past nlayers - 1");
+        std::vector<std::unique_ptr<StackEvent>> events;
+        const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
+        tm_quality3d q;
+        stack_quality_run(p, dc, block, ni, nj, &q, st, &sf);   // the orientation first
+        stack_quality_field_run(p, dc, ni, nj, k_begin, k_count, q.orientation, min_scaled_jacobian, st, &sf);
         return TM_OK;
     });
 }

@@ -277,6 +277,68 @@ static int stackCuts(std::size_t ni, std::size_t nj, std::size_t ncuts, std::siz
     return ok ? 0 : 1;
 }
 
+// tm_harness stack-revolution <ni> <nj> <ncuts> <nlayers>: the cuts of `stack`, read as cuts in the unrolled plane of coaxial cones
+// r = (1 + c/4) + (x + 1/2)/2, x = u (nine knots over [-1/2, 3/2], all dyadic, so the knots lie on their cone exactly; natural splines
+// through them): the layers from the coordinates resident in the handles (stack::stack_block -> tm_stack_smoothers_surf).  A layer at a
+// cut must lie on the cut's cone, and the device's 3-D quality record must equal the CPU's report of those planes.
+static int stackRevolution(std::size_t ni, std::size_t nj, std::size_t ncuts, std::size_t nlayers) {
+    if (ncuts < 2 || nlayers < 2) throw Error(TM_E_ARG, "stack-revolution <ni> <nj> <ncuts> <nlayers>: at least two cuts and two layers");
+    smoothing::solver::Option opt;
+    opt.inner = TM_INNER_RELAX;
+    std::vector<discrete::Mesh> meshes;
+    meshes.reserve(ncuts);
+    for (std::size_t c = 0; c < ncuts; ++c) meshes.push_back(buildSingle(ni, nj, 0.05 + 0.001 * static_cast<double>(c)));
+    std::vector<std::unique_ptr<smoothing::smooth::Smoother>> handles;
+    std::vector<smoothing::smooth::Smoother*> cuts;
+    for (std::size_t c = 0; c < ncuts; ++c) {
+        handles.push_back(std::make_unique<smoothing::smooth::Smoother>(meshes[c], opt, smoothing::wall_control_function::Algorithm::laplace()));
+        handles.back()->iterate(5);
+        cuts.push_back(handles.back().get());
+    }
+    stack::Option so;
+    so.mapping = TM_STACK_REVOLUTION;
+    stack::Surfaces sf;
+    for (std::size_t c = 0; c < ncuts; ++c) {
+        so.span.push_back(static_cast<double>(c));
+        const double r0 = 1.0 + 0.25 * static_cast<double>(c);
+        sf.rref.push_back(r0);
+        std::vector<double> u, r;
+        for (int n = 0; n < 9; ++n) u.push_back(-0.5 + 0.25 * n), r.push_back(r0 + 0.5 * (u.back() + 0.5));
+        sf.u.push_back(u), sf.x.push_back(u), sf.r.push_back(r);
+    }
+    const double z1 = so.span.back();
+    for (std::size_t k = 0; k < nlayers; ++k) so.layers.push_back(k + 1 == nlayers ? z1 : z1 * (static_cast<double>(k) / static_cast<double>(nlayers - 1)));
+    std::vector<uint64_t> outside;
+    const stack::Block3d b = stack::stack_block(cuts, so, sf, 0, 0, nlayers, &outside);
+    const tm_quality3d q = stack::quality(cuts, so, sf, 0), qh = stack::quality(b);
+    const std::size_t n = ni * nj;
+    std::size_t compared = 0;
+    bool on = true;
+    for (std::size_t k = 0; k < nlayers; ++k) {
+        double sx = 0, sr = 0;
+        for (std::size_t p = 0; p < n; ++p) sx += b.x[k * n + p], sr += std::hypot(b.y[k * n + p], b.z[k * n + p]);
+        std::printf("stack-revolution: layer %zu s %.17g sum_x %.17g sum_r %.17g\n", k, so.layers[k], sx, sr);
+        for (std::size_t c = 0; c < ncuts; ++c) {
+            if (so.layers[k] != so.span[c]) continue;
+            ++compared;
+            for (std::size_t p = 0; p < n; ++p) {
+                const double x = b.x[k * n + p], r = std::hypot(b.y[k * n + p], b.z[k * n + p]), want = sf.rref[c] + 0.5 * (x + 0.5);
+                if (!(std::fabs(r - want) <= 64 * 2.220446049250313e-16 * (std::fabs(want) + std::fabs(x) + 1.0))) on = false;
+            }
+        }
+    }
+    for (std::size_t c = 0; c < ncuts; ++c) std::printf("stack-revolution: cut %zu extrapolated nodes %llu\n", c, static_cast<unsigned long long>(outside[c]));
+    tm_quality3d a = q, h = qh;
+    a.total_volume = h.total_volume = 0.0;   // a sum, added in another order on the device
+    const bool same = std::memcmp(&a, &h, sizeof(a)) == 0;
+    std::printf("stack-revolution: quality cells %llu inverted %llu degenerate %llu min_scaled_jacobian %.17g device equals host: %s\n",
+                static_cast<unsigned long long>(q.cells), static_cast<unsigned long long>(q.inverted), static_cast<unsigned long long>(q.degenerate),
+                q.min_scaled_jacobian, same ? "yes" : "no");
+    const bool ok = on && same && compared >= 2;
+    std::printf("stack-revolution: layers at cuts lie on their surfaces: %s\n", on && compared >= 2 ? "yes" : "no");
+    return ok ? 0 : 1;
+}
+
 // tm_harness stack-quality <ni> <nj> <ncuts> <nlayers>: the cuts of `stack`; the 3-D quality record of the stacked block from the
 // coordinates resident in the handles (stack::quality -> tm_stack_smoothers_quality), compared with the CPU's report of the planes
 // tm_stack_smoothers returns for the same handles (every field but the summed total_volume bit for bit).
@@ -387,6 +449,8 @@ int main(int argc, char** argv) {
             return elevateBlock(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), static_cast<int>(std::strtol(argv[4], nullptr, 10)));
         if (argc >= 6 && std::strcmp(argv[1], "stack-quality") == 0)
             return stackQuality(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10));
+        if (argc >= 6 && std::strcmp(argv[1], "stack-revolution") == 0)
+            return stackRevolution(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10));
         if (argc >= 6 && std::strcmp(argv[1], "stack") == 0)
             return stackCuts(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "csr") == 0) return csrKat();
@@ -394,7 +458,7 @@ int main(int argc, char** argv) {
             return thomasMiddlecoff(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "ranks") == 0) return runRank(argc, argv);
         if (argc < 5) {
-            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 2;
         }
         int a = 2;

@@ -480,6 +480,94 @@ inline Block3d stack_block(const std::vector<discrete::Mesh*>& cuts, const Optio
     b.x.resize(n), b.y.resize(n), b.z.resize(n);
     return b;
 }
+// cuts on stream surfaces of revolution (tm_hip.h): one meridional table x(u), r(u) per cut, for Option::mapping == TM_STACK_REVOLUTION
+struct Surfaces {
+    std::vector<std::vector<double>> u, x, r;   // per cut: knots (strictly increasing), axial position, radius (> 0); 2 .. 256 entries
+    std::vector<double> rref;                   // per cut, or empty: the span coordinates
+    int32_t interpolation = TM_SURF_CUBIC;
+    struct CStruct {                            // tm_stack_surfaces and the pointer lists it points into
+        std::vector<uint64_t> nknots;
+        std::vector<const double*> u, x, r;
+        tm_stack_surfaces s{};
+    };
+    std::unique_ptr<CStruct> c_struct() const {
+        if (u.size() != x.size() || u.size() != r.size()) throw Error(TM_E_ARG, "u, x, r: one table per cut each");
+        auto c = std::make_unique<CStruct>();
+        for (std::size_t k = 0; k < u.size(); ++k) {
+            if (u[k].size() != x[k].size() || u[k].size() != r[k].size()) throw Error(TM_E_ARG, "the u, x and r columns of a cut differ in length");
+            c->nknots.push_back(u[k].size());
+            c->u.push_back(u[k].data()), c->x.push_back(x[k].data()), c->r.push_back(r[k].data());
+        }
+        if (!rref.empty() && rref.size() != u.size()) throw Error(TM_E_ARG, "one reference radius per cut");
+        c->s = tm_stack_surfaces{u.size(), c->nknots.data(), c->u.data(), c->x.data(), c->r.data(), rref.empty() ? nullptr : rref.data(), interpolation, 0};
+        return c;
+    }
+};
+// per interval ax bx cx dx ar br cr dr, cut after cut (tm_stack_surface_tables: host only)
+inline std::vector<double> surface_tables(const Option& o, const Surfaces& sf) {
+    std::size_t n = 0;
+    for (const auto& k : sf.u) n += k.empty() ? 0 : 8 * (k.size() - 1);
+    std::vector<double> coef(n + 1);
+    const tm_stack_opt so = o.c_struct();
+    const auto cs = sf.c_struct();
+    check(tm_stack_surface_tables(&so, &cs->s, coef.data()));
+    coef.resize(n);
+    return coef;
+}
+// stack_block on the surfaces (tm_stack_smoothers_surf); outside, when given, receives per cut the number of extrapolated nodes
+inline Block3d stack_block(const std::vector<smoothing::smooth::Smoother*>& cuts, const Option& o, const Surfaces& sf, std::size_t block, std::size_t k_begin,
+                           std::size_t k_count, std::vector<uint64_t>* outside = nullptr) {
+    if (cuts.empty() || cuts.size() != o.span.size()) throw Error(TM_E_ARG, "one handle per span position");
+    std::vector<tm_smoother*> h;
+    for (const auto* c : cuts) h.push_back(c ? c->handle() : nullptr);
+    const tm_mesh_desc& d = cuts[0]->desc();
+    if (block >= d.nblocks) throw Error(TM_E_ARG, "block index past the mesh");
+    Block3d b;
+    b.ni = d.blocks[block].ni, b.nj = d.blocks[block].nj, b.nk = k_count;
+    const std::size_t n = b.ni * b.nj * k_count;
+    b.x.resize(n + 1), b.y.resize(n + 1), b.z.resize(n + 1);
+    const tm_stack_opt so = o.c_struct();
+    const auto cs = sf.c_struct();
+    if (outside) outside->assign(cuts.size(), 0);
+    check(tm_stack_smoothers_surf(h.data(), &so, &cs->s, block, k_begin, k_count, b.x.data(), b.y.data(), b.z.data(), outside ? outside->data() : nullptr));
+    b.x.resize(n), b.y.resize(n), b.z.resize(n);
+    return b;
+}
+// the same from host coordinates (tm_stack_block_surf; host = true: tm_stack_block_surf_host)
+inline Block3d stack_block(const std::vector<discrete::Mesh*>& cuts, const Option& o, const Surfaces& sf, std::size_t block, std::size_t k_begin, std::size_t k_count,
+                           bool host = false, std::vector<uint64_t>* outside = nullptr) {
+    if (cuts.empty() || cuts.size() != o.span.size()) throw Error(TM_E_ARG, "one mesh per span position");
+    std::vector<std::unique_ptr<smoothing::smooth::Desc>> descs;
+    std::vector<const tm_mesh_desc*> d;
+    for (auto* m : cuts) {
+        if (!m) throw Error(TM_E_ARG, "null mesh");
+        descs.push_back(std::make_unique<smoothing::smooth::Desc>(*m));
+        d.push_back(&descs.back()->desc);
+    }
+    if (block >= cuts[0]->blocks.size()) throw Error(TM_E_ARG, "block index past the mesh");
+    Block3d b;
+    b.ni = cuts[0]->blocks[block].points.size[0], b.nj = cuts[0]->blocks[block].points.size[1], b.nk = k_count;
+    const std::size_t n = b.ni * b.nj * k_count;
+    b.x.resize(n + 1), b.y.resize(n + 1), b.z.resize(n + 1);
+    const tm_stack_opt so = o.c_struct();
+    const auto cs = sf.c_struct();
+    if (outside) outside->assign(cuts.size(), 0);
+    check((host ? tm_stack_block_surf_host : tm_stack_block_surf)(d.data(), &so, &cs->s, block, k_begin, k_count, b.x.data(), b.y.data(), b.z.data(),
+                                                                  outside ? outside->data() : nullptr));
+    b.x.resize(n), b.y.resize(n), b.z.resize(n);
+    return b;
+}
+// 3-D quality of the blocks stacked on their surfaces, from the resident coordinates (tm_stack_smoothers_quality_surf)
+inline tm_quality3d quality(const std::vector<smoothing::smooth::Smoother*>& cuts, const Option& o, const Surfaces& sf, std::size_t block) {
+    if (cuts.empty() || cuts.size() != o.span.size()) throw Error(TM_E_ARG, "one handle per span position");
+    std::vector<tm_smoother*> h;
+    for (const auto* c : cuts) h.push_back(c ? c->handle() : nullptr);
+    const tm_stack_opt so = o.c_struct();
+    const auto cs = sf.c_struct();
+    tm_quality3d q;
+    check(tm_stack_smoothers_quality_surf(h.data(), &so, &cs->s, block, &q));
+    return q;
+}
 // 3-D quality of stacked blocks (tm_hip.h): the hexahedra of `block` of the stack, evaluated on the device straight from the coordinates
 // RESIDENT in one handle per cut (tm_stack_smoothers_quality: the 3-D block is never stored)
 inline tm_quality3d quality(const std::vector<smoothing::smooth::Smoother*>& cuts, const Option& o, std::size_t block) {

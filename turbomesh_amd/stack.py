@@ -8,6 +8,12 @@ natural-cubic-spline weights from the span positions alone, planar (x, y, s) or 
     X, Y, Z = st.block(cuts, b)            # cuts: a list of Mesh (uploaded per call) or of Smoother (resident coordinates)
     st.mesh3d(cuts).write("blade.xyz")     # multi-block 3-D PLOT3D
 
+Cuts meshed in the unrolled plane (u, v) of stream surfaces of revolution -- contoured end walls, mixed-flow and radial stages -- take
+mapping="revolution" and one meridional table x(u), r(u) per cut ("cuts on stream surfaces of revolution" in the header):
+
+    sf = Surfaces(u=[u0, u1], x=[x0, x1], r=[r0, r1], rref=[0.3, 0.5])       # meridional_from_contour gives u from a contour (x, r)
+    st = Stack(span, layers, mapping="revolution", surfaces=sf)
+
 Evaluated on the MI355X (kernel K11); `host=True` evaluates the same definition on the CPU (lists of Mesh only)."""
 from __future__ import annotations
 
@@ -21,7 +27,8 @@ from . import _capi
 from . import clustering as cluster
 
 INTERPOLATION = {"linear": _capi.TM_STACK_LINEAR, "cubic": _capi.TM_STACK_CUBIC}
-MAPPING = {"planar": _capi.TM_STACK_PLANAR, "cylindrical": _capi.TM_STACK_CYLINDRICAL}
+MAPPING = {"planar": _capi.TM_STACK_PLANAR, "cylindrical": _capi.TM_STACK_CYLINDRICAL, "revolution": _capi.TM_STACK_REVOLUTION}
+SURFACE_INTERPOLATION = {"linear": _capi.TM_SURF_LINEAR, "cubic": _capi.TM_SURF_CUBIC}
 
 
 def layers_from(span, nk, clustering=None):
@@ -38,6 +45,84 @@ def layers_from(span, nk, clustering=None):
     s = np.clip(z[0] + u * (z[-1] - z[0]), z[0], z[-1])
     s[0], s[-1] = z[0], z[-1]
     return s
+
+
+def meridional_from_contour(x, r, rref):
+    """The conformal parameter u of a meridional contour polyline (x_n, r_n): u_0 = 0, u_n = u_{n-1} + rref dm ln(r_n / r_{n-1}) /
+    (r_n - r_{n-1}) with dm the segment's length (the factor is 1 / r_n where the two radii are equal) -- rref times the integral of
+    dm / r along straight segments.  Host only, in longdouble, rounded once.  With it a cut meshed angle-preserving in (u, v = rref theta)
+    maps angle-preserving onto the surface; the u column of a hub or shroud table comes from here."""
+    LD = np.longdouble
+    x, r = np.asarray(x, dtype=np.float64).astype(LD).reshape(-1), np.asarray(r, dtype=np.float64).astype(LD).reshape(-1)
+    if x.size != r.size or x.size < 2:
+        raise ValueError("a contour needs at least two points (x_n, r_n)")
+    if not np.all(r > 0) or not float(rref) > 0:
+        raise ValueError("radii and the reference radius must be > 0")
+    dx, dr = np.diff(x), np.diff(r)
+    dm = np.sqrt(dx * dx + dr * dr)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f = np.where(dr == 0, 1 / r[1:], np.log(r[1:] / r[:-1]) / np.where(dr == 0, LD(1), dr))
+    u = np.concatenate([[LD(0)], np.cumsum(LD(np.float64(rref)) * dm * f)])
+    return np.asarray(u, dtype=np.float64)
+
+
+class Surfaces:
+    """tm_stack_surfaces: one meridional table per cut, lists of per-cut arrays u (strictly increasing), x, r (> 0), 2 .. 256 knots each,
+    the counts may differ between cuts.  rref: one reference radius per cut (None: the span coordinates of the Stack, which must then be
+    > 0).  interpolation: of x(u) and r(u) along the curve, "linear" or "cubic" (the natural spline)."""
+
+    def __init__(self, u, x, r, rref=None, interpolation="cubic"):
+        if interpolation not in SURFACE_INTERPOLATION:
+            raise ValueError(f"interpolation {interpolation!r}: one of {sorted(SURFACE_INTERPOLATION)}")
+        if not (len(u) == len(x) == len(r)):
+            raise ValueError("u, x, r: one array per cut each")
+        self.u = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in u]
+        self.x = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in x]
+        self.r = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in r]
+        for a, b, c in zip(self.u, self.x, self.r):
+            if not (a.size == b.size == c.size):
+                raise ValueError("the u, x and r columns of a cut differ in length")
+        self.rref = None if rref is None else np.ascontiguousarray(rref, dtype=np.float64).reshape(-1)
+        if self.rref is not None and self.rref.size != len(self.u):
+            raise ValueError(f"{self.rref.size} reference radii for {len(self.u)} cuts")
+        self.interpolation = interpolation
+        K = len(self.u)
+        self._nknots = np.array([a.size for a in self.u], dtype=np.uint64)
+        cols = lambda arrs: (C.POINTER(C.c_double) * max(1, K))(*[_capi.f64ptr(a) for a in arrs])   # noqa: E731
+        self._cols = [cols(self.u), cols(self.x), cols(self.r)]
+        self._struct = _capi.tm_stack_surfaces(K, self._nknots.ctypes.data_as(C.POINTER(C.c_uint64)), *self._cols,
+                                               None if self.rref is None else _capi.f64ptr(self.rref), SURFACE_INTERPOLATION[interpolation], 0)
+
+    @property
+    def ncuts(self):
+        return len(self.u)
+
+    def ref(self):
+        return C.byref(self._struct)
+
+    @classmethod
+    def read(cls, files, rref=None, interpolation="cubic"):
+        """One text file per cut, rows `u x r`, `#` comments and blank lines skipped, blanks, commas or semicolons between the numbers."""
+        cols = []
+        for f in files:
+            rows = []
+            with open(f) as fh:
+                for ln, line in enumerate(fh, 1):
+                    line = line.split("#", 1)[0].strip()
+                    if not line:
+                        continue
+                    parts = line.replace(",", " ").replace(";", " ").split()
+                    try:
+                        row = [float(p) for p in parts]
+                    except ValueError:
+                        row = []
+                    if len(row) != 3:
+                        raise ValueError(f"{f}:{ln}: a row of a meridional table is `u x r`")
+                    rows.append(row)
+            if len(rows) < 2:
+                raise ValueError(f"{f}: a meridional table needs at least two rows")
+            cols.append(np.array(rows, dtype=np.float64))
+        return cls([a[:, 0] for a in cols], [a[:, 1] for a in cols], [a[:, 2] for a in cols], rref, interpolation)
 
 
 def quality_of_planes(X, Y, Z, block=0, field=False):
@@ -79,11 +164,14 @@ class Mesh3d:
 class Stack:
     """tm_stack_opt + the calls that take it."""
 
-    def __init__(self, span, layers, interpolation="cubic", mapping="planar"):
+    def __init__(self, span, layers, interpolation="cubic", mapping="planar", surfaces=None):
         if interpolation not in INTERPOLATION:
             raise ValueError(f"interpolation {interpolation!r}: one of {sorted(INTERPOLATION)}")
         if mapping not in MAPPING:
             raise ValueError(f"mapping {mapping!r}: one of {sorted(MAPPING)}")
+        if (mapping == "revolution") != (surfaces is not None):
+            raise ValueError("mapping='revolution' takes surfaces=Surfaces(...), and only it does")
+        self.surfaces = surfaces
         self.span = np.ascontiguousarray(span, dtype=np.float64).reshape(-1)
         self.layers = np.ascontiguousarray(layers, dtype=np.float64).reshape(-1)
         self.interpolation, self.mapping = interpolation, mapping
@@ -101,18 +189,38 @@ class Stack:
     def weights(self):
         """The (nlayers, ncuts) weight matrix (tm_stack_weights: host only)."""
         w = np.empty((max(1, self.nlayers), max(1, self.ncuts)), dtype=np.float64)
-        _capi.check(_capi.lib().tm_stack_weights(C.byref(self._opt), _capi.f64ptr(w)))
+        opt = self._opt
+        if self.surfaces is not None:   # A depends on span, layers and interpolation alone; tm_stack_weights has no tables and refuses mapping 2
+            opt = _capi.tm_stack_opt(opt.ncuts, opt.span, opt.nlayers, opt.layers, opt.interpolation, _capi.TM_STACK_PLANAR)
+        _capi.check(_capi.lib().tm_stack_weights(C.byref(opt), _capi.f64ptr(w)))
         return w[:self.nlayers, :self.ncuts]
+
+    def surface_tables(self):
+        """Per cut the (nknots - 1, 8) coefficients ax bx cx dx ar br cr dr of its intervals (tm_stack_surface_tables: host only)."""
+        if self.surfaces is None:
+            raise ValueError("surface_tables: only with mapping='revolution'")
+        n = [max(0, int(a.size) - 1) for a in self.surfaces.u]
+        out = np.empty(max(1, 8 * sum(n)), dtype=np.float64)
+        _capi.check(_capi.lib().tm_stack_surface_tables(C.byref(self._opt), self.surfaces.ref(), _capi.f64ptr(out)))
+        off = np.concatenate([[0], np.cumsum(n)])
+        return [out[8 * off[c]:8 * off[c + 1]].reshape(-1, 8).copy() for c in range(len(n))]
 
     def _check_count(self, cuts):
         if len(cuts) != self.ncuts:
             raise ValueError(f"{len(cuts)} cuts for {self.ncuts} span positions")
 
-    def block(self, cuts, b, k_begin=0, k_count=None, host=False):
+    def block(self, cuts, b, k_begin=0, k_count=None, host=False, return_outside=False):
         """Layers [k_begin, k_begin + k_count) of block b as three (k_count, nj, ni) arrays.  cuts: one discrete.Mesh per cut (host
         coordinates, uploaded per call: tm_stack_block; host=True: tm_stack_block_host, no GPU) or one smooth.Smoother per cut (the
-        coordinates resident in the handles: tm_stack_smoothers)."""
+        coordinates resident in the handles: tm_stack_smoothers).  mapping="revolution" routes to the *_surf calls; return_outside=True
+        then adds a fourth entry, per cut the number of the block's nodes whose u lies outside the cut's table (extrapolated)."""
         self._check_count(cuts)
+        sf = self.surfaces
+        if return_outside and sf is None:
+            raise ValueError("return_outside: only with mapping='revolution'")
+        outside = np.zeros(max(1, self.ncuts), dtype=np.uint64)
+        extra = () if sf is None else (outside.ctypes.data_as(C.POINTER(C.c_uint64)) if return_outside else None,)
+        head = lambda a: (a, C.byref(self._opt)) + (() if sf is None else (sf.ref(),))   # noqa: E731
         if k_count is None:
             k_count = self.nlayers - k_begin
         resident = all(hasattr(c, "_h") for c in cuts)
@@ -125,13 +233,16 @@ class Stack:
             if host:
                 raise ValueError("host=True evaluates host coordinates: pass the meshes, not the handles")
             handles = (C.c_void_p * len(cuts))(*[c._h for c in cuts])
-            _capi.check(L.tm_stack_smoothers(handles, C.byref(self._opt), b, k_begin, k_count, *ptrs))
+            _capi.check((L.tm_stack_smoothers if sf is None else L.tm_stack_smoothers_surf)(*head(handles), b, k_begin, k_count, *ptrs, *extra))
         else:
             descs = [_capi.MeshDesc(m) for m in meshes]
             arr = (C.POINTER(_capi.tm_mesh_desc) * len(descs))(*[C.pointer(d.desc) for d in descs])
-            fn = L.tm_stack_block_host if host else L.tm_stack_block
-            _capi.check(fn(arr, C.byref(self._opt), b, k_begin, k_count, *ptrs))
-        return tuple(out)
+            if sf is None:
+                fn = L.tm_stack_block_host if host else L.tm_stack_block
+            else:
+                fn = L.tm_stack_block_surf_host if host else L.tm_stack_block_surf
+            _capi.check(fn(*head(arr), b, k_begin, k_count, *ptrs, *extra))
+        return tuple(out) + ((outside[:self.ncuts].copy(),) if return_outside else ())
 
     def quality(self, cuts, host=False):
         """(per_block, total): the 3-D quality report of every stacked block (quality.Quality3d) and their total -- negative and degenerate
@@ -144,6 +255,8 @@ class Stack:
         resident = all(hasattr(c, "_h") for c in cuts)
         meshes = [c._mesh for c in cuts] if resident else cuts
         L = _capi.lib()
+        sf = self.surfaces
+        head = lambda a: (a, C.byref(self._opt)) + (() if sf is None else (sf.ref(),))   # noqa: E731
         per_block = []
         if resident:
             if host:
@@ -155,9 +268,11 @@ class Stack:
         for b in range(len(meshes[0].blocks)):
             q = _capi.tm_quality3d()
             if resident:
-                _capi.check(L.tm_stack_smoothers_quality(handles, C.byref(self._opt), b, C.byref(q)))
+                _capi.check((L.tm_stack_smoothers_quality if sf is None else L.tm_stack_smoothers_quality_surf)(*head(handles), b, C.byref(q)))
+            elif sf is None:
+                _capi.check((L.tm_stack_quality_host if host else L.tm_stack_quality)(*head(arr), b, C.byref(q)))
             else:
-                _capi.check((L.tm_stack_quality_host if host else L.tm_stack_quality)(arr, C.byref(self._opt), b, C.byref(q)))
+                _capi.check((L.tm_stack_quality_surf_host if host else L.tm_stack_quality_surf)(*head(arr), b, C.byref(q)))
             per_block.append(_quality.Quality3d.from_struct(q))
         return per_block, _quality.total_3d(per_block)
 
@@ -172,7 +287,10 @@ class Stack:
         ni, nj = cuts[0]._mesh.blocks[b].points.size
         out = np.empty((max(0, k_count), max(0, nj - 1), max(0, ni - 1)), dtype=np.float64)
         handles = (C.c_void_p * len(cuts))(*[c._h for c in cuts])
-        _capi.check(_capi.lib().tm_stack_smoothers_quality_field(handles, C.byref(self._opt), b, k_begin, k_count, _capi.f64ptr(out)))
+        if self.surfaces is None:
+            _capi.check(_capi.lib().tm_stack_smoothers_quality_field(handles, C.byref(self._opt), b, k_begin, k_count, _capi.f64ptr(out)))
+        else:
+            _capi.check(_capi.lib().tm_stack_smoothers_quality_field_surf(handles, C.byref(self._opt), self.surfaces.ref(), b, k_begin, k_count, _capi.f64ptr(out)))
         return out
 
     def mesh3d(self, cuts, host=False) -> Mesh3d:
