@@ -705,7 +705,8 @@ int tm_quality3d_total(const tm_quality3d* per_block, uint64_t n, tm_quality3d* 
  * the same unless that sum lies within rounding of the zero tolerance).
  * tm_ho_quality_total: counts and hist summed, extremes combined, the worst element the one with the smallest value, orientation and
  * order the blocks' common one or 0; records with elements == 0 are left out.  Host only.
- * Not served: order elevation in span for stacked blocks; re-projection of wall nodes onto the blade spline (the interpolant of the
+ * Order elevation in span for stacked blocks: "high-order hexahedra of stacked blocks" below.
+ * Not served: re-projection of wall nodes onto the blade spline (the interpolant of the
  * on-spline nodes is used as it is); reconciling interface nodes across blocks; Gmsh and HOPR output; repairing invalid elements. */
 #define TM_HO_MAX_ORDER 8
 enum { TM_HO_EQUIDISTANT = 0, TM_HO_GAUSS_LOBATTO = 1, TM_HO_PRESCRIBED = 2 };
@@ -806,6 +807,92 @@ int tm_smoother_certify(tm_smoother* s, const tm_ho_opt* opt, int32_t max_depth,
 /* The (2p)^2 coefficients of element (e, f) as B[k*2p + l], NOT multiplied by o.  An element past the block: TM_E_ARG.  Host only */
 int tm_ho_jacobian_bezier_host(const tm_mesh_desc* mesh, const tm_ho_opt* opt, uint64_t block, uint64_t e, uint64_t f, double* B);
 int tm_ho_certificate_total(const tm_ho_certificate* per_block, uint64_t n, tm_ho_certificate* total);
+
+/* ------------------------------------------------------------------ high-order hexahedra of stacked blocks
+ * The reference's roadmap asks for "high order meshes" and "3D based on meshed 2d cuts"; this section serves the two together: the
+ * layers of a stacked block are agglomerated into curved hexahedra of order p, in span exactly as in i and j.
+ * Elements.
+ *   - The order p is the same in i, j and span, 1 <= p <= TM_HO3_MAX_ORDER = 4.  Orders 5 .. 8 answer TM_E_ARG: the (p+1)^3 working set
+ *     of an element -- fine nodes and the intermediate results of three contraction stages, three components each -- is held on chip
+ *     by the kernel, and above p = 4 it no longer fits beside the K cut values of the nodes.
+ *   - A stacked block of ni x nj nodes and nk layers qualifies iff (ni-1), (nj-1) and (nk-1) are multiples of p, ni, nj >= 2 and
+ *     nk >= p+1.  Anything else: TM_E_SIZE.  It has Ei x Ej x Eg elements, Ei = (ni-1)/p, Ej = (nj-1)/p, Eg = (nk-1)/p.
+ *   - Element (e, f, g) owns the fine nodes F[e*p+m][f*p+n][g*p+l], m, n, l = 0 .. p, at the parametric positions (u, v, w) = (m, n, l).
+ *   - Span is parametrised by the layer INDEX, as i and j are by the node index.  The layers need not be ordered: a layer out of order
+ *     shows up as invalid elements.
+ * Fine nodes: exactly what tm_stack_block / tm_stack_block_surf return for the layer -- the same weight table, the same sum over the
+ *   cuts c = 0 .. K-1, the same theta_c division and sincos, the same surface stage (K15).  The device path sees bit for bit what K11
+ *   writes, which is the contract the 3-D quality report (K12) already has.
+ * Tables: tm_ho_tables of the tm_ho_opt (nodes, T, D), unchanged.
+ * Contraction.  All arithmetic IEEE fp64, nothing fused, the three components alike, every sum started at index 0 and continued in
+ *   ascending order.  For (A, B, C) in {(T,T,T), (D,T,T), (T,D,T), (T,T,D)}:
+ *     V[m][n][c] = sum_l C[c][l]*F[m][n][l];   W[m][b][c] = sum_n B[b][n]*V[m][n][c];   R[a][b][c] = sum_m A[a][m]*W[m][b][c]
+ *   (T,T,T): the elevated node Y[e*p+a][f*p+b][g*p+c];  the other three: its derivatives d/du, d/dv, d/dw.
+ *   - With TM_HO_EQUIDISTANT, or p = 1, the (T,T,T) contraction is skipped and the nodes are copied: the planes equal tm_stack_block's
+ *     bit for bit.
+ *   - Rows 0 and p of T are unit vectors, so a node on an element face, edge or corner depends only on the fine nodes of that face,
+ *     edge or corner, and neighbouring elements compute the same value: the result is again an ni x nj x nk structured array.  A node
+ *     shared between elements is written by the element above it in each direction, the last node of a grid line by the last element.
+ *   - Consequence: layer k = g*p of the output equals tm_ho_elevate_host applied to fine layer k (x and y, or any two components),
+ *     numerically equal -- only a -0 may become +0.
+ * Element record.
+ *   J = x_u*(y_v*z_w - y_w*z_v) - x_v*(y_u*z_w - y_w*z_u) + x_w*(y_u*z_v - y_v*z_u) at the element's own (p+1)^3 nodes
+ *   orientation  o: sign of the sum of V over the hexahedra of element corners, V the exact trilinear volume of "3-D quality of stacked
+ *                blocks" with x[a + 2b + 4c] the corner (a*p, b*p, c*p) of the element; 0 (reported as +1) when
+ *                |sum V| <= elements * 2^-53 * sum |V|
+ *   per element  Jmin, Jmax of o*J over its nodes; invalid if Jmin <= 0 or any J is non-finite; otherwise sj = Jmin/Jmax (for o = -1
+ *                formed as Jmax/Jmin of the unoriented values, so that a mirrored block has the same bits)
+ *   min_scaled_jacobian  min of sj over valid elements, (worst_block, worst_e, worst_f, worst_g) its element, ties to the lowest
+ *                (block, g, f, e); NaN and zeros when no element is valid
+ *   min_jacobian / max_jacobian, hist[k]: as in tm_ho_quality
+ *   The record is SAMPLED AT THE NODES: a positive sj is necessary for a valid element, not sufficient.  A certificate for hexahedra
+ *   (the 3-D counterpart of tm_ho_certify) is not built.
+ *   No summed field: device and host agree bit for bit in every field (the orientation is decided from a sum and is the same unless
+ *   that sum lies within rounding of the zero tolerance).
+ * tm_ho3_quality_total: the rules of tm_ho_quality_total.  Host only.
+ * Not served: a Bezier certificate for hexahedra; orders above 4; different orders in-plane and in span; span nodes evaluated from the
+ * spline weights instead of by agglomeration; cuts spread over ranks; re-projection onto the blade; reconciling interface nodes across
+ * blocks; Gmsh, HOPR and CGNS output. */
+#define TM_HO3_MAX_ORDER 4
+typedef struct tm_ho3_quality {          /* 160 bytes */
+    uint64_t elements, invalid;
+    int32_t  orientation, order;
+    double   min_scaled_jacobian;
+    uint64_t worst_block, worst_e, worst_f, worst_g;
+    double   min_jacobian, max_jacobian;
+    uint64_t hist[10];
+} tm_ho3_quality;
+/* TM_OK, or TM_E_SIZE with tm_last_error naming the first offender: a block of the cut whose ni-1 or nj-1 is not a multiple of p, then
+ * a connection range off the element grid (as tm_ho_check), then the layer count of `stack`.  Only sizes and topology are read from
+ * `cut0` and only nlayers from `stack`.  An order above TM_HO3_MAX_ORDER: TM_E_ARG.  Host only */
+int tm_ho3_check(const tm_mesh_desc* cut0, const tm_stack_opt* stack, const tm_ho_opt* opt);
+/* Any 3-D block in PLOT3D order (planes of nk*nj*ni doubles, i fastest).  No GPU touched.  X, Y, Z: the elevated planes, the same shape;
+ * all three NULL for a report alone.  q may be NULL.  sj, when given: Ei*Ej*Eg values as sj[(g*Ej + f)*Ei + e], NaN for invalid
+ * elements.  `block` only labels the record. */
+int tm_ho3_planes_host(const double* x, const double* y, const double* z, uint64_t ni, uint64_t nj, uint64_t nk, const tm_ho_opt* opt,
+                       uint64_t block, double* X, double* Y, double* Z, tm_ho3_quality* q, double* sj);
+/* Block `block` of the stack of K meshes given on the host, elevated on the device (kernel K16) straight from the K cuts: the fine 3-D
+ * block is never stored.  surfaces: NULL unless stack->mapping is TM_STACK_REVOLUTION, then required (anything else TM_E_ARG).
+ * x, y, z: the node layers [g_begin*p, (g_begin + g_count)*p] of the elevated block, g_count*p + 1 planes of ni*nj doubles, i fastest;
+ * all three NULL for a report alone (g_count is then ignored and may be 0).  q and sj (either may be NULL) always cover the WHOLE block;
+ * with both NULL only the window's elements are evaluated.  outside (may be NULL) is written with TM_STACK_REVOLUTION only, as by
+ * tm_stack_block_surf.  Errors: those of tm_stack_block / tm_stack_block_surf, the size rule above (TM_E_SIZE), an order above
+ * TM_HO3_MAX_ORDER, planes with an empty window or a window past Eg (TM_E_ARG).  Planes, sj and every field of the record equal
+ * tm_ho3_planes_host applied to the planes tm_stack_block[_surf] returns, bit for bit. */
+int tm_stack_elevate(const tm_mesh_desc* const* cuts, const tm_stack_opt* stack, const tm_stack_surfaces* surfaces, const tm_ho_opt* opt,
+                     uint64_t block, uint64_t g_begin, uint64_t g_count, double* x, double* y, double* z, tm_ho3_quality* q, double* sj,
+                     uint64_t* outside);
+/* tm_stack_block[_surf]_host followed by the host definition, p+1 fine layers held at a time; no GPU touched */
+int tm_stack_elevate_host(const tm_mesh_desc* const* cuts, const tm_stack_opt* stack, const tm_stack_surfaces* surfaces, const tm_ho_opt* opt,
+                          uint64_t block, uint64_t g_begin, uint64_t g_count, double* x, double* y, double* z, tm_ho3_quality* q, double* sj,
+                          uint64_t* outside);
+/* The same kernel on the coordinates RESIDENT in K handles.  Ordered behind the pending work of every handle exactly as
+ * tm_stack_smoothers is; modifies no handle.  Errors as tm_stack_smoothers[_surf], plus the cases above.  Bit-identical to
+ * tm_stack_elevate on the downloaded coordinates. */
+int tm_stack_smoothers_elevate(tm_smoother* const* cuts, const tm_stack_opt* stack, const tm_stack_surfaces* surfaces, const tm_ho_opt* opt,
+                               uint64_t block, uint64_t g_begin, uint64_t g_count, double* x, double* y, double* z, tm_ho3_quality* q,
+                               double* sj, uint64_t* outside);
+int tm_ho3_quality_total(const tm_ho3_quality* per_block, uint64_t n, tm_ho3_quality* total);
 
 /* ------------------------------------------------------------------ host-only planning (no GPU needed)
  * The perimeter-row table the device kernels consume, exported as CSR so it can be compared with

@@ -25,6 +25,11 @@ and for the mesh, and --output takes the elevated nodes (.vtk: Lagrange quadrila
 to DEPTH (default 3, at most 4) subdivisions (include/tm_hip.h "high-order elements: certificate"): proven, invalid or undecided per
 element, logged per block and for the mesh next to the nodal report; --fail-on-invalid-elements then also counts the elements that
 are folded between their nodes, and --fail-on-unproven-elements exits non-zero when any element is not proven.
+With --stack, --order P (1 .. 4) turns the stacked blocks into curved hexahedra of order P, in span as in-plane (stack.Stack.elevate,
+include/tm_hip.h "high-order hexahedra of stacked blocks"): the cell counts of every block, the interface ranges and --layers minus one
+must be multiples of P, checked before anything is smoothed; the elements are formed on the device straight from the resident cuts, their
+report is logged per block and for the mesh, and --output takes the elevated nodes (.vtk: Lagrange hexahedra, equidistant nodes only;
+.xyz / .p3d: 3-D PLOT3D).  --certify does not go with --stack: a 3-D certificate is not built.
 Without --order nothing changes; without --certify neither does --order."""
 from __future__ import annotations
 
@@ -39,9 +44,10 @@ from . import quality
 from .smoothing import smooth, solver, wall_control_function
 
 
-def _run(ap, args, config, keep=None, tag=""):
+def _run(ap, args, config, keep=None, tag="", stack=None):
     """One input file through the existing path: parse, block, seed, smooth, download.  keep: an ExitStack that takes the handle over
-    (None: it is closed here, as ever); tag: prefix of the quality report's stage names."""
+    (None: it is closed here, as ever); tag: prefix of the quality report's stage names; stack: the stack.Stack this file is a cut of
+    (--order then elevates the stacked blocks, not this cut: only the check runs here, before anything is smoothed)."""
     with open(config) as f:
         inp = tm_input.Input.parse(f.read())
     if args.hip == "file":
@@ -70,8 +76,11 @@ def _run(ap, args, config, keep=None, tag=""):
         from . import _capi, highorder
 
         elevation = highorder.Elevation(args.order, args.nodes)
-        try:
-            elevation.check(mesh)   # before anything is smoothed
+        try:   # before anything is smoothed
+            if stack is None:
+                elevation.check(mesh)
+            else:
+                stack.check_elevation(mesh, elevation)
         except _capi.TmError as e:
             sys.exit(f"high-order elements of order {args.order}: {e}")
     iterations = inp.iterations if args.iterations is None else args.iterations
@@ -108,7 +117,7 @@ def _run(ap, args, config, keep=None, tag=""):
             if args.quality:
                 quality.log_report(qlog, mesh.names, *after, tag + "after")
             stats["quality"] = {"before": before, "after": after}
-        if elevation is not None:
+        if elevation is not None and stack is None:
             hom = elevation.mesh(sm)   # from the resident coordinates
             quality.log_report_ho(qlog, hom.names, hom.per_block, hom.total, tag + "elevate")
             stats["highorder"] = hom
@@ -141,7 +150,9 @@ def _main_stack(ap, args):
     coordinates resident in the handles (tm_stack_smoothers)."""
     from . import output, stack
 
-    output._format_of(args.output)
+    vtk = args.order is not None and args.output.lower().endswith(".vtk")
+    if not vtk:
+        output._format_of(args.output)
     surfaces = None
     if args.stack_mapping == "revolution":
         try:
@@ -158,12 +169,23 @@ def _main_stack(ap, args):
     with contextlib.ExitStack() as keep:
         handles = []
         for c, config in enumerate(files):
-            _, mesh, sm, stats, after = _run(ap, args, config, keep=keep, tag=f"cut {c} ")
+            _, mesh, sm, stats, after = _run(ap, args, config, keep=keep, tag=f"cut {c} ", stack=st)
             handles.append(sm)
             all_stats.append(stats)
             if after is not None and not after[1].ok and worst is None:
                 worst = (c, after[1])
-        if surfaces is None:
+        hom = None
+        if args.order is not None:   # curved hexahedra straight from the resident cuts: the fine 3-D block is never formed
+            from . import highorder
+
+            hom = m3 = st.mesh3d_ho(handles, highorder.Elevation(args.order, args.nodes))
+            quality.log_report_ho3(logging.getLogger("quality"), hom.names, hom.per_block, hom.total)
+            for b, outside in enumerate(hom.outside):
+                for c, n in enumerate(outside):
+                    if n:
+                        logging.getLogger("stack").warning("block %d (%s), cut %d: %d nodes lie outside the meridional table %s and are extrapolated", b, hom.names[b],
+                                                           c, int(n), args.meridional[c])
+        elif surfaces is None:
             m3 = st.mesh3d(handles)
         else:   # the same blocks, with the count of extrapolated nodes per cut
             m3 = stack.Mesh3d()
@@ -179,15 +201,23 @@ def _main_stack(ap, args):
     m3.write(args.output)
     logging.getLogger("output").info("wrote %s (%d blocks, %d cuts, %d layers, %d nodes)", args.output, len(m3.blocks), len(files), st.nlayers,
                                      sum(x.size for x, _, _ in m3.blocks))
+    if hom is not None:
+        logging.getLogger("output").info("%d hexahedra of order %d, %s nodes", hom.total.elements, hom.order, hom.distribution)
     if q3 is not None and args.stack_quality:
         quality.log_report_3d(logging.getLogger("quality"), m3.names, *q3)
     if args.fail_on_inverted and worst is not None:
         sys.exit(f"mesh quality: cut {worst[0]} has {worst[1].inverted} inverted and {worst[1].degenerate} degenerate cells after smoothing")
+    if args.fail_on_invalid_elements and not hom.total.ok:
+        b, bad = next((b, q) for b, q in enumerate(hom.per_block) if not q.ok)
+        sys.exit(f"high-order elements: {hom.total.invalid} invalid hexahedra of order {hom.order} in the stacked mesh "
+                 f"(first in block {b}: {bad.invalid} of {bad.elements})")
     if args.fail_on_inverted_3d and not q3[1].ok:
         b, bad = next((b, q) for b, q in enumerate(q3[0]) if not q.ok)
         sys.exit(f"mesh quality: the stacked mesh has {q3[1].inverted} inverted and {q3[1].degenerate} degenerate hexahedra "
                  f"(block {b}: {bad.inverted} inverted, {bad.degenerate} degenerate, worst cell i {bad.worst_i}, j {bad.worst_j}, k {bad.worst_k})")
     out = {"cuts": all_stats, "blocks": len(m3.blocks), "layers": st.nlayers}
+    if hom is not None:
+        out["highorder"] = hom
     if q3 is not None:
         out["quality3d"] = {"per_block": q3[0], "total": q3[1]}
     return out
@@ -218,7 +248,8 @@ def main(argv=None):
     ap.add_argument("--order", type=int, metavar="P",
                     help="curved elements of order P (1 .. 8) from the smoothed blocks: every P x P group of cells is one element; the cell counts "
                          "of every block and the interface ranges must be multiples of P (checked before smoothing).  --output then takes the "
-                         "elevated nodes: .vtk (Lagrange quadrilaterals, --nodes equidistant) or PLOT3D")
+                         "elevated nodes: .vtk (Lagrange quadrilaterals, --nodes equidistant) or PLOT3D.  With --stack: curved hexahedra of order "
+                         "P (1 .. 4) from the stacked blocks, --layers minus one a multiple of P as well; .vtk holds Lagrange hexahedra")
     ap.add_argument("--nodes", default=None, choices=["equidistant", "gauss-lobatto"],
                     help="with --order: node distribution inside the elements (default: gauss-lobatto; equidistant for a .vtk output)")
     ap.add_argument("--fail-on-invalid-elements", action="store_true",
@@ -267,10 +298,10 @@ def main(argv=None):
         if not 0 <= args.certify <= 4:
             ap.error("--certify: 0 .. 4")
     if args.order is not None:
-        if args.stack is not None:
-            ap.error("--order elevates 2-D blocks: it does not go with --stack")
-        if not 1 <= args.order <= 8:
-            ap.error("--order: 1 .. 8")
+        if args.stack is not None and args.certify is not None:
+            ap.error("--certify judges 2-D elements: a 3-D certificate is not built, so it does not go with --stack")
+        if not 1 <= args.order <= (8 if args.stack is None else 4):
+            ap.error("--order: 1 .. 8" if args.stack is None else "--order: 1 .. 4 with --stack (curved hexahedra)")
         vtk = bool(args.output) and args.output.lower().endswith(".vtk")
         if args.nodes is None:
             args.nodes = "equidistant" if vtk else "gauss-lobatto"

@@ -32,6 +32,7 @@ TM_SURF_LINEAR, TM_SURF_CUBIC = 0, 1
 TM_HO_MAX_ORDER = 8
 TM_HO_EQUIDISTANT, TM_HO_GAUSS_LOBATTO, TM_HO_PRESCRIBED = 0, 1, 2
 TM_HO_CERT_MAX_DEPTH = 4
+TM_HO3_MAX_ORDER = 4
 TM_HO_PROVEN, TM_HO_INVALID, TM_HO_UNDECIDED = 0, 1, 2
 
 
@@ -165,6 +166,12 @@ class tm_ho_quality(C.Structure):
                 ("min_jacobian", C.c_double), ("max_jacobian", C.c_double), ("hist", C.c_uint64 * 10)]
 
 
+class tm_ho3_quality(C.Structure):   # 160 bytes
+    _fields_ = [("elements", C.c_uint64), ("invalid", C.c_uint64), ("orientation", C.c_int32), ("order", C.c_int32),
+                ("min_scaled_jacobian", C.c_double), ("worst_block", C.c_uint64), ("worst_e", C.c_uint64), ("worst_f", C.c_uint64),
+                ("worst_g", C.c_uint64), ("min_jacobian", C.c_double), ("max_jacobian", C.c_double), ("hist", C.c_uint64 * 10)]
+
+
 class tm_ho_certificate(C.Structure):   # 152 bytes
     _fields_ = [("elements", C.c_uint64), ("proven", C.c_uint64), ("invalid", C.c_uint64), ("undecided", C.c_uint64), ("hidden_invalid", C.c_uint64),
                 ("orientation", C.c_int32), ("order", C.c_int32), ("max_depth", C.c_int32), ("has_unproven", C.c_int32),
@@ -190,6 +197,7 @@ EXPORTS = [
     "tm_stack_quality_surf", "tm_stack_quality_surf_host", "tm_stack_smoothers_quality_surf", "tm_stack_smoothers_quality_field_surf",
     "tm_ho_tables", "tm_ho_check", "tm_ho_elevate", "tm_ho_elevate_host", "tm_smoother_elevate", "tm_ho_quality_total",
     "tm_ho_certify_tables", "tm_ho_certify", "tm_ho_certify_host", "tm_smoother_certify", "tm_ho_jacobian_bezier_host", "tm_ho_certificate_total",
+    "tm_ho3_check", "tm_ho3_planes_host", "tm_stack_elevate", "tm_stack_elevate_host", "tm_stack_smoothers_elevate", "tm_ho3_quality_total",
     "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
 ]
 
@@ -310,6 +318,13 @@ def lib():
         L.tm_smoother_certify.argtypes = [C.c_void_p, C.POINTER(tm_ho_opt), C.c_int32, C.c_uint64, C.POINTER(tm_ho_certificate), C.POINTER(C.c_uint8), _dp]
         L.tm_ho_jacobian_bezier_host.argtypes = [C.POINTER(tm_mesh_desc), C.POINTER(tm_ho_opt), C.c_uint64, C.c_uint64, C.c_uint64, _dp]
         L.tm_ho_certificate_total.argtypes = [C.POINTER(tm_ho_certificate), C.c_uint64, C.POINTER(tm_ho_certificate)]
+        L.tm_ho3_check.argtypes = [C.POINTER(tm_mesh_desc), C.POINTER(tm_stack_opt), C.POINTER(tm_ho_opt)]
+        L.tm_ho3_planes_host.argtypes = [_dp, _dp, _dp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(tm_ho_opt), C.c_uint64, _dp, _dp, _dp, C.POINTER(tm_ho3_quality), _dp]
+        _ho3_tail = [_sfp, C.POINTER(tm_ho_opt), C.c_uint64, C.c_uint64, C.c_uint64, _dp, _dp, _dp, C.POINTER(tm_ho3_quality), _dp, _u64p]
+        L.tm_stack_elevate.argtypes = [C.POINTER(C.POINTER(tm_mesh_desc)), C.POINTER(tm_stack_opt)] + _ho3_tail
+        L.tm_stack_elevate_host.argtypes = L.tm_stack_elevate.argtypes
+        L.tm_stack_smoothers_elevate.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt)] + _ho3_tail
+        L.tm_ho3_quality_total.argtypes = [C.POINTER(tm_ho3_quality), C.c_uint64, C.POINTER(tm_ho3_quality)]
         L.tm_rccl_unique_id.argtypes =[C.c_char_p, C.c_void_p]
         L.tm_rccl_comm_create.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.tm_rccl_comm_destroy.argtypes = [C.c_void_p]

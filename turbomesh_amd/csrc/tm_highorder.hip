@@ -147,19 +147,6 @@ __global__ __launch_bounds__(HO_THREADS) void k_ho_elevate(const double2* __rest
     }
 }
 
-// lane t of a wave combines records t, t + 64, ... in that order, then the 64 lanes' records pairwise through LDS (32, 16, ... 1): a
-// fixed order, so the sums are the same on every run
-__device__ __forceinline__ void ho_reduce_wave(const HoAcc* __restrict__ partials, int begin, int end, HoAcc* sh) {
-    HoAcc a;
-    ho_init(a);
-    for (int r = begin + static_cast<int>(threadIdx.x); r < end; r += 64) ho_combine(a, partials[r]);
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int off = 32; off > 0; off >>= 1) {
-        if (static_cast<int>(threadIdx.x) < off) ho_combine(sh[threadIdx.x], sh[threadIdx.x + off]);
-        __syncthreads();
-    }
-}
 // large blocks: workgroup g reduces the records [g * chunk, (g+1) * chunk) to one (a lone wave over the 16 641 records of a 4097^2 block
 // takes as long as the elevation itself)
 __global__ __launch_bounds__(64) void k_ho_reduce(const HoAcc* __restrict__ partials, int nwg, int chunk, HoAcc* __restrict__ out) {

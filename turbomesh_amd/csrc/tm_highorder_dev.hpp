@@ -23,4 +23,20 @@ struct HoDev {
     void run(const HoPlan& plan, const double2* X, int ni, int nj, uint64_t block, hipStream_t st, double* x, double* y, tm_ho_quality* q, double* sj);
 };
 
+#ifdef __HIP__
+// lane t of a wave combines records t, t + 64, ... in that order, then the 64 lanes' records pairwise through LDS (32, 16, ... 1): a
+// fixed order, so the sums are the same on every run
+__device__ __forceinline__ void ho_reduce_wave(const HoAcc* __restrict__ partials, int begin, int end, HoAcc* sh) {
+    HoAcc a;
+    ho_init(a);
+    for (int r = begin + static_cast<int>(threadIdx.x); r < end; r += 64) ho_combine(a, partials[r]);
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    for (int off = 32; off > 0; off >>= 1) {
+        if (static_cast<int>(threadIdx.x) < off) ho_combine(sh[threadIdx.x], sh[threadIdx.x + off]);
+        __syncthreads();
+    }
+}
+#endif
+
 }  // namespace tmh

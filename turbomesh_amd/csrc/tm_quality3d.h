@@ -72,6 +72,14 @@ TM_Q_FN double q3_det(const Q3Point& p, const Q3Point& q, const Q3Point& r) {
 TM_Q_FN Q3Point q3_sub(const Q3Point& a, const Q3Point& b) { return Q3Point{a.x - b.x, a.y - b.y, a.z - b.z}; }
 TM_Q_FN Q3Point q3_add(const Q3Point& a, const Q3Point& b) { return Q3Point{a.x + b.x, a.y + b.y, a.z + b.z}; }
 
+// exact volume of the trilinear hexahedron with corners x[a + 2b + 4c] (also the corner hexahedron of a high-order element: tm_highorder3.hpp)
+TM_Q_FN double q3_volume(const Q3Point* x) {
+    const Q3Point d71 = q3_sub(x[7], x[1]), d60 = q3_sub(x[6], x[0]), d72 = q3_sub(x[7], x[2]), d30 = q3_sub(x[3], x[0]), d50 = q3_sub(x[5], x[0]),
+                  d74 = q3_sub(x[7], x[4]);
+    const double v12 = (q3_det(q3_add(d71, d60), d72, d30) + q3_det(d60, q3_add(d72, d50), d74)) + q3_det(d71, d50, q3_add(d74, d30));
+    return v12 / 12.0;
+}
+
 struct Q3Cell {
     bool degenerate;
     double jmin, jmax;   // over the eight corners
@@ -115,11 +123,7 @@ TM_Q_FN Q3Cell q3_cell(const Q3Point* x, const double* li, const double* lj, con
         for (int b = 0; b < 2; ++b)
 #pragma unroll
             for (int a = 0; a < 2; ++a) q3_corner(ei[b + 2 * c], ej[a + 2 * c], ek[a + 2 * b], li[b + 2 * c], lj[a + 2 * c], lk[a + 2 * b], r);
-    // exact volume of the trilinear hexahedron
-    const Q3Point d71 = q3_sub(x[7], x[1]), d60 = q3_sub(x[6], x[0]), d72 = q3_sub(x[7], x[2]), d30 = q3_sub(x[3], x[0]), d50 = q3_sub(x[5], x[0]),
-                  d74 = q3_sub(x[7], x[4]);
-    const double v12 = (q3_det(q3_add(d71, d60), d72, d30) + q3_det(d60, q3_add(d72, d50), d74)) + q3_det(d71, d50, q3_add(d74, d30));
-    r.volume = v12 / 12.0;
+    r.volume = q3_volume(x);
     const double Li = ((li[0] + li[1]) + li[2]) + li[3], Lj = ((lj[0] + lj[1]) + lj[2]) + lj[3], Lk = ((lk[0] + lk[1]) + lk[2]) + lk[3];
     double hi = Li > Lj ? Li : Lj, lo = Li > Lj ? Lj : Li;
     hi = Lk > hi ? Lk : hi;

@@ -12,7 +12,14 @@ the fine mesh itself (equidistant) or the element's degree-p tensor-product inte
 
     cert, status, bounds = el.certify(smoother, b)   # quality.HoCertificate, (Ej, Ei) uint8 status, (Ej, Ei, 2) bounds of o*J
 
-Evaluated on the MI355X (kernels K13, K14); `host=True` evaluates the same definition on the CPU (a Mesh only), bit for bit."""
+Stacked blocks (stack.Stack) become curved hexahedra of order p <= 4 the same way, in span as in i and j ("high-order hexahedra of stacked
+blocks", kernel K16):
+
+    X, Y, Z, q, sj = st.elevate(cuts, el, b)   # planes (nk, nj, ni), quality.HoQuality3d, scaled Jacobian per element (Eg, Ej, Ei)
+    st.mesh3d_ho(cuts, Elevation(2, "equidistant")).write("blade.vtk")
+    X, Y, Z, q, sj = planes3d(X0, Y0, Z0, el)  # any 3-D block, on the CPU
+
+Evaluated on the MI355X (kernels K13, K14, K16); `host=True` evaluates the same definition on the CPU (a Mesh only), bit for bit."""
 from __future__ import annotations
 
 import ctypes as C
@@ -26,6 +33,7 @@ from . import quality as _quality
 
 DISTRIBUTION = {"equidistant": _capi.TM_HO_EQUIDISTANT, "gauss_lobatto": _capi.TM_HO_GAUSS_LOBATTO, "prescribed": _capi.TM_HO_PRESCRIBED}
 VTK_LAGRANGE_QUADRILATERAL = 70
+VTK_LAGRANGE_HEXAHEDRON = 72
 
 
 def lagrange_quad_order(p):
@@ -39,6 +47,74 @@ def lagrange_quad_order(p):
     order += [(0, b) for b in range(1, p)]
     order += [(a, b) for b in range(1, p) for a in range(1, p)]
     return order
+
+
+def lagrange_hex_order(p):
+    """Local nodes (a, b, c) of an element of order p in the order of VTK 9's Lagrange hexahedron (vtkLagrangeHexahedron::
+    PointIndexFromIJK): the corners of the face c = 0 counter-clockwise from (0,0,0), then those of c = p; the edges of c = 0 in the order
+    of the quadrilateral (b = 0, a = p, b = p, a = 0, each ascending), those of c = p, then the four vertical edges at (0,0), (p,0), (p,p),
+    (0,p) -- the numbering of VTK >= 9 --; the faces a = 0, a = p (b fastest), b = 0, b = p (a fastest), c = 0, c = p (a fastest); the
+    interior with a fastest, then b."""
+    r = range(1, p)
+    ring = [(0, 0), (p, 0), (p, p), (0, p)]
+    order = [(a, b, c) for c in (0, p) for a, b in ring]
+    for c in (0, p):
+        order += [(a, 0, c) for a in r] + [(p, b, c) for b in r] + [(a, p, c) for a in r] + [(0, b, c) for b in r]
+    order += [(a, b, c) for a, b in ring for c in r]
+    order += [(a, b, c) for a in (0, p) for c in r for b in r]
+    order += [(a, b, c) for b in (0, p) for c in r for a in r]
+    order += [(a, b, c) for c in (0, p) for b in r for a in r]
+    order += [(a, b, c) for c in r for b in r for a in r]
+    return order
+
+
+def planes3d(X, Y, Z, elevation, block=0, planes=True):
+    """(X, Y, Z, HoQuality3d, sj) of any 3-D block given as (nk, nj, ni) arrays (PLOT3D order: what Stack.block returned, or a file read
+    with output.read_plot3d_3d), elevated on the CPU (tm_ho3_planes_host: no GPU needed).  The planes have the same shape (None with
+    planes=False: the report alone); sj is the scaled Jacobian per element as an (Eg, Ej, Ei) array, NaN for invalid elements."""
+    X, Y, Z = (np.ascontiguousarray(a, dtype=np.float64) for a in (X, Y, Z))
+    if X.ndim != 3 or Y.shape != X.shape or Z.shape != X.shape:
+        raise ValueError("X, Y, Z: three (nk, nj, ni) arrays of one shape")
+    nk, nj, ni = X.shape
+    p = max(1, elevation.order)
+    out = [np.empty_like(X) if planes else None for _ in range(3)]
+    sj = np.empty((max(0, (nk - 1) // p), max(0, (nj - 1) // p), max(0, (ni - 1) // p)), dtype=np.float64)
+    q = _capi.tm_ho3_quality()
+    _capi.check(_capi.lib().tm_ho3_planes_host(_capi.f64ptr(X), _capi.f64ptr(Y), _capi.f64ptr(Z), ni, nj, nk, C.byref(elevation._opt), block,
+                                               *[_capi.f64ptr(o) if planes else None for o in out], C.byref(q), _capi.f64ptr(sj)))
+    return out[0], out[1], out[2], _quality.HoQuality3d.from_struct(q), sj
+
+
+@dataclass
+class HighOrderMesh3d:
+    """The elevated blocks of a stacked mesh: per block the X, Y, Z coordinates as (nk, nj, ni) arrays (PLOT3D order, i fastest), the
+    per-block and total quality.HoQuality3d and the scaled Jacobian per element as (Eg, Ej, Ei) arrays."""
+
+    order: int
+    distribution: str
+    names: List[str] = field(default_factory=list)
+    blocks: List[Tuple[np.ndarray, np.ndarray, np.ndarray]] = field(default_factory=list)
+    per_block: List["_quality.HoQuality3d"] = field(default_factory=list)
+    scaled_jacobian: List[np.ndarray] = field(default_factory=list)
+    total: "_quality.HoQuality3d | None" = None
+    outside: List[np.ndarray] = field(default_factory=list)   # mapping="revolution": per block the extrapolated nodes of every cut
+
+    def sizes(self):
+        return [(x.shape[2], x.shape[1], x.shape[0]) for x, _, _ in self.blocks]
+
+    def write(self, filename):
+        """`*.vtk`: a legacy ASCII VTK unstructured grid with one VTK_LAGRANGE_HEXAHEDRON (type 72) per element -- points per block in
+        PLOT3D order, blocks concatenated (interface nodes are not merged), coordinates as %.17g; VTK's Lagrange cells assume equidistant
+        nodes, so any other distribution raises ValueError.  Any other name: multi-block 3-D PLOT3D of the elevated nodes."""
+        from . import output
+
+        if str(filename).lower().endswith(".vtk"):
+            if self.distribution != "equidistant":
+                raise ValueError(f"VTK Lagrange cells assume equidistant nodes: a {self.distribution} elevation goes to PLOT3D")
+            output.write_vtk_lagrange_hex(filename, self.order, self.blocks)
+            return
+        output._format_of(filename)
+        output.write_plot3d_3d(filename, self.sizes(), self.blocks)
 
 
 @dataclass

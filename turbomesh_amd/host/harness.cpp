@@ -8,6 +8,7 @@
 //                                                      device by the natural cubic spline: a checksum per layer (exit 0: layers at cuts equal the cuts)
 //   tm_harness certify <ni> <nj> <order>   Bezier certificate of those elements (kernel K14; exit 0: equal to the CPU's, counts add up)
 //   tm_harness elevate <ni> <nj> <order>   curved elements of that order from a smoothed block (kernel K13; exit 0: corners unchanged, equal to the CPU's)
+//   tm_harness stack-elevate <ni> <nj> <ncuts> <nlayers> <order>   the same cuts: curved hexahedra of that order from the stacked block (kernel K16; exit 0: corners unchanged, equal to the CPU's)
 //   tm_harness stack-quality <ni> <nj> <ncuts> <nlayers>   the same cuts: the 3-D quality record of the stacked block (kernel K12; exit 0: equal to the CPU's)
 //   tm_harness csr                                     the linear-solver slot (seam 2) on the reference's 5 x 5 known answer
 //   tm_harness ranks <world> <rank> <idfile> <nblocks> <ni> <nj> <iterations> [relax|bicgstab] [dump.bin]
@@ -377,6 +378,58 @@ static int stackQuality(std::size_t ni, std::size_t nj, std::size_t ncuts, std::
     return same ? 0 : 1;
 }
 
+// tm_harness stack-elevate <ni> <nj> <ncuts> <nlayers> <order>: the cuts of `stack`; Gauss-Lobatto hexahedra of `order` from the
+// coordinates resident in the handles (stack::elevate -> tm_stack_smoothers_elevate), compared with the CPU's evaluation of the downloaded
+// coordinates (the planar mapping: planes, scaled Jacobians and the record bit for bit); the nodes at element corners must be the nodes
+// tm_stack_smoothers returns for the same handles.
+static int stackElevate(std::size_t ni, std::size_t nj, std::size_t ncuts, std::size_t nlayers, int order) {
+    if (ncuts < 2 || nlayers < 2) throw Error(TM_E_ARG, "stack-elevate <ni> <nj> <ncuts> <nlayers> <order>: at least two cuts and two layers");
+    smoothing::solver::Option opt;
+    opt.inner = TM_INNER_RELAX;
+    std::vector<discrete::Mesh> meshes;
+    meshes.reserve(ncuts);
+    for (std::size_t c = 0; c < ncuts; ++c) meshes.push_back(buildSingle(ni, nj, 0.05 + 0.001 * static_cast<double>(c)));
+    std::vector<std::unique_ptr<smoothing::smooth::Smoother>> handles;
+    std::vector<smoothing::smooth::Smoother*> cuts;
+    std::vector<discrete::Mesh*> host_cuts;
+    for (std::size_t c = 0; c < ncuts; ++c) {
+        handles.push_back(std::make_unique<smoothing::smooth::Smoother>(meshes[c], opt, smoothing::wall_control_function::Algorithm::laplace()));
+        handles.back()->iterate(5);
+        cuts.push_back(handles.back().get());
+        host_cuts.push_back(&meshes[c]);
+    }
+    stack::Option so;
+    for (std::size_t c = 0; c < ncuts; ++c) so.span.push_back(static_cast<double>(c));
+    const double z1 = so.span.back();
+    for (std::size_t k = 0; k < nlayers; ++k) so.layers.push_back(k + 1 == nlayers ? z1 : z1 * (static_cast<double>(k) / static_cast<double>(nlayers - 1)));
+    highorder::Option ho;
+    ho.order = order;
+    const std::size_t p = static_cast<std::size_t>(order > 0 ? order : 1), Eg = (nlayers - 1) / p;
+    const stack::Elevated3d dev = stack::elevate(cuts, so, ho, 0, 0, Eg);
+    const stack::Block3d fine = stack::stack_block(cuts, so, 0, 0, nlayers);
+    for (auto& h : handles) h->download();
+    const stack::Elevated3d host = stack::elevate(host_cuts, so, ho, 0, 0, Eg, true);
+    const tm_ho3_quality& q = dev.quality;
+    std::printf("stack-elevate: hexahedra %llu invalid %llu min sj %.17g at (e %llu, f %llu, g %llu) jacobian %.17g .. %.17g orientation %d order %d\n",
+                static_cast<unsigned long long>(q.elements), static_cast<unsigned long long>(q.invalid), q.min_scaled_jacobian, static_cast<unsigned long long>(q.worst_e),
+                static_cast<unsigned long long>(q.worst_f), static_cast<unsigned long long>(q.worst_g), q.min_jacobian, q.max_jacobian, q.orientation, q.order);
+    bool corners = dev.nk == nlayers;
+    for (std::size_t k = 0; corners && k < nlayers; k += p)
+        for (std::size_t j = 0; j < nj; j += p)
+            for (std::size_t i = 0; i < ni; i += p) {
+                const std::size_t o = (k * nj + j) * ni + i;
+                if (!(dev.x[o] == fine.x[o] && dev.y[o] == fine.y[o] && dev.z[o] == fine.z[o])) corners = false;
+            }
+    std::printf("stack-elevate: corners unchanged: %s\n", corners ? "yes" : "no");
+    const auto same_bits = [](const std::vector<double>& a, const std::vector<double>& b) {
+        return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), sizeof(double) * a.size()) == 0);
+    };
+    const bool same = same_bits(dev.x, host.x) && same_bits(dev.y, host.y) && same_bits(dev.z, host.z) && same_bits(dev.sj, host.sj) &&
+                      std::memcmp(&dev.quality, &host.quality, sizeof(tm_ho3_quality)) == 0;
+    std::printf("stack-elevate: device equals host: %s\n", same ? "yes" : "no");
+    return corners && same ? 0 : 1;
+}
+
 // tm_harness elevate <ni> <nj> <order>: the config-2 block, five relaxation sweeps; Gauss-Lobatto elements of `order` from the
 // coordinates resident in the handle (highorder::elevate -> tm_smoother_elevate), compared with the CPU's evaluation of the
 // downloaded coordinates (planes, scaled Jacobians and the record bit for bit); element corners must be the smoothed nodes.
@@ -447,6 +500,9 @@ int main(int argc, char** argv) {
             return certifyBlock(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), static_cast<int>(std::strtol(argv[4], nullptr, 10)));
         if (argc >= 5 && std::strcmp(argv[1], "elevate") == 0)
             return elevateBlock(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), static_cast<int>(std::strtol(argv[4], nullptr, 10)));
+        if (argc >= 7 && std::strcmp(argv[1], "stack-elevate") == 0)
+            return stackElevate(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10),
+                                static_cast<int>(std::strtol(argv[6], nullptr, 10)));
         if (argc >= 6 && std::strcmp(argv[1], "stack-quality") == 0)
             return stackQuality(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10));
         if (argc >= 6 && std::strcmp(argv[1], "stack-revolution") == 0)
@@ -458,7 +514,7 @@ int main(int argc, char** argv) {
             return thomasMiddlecoff(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "ranks") == 0) return runRank(argc, argv);
         if (argc < 5) {
-            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-elevate <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 2;
         }
         int a = 2;

@@ -676,6 +676,71 @@ inline Certified certify(discrete::Mesh& mesh, const Option& o, std::size_t bloc
 }
 }  // namespace highorder
 
+// high-order hexahedra of stacked blocks (tm_hip.h): the layers of a stacked block agglomerated into curved hexahedra of order p <= 4
+namespace stack {
+struct Elevated3d {               // planes in PLOT3D order: element (k*nj + j)*ni + i, nk = g_count*p + 1; sj[(g*Ej + f)*Ei + e] of the WHOLE block
+    std::size_t ni = 0, nj = 0, nk = 0, Ei = 0, Ej = 0, Eg = 0;
+    std::vector<double> x, y, z, sj;
+    tm_ho3_quality quality{};
+};
+namespace detail {
+inline Elevated3d sized(std::size_t ni, std::size_t nj, const Option& o, const highorder::Option& ho, std::size_t g_count) {
+    if (ho.order < 1 || ho.order > TM_HO3_MAX_ORDER) throw Error(TM_E_ARG, "the order must be 1 .. TM_HO3_MAX_ORDER");
+    const std::size_t p = static_cast<std::size_t>(ho.order);
+    Elevated3d r;
+    r.ni = ni, r.nj = nj, r.nk = g_count * p + 1, r.Ei = (ni - 1) / p, r.Ej = (nj - 1) / p, r.Eg = o.layers.empty() ? 0 : (o.layers.size() - 1) / p;
+    const std::size_t n = ni * nj * r.nk;
+    r.x.resize(n + 1), r.y.resize(n + 1), r.z.resize(n + 1), r.sj.resize(r.Ei * r.Ej * r.Eg + 1);
+    return r;
+}
+inline void trim(Elevated3d& r) {
+    const std::size_t n = r.ni * r.nj * r.nk;
+    r.x.resize(n), r.y.resize(n), r.z.resize(n), r.sj.resize(r.Ei * r.Ej * r.Eg);
+}
+}  // namespace detail
+// the span elements [g_begin, g_begin + g_count) of `block` from the coordinates RESIDENT in one handle per cut (tm_stack_smoothers_elevate,
+// kernel K16: the fine 3-D block is never stored); sf: the meridional tables of TM_STACK_REVOLUTION, else null
+inline Elevated3d elevate(const std::vector<smoothing::smooth::Smoother*>& cuts, const Option& o, const highorder::Option& ho, std::size_t block, std::size_t g_begin,
+                          std::size_t g_count, const Surfaces* sf = nullptr, std::vector<uint64_t>* outside = nullptr) {
+    if (cuts.empty() || cuts.size() != o.span.size()) throw Error(TM_E_ARG, "one handle per span position");
+    std::vector<tm_smoother*> h;
+    for (const auto* c : cuts) h.push_back(c ? c->handle() : nullptr);
+    const tm_mesh_desc& d = cuts[0]->desc();
+    if (block >= d.nblocks) throw Error(TM_E_ARG, "block index past the mesh");
+    Elevated3d r = detail::sized(d.blocks[block].ni, d.blocks[block].nj, o, ho, g_count);
+    const tm_stack_opt so = o.c_struct();
+    const tm_ho_opt hopt = ho.c_struct();
+    const auto cs = sf ? sf->c_struct() : nullptr;
+    if (outside) outside->assign(cuts.size(), 0);
+    check(tm_stack_smoothers_elevate(h.data(), &so, cs ? &cs->s : nullptr, &hopt, block, g_begin, g_count, r.x.data(), r.y.data(), r.z.data(), &r.quality, r.sj.data(),
+                                     outside ? outside->data() : nullptr));
+    detail::trim(r);
+    return r;
+}
+// the same from host coordinates, uploaded per call (tm_stack_elevate) or, host = true, evaluated on the CPU (tm_stack_elevate_host)
+inline Elevated3d elevate(const std::vector<discrete::Mesh*>& cuts, const Option& o, const highorder::Option& ho, std::size_t block, std::size_t g_begin,
+                          std::size_t g_count, bool host = false, const Surfaces* sf = nullptr, std::vector<uint64_t>* outside = nullptr) {
+    if (cuts.empty() || cuts.size() != o.span.size()) throw Error(TM_E_ARG, "one mesh per span position");
+    std::vector<std::unique_ptr<smoothing::smooth::Desc>> descs;
+    std::vector<const tm_mesh_desc*> d;
+    for (auto* m : cuts) {
+        if (!m) throw Error(TM_E_ARG, "null mesh");
+        descs.push_back(std::make_unique<smoothing::smooth::Desc>(*m));
+        d.push_back(&descs.back()->desc);
+    }
+    if (block >= cuts[0]->blocks.size()) throw Error(TM_E_ARG, "block index past the mesh");
+    Elevated3d r = detail::sized(cuts[0]->blocks[block].points.size[0], cuts[0]->blocks[block].points.size[1], o, ho, g_count);
+    const tm_stack_opt so = o.c_struct();
+    const tm_ho_opt hopt = ho.c_struct();
+    const auto cs = sf ? sf->c_struct() : nullptr;
+    if (outside) outside->assign(cuts.size(), 0);
+    check((host ? tm_stack_elevate_host : tm_stack_elevate)(d.data(), &so, cs ? &cs->s : nullptr, &hopt, block, g_begin, g_count, r.x.data(), r.y.data(), r.z.data(),
+                                                            &r.quality, r.sj.data(), outside ? outside->data() : nullptr));
+    detail::trim(r);
+    return r;
+}
+}  // namespace stack
+
 namespace discrete {
 inline Quality Mesh::quality(bool host) {
     smoothing::smooth::Desc d(*this);

@@ -136,9 +136,44 @@ def write_vtk_lagrange(filename, order, blocks):
         fh.write(f"{VTK_LAGRANGE_QUADRILATERAL}\n" * len(cells))
 
 
+def write_vtk_lagrange_hex(filename, order, blocks):
+    """Legacy ASCII VTK unstructured grid of curved hexahedra: one VTK_LAGRANGE_HEXAHEDRON (type 72) of `order` per element.
+    blocks: per block the (X, Y, Z) coordinates as (nk, nj, ni) arrays whose ni-1, nj-1 and nk-1 are multiples of `order`
+    (highorder.HighOrderMesh3d.blocks).  Points: per block in PLOT3D order (i fastest), blocks concatenated, %.17g (reads back bit for
+    bit).  Local node (a, b, c) of element (e, f, g) is point ((g*order + c)*nj + f*order + b)*ni + e*order + a of its block, listed in
+    the order of highorder.lagrange_hex_order.  Pure file writing (no device)."""
+    from .highorder import VTK_LAGRANGE_HEXAHEDRON, lagrange_hex_order
+
+    p = int(order)
+    local = np.array(lagrange_hex_order(p), dtype=np.int64)
+    la, lb, lc = local[:, 0], local[:, 1], local[:, 2]
+    cells, offset = [], 0
+    for X, _, _ in blocks:
+        nk, nj, ni = X.shape
+        if (ni - 1) % p or (nj - 1) % p or (nk - 1) % p or nk < 2:
+            raise ValueError(f"a block of {ni} x {nj} x {nk} nodes has no elements of order {p}")
+        Ei, Ej, Eg = (ni - 1) // p, (nj - 1) // p, (nk - 1) // p
+        g, f, e = np.meshgrid(np.arange(Eg, dtype=np.int64), np.arange(Ej, dtype=np.int64), np.arange(Ei, dtype=np.int64), indexing="ij")   # e fastest
+        g, f, e = g.reshape(-1, 1), f.reshape(-1, 1), e.reshape(-1, 1)
+        cells.append(offset + ((g * p + lc) * nj + f * p + lb) * ni + e * p + la)
+        offset += ni * nj * nk
+    cells = np.concatenate(cells) if cells else np.empty((0, len(local)), dtype=np.int64)
+    with open(filename, "w") as fh:
+        fh.write(f"# vtk DataFile Version 4.2\ncurved hexahedra of order {p}\nASCII\nDATASET UNSTRUCTURED_GRID\n")
+        fh.write(f"POINTS {offset} double\n")
+        for X, Y, Z in blocks:
+            fh.write("".join("%.17g %.17g %.17g\n" % xyz for xyz in zip(X.reshape(-1).tolist(), Y.reshape(-1).tolist(), Z.reshape(-1).tolist())))
+        fh.write(f"CELLS {len(cells)} {len(cells) * (len(local) + 1)}\n")
+        head = str(len(local))
+        fh.write("".join(head + " " + " ".join(map(str, row)) + "\n" for row in cells.tolist()))
+        fh.write(f"CELL_TYPES {len(cells)}\n")
+        fh.write(f"{VTK_LAGRANGE_HEXAHEDRON}\n" * len(cells))
+
+
 def read_vtk_lagrange(filename):
     """-> (points (n, 3) float64, cells (ncells, nodes per cell) int64, cell_types (ncells,) int64) of a file written by
-    write_vtk_lagrange (legacy ASCII, every cell with the same number of nodes)."""
+    write_vtk_lagrange or write_vtk_lagrange_hex (legacy ASCII, every cell with the same number of nodes: (p+1)^2 of type 70, or
+    (p+1)^3 of type 72 with all three coordinates of the points in use)."""
     with open(filename) as fh:
         tok = fh.read().split("\n", 4)
     if len(tok) < 5 or not tok[0].startswith("# vtk DataFile") or tok[2].strip() != "ASCII" or tok[3].split() != ["DATASET", "UNSTRUCTURED_GRID"]:

@@ -164,6 +164,61 @@ def log_report_ho(logger, names, per_block, total, stage="elevate"):
 
 
 @dataclass
+class HoQuality3d:
+    """tm_ho3_quality as a record: the curved hexahedra of a stacked block judged at their nodes (include/tm_hip.h, "high-order hexahedra
+    of stacked blocks").  Sampled at the nodes: necessary for valid elements, not sufficient."""
+
+    elements: int
+    invalid: int
+    orientation: int
+    order: int
+    min_scaled_jacobian: float
+    worst_block: int
+    worst_e: int
+    worst_f: int
+    worst_g: int
+    min_jacobian: float
+    max_jacobian: float
+    hist: Tuple[int, ...]      # valid elements by scaled Jacobian, bins [k/10, (k+1)/10)
+
+    @classmethod
+    def from_struct(cls, q: "_capi.tm_ho3_quality") -> "HoQuality3d":
+        return cls(int(q.elements), int(q.invalid), int(q.orientation), int(q.order), float(q.min_scaled_jacobian), int(q.worst_block),
+                   int(q.worst_e), int(q.worst_f), int(q.worst_g), float(q.min_jacobian), float(q.max_jacobian), tuple(int(h) for h in q.hist))
+
+    def to_struct(self) -> "_capi.tm_ho3_quality":
+        return _capi.tm_ho3_quality(self.elements, self.invalid, self.orientation, self.order, self.min_scaled_jacobian, self.worst_block,
+                                    self.worst_e, self.worst_f, self.worst_g, self.min_jacobian, self.max_jacobian, (C.c_uint64 * 10)(*self.hist))
+
+    @property
+    def ok(self) -> bool:
+        return self.invalid == 0
+
+    def line(self, name: str) -> str:
+        """One log line: name, order, elements, invalid, min scaled Jacobian with its element, Jacobian range."""
+        return (f"{name}: order {self.order} elements {self.elements} invalid {self.invalid} "
+                f"min scaled jacobian {self.min_scaled_jacobian:.4f} at (block {self.worst_block}, e {self.worst_e}, f {self.worst_f}, g {self.worst_g}) "
+                f"jacobian {self.min_jacobian:.3e}..{self.max_jacobian:.3e}")
+
+
+def total_ho3(per_block: List[HoQuality3d]) -> HoQuality3d:
+    """tm_ho3_quality_total of the blocks' records (host only)."""
+    arr = (_capi.tm_ho3_quality * max(1, len(per_block)))()
+    for k, q in enumerate(per_block):
+        arr[k] = q.to_struct()
+    total = _capi.tm_ho3_quality()
+    _capi.check(_capi.lib().tm_ho3_quality_total(arr, len(per_block), C.byref(total)))
+    return HoQuality3d.from_struct(total)
+
+
+def log_report_ho3(logger, names, per_block, total, stage="elevate3d"):
+    """One line per block and a total, on `logger` at INFO; every line starts with `stage`."""
+    for name, q in zip(names, per_block):
+        logger.info("%s", q.line(f"{stage} {name}"))
+    logger.info("%s", total.line(f"{stage} total"))
+
+
+@dataclass
 class HoCertificate:
     """tm_ho_certificate as a record: the elements of a block judged by the Bernstein coefficients of their Jacobian (include/tm_hip.h,
     "high-order elements: certificate").  proven: o*J > 0 on the whole element; invalid: o*J <= 0 at a point; undecided: neither shown

@@ -14,7 +14,13 @@ mapping="revolution" and one meridional table x(u), r(u) per cut ("cuts on strea
     sf = Surfaces(u=[u0, u1], x=[x0, x1], r=[r0, r1], rref=[0.3, 0.5])       # meridional_from_contour gives u from a contour (x, r)
     st = Stack(span, layers, mapping="revolution", surfaces=sf)
 
-Evaluated on the MI355X (kernel K11); `host=True` evaluates the same definition on the CPU (lists of Mesh only)."""
+Curved hexahedra of order p <= 4 come from the same cuts ("high-order hexahedra of stacked blocks" in the header, kernel K16), the layers
+agglomerated in span as the nodes are in-plane; the layer count minus one must be a multiple of p like the cell counts of the blocks:
+
+    X, Y, Z, q, sj = st.elevate(cuts, highorder.Elevation(2), b)          # planes, quality.HoQuality3d, scaled Jacobian per element
+    st.mesh3d_ho(cuts, highorder.Elevation(2, "equidistant")).write("blade.vtk")
+
+Evaluated on the MI355X (kernels K11, K16); `host=True` evaluates the same definition on the CPU (lists of Mesh only)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -292,6 +298,74 @@ class Stack:
         else:
             _capi.check(_capi.lib().tm_stack_smoothers_quality_field_surf(handles, C.byref(self._opt), self.surfaces.ref(), b, k_begin, k_count, _capi.f64ptr(out)))
         return out
+
+    def check_elevation(self, cut, elevation):
+        """TmError (InconsistentSize) naming the first offender of an elevation to curved hexahedra: a block of the cut (a discrete.Mesh:
+        sizes and topology alone are read) or a connection range off the element grid, or the layer count (tm_ho3_check: host only)."""
+        md = _capi.MeshDesc(cut, with_coordinates=False)
+        _capi.check(_capi.lib().tm_ho3_check(md.ref(), C.byref(self._opt), C.byref(elevation._opt)))
+
+    def elevate(self, cuts, elevation, b, g_begin=0, g_count=None, host=False, planes=True, return_outside=False):
+        """(X, Y, Z, HoQuality3d, sj) of block b as curved hexahedra of the order of `elevation` (highorder.Elevation, order <= 4; "high-order
+        hexahedra of stacked blocks" in the header), evaluated on the device straight from the cuts (kernel K16: the fine 3-D block is never
+        stored).  X, Y, Z: the node layers [g_begin*p, (g_begin + g_count)*p] of the span elements [g_begin, g_begin + g_count) as
+        (g_count*p + 1, nj, ni) arrays (None with planes=False: the report alone); the record and sj -- the scaled Jacobian per element as an
+        (Eg, Ej, Ei) array, NaN for invalid elements -- always cover the whole block.  cuts as in block(): Mesh (tm_stack_elevate;
+        host=True: tm_stack_elevate_host, no GPU) or Smoother (tm_stack_smoothers_elevate, the resident coordinates).
+        return_outside=True (mapping="revolution") adds the per-cut count of extrapolated nodes."""
+        from . import quality as _quality
+
+        self._check_count(cuts)
+        sf = self.surfaces
+        if return_outside and sf is None:
+            raise ValueError("return_outside: only with mapping='revolution'")
+        resident = all(hasattr(c, "_h") for c in cuts)
+        if resident and host:
+            raise ValueError("host=True evaluates host coordinates: pass the meshes, not the handles")
+        meshes = [c._mesh for c in cuts] if resident else cuts
+        ni, nj = meshes[0].blocks[b].points.size
+        p = max(1, elevation.order)
+        Ei, Ej, Eg = max(0, (ni - 1) // p), max(0, (nj - 1) // p), max(0, (self.nlayers - 1) // p)
+        if g_count is None:
+            g_count = max(0, Eg - g_begin)
+        out = [np.empty((g_count * p + 1, nj, ni), dtype=np.float64) if planes else None for _ in range(3)]
+        sj = np.empty((Eg, Ej, Ei), dtype=np.float64)
+        q = _capi.tm_ho3_quality()
+        outside = np.zeros(max(1, self.ncuts), dtype=np.uint64)
+        args = (C.byref(self._opt), None if sf is None else sf.ref(), C.byref(elevation._opt), b, g_begin, g_count if planes else 0,
+                *[_capi.f64ptr(o) if planes else None for o in out], C.byref(q), _capi.f64ptr(sj),
+                outside.ctypes.data_as(C.POINTER(C.c_uint64)) if return_outside else None)
+        L = _capi.lib()
+        if resident:
+            handles = (C.c_void_p * len(cuts))(*[c._h for c in cuts])
+            _capi.check(L.tm_stack_smoothers_elevate(handles, *args))
+        else:
+            descs = [_capi.MeshDesc(m) for m in meshes]
+            arr = (C.POINTER(_capi.tm_mesh_desc) * len(descs))(*[C.pointer(d.desc) for d in descs])
+            _capi.check((L.tm_stack_elevate_host if host else L.tm_stack_elevate)(arr, *args))
+        res = (out[0], out[1], out[2], _quality.HoQuality3d.from_struct(q), sj)
+        return res + ((outside[:self.ncuts].copy(),) if return_outside else ())
+
+    def mesh3d_ho(self, cuts, elevation, host=False):
+        """Every block of the cuts as curved hexahedra: a highorder.HighOrderMesh3d with the per-block and total quality.HoQuality3d (and,
+        with mapping="revolution", per block the count of extrapolated nodes of every cut).  The size rule is checked first for all blocks
+        (check_elevation)."""
+        from . import highorder as _highorder
+        from . import quality as _quality
+
+        self._check_count(cuts)
+        first = cuts[0]._mesh if hasattr(cuts[0], "_h") else cuts[0]
+        self.check_elevation(first, elevation)
+        m = _highorder.HighOrderMesh3d(elevation.order, elevation.distribution)
+        for b, name in enumerate(first.names):
+            X, Y, Z, q, sj, *outside = self.elevate(cuts, elevation, b, host=host, return_outside=self.surfaces is not None)
+            m.outside += outside
+            m.names.append(name)
+            m.blocks.append((X, Y, Z))
+            m.per_block.append(q)
+            m.scaled_jacobian.append(sj)
+        m.total = _quality.total_ho3(m.per_block)
+        return m
 
     def mesh3d(self, cuts, host=False) -> Mesh3d:
         """Every block of the cuts, all layers."""
