@@ -845,12 +845,12 @@ int tm_ho_certificate_total(const tm_ho_certificate* per_block, uint64_t n, tm_h
  *   min_scaled_jacobian  min of sj over valid elements, (worst_block, worst_e, worst_f, worst_g) its element, ties to the lowest
  *                (block, g, f, e); NaN and zeros when no element is valid
  *   min_jacobian / max_jacobian, hist[k]: as in tm_ho_quality
- *   The record is SAMPLED AT THE NODES: a positive sj is necessary for a valid element, not sufficient.  A certificate for hexahedra
- *   (the 3-D counterpart of tm_ho_certify) is not built.
+ *   The record is SAMPLED AT THE NODES: a positive sj is necessary for a valid element, not sufficient.  The sufficient test is
+ *   tm_stack_certify ("high-order hexahedra: certificate" below).
  *   No summed field: device and host agree bit for bit in every field (the orientation is decided from a sum and is the same unless
  *   that sum lies within rounding of the zero tolerance).
  * tm_ho3_quality_total: the rules of tm_ho_quality_total.  Host only.
- * Not served: a Bezier certificate for hexahedra; orders above 4; different orders in-plane and in span; span nodes evaluated from the
+ * Not served: orders above 4; different orders in-plane and in span; span nodes evaluated from the
  * spline weights instead of by agglomeration; cuts spread over ranks; re-projection onto the blade; reconciling interface nodes across
  * blocks; Gmsh, HOPR and CGNS output. */
 #define TM_HO3_MAX_ORDER 4
@@ -893,6 +893,83 @@ int tm_stack_smoothers_elevate(tm_smoother* const* cuts, const tm_stack_opt* sta
                                uint64_t block, uint64_t g_begin, uint64_t g_count, double* x, double* y, double* z, tm_ho3_quality* q,
                                double* sj, uint64_t* outside);
 int tm_ho3_quality_total(const tm_ho3_quality* per_block, uint64_t n, tm_ho3_quality* total);
+
+/* ------------------------------------------------------------------ high-order hexahedra: certificate (Bezier bounds of the Jacobian)
+ * The record above samples J at the (p+1)^3 nodes.  The certificate bounds J on the WHOLE hexahedron: J of the degree-p interpolant of the
+ * fine nodes is a polynomial of degree 3p-1 per direction, and its (3p)^3 Bernstein coefficients enclose it.
+ * Elements, the order rule (1 <= p <= TM_HO3_MAX_ORDER), the size rule and the fine nodes are those of the section above: the fine nodes are
+ *   exactly what tm_stack_block[_surf] returns.  The certificate depends on the order alone: `distribution` and `nodes` are validated and
+ *   otherwise ignored.  All arithmetic IEEE fp64, nothing fused.  N1 = p+1, N = 3p.
+ * Tables, on the host in long double from exact integers, every entry rounded once:
+ *   M[i][m]          tm_ho_certify_tables' M, unchanged
+ *   w^{a,b}[k][i]  = C(a,i) C(b,k-i) / C(a+b,k)  (0 <= k-i <= b, else 0), k = 0 .. a+b, i = 0 .. a: the weights of the Bernstein product of a
+ *                    degree-a and a degree-b polynomial.  wA packs w^{p,p}, w^{p-1,p}, w^{p,p-1}; wB packs w^{p-1,2p}, w^{p,2p-1} (the latter
+ *                    serves v and w alike), each row-major with a+1 entries per row.
+ * Control points, per component: d[m][n][l] = F[e*p+m][f*p+n][g*p+l] - F[e*p][f*p][g*p], then three stages, span first:
+ *   V[m][n][k] = M[k][0]*d[m][n][0], then + M[k][l]*d[m][n][l] for l = 1 .. p;
+ *   W[m][j][k] = M[j][0]*V[m][0][k], then + M[j][n]*V[m][n][k] for n = 1 .. p;
+ *   C[i][j][k] = M[i][0]*W[0][j][k], then + M[i][m]*W[m][j][k] for m = 1 .. p.
+ * Derivative coefficients on [0, p]^3 (K16's units, no factor):
+ *   xu[i][j][k] = C[i+1][j][k] - C[i][j][k]  (p x N1 x N1),  xv[i][j][k] = C[i][j+1][k] - C[i][j][k]  (N1 x p x N1),
+ *   xw[i][j][k] = C[i][j][k+1] - C[i][j][k]  (N1 x N1 x p), likewise y and z.
+ * Jacobian J = Xu . (Xv x Xw), in two Bernstein products.  Every sum runs over its admissible index range in ascending order and starts
+ * from 0 (s = 0, then s = s + weight * value); the sums are nested u outside, then v, then w inside.
+ *   1. cofactors, (2p+1) x 2p x 2p coefficients each, for (f, g) = (y, z), (z, x), (x, y) giving cx, cy, cz:
+ *        c[a][b][c] = sum_i w^{p,p}[a][i] * ( sum_j w^{p-1,p}[b][j] * ( sum_k w^{p,p-1}[c][k] * t ) ),
+ *        t = fv[i][j][k]*gw[a-i][b-j][c-k] - gv[i][j][k]*fw[a-i][b-j][c-k]
+ *        (cx = yv zw - zv yw, cy = zv xw - xv zw, cz = xv yw - yv xw);
+ *        i over max(0,a-p) .. min(p,a), j over max(0,b-p) .. min(p-1,b), k over max(0,c-p+1) .. min(p,c).
+ *   2. B[a][b][c] = sum_i w^{p-1,2p}[a][i] * ( sum_j w^{p,2p-1}[b][j] * ( sum_k w^{p,2p-1}[c][k] * t ) ),
+ *        t = xu[i][j][k]*cx[a-i][b-j][c-k] + yu[i][j][k]*cy[a-i][b-j][c-k] + zu[i][j][k]*cz[a-i][b-j][c-k]   (left to right);
+ *        i over max(0,a-2p) .. min(p-1,a), j over max(0,b-2p+1) .. min(p,b), k likewise with c.
+ *   The eight corner coefficients are J at the element's corners; min B <= J <= max B on the patch.
+ * Subdivision: a patch is split at its midpoint in u (index a), then each half in v, then each quarter in w, by de Casteljau with
+ *   0.5*(a + b) along every line of the direction: eight children, child q = (u half) + 2 (v half) + 4 (w half).  The corners of the
+ *   patches of level L are values of J at multiples of p/2^L.
+ * Orientation o and the nodal verdict: K16's (0 counts as +1); the call runs K16's report on the block first.
+ * Guard: g = (G3(p) * 2^-53) * R3,  R3 = (sx * sy) * sz,  sx = (max|xu| + max|xv|) + max|xw| over the element's derivative coefficients,
+ *   sy and sz likewise.  G3(p) = 9 p (6p+20) L^3 + 99p + 52 with L = ||M||_inf (fp64, rounded once; the expression in long double, rounded
+ *   once): g bounds the rounding error of a coefficient at any level up to TM_HO3_CERT_MAX_DEPTH with no condition on the element's shape
+ *   (DESIGN.md, section 4, K17 derives it).  It is the only tolerance.
+ * Status of an element, levels, lo / hi, hidden_invalid, decided_at, min_scaled_bound, the first unproven element and the tie rules: those of
+ *   "high-order elements: certificate" above, with "patch corner" meaning the eight corners, 0 <= max_depth <= TM_HO3_CERT_MAX_DEPTH = 3 (at
+ *   depth 3 an element has up to 512 leaf patches of (3p)^3 coefficients: one level less than in 2-D), elements ordered by (block, g, f, e).
+ *   No summed floating-point field: device and host agree bit for bit in record, status and bounds.
+ * tm_ho3_certificate_total: the rules of tm_ho_certificate_total.  Host only.
+ * Not served: repairing the elements the certificate rejects; adaptive subdivision; orders above 4; cuts spread over ranks. */
+#define TM_HO3_CERT_MAX_DEPTH 3
+typedef struct tm_ho3_certificate {     /* 160 bytes */
+    uint64_t elements, proven, invalid, undecided, hidden_invalid;
+    int32_t  orientation, order, max_depth, has_unproven;
+    uint64_t decided_at[4];
+    double   min_scaled_bound;
+    uint64_t worst_block, worst_e, worst_f, worst_g;
+    uint64_t first_unproven_block, first_unproven_e, first_unproven_f, first_unproven_g;
+} tm_ho3_certificate;
+/* M [(p+1)^2]; wA [(2p+1)(p+1) + 2p*p + 2p(p+1)]; wB [3p*p + 3p(p+1)]; G3(p) and ||M||_inf; any output may be NULL.  Host only */
+int tm_ho3_certify_tables(const tm_ho_opt* opt, double* M, double* wA, double* wB, double* G, double* norm);
+/* The (3p)^3 coefficients of element (e, f, g) of any 3-D block in PLOT3D order as B[(a*3p + b)*3p + c], NOT multiplied by o.  An element
+ * past the block: TM_E_ARG; the size rule: TM_E_SIZE.  Host only */
+int tm_ho3_jacobian_bezier_host(const double* x, const double* y, const double* z, uint64_t ni, uint64_t nj, uint64_t nk, const tm_ho_opt* opt,
+                                uint64_t e, uint64_t f, uint64_t g, double* B);
+/* Any 3-D block in PLOT3D order (what tm_stack_block returned, or a file read back).  No GPU touched.  status, when given, receives
+ * Ei*Ej*Eg bytes as status[(g*Ej + f)*Ei + e]; bounds 2 doubles (lo, hi) per element in the same order; cert may be NULL.  `block` only
+ * labels the record.  A max_depth outside 0 .. TM_HO3_CERT_MAX_DEPTH: TM_E_ARG. */
+int tm_ho3_certify_planes_host(const double* x, const double* y, const double* z, uint64_t ni, uint64_t nj, uint64_t nk, const tm_ho_opt* opt,
+                               int32_t max_depth, uint64_t block, tm_ho3_certificate* cert, uint8_t* status, double* bounds);
+/* Block `block` of the stack of K meshes given on the host, certified on the device: K16's report, then per window of span elements K11
+ * into device planes and kernel K17 on them.  surfaces, outside and the errors as tm_stack_elevate.  Every output equals
+ * tm_ho3_certify_planes_host applied to the planes tm_stack_block[_surf] returns, bit for bit. */
+int tm_stack_certify(const tm_mesh_desc* const* cuts, const tm_stack_opt* stack, const tm_stack_surfaces* surfaces, const tm_ho_opt* opt,
+                     int32_t max_depth, uint64_t block, tm_ho3_certificate* cert, uint8_t* status, double* bounds, uint64_t* outside);
+/* tm_stack_block[_surf]_host followed by tm_ho3_certify_planes_host; no GPU touched */
+int tm_stack_certify_host(const tm_mesh_desc* const* cuts, const tm_stack_opt* stack, const tm_stack_surfaces* surfaces, const tm_ho_opt* opt,
+                          int32_t max_depth, uint64_t block, tm_ho3_certificate* cert, uint8_t* status, double* bounds, uint64_t* outside);
+/* The same kernels on the coordinates RESIDENT in K handles.  Ordered behind the pending work of every handle exactly as
+ * tm_stack_smoothers is; modifies no handle.  Errors as tm_stack_smoothers_elevate.  Bit-identical to tm_stack_certify on the download. */
+int tm_stack_smoothers_certify(tm_smoother* const* cuts, const tm_stack_opt* stack, const tm_stack_surfaces* surfaces, const tm_ho_opt* opt,
+                               int32_t max_depth, uint64_t block, tm_ho3_certificate* cert, uint8_t* status, double* bounds, uint64_t* outside);
+int tm_ho3_certificate_total(const tm_ho3_certificate* per_block, uint64_t n, tm_ho3_certificate* total);
 
 /* ------------------------------------------------------------------ host-only planning (no GPU needed)
  * The perimeter-row table the device kernels consume, exported as CSR so it can be compared with

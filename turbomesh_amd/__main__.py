@@ -29,7 +29,11 @@ With --stack, --order P (1 .. 4) turns the stacked blocks into curved hexahedra 
 include/tm_hip.h "high-order hexahedra of stacked blocks"): the cell counts of every block, the interface ranges and --layers minus one
 must be multiples of P, checked before anything is smoothed; the elements are formed on the device straight from the resident cuts, their
 report is logged per block and for the mesh, and --output takes the elevated nodes (.vtk: Lagrange hexahedra, equidistant nodes only;
-.xyz / .p3d: 3-D PLOT3D).  --certify does not go with --stack: a 3-D certificate is not built.
+.xyz / .p3d: 3-D PLOT3D).  --stack-certify [DEPTH] with --stack --order: the hexahedra are also judged on their WHOLE volume by the
+Bernstein coefficients of their Jacobian, with up to DEPTH (default 2, at most 3) octree subdivisions, from the resident cuts (include/tm_hip.h
+"high-order hexahedra: certificate"), logged per block and for the mesh; --fail-on-invalid-elements then also counts the hexahedra folded
+between their nodes, and --fail-on-unproven-elements exits non-zero when any is not proven.  --certify itself judges 2-D elements and does
+not go with --stack.
 Without --order nothing changes; without --certify neither does --order."""
 from __future__ import annotations
 
@@ -174,7 +178,7 @@ def _main_stack(ap, args):
             all_stats.append(stats)
             if after is not None and not after[1].ok and worst is None:
                 worst = (c, after[1])
-        hom = None
+        hom = cert = None
         if args.order is not None:   # curved hexahedra straight from the resident cuts: the fine 3-D block is never formed
             from . import highorder
 
@@ -185,6 +189,10 @@ def _main_stack(ap, args):
                     if n:
                         logging.getLogger("stack").warning("block %d (%s), cut %d: %d nodes lie outside the meridional table %s and are extrapolated", b, hom.names[b],
                                                            c, int(n), args.meridional[c])
+            if args.stack_certify is not None:   # from the resident cuts as well
+                ctotal, cper, _, _ = st.certify(handles, highorder.Elevation(args.order, args.nodes), max_depth=args.stack_certify)
+                quality.log_report_ho3_certificate(logging.getLogger("quality"), hom.names, cper, ctotal)
+                cert = {"per_block": cper, "total": ctotal}
         elif surfaces is None:
             m3 = st.mesh3d(handles)
         else:   # the same blocks, with the count of extrapolated nodes per cut
@@ -211,6 +219,14 @@ def _main_stack(ap, args):
         b, bad = next((b, q) for b, q in enumerate(hom.per_block) if not q.ok)
         sys.exit(f"high-order elements: {hom.total.invalid} invalid hexahedra of order {hom.order} in the stacked mesh "
                  f"(first in block {b}: {bad.invalid} of {bad.elements})")
+    if args.fail_on_invalid_elements and cert is not None and cert["total"].hidden_invalid:
+        sys.exit(f"high-order elements: {cert['total'].hidden_invalid} hexahedra of order {hom.order} are valid at their nodes and folded between them "
+                 f"({cert['total'].invalid} invalid by the certificate)")
+    if args.fail_on_unproven_elements and not cert["total"].ok:
+        t = cert["total"]
+        sys.exit(f"high-order elements: {t.elements - t.proven} of {t.elements} hexahedra of order {hom.order} are not proven valid ({t.invalid} invalid, "
+                 f"{t.undecided} undecided at depth {t.max_depth}; first: block {t.first_unproven_block}, e {t.first_unproven_e}, f {t.first_unproven_f}, "
+                 f"g {t.first_unproven_g})")
     if args.fail_on_inverted_3d and not q3[1].ok:
         b, bad = next((b, q) for b, q in enumerate(q3[0]) if not q.ok)
         sys.exit(f"mesh quality: the stacked mesh has {q3[1].inverted} inverted and {q3[1].degenerate} degenerate hexahedra "
@@ -218,6 +234,8 @@ def _main_stack(ap, args):
     out = {"cuts": all_stats, "blocks": len(m3.blocks), "layers": st.nlayers}
     if hom is not None:
         out["highorder"] = hom
+    if cert is not None:
+        out["certificate"] = cert
     if q3 is not None:
         out["quality3d"] = {"per_block": q3[0], "total": q3[1]}
     return out
@@ -258,8 +276,12 @@ def main(argv=None):
                     help="with --order: certify every element on its whole area by the Bernstein coefficients of its Jacobian with up to DEPTH "
                          "(0 .. 4, default 3) subdivisions; logged per block and for the mesh; --fail-on-invalid-elements then counts the "
                          "elements folded between their nodes too")
+    ap.add_argument("--stack-certify", nargs="?", type=int, const=2, default=None, metavar="DEPTH",
+                    help="with --stack --order: the 3-D certificate -- certify every curved hexahedron on its whole volume by the Bernstein "
+                         "coefficients of its Jacobian with up to DEPTH (0 .. 3, default 2) octree subdivisions, from the resident cuts; logged per "
+                         "block and for the mesh; --fail-on-invalid-elements then counts the hexahedra folded between their nodes too")
     ap.add_argument("--fail-on-unproven-elements", action="store_true",
-                    help="with --certify: exit non-zero, after the file is written, when any element is not proven valid (invalid or undecided)")
+                    help="with --certify or --stack-certify: exit non-zero, after the file is written, when any element is not proven valid (invalid or undecided)")
     ap.add_argument("--stack", nargs="+", metavar="CFG", default=None,
                     help="further input files: the spanwise cuts after `config`, in span order.  Every file runs the path above with its own "
                          "handle; the smoothed cuts are then stacked into 3-D blocks on the device and --output becomes a multi-block 3-D PLOT3D file")
@@ -290,8 +312,13 @@ def main(argv=None):
         ap.error("--stack-quality and --fail-on-inverted-3d go with --stack")
     if args.order is None and (args.nodes or args.fail_on_invalid_elements):
         ap.error("--nodes and --fail-on-invalid-elements go with --order")
-    if args.certify is None and args.fail_on_unproven_elements:
-        ap.error("--fail-on-unproven-elements goes with --certify")
+    if args.certify is None and args.stack_certify is None and args.fail_on_unproven_elements:
+        ap.error("--fail-on-unproven-elements goes with --certify or --stack-certify")
+    if args.stack_certify is not None:
+        if args.stack is None or args.order is None:
+            ap.error("--stack-certify goes with --stack and --order")
+        if not 0 <= args.stack_certify <= 3:
+            ap.error("--stack-certify: 0 .. 3")
     if args.certify is not None:
         if args.order is None:
             ap.error("--certify goes with --order")

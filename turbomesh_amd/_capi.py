@@ -33,6 +33,7 @@ TM_HO_MAX_ORDER = 8
 TM_HO_EQUIDISTANT, TM_HO_GAUSS_LOBATTO, TM_HO_PRESCRIBED = 0, 1, 2
 TM_HO_CERT_MAX_DEPTH = 4
 TM_HO3_MAX_ORDER = 4
+TM_HO3_CERT_MAX_DEPTH = 3
 TM_HO_PROVEN, TM_HO_INVALID, TM_HO_UNDECIDED = 0, 1, 2
 
 
@@ -179,6 +180,14 @@ class tm_ho_certificate(C.Structure):   # 152 bytes
                 ("worst_f", C.c_uint64), ("first_unproven_block", C.c_uint64), ("first_unproven_e", C.c_uint64), ("first_unproven_f", C.c_uint64)]
 
 
+class tm_ho3_certificate(C.Structure):   # 160 bytes
+    _fields_ = [("elements", C.c_uint64), ("proven", C.c_uint64), ("invalid", C.c_uint64), ("undecided", C.c_uint64), ("hidden_invalid", C.c_uint64),
+                ("orientation", C.c_int32), ("order", C.c_int32), ("max_depth", C.c_int32), ("has_unproven", C.c_int32),
+                ("decided_at", C.c_uint64 * 4), ("min_scaled_bound", C.c_double), ("worst_block", C.c_uint64), ("worst_e", C.c_uint64),
+                ("worst_f", C.c_uint64), ("worst_g", C.c_uint64), ("first_unproven_block", C.c_uint64), ("first_unproven_e", C.c_uint64),
+                ("first_unproven_f", C.c_uint64), ("first_unproven_g", C.c_uint64)]
+
+
 # every symbol include/tm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "tm_last_error", "tm_abi_version", "tm_set_log", "tm_csr_solve", "tm_tfi_block", "tm_tfi_linear2d", "tm_smooth_mesh", "tm_smoother_create",
@@ -198,6 +207,8 @@ EXPORTS = [
     "tm_ho_tables", "tm_ho_check", "tm_ho_elevate", "tm_ho_elevate_host", "tm_smoother_elevate", "tm_ho_quality_total",
     "tm_ho_certify_tables", "tm_ho_certify", "tm_ho_certify_host", "tm_smoother_certify", "tm_ho_jacobian_bezier_host", "tm_ho_certificate_total",
     "tm_ho3_check", "tm_ho3_planes_host", "tm_stack_elevate", "tm_stack_elevate_host", "tm_stack_smoothers_elevate", "tm_ho3_quality_total",
+    "tm_ho3_certify_tables", "tm_ho3_jacobian_bezier_host", "tm_ho3_certify_planes_host", "tm_stack_certify", "tm_stack_certify_host",
+    "tm_stack_smoothers_certify", "tm_ho3_certificate_total",
     "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
 ]
 
@@ -325,6 +336,15 @@ def lib():
         L.tm_stack_elevate_host.argtypes = L.tm_stack_elevate.argtypes
         L.tm_stack_smoothers_elevate.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt)] + _ho3_tail
         L.tm_ho3_quality_total.argtypes = [C.POINTER(tm_ho3_quality), C.c_uint64, C.POINTER(tm_ho3_quality)]
+        _u8p, _c3p = C.POINTER(C.c_uint8), C.POINTER(tm_ho3_certificate)
+        L.tm_ho3_certify_tables.argtypes = [C.POINTER(tm_ho_opt), _dp, _dp, _dp, _dp, _dp]
+        L.tm_ho3_jacobian_bezier_host.argtypes = [_dp, _dp, _dp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(tm_ho_opt), C.c_uint64, C.c_uint64, C.c_uint64, _dp]
+        L.tm_ho3_certify_planes_host.argtypes = [_dp, _dp, _dp, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(tm_ho_opt), C.c_int32, C.c_uint64, _c3p, _u8p, _dp]
+        _h3_tail = [_sfp, C.POINTER(tm_ho_opt), C.c_int32, C.c_uint64, _c3p, _u8p, _dp, _u64p]
+        L.tm_stack_certify.argtypes = [C.POINTER(C.POINTER(tm_mesh_desc)), C.POINTER(tm_stack_opt)] + _h3_tail
+        L.tm_stack_certify_host.argtypes = L.tm_stack_certify.argtypes
+        L.tm_stack_smoothers_certify.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt)] + _h3_tail
+        L.tm_ho3_certificate_total.argtypes = [_c3p, C.c_uint64, _c3p]
         L.tm_rccl_unique_id.argtypes =[C.c_char_p, C.c_void_p]
         L.tm_rccl_comm_create.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.tm_rccl_comm_destroy.argtypes = [C.c_void_p]

@@ -32,11 +32,11 @@ static hipError_t ho3_launch_p(int p, int K, const Ho3Launch& a, hipStream_t st)
 }
 
 // Tables up, K16 and the finalize on `st`, planes / record / pairs back; returns when they have arrived.  The sizes have been checked.
-static void ho3_run(const StackPlan& p, const HoPlan& pl, StackCuts& cuts, uint64_t block, uint64_t ni, uint64_t nj, uint64_t g_begin, uint64_t g_count, double* x,
-                    double* y, double* z, tm_ho3_quality* q, double* sj, hipStream_t st, const SurfPlan* sf, uint64_t* outside) {
+void ho3_run(const StackPlan& p, const HoPlan& pl, StackCuts& cuts, uint64_t block, uint64_t ni, uint64_t nj, uint64_t g_begin, uint64_t g_count, double* x,
+             double* y, double* z, tm_ho3_quality* q, double* sj, hipStream_t st, const SurfPlan* sf, uint64_t* outside, double2* pairs_dev) {
     const int K = p.ncuts, P = pl.order;
     const uint64_t Ei = (ni - 1) / P, Ej = (nj - 1) / P, Eg = (p.nlayers - 1) / P;
-    const bool planes = x != nullptr, report = q || sj;
+    const bool planes = x != nullptr, report = q || sj || pairs_dev;
     if (!planes && !report && !(sf && outside)) return;
     stack_fill_radii(p, cuts);
     StackSurfDev sd;
@@ -59,7 +59,7 @@ static void ho3_run(const StackPlan& p, const HoPlan& pl, StackCuts& cuts, uint6
     if (grid.y > 65535u) throw TmError(TM_E_SIZE, "InconsistentSize: too many element rows for one launch");
     const size_t nwg = static_cast<size_t>(grid.x) * grid.y;   // the records buffer is sized from the very grid the launcher forms
     StackBuf d_table(sizeof(double) * table.size(), "stack weights and elevation tables"), d_out(sizeof(double) * 3 * n, "elevated planes"),
-        d_pairs(sj ? sizeof(double2) * elements : 0, "element pairs"), d_rec(report ? sizeof(HoAcc) * (nwg + HO3_REDUCE_GROUPS) : 0, "elevation records"),
+        d_pairs(sj && !pairs_dev ? sizeof(double2) * elements : 0, "element pairs"), d_rec(report ? sizeof(HoAcc) * (nwg + HO3_REDUCE_GROUPS) : 0, "elevation records"),
         d_q(sizeof(tm_ho3_quality), "elevation record");
     HIPCHK(hipMemcpyAsync(d_table.p, table.data(), sizeof(double) * table.size(), hipMemcpyHostToDevice, st));
     Ho3Launch a{};
@@ -80,7 +80,7 @@ static void ho3_run(const StackPlan& p, const HoPlan& pl, StackCuts& cuts, uint6
     a.X = planes ? d_out.as<double>() : nullptr;
     a.Y = planes ? d_out.as<double>() + n : nullptr;
     a.Z = planes ? d_out.as<double>() + 2 * n : nullptr;
-    a.pairs = sj ? d_pairs.as<double2>() : nullptr;
+    a.pairs = pairs_dev ? pairs_dev : sj ? d_pairs.as<double2>() : nullptr;
     a.partials = report ? d_rec.as<HoAcc>() : nullptr;
     a.outside = d_outside ? d_outside->as<unsigned long long>() : nullptr;
     HIPCHK(ho3_launch_p(P, K, a, st));

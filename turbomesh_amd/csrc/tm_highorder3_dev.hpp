@@ -29,4 +29,9 @@ struct Ho3Launch {
 template <int P>
 hipError_t ho3_launch(int K, const Ho3Launch& a, hipStream_t st);
 
+// Tables up, K16 and the finalize on `st`, planes / record / pairs back; returns when they have arrived.  The sizes have been checked.
+// pairs_dev (may be null; then sj must be null): the (Jmin, Jmax) pairs of the whole block stay on the device in the caller's buffer (K17).
+void ho3_run(const StackPlan& p, const HoPlan& pl, StackCuts& cuts, uint64_t block, uint64_t ni, uint64_t nj, uint64_t g_begin, uint64_t g_count, double* x,
+             double* y, double* z, tm_ho3_quality* q, double* sj, hipStream_t st, const SurfPlan* sf, uint64_t* outside, double2* pairs_dev = nullptr);
+
 }  // namespace tmh

@@ -116,8 +116,8 @@ static void stack_launch_k(const StackCuts& cuts, const StackSurf& surf, int map
         hipLaunchKernelGGL((k_stack_planes<K, TM_STACK_PLANAR>), grid, block, 0, st, cuts, surf, table, nk, ni, nj, X, Y, Z, outside);
 }
 
-static hipError_t launch_stack_planes(int K, const StackCuts& cuts, const StackSurf& surf, int mapping, const double* table, int nk, int ni, int nj, double* X,
-                                      double* Y, double* Z, unsigned long long* outside, hipStream_t st) {
+hipError_t launch_stack_planes(int K, const StackCuts& cuts, const StackSurf& surf, int mapping, const double* table, int nk, int ni, int nj, double* X, double* Y,
+                               double* Z, unsigned long long* outside, hipStream_t st) {
     switch (K) {
 #define TM_STACK_CASE(n) \
     case n: stack_launch_k<n>(cuts, surf, mapping, table, nk, ni, nj, X, Y, Z, outside, st); break;

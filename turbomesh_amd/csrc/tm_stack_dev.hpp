@@ -85,6 +85,9 @@ struct StackSurfDev {
     StackSurf surf{};
 };
 void stack_surf_upload(const StackPlan& p, const SurfPlan& sf, StackCuts& cuts, StackSurfDev& d, hipStream_t st);
+// K11 on `st`: nk layers of the block into the device planes X, Y, Z; table: per layer K weights followed by s[k] (tm_stack.hip)
+hipError_t launch_stack_planes(int K, const StackCuts& cuts, const StackSurf& surf, int mapping, const double* table, int nk, int ni, int nj, double* X, double* Y,
+                               double* Z, unsigned long long* outside, hipStream_t st);
 
 inline void require_gfx950_stack() {
     int dev = 0;

@@ -85,6 +85,42 @@ def planes3d(X, Y, Z, elevation, block=0, planes=True):
     return out[0], out[1], out[2], _quality.HoQuality3d.from_struct(q), sj
 
 
+def _planes_of(X, Y, Z):
+    X, Y, Z = (np.ascontiguousarray(a, dtype=np.float64) for a in (X, Y, Z))
+    if X.ndim != 3 or Y.shape != X.shape or Z.shape != X.shape:
+        raise ValueError("X, Y, Z: three (nk, nj, ni) arrays of one shape")
+    return X, Y, Z
+
+
+def certify3d(X, Y, Z, elevation, max_depth=2, block=0):
+    """(HoCertificate3d, status, bounds) of any 3-D block given as (nk, nj, ni) arrays (PLOT3D order), certified on the CPU
+    (tm_ho3_certify_planes_host: no GPU needed): status an (Eg, Ej, Ei) uint8 array of TM_HO_PROVEN / TM_HO_INVALID / TM_HO_UNDECIDED,
+    bounds an (Eg, Ej, Ei, 2) array of (lo, hi) with lo <= o*J <= hi on the whole element."""
+    X, Y, Z = _planes_of(X, Y, Z)
+    nk, nj, ni = X.shape
+    p = max(1, elevation.order)
+    E = (max(0, (nk - 1) // p), max(0, (nj - 1) // p), max(0, (ni - 1) // p))
+    status = np.empty(E, dtype=np.uint8)
+    bounds = np.empty(E + (2,), dtype=np.float64)
+    c = _capi.tm_ho3_certificate()
+    _capi.check(_capi.lib().tm_ho3_certify_planes_host(_capi.f64ptr(X), _capi.f64ptr(Y), _capi.f64ptr(Z), ni, nj, nk, C.byref(elevation._opt),
+                                                       int(max_depth), block, C.byref(c), status.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                       _capi.f64ptr(bounds)))
+    return _quality.HoCertificate3d.from_struct(c), status, bounds
+
+
+def jacobian_bezier3d(X, Y, Z, elevation, e, f, g):
+    """The (3p, 3p, 3p) Bernstein coefficients B[a, b, c] (a along i, b along j, c along span) of the Jacobian of element (e, f, g) of a
+    3-D block given as (nk, nj, ni) arrays, not multiplied by the orientation (tm_ho3_jacobian_bezier_host: host only)."""
+    X, Y, Z = _planes_of(X, Y, Z)
+    nk, nj, ni = X.shape
+    n = 3 * max(1, elevation.order)
+    B = np.empty((n, n, n))
+    _capi.check(_capi.lib().tm_ho3_jacobian_bezier_host(_capi.f64ptr(X), _capi.f64ptr(Y), _capi.f64ptr(Z), ni, nj, nk, C.byref(elevation._opt),
+                                                        e, f, g, _capi.f64ptr(B)))
+    return B
+
+
 @dataclass
 class HighOrderMesh3d:
     """The elevated blocks of a stacked mesh: per block the X, Y, Z coordinates as (nk, nj, ni) arrays (PLOT3D order, i fastest), the
@@ -215,6 +251,27 @@ class Elevation:
         G, norm = C.c_double(), C.c_double()
         _capi.check(_capi.lib().tm_ho_certify_tables(C.byref(self._opt), _capi.f64ptr(M), _capi.f64ptr(wu), _capi.f64ptr(wv), C.byref(G), C.byref(norm)))
         return M, wu, wv, G.value, norm.value
+
+    def certify3d_tables(self):
+        """(M[p+1, p+1], wA, wB, G3, norm) of the certificate of hexahedra: wA = (w^{p,p}[2p+1, p+1], w^{p-1,p}[2p, p], w^{p,p-1}[2p, p+1]),
+        wB = (w^{p-1,2p}[3p, p], w^{p,2p-1}[3p, p+1]), the Bernstein product weights w^{a,b}[k, i] = C(a,i) C(b,k-i) / C(a+b,k); the
+        guard factor G3(p) and ||M||_inf (tm_ho3_certify_tables: host only)."""
+        p = max(1, self.order)
+        M = np.empty((p + 1, p + 1))
+        sa = [(2 * p + 1, p + 1), (2 * p, p), (2 * p, p + 1)]
+        sb = [(3 * p, p), (3 * p, p + 1)]
+        wA, wB = np.empty(sum(a * b for a, b in sa)), np.empty(sum(a * b for a, b in sb))
+        G, norm = C.c_double(), C.c_double()
+        _capi.check(_capi.lib().tm_ho3_certify_tables(C.byref(self._opt), _capi.f64ptr(M), _capi.f64ptr(wA), _capi.f64ptr(wB), C.byref(G), C.byref(norm)))
+
+        def split(w, shapes):
+            out, at = [], 0
+            for a, b in shapes:
+                out.append(w[at:at + a * b].reshape(a, b).copy())
+                at += a * b
+            return tuple(out)
+
+        return M, split(wA, sa), split(wB, sb), G.value, norm.value
 
     def jacobian_bezier(self, mesh, b, e, f):
         """The (2p, 2p) Bernstein coefficients of the Jacobian of element (e, f) of block b (tm_ho_jacobian_bezier_host: host only)."""

@@ -8,6 +8,7 @@
 //                                                      device by the natural cubic spline: a checksum per layer (exit 0: layers at cuts equal the cuts)
 //   tm_harness certify <ni> <nj> <order>   Bezier certificate of those elements (kernel K14; exit 0: equal to the CPU's, counts add up)
 //   tm_harness elevate <ni> <nj> <order>   curved elements of that order from a smoothed block (kernel K13; exit 0: corners unchanged, equal to the CPU's)
+//   tm_harness stack-certify <ni> <nj> <ncuts> <nlayers> <order>   the same cuts: the certificate of those hexahedra (kernel K17; exit 0: counts add up, equal to the CPU's)
 //   tm_harness stack-elevate <ni> <nj> <ncuts> <nlayers> <order>   the same cuts: curved hexahedra of that order from the stacked block (kernel K16; exit 0: corners unchanged, equal to the CPU's)
 //   tm_harness stack-quality <ni> <nj> <ncuts> <nlayers>   the same cuts: the 3-D quality record of the stacked block (kernel K12; exit 0: equal to the CPU's)
 //   tm_harness csr                                     the linear-solver slot (seam 2) on the reference's 5 x 5 known answer
@@ -430,6 +431,49 @@ static int stackElevate(std::size_t ni, std::size_t nj, std::size_t ncuts, std::
     return corners && same ? 0 : 1;
 }
 
+// tm_harness stack-certify <ni> <nj> <ncuts> <nlayers> <order>: the cuts of `stack-elevate`; the certificate of the curved hexahedra from the
+// coordinates resident in the handles (stack::certify -> tm_stack_smoothers_certify, kernel K17), compared with the CPU's evaluation of
+// the downloaded coordinates (the planar mapping: record, status and bounds bit for bit).
+static int stackCertify(std::size_t ni, std::size_t nj, std::size_t ncuts, std::size_t nlayers, int order) {
+    if (ncuts < 2 || nlayers < 2) throw Error(TM_E_ARG, "stack-certify <ni> <nj> <ncuts> <nlayers> <order>: at least two cuts and two layers");
+    smoothing::solver::Option opt;
+    opt.inner = TM_INNER_RELAX;
+    std::vector<discrete::Mesh> meshes;
+    meshes.reserve(ncuts);
+    for (std::size_t c = 0; c < ncuts; ++c) meshes.push_back(buildSingle(ni, nj, 0.05 + 0.001 * static_cast<double>(c)));
+    std::vector<std::unique_ptr<smoothing::smooth::Smoother>> handles;
+    std::vector<smoothing::smooth::Smoother*> cuts;
+    std::vector<discrete::Mesh*> host_cuts;
+    for (std::size_t c = 0; c < ncuts; ++c) {
+        handles.push_back(std::make_unique<smoothing::smooth::Smoother>(meshes[c], opt, smoothing::wall_control_function::Algorithm::laplace()));
+        handles.back()->iterate(5);
+        cuts.push_back(handles.back().get());
+        host_cuts.push_back(&meshes[c]);
+    }
+    stack::Option so;
+    for (std::size_t c = 0; c < ncuts; ++c) so.span.push_back(static_cast<double>(c));
+    const double z1 = so.span.back();
+    for (std::size_t k = 0; k < nlayers; ++k) so.layers.push_back(k + 1 == nlayers ? z1 : z1 * (static_cast<double>(k) / static_cast<double>(nlayers - 1)));
+    highorder::Option ho;
+    ho.order = order;
+    const stack::Certified3d dev = stack::certify(cuts, so, ho, 0);
+    for (auto& h : handles) h->download();
+    const stack::Certified3d host = stack::certify(host_cuts, so, ho, 0, 2, true);
+    const tm_ho3_certificate& c = dev.certificate;
+    std::printf("stack-certify: hexahedra %llu proven %llu invalid %llu undecided %llu hidden invalid %llu min scaled bound %.17g at (e %llu, f %llu, g %llu) orientation %d order %d depth %d\n",
+                static_cast<unsigned long long>(c.elements), static_cast<unsigned long long>(c.proven), static_cast<unsigned long long>(c.invalid),
+                static_cast<unsigned long long>(c.undecided), static_cast<unsigned long long>(c.hidden_invalid), c.min_scaled_bound,
+                static_cast<unsigned long long>(c.worst_e), static_cast<unsigned long long>(c.worst_f), static_cast<unsigned long long>(c.worst_g), c.orientation, c.order,
+                c.max_depth);
+    const bool adds = c.proven + c.invalid + c.undecided == c.elements && c.elements == dev.Ei * dev.Ej * dev.Eg;
+    std::printf("stack-certify: counts add up: %s\n", adds ? "yes" : "no");
+    const bool same = dev.status == host.status && dev.bounds.size() == host.bounds.size() &&
+                      (dev.bounds.empty() || std::memcmp(dev.bounds.data(), host.bounds.data(), sizeof(double) * dev.bounds.size()) == 0) &&
+                      std::memcmp(&dev.certificate, &host.certificate, sizeof(tm_ho3_certificate)) == 0;
+    std::printf("stack-certify: device equals host: %s\n", same ? "yes" : "no");
+    return adds && same ? 0 : 1;
+}
+
 // tm_harness elevate <ni> <nj> <order>: the config-2 block, five relaxation sweeps; Gauss-Lobatto elements of `order` from the
 // coordinates resident in the handle (highorder::elevate -> tm_smoother_elevate), compared with the CPU's evaluation of the
 // downloaded coordinates (planes, scaled Jacobians and the record bit for bit); element corners must be the smoothed nodes.
@@ -500,6 +544,9 @@ int main(int argc, char** argv) {
             return certifyBlock(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), static_cast<int>(std::strtol(argv[4], nullptr, 10)));
         if (argc >= 5 && std::strcmp(argv[1], "elevate") == 0)
             return elevateBlock(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), static_cast<int>(std::strtol(argv[4], nullptr, 10)));
+        if (argc >= 7 && std::strcmp(argv[1], "stack-certify") == 0)
+            return stackCertify(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10),
+                                static_cast<int>(std::strtol(argv[6], nullptr, 10)));
         if (argc >= 7 && std::strcmp(argv[1], "stack-elevate") == 0)
             return stackElevate(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10),
                                 static_cast<int>(std::strtol(argv[6], nullptr, 10)));
@@ -514,7 +561,7 @@ int main(int argc, char** argv) {
             return thomasMiddlecoff(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "ranks") == 0) return runRank(argc, argv);
         if (argc < 5) {
-            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-elevate <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-elevate <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-certify <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 2;
         }
         int a = 2;

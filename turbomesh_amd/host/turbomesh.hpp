@@ -739,6 +739,65 @@ inline Elevated3d elevate(const std::vector<discrete::Mesh*>& cuts, const Option
     detail::trim(r);
     return r;
 }
+// the certificate of the curved hexahedra of `block` (tm_hip.h, "high-order hexahedra: certificate"; kernel K17): status[(g*Ej + f)*Ei + e],
+// bounds (lo, hi) per element in the same order
+struct Certified3d {
+    std::size_t Ei = 0, Ej = 0, Eg = 0;
+    std::vector<uint8_t> status;
+    std::vector<double> bounds;
+    tm_ho3_certificate certificate{};
+};
+namespace detail {
+inline Certified3d certified(std::size_t ni, std::size_t nj, const Option& o, const highorder::Option& ho) {
+    if (ho.order < 1 || ho.order > TM_HO3_MAX_ORDER) throw Error(TM_E_ARG, "the order must be 1 .. TM_HO3_MAX_ORDER");
+    const std::size_t p = static_cast<std::size_t>(ho.order);
+    Certified3d r;
+    r.Ei = (ni - 1) / p, r.Ej = (nj - 1) / p, r.Eg = o.layers.empty() ? 0 : (o.layers.size() - 1) / p;
+    r.status.resize(r.Ei * r.Ej * r.Eg + 1), r.bounds.resize(2 * r.Ei * r.Ej * r.Eg + 2);
+    return r;
+}
+inline void trim(Certified3d& r) { r.status.resize(r.Ei * r.Ej * r.Eg), r.bounds.resize(2 * r.Ei * r.Ej * r.Eg); }
+}  // namespace detail
+// from the coordinates RESIDENT in one handle per cut (tm_stack_smoothers_certify)
+inline Certified3d certify(const std::vector<smoothing::smooth::Smoother*>& cuts, const Option& o, const highorder::Option& ho, std::size_t block, int max_depth = 2,
+                           const Surfaces* sf = nullptr, std::vector<uint64_t>* outside = nullptr) {
+    if (cuts.empty() || cuts.size() != o.span.size()) throw Error(TM_E_ARG, "one handle per span position");
+    std::vector<tm_smoother*> h;
+    for (const auto* c : cuts) h.push_back(c ? c->handle() : nullptr);
+    const tm_mesh_desc& d = cuts[0]->desc();
+    if (block >= d.nblocks) throw Error(TM_E_ARG, "block index past the mesh");
+    Certified3d r = detail::certified(d.blocks[block].ni, d.blocks[block].nj, o, ho);
+    const tm_stack_opt so = o.c_struct();
+    const tm_ho_opt hopt = ho.c_struct();
+    const auto cs = sf ? sf->c_struct() : nullptr;
+    if (outside) outside->assign(cuts.size(), 0);
+    check(tm_stack_smoothers_certify(h.data(), &so, cs ? &cs->s : nullptr, &hopt, max_depth, block, &r.certificate, r.status.data(), r.bounds.data(),
+                                     outside ? outside->data() : nullptr));
+    detail::trim(r);
+    return r;
+}
+// the same from host coordinates, uploaded per call (tm_stack_certify) or, host = true, evaluated on the CPU (tm_stack_certify_host)
+inline Certified3d certify(const std::vector<discrete::Mesh*>& cuts, const Option& o, const highorder::Option& ho, std::size_t block, int max_depth = 2,
+                           bool host = false, const Surfaces* sf = nullptr, std::vector<uint64_t>* outside = nullptr) {
+    if (cuts.empty() || cuts.size() != o.span.size()) throw Error(TM_E_ARG, "one mesh per span position");
+    std::vector<std::unique_ptr<smoothing::smooth::Desc>> descs;
+    std::vector<const tm_mesh_desc*> d;
+    for (auto* m : cuts) {
+        if (!m) throw Error(TM_E_ARG, "null mesh");
+        descs.push_back(std::make_unique<smoothing::smooth::Desc>(*m));
+        d.push_back(&descs.back()->desc);
+    }
+    if (block >= cuts[0]->blocks.size()) throw Error(TM_E_ARG, "block index past the mesh");
+    Certified3d r = detail::certified(cuts[0]->blocks[block].points.size[0], cuts[0]->blocks[block].points.size[1], o, ho);
+    const tm_stack_opt so = o.c_struct();
+    const tm_ho_opt hopt = ho.c_struct();
+    const auto cs = sf ? sf->c_struct() : nullptr;
+    if (outside) outside->assign(cuts.size(), 0);
+    check((host ? tm_stack_certify_host : tm_stack_certify)(d.data(), &so, cs ? &cs->s : nullptr, &hopt, max_depth, block, &r.certificate, r.status.data(),
+                                                            r.bounds.data(), outside ? outside->data() : nullptr));
+    detail::trim(r);
+    return r;
+}
 }  // namespace stack
 
 namespace discrete {

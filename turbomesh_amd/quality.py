@@ -285,6 +285,78 @@ def log_report_ho_certificate(logger, names, per_block, total, stage="certify"):
     logger.info("%s", total.line(f"{stage} total"))
 
 
+@dataclass
+class HoCertificate3d:
+    """tm_ho3_certificate as a record: the curved hexahedra of a stacked block judged by the Bernstein coefficients of their Jacobian
+    (include/tm_hip.h, "high-order hexahedra: certificate").  proven: o*J > 0 on the whole element; invalid: o*J <= 0 at a point;
+    undecided: neither shown within max_depth subdivisions.  hidden_invalid counts the invalid elements that the nodal record
+    (HoQuality3d) calls valid."""
+
+    elements: int
+    proven: int
+    invalid: int
+    undecided: int
+    hidden_invalid: int
+    orientation: int
+    order: int
+    max_depth: int             # -1: blocks differ (total)
+    has_unproven: bool
+    decided_at: Tuple[int, ...]   # proven and invalid elements by the subdivision level that decided them
+    min_scaled_bound: float    # min over proven elements of the certified lower bound of min J / max J
+    worst_block: int
+    worst_e: int
+    worst_f: int
+    worst_g: int
+    first_unproven_block: int
+    first_unproven_e: int
+    first_unproven_f: int
+    first_unproven_g: int
+
+    @classmethod
+    def from_struct(cls, c: "_capi.tm_ho3_certificate") -> "HoCertificate3d":
+        return cls(int(c.elements), int(c.proven), int(c.invalid), int(c.undecided), int(c.hidden_invalid), int(c.orientation), int(c.order),
+                   int(c.max_depth), bool(c.has_unproven), tuple(int(d) for d in c.decided_at), float(c.min_scaled_bound), int(c.worst_block),
+                   int(c.worst_e), int(c.worst_f), int(c.worst_g), int(c.first_unproven_block), int(c.first_unproven_e),
+                   int(c.first_unproven_f), int(c.first_unproven_g))
+
+    def to_struct(self) -> "_capi.tm_ho3_certificate":
+        return _capi.tm_ho3_certificate(self.elements, self.proven, self.invalid, self.undecided, self.hidden_invalid, self.orientation, self.order,
+                                        self.max_depth, int(self.has_unproven), (C.c_uint64 * 4)(*self.decided_at), self.min_scaled_bound,
+                                        self.worst_block, self.worst_e, self.worst_f, self.worst_g, self.first_unproven_block,
+                                        self.first_unproven_e, self.first_unproven_f, self.first_unproven_g)
+
+    @property
+    def ok(self) -> bool:
+        return self.proven == self.elements
+
+    def line(self, name: str) -> str:
+        """One log line: name, order, depth, the three counts, the hidden folds, the levels and the certified bound."""
+        s = (f"{name}: order {self.order} depth {self.max_depth} elements {self.elements} proven {self.proven} invalid {self.invalid} "
+             f"undecided {self.undecided} hidden invalid {self.hidden_invalid} decided at {'/'.join(str(d) for d in self.decided_at)} "
+             f"min scaled bound {self.min_scaled_bound:.4f} at (block {self.worst_block}, e {self.worst_e}, f {self.worst_f}, g {self.worst_g})")
+        if self.has_unproven:
+            s += (f" first unproven (block {self.first_unproven_block}, e {self.first_unproven_e}, f {self.first_unproven_f}, "
+                  f"g {self.first_unproven_g})")
+        return s
+
+
+def total_ho3_certificate(per_block: List[HoCertificate3d]) -> HoCertificate3d:
+    """tm_ho3_certificate_total of the blocks' records (host only)."""
+    arr = (_capi.tm_ho3_certificate * max(1, len(per_block)))()
+    for k, c in enumerate(per_block):
+        arr[k] = c.to_struct()
+    total = _capi.tm_ho3_certificate()
+    _capi.check(_capi.lib().tm_ho3_certificate_total(arr, len(per_block), C.byref(total)))
+    return HoCertificate3d.from_struct(total)
+
+
+def log_report_ho3_certificate(logger, names, per_block, total, stage="certify3d"):
+    """One line per block and a total, on `logger` at INFO; every line starts with `stage`."""
+    for name, c in zip(names, per_block):
+        logger.info("%s", c.line(f"{stage} {name}"))
+    logger.info("%s", total.line(f"{stage} total"))
+
+
 def records(per_block, total) -> Tuple[List[Quality], Quality]:
     return [Quality.from_struct(q) for q in per_block], Quality.from_struct(total)
 

@@ -20,7 +20,12 @@ agglomerated in span as the nodes are in-plane; the layer count minus one must b
     X, Y, Z, q, sj = st.elevate(cuts, highorder.Elevation(2), b)          # planes, quality.HoQuality3d, scaled Jacobian per element
     st.mesh3d_ho(cuts, highorder.Elevation(2, "equidistant")).write("blade.vtk")
 
-Evaluated on the MI355X (kernels K11, K16); `host=True` evaluates the same definition on the CPU (lists of Mesh only)."""
+Those hexahedra are judged at their nodes; Stack.certify bounds their Jacobian on the whole element ("high-order hexahedra: certificate" in
+the header, kernel K17):
+
+    cert, status, bounds = st.certify(cuts, highorder.Elevation(2), b, max_depth=2)   # quality.HoCertificate3d, (Eg, Ej, Ei) status, (lo, hi)
+
+Evaluated on the MI355X (kernels K11, K16, K17); `host=True` evaluates the same definition on the CPU (lists of Mesh only)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -345,6 +350,43 @@ class Stack:
             _capi.check((L.tm_stack_elevate_host if host else L.tm_stack_elevate)(arr, *args))
         res = (out[0], out[1], out[2], _quality.HoQuality3d.from_struct(q), sj)
         return res + ((outside[:self.ncuts].copy(),) if return_outside else ())
+
+    def certify(self, cuts, elevation, b=None, host=False, max_depth=2):
+        """The certificate of the curved hexahedra of block b ("high-order hexahedra: certificate" in the header, kernel K17) --
+        (quality.HoCertificate3d, status, bounds): status an (Eg, Ej, Ei) uint8 array of TM_HO_PROVEN / TM_HO_INVALID / TM_HO_UNDECIDED,
+        bounds an (Eg, Ej, Ei, 2) array of (lo, hi) with lo <= o*J <= hi on the whole element.  b=None: every block -- (total,
+        [record per block], [status], [bounds]).  cuts as in block(): Mesh (tm_stack_certify; host=True: tm_stack_certify_host, no GPU)
+        or Smoother (tm_stack_smoothers_certify, the resident coordinates)."""
+        from . import quality as _quality
+
+        self._check_count(cuts)
+        resident = all(hasattr(c, "_h") for c in cuts)
+        if resident and host:
+            raise ValueError("host=True evaluates host coordinates: pass the meshes, not the handles")
+        meshes = [c._mesh for c in cuts] if resident else cuts
+        if b is None:
+            self.check_elevation(meshes[0], elevation)
+            out = [self.certify(cuts, elevation, k, host=host, max_depth=max_depth) for k in range(len(meshes[0].blocks))]
+            per_block = [o[0] for o in out]
+            return _quality.total_ho3_certificate(per_block), per_block, [o[1] for o in out], [o[2] for o in out]
+        ni, nj = meshes[0].blocks[b].points.size
+        p = max(1, elevation.order)
+        E = (max(0, (self.nlayers - 1) // p), max(0, (nj - 1) // p), max(0, (ni - 1) // p))
+        status = np.empty(E, dtype=np.uint8)
+        bounds = np.empty(E + (2,), dtype=np.float64)
+        c = _capi.tm_ho3_certificate()
+        sf = self.surfaces
+        args = (C.byref(self._opt), None if sf is None else sf.ref(), C.byref(elevation._opt), int(max_depth), b, C.byref(c),
+                status.ctypes.data_as(C.POINTER(C.c_uint8)), _capi.f64ptr(bounds), None)
+        L = _capi.lib()
+        if resident:
+            handles = (C.c_void_p * len(cuts))(*[h._h for h in cuts])
+            _capi.check(L.tm_stack_smoothers_certify(handles, *args))
+        else:
+            descs = [_capi.MeshDesc(m) for m in meshes]
+            arr = (C.POINTER(_capi.tm_mesh_desc) * len(descs))(*[C.pointer(d.desc) for d in descs])
+            _capi.check((L.tm_stack_certify_host if host else L.tm_stack_certify)(arr, *args))
+        return _quality.HoCertificate3d.from_struct(c), status, bounds
 
     def mesh3d_ho(self, cuts, elevation, host=False):
         """Every block of the cuts as curved hexahedra: a highorder.HighOrderMesh3d with the per-block and total quality.HoQuality3d (and,
