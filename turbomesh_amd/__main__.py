@@ -34,7 +34,11 @@ Bernstein coefficients of their Jacobian, with up to DEPTH (default 2, at most 3
 "high-order hexahedra: certificate"), logged per block and for the mesh; --fail-on-invalid-elements then also counts the hexahedra folded
 between their nodes, and --fail-on-unproven-elements exits non-zero when any is not proven.  --certify itself judges 2-D elements and does
 not go with --stack.
-Without --order nothing changes; without --certify neither does --order."""
+--weld with --output NAME.vtk (with or without --order, with or without --stack): the blocks are welded into ONE conforming unstructured mesh
+(weld.py, include/tm_hip.h "welded unstructured mesh") -- the interface nodes merged, quadrilaterals / hexahedra (Lagrange cells with --order)
+over one node numbering -- and NAME.vtk holds that mesh; one line per mesh on the `weld` logger: nodes in -> out, classes by size, periodic
+pairs (periodic sides are not glued), max_gap.  Any other output format with --weld is refused.
+Without --order nothing changes; without --certify neither does --order; without --weld every output is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -129,6 +133,12 @@ def _run(ap, args, config, keep=None, tag="", stack=None):
                 total, per_block, _, _ = elevation.certify(sm, max_depth=args.certify)   # from the resident coordinates
                 quality.log_report_ho_certificate(qlog, hom.names, per_block, total, tag + "certify")
                 stats["certificate"] = {"per_block": per_block, "total": total}
+        if getattr(args, "weld", False) and stack is None:   # while the handle lives: the linear mesh comes from the resident coordinates
+            from . import weld
+
+            welded = stats["highorder"].weld(mesh) if elevation is not None else sm.weld()
+            weld.log_report(logging.getLogger("weld"), welded.info, tag + os.path.basename(config))
+            stats["welded"] = welded
     return inp, mesh, sm, stats, after
 
 
@@ -154,7 +164,7 @@ def _main_stack(ap, args):
     coordinates resident in the handles (tm_stack_smoothers)."""
     from . import output, stack
 
-    vtk = args.order is not None and args.output.lower().endswith(".vtk")
+    vtk = (args.order is not None or args.weld) and args.output.lower().endswith(".vtk")
     if not vtk:
         output._format_of(args.output)
     surfaces = None
@@ -206,9 +216,16 @@ def _main_stack(ap, args):
                         logging.getLogger("stack").warning("block %d (%s), cut %d: %d nodes lie outside the meridional table %s and are extrapolated", b, name, c,
                                                            int(n), args.meridional[c])
         q3 = st.quality(handles) if (args.stack_quality or args.fail_on_inverted_3d) else None   # from the resident cuts: no 3-D block is formed
-    m3.write(args.output)
+    if args.weld:   # sizes and connections are those of any cut
+        from . import weld
+
+        welded = weld.Weld(mesh).mesh(m3, args.order or 1, args.nodes or "equidistant")
+        weld.log_report(logging.getLogger("weld"), welded.info, "stacked mesh")
+        welded.write(args.output)
+    else:
+        m3.write(args.output)
     logging.getLogger("output").info("wrote %s (%d blocks, %d cuts, %d layers, %d nodes)", args.output, len(m3.blocks), len(files), st.nlayers,
-                                     sum(x.size for x, _, _ in m3.blocks))
+                                     len(welded.points) if args.weld else sum(x.size for x, _, _ in m3.blocks))
     if hom is not None:
         logging.getLogger("output").info("%d hexahedra of order %d, %s nodes", hom.total.elements, hom.order, hom.distribution)
     if q3 is not None and args.stack_quality:
@@ -303,7 +320,12 @@ def main(argv=None):
     ap.add_argument("--fail-on-inverted-3d", action="store_true",
                     help="with --stack: exit non-zero, after the file is written, when the stacked mesh has inverted or degenerate hexahedra "
                          "(implies the 3-D quality evaluation)")
+    ap.add_argument("--weld", action="store_true",
+                    help="with --output NAME.vtk: weld the blocks into one conforming unstructured mesh (interface nodes merged; quadrilaterals, "
+                         "hexahedra with --stack, Lagrange cells with --order) and write that; logs node counts, classes and max_gap on the `weld` logger")
     args = ap.parse_args(argv)
+    if args.weld and not (args.output and args.output.lower().endswith(".vtk")):
+        ap.error(f"--weld writes one welded unstructured mesh as legacy VTK: --output NAME.vtk, not {args.output!r}")
     if args.stack is None and (args.span or args.layers is not None):
         ap.error("--span and --layers go with --stack")
     if args.stack is None and (args.meridional or args.reference_radius or args.meridional_interpolation):
@@ -376,7 +398,11 @@ def main(argv=None):
     inp, mesh, _, stats, after = _run(ap, args, args.config)
     out = args.output or inp.output
     hom = stats.get("highorder")
-    if out and hom is not None:
+    if args.weld:
+        welded = stats["welded"]
+        welded.write(out)
+        logging.getLogger("output").info("wrote %s (%d welded nodes, %d cells of type %d)", out, len(welded.points), len(welded.cells), welded.cell_type)
+    elif out and hom is not None:
         hom.write(out)
         logging.getLogger("output").info("wrote %s (%d blocks, %d elements of order %d, %s nodes)", out, len(hom.blocks), hom.total.elements, hom.order, hom.distribution)
     elif out:

@@ -188,6 +188,15 @@ class tm_ho3_certificate(C.Structure):   # 160 bytes
                 ("first_unproven_f", C.c_uint64), ("first_unproven_g", C.c_uint64)]
 
 
+class tm_weld_info(C.Structure):   # 88 bytes
+    _fields_ = [("nodes_in", C.c_uint64), ("nodes_out", C.c_uint64), ("classes_2", C.c_uint64), ("classes_3", C.c_uint64), ("classes_4", C.c_uint64),
+                ("classes_5_up", C.c_uint64), ("max_class", C.c_uint64), ("periodic_pairs", C.c_uint64), ("gap_node", C.c_uint64),
+                ("max_gap", C.c_double), ("periodic_gap", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/tm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "tm_last_error", "tm_abi_version", "tm_set_log", "tm_csr_solve", "tm_tfi_block", "tm_tfi_linear2d", "tm_smooth_mesh", "tm_smoother_create",
@@ -209,6 +218,8 @@ EXPORTS = [
     "tm_ho3_check", "tm_ho3_planes_host", "tm_stack_elevate", "tm_stack_elevate_host", "tm_stack_smoothers_elevate", "tm_ho3_quality_total",
     "tm_ho3_certify_tables", "tm_ho3_jacobian_bezier_host", "tm_ho3_certify_planes_host", "tm_stack_certify", "tm_stack_certify_host",
     "tm_stack_smoothers_certify", "tm_ho3_certificate_total",
+    "tm_weld_map", "tm_weld_map_host", "tm_weld_points", "tm_weld_points_host", "tm_smoother_weld", "tm_weld_cells", "tm_weld_cells_host",
+    "tm_weld_periodic_pairs",
     "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
 ]
 
@@ -345,6 +356,15 @@ def lib():
         L.tm_stack_certify_host.argtypes = L.tm_stack_certify.argtypes
         L.tm_stack_smoothers_certify.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt)] + _h3_tail
         L.tm_ho3_certificate_total.argtypes = [_c3p, C.c_uint64, _c3p]
+        _wip, _dpp = C.POINTER(tm_weld_info), C.POINTER(_dp)
+        L.tm_weld_map.argtypes = [C.POINTER(tm_mesh_desc), _i32p, _wip]
+        L.tm_weld_map_host.argtypes = L.tm_weld_map.argtypes
+        L.tm_weld_points.argtypes = [C.POINTER(tm_mesh_desc), _i32p, C.c_int32, C.c_uint64, _dpp, _dpp, _wip]
+        L.tm_weld_points_host.argtypes = L.tm_weld_points.argtypes
+        L.tm_smoother_weld.argtypes = [C.c_void_p, _i32p, _dp, _dp, _wip]
+        L.tm_weld_cells.argtypes = [C.POINTER(tm_mesh_desc), _i32p, C.c_uint64, C.c_int32, C.c_uint64, _i32p]
+        L.tm_weld_cells_host.argtypes = L.tm_weld_cells.argtypes
+        L.tm_weld_periodic_pairs.argtypes = [C.POINTER(tm_mesh_desc), _i32p, _i32p]
         L.tm_rccl_unique_id.argtypes =[C.c_char_p, C.c_void_p]
         L.tm_rccl_comm_create.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.tm_rccl_comm_destroy.argtypes = [C.c_void_p]

@@ -14,6 +14,7 @@
 #include "tm_quality_dev.hpp"
 #include "tm_highorder_dev.hpp"
 #include "tm_highorder_cert_dev.hpp"
+#include "tm_weld_dev.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -134,6 +135,7 @@ Smoother::~Smoother() {
     delete qdev;
     delete hodev;
     delete hcdev;
+    delete welddev;
     delete ref;
     ref = nullptr;
     csr_free();

@@ -48,6 +48,7 @@ class DeviceArena {
 
 struct QualityDev;
 struct HoDev;
+struct WeldDev;
 struct HcDev;
 
 struct Smoother {
@@ -212,6 +213,9 @@ struct Smoother {
     // certificate of an owned block's elements from the resident coordinates (tm_highorder_cert.hip): K13's report through hodev, then K14
     HcDev* hcdev = nullptr;
     void certify_host(const tm_ho_opt* opt, int max_depth, int64_t block, tm_ho_certificate* cert, uint8_t* status, double* bounds);
+    // welded map and points of the resident coordinates (tm_weld.hip, K18): reads X only; buffers as for the quality report
+    WeldDev* welddev = nullptr;
+    void weld_host(int32_t* map, double* x, double* y, tm_weld_info* info);
 
     // building blocks
     void exchange(double2* vec, hipStream_t on = nullptr);   // start (and, without a split hook, finish) the halo exchange of `vec`; on = the handle's stream unless given

@@ -140,7 +140,7 @@ class HighOrderMesh3d:
 
     def write(self, filename):
         """`*.vtk`: a legacy ASCII VTK unstructured grid with one VTK_LAGRANGE_HEXAHEDRON (type 72) per element -- points per block in
-        PLOT3D order, blocks concatenated (interface nodes are not merged), coordinates as %.17g; VTK's Lagrange cells assume equidistant
+        PLOT3D order, blocks concatenated (interface nodes are not merged: weld() does that), coordinates as %.17g; VTK's Lagrange cells assume equidistant
         nodes, so any other distribution raises ValueError.  Any other name: multi-block 3-D PLOT3D of the elevated nodes."""
         from . import output
 
@@ -151,6 +151,13 @@ class HighOrderMesh3d:
             return
         output._format_of(filename)
         output.write_plot3d_3d(filename, self.sizes(), self.blocks)
+
+    def weld(self, mesh, host=False):
+        """weld.UnstructuredMesh of these blocks: the interface nodes of `mesh` (the cut the blocks were stacked from: sizes and
+        connections) merged, one Lagrange hexahedron of `order` per element (include/tm_hip.h, "welded unstructured mesh")."""
+        from . import weld
+
+        return weld.Weld(mesh, host=host).mesh(self, self.order, self.distribution)
 
 
 @dataclass
@@ -175,7 +182,7 @@ class HighOrderMesh:
 
     def write(self, filename):
         """`*.vtk`: a legacy ASCII VTK unstructured grid with one VTK_LAGRANGE_QUADRILATERAL (type 70) per element -- points per block
-        in plane order, blocks concatenated (interface nodes are not merged), coordinates as %.17g; VTK's Lagrange cells assume
+        in plane order, blocks concatenated (interface nodes are not merged: weld() does that), coordinates as %.17g; VTK's Lagrange cells assume
         equidistant nodes, so any other distribution raises ValueError.  Any other name: multi-block 2-D PLOT3D of the elevated nodes
         (output.write_plot3d)."""
         from . import output
@@ -187,6 +194,13 @@ class HighOrderMesh:
             return
         output._format_of(filename)
         output.write_plot3d(filename, self.sizes(), [(x.reshape(-1), y.reshape(-1)) for x, y in self.blocks])
+
+    def weld(self, mesh, host=False):
+        """weld.UnstructuredMesh of these blocks: the interface nodes of `mesh` (sizes and connections) merged, one Lagrange
+        quadrilateral of `order` per element (include/tm_hip.h, "welded unstructured mesh")."""
+        from . import weld
+
+        return weld.Weld(mesh, host=host).mesh(self, self.order, self.distribution)
 
 
 class Elevation:

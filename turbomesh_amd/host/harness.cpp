@@ -11,6 +11,7 @@
 //   tm_harness stack-certify <ni> <nj> <ncuts> <nlayers> <order>   the same cuts: the certificate of those hexahedra (kernel K17; exit 0: counts add up, equal to the CPU's)
 //   tm_harness stack-elevate <ni> <nj> <ncuts> <nlayers> <order>   the same cuts: curved hexahedra of that order from the stacked block (kernel K16; exit 0: corners unchanged, equal to the CPU's)
 //   tm_harness stack-quality <ni> <nj> <ncuts> <nlayers>   the same cuts: the 3-D quality record of the stacked block (kernel K12; exit 0: equal to the CPU's)
+//   tm_harness weld <ni> <nj> <nblocks>   the strip welded into one unstructured mesh from the resident coordinates (kernel K18; exit 0: equal to the CPU's)
 //   tm_harness csr                                     the linear-solver slot (seam 2) on the reference's 5 x 5 known answer
 //   tm_harness ranks <world> <rank> <idfile> <nblocks> <ni> <nj> <iterations> [relax|bicgstab] [dump.bin]
 //        one process per GPU (start each with HIP_VISIBLE_DEVICES=<its GPU>): the strip's blocks are dealt to the ranks in order, the
@@ -538,8 +539,33 @@ static int certifyBlock(std::size_t ni, std::size_t nj, int order) {
     return adds && same ? 0 : 1;
 }
 
+// tm_harness weld <ni> <nj> <nblocks>: the config-4 strip, two Picard iterations; map and welded points from the coordinates resident in
+// the handle (weld::points -> tm_smoother_weld), quadrilaterals from the map (weld::cells), compared with the CPU's map and cells; the
+// strip welds to nblocks * ni * nj - (nblocks - 1) * nj nodes.
+static int weldStrip(std::size_t ni, std::size_t nj, std::size_t nb) {
+    discrete::Mesh mesh = buildStrip(nb, ni, nj);
+    smoothing::smooth::Smoother sm(mesh, smoothing::solver::Option{}, smoothing::wall_control_function::Algorithm::laplace());
+    sm.iterate(2);
+    weld::Map dev;
+    const weld::Points pts = weld::points(sm, &dev);
+    const std::vector<int32_t> cells = weld::cells(mesh, dev);
+    const weld::Map host = weld::map(mesh, true);
+    const tm_weld_info& w = pts.info;
+    std::printf("weld: %llu -> %llu nodes, classes of 2 / 3 / 4 / 5+: %llu / %llu / %llu / %llu, max_gap %.3e at node %llu, %zu quadrilaterals\n",
+                static_cast<unsigned long long>(w.nodes_in), static_cast<unsigned long long>(w.nodes_out), static_cast<unsigned long long>(w.classes_2),
+                static_cast<unsigned long long>(w.classes_3), static_cast<unsigned long long>(w.classes_4), static_cast<unsigned long long>(w.classes_5_up), w.max_gap,
+                static_cast<unsigned long long>(w.gap_node), cells.size() / 4);
+    const bool count = w.nodes_out == nb * ni * nj - (nb - 1) * nj && pts.x.size() == w.nodes_out && cells.size() == 4 * nb * (ni - 1) * (nj - 1);
+    std::printf("weld: node and cell counts: %s\n", count ? "yes" : "no");
+    const bool same = dev.map == host.map && host.info.nodes_out == w.nodes_out && host.info.classes_2 == w.classes_2 && cells == weld::cells(mesh, host, 1, 0, true);
+    std::printf("weld: device equals host: %s\n", same ? "yes" : "no");
+    return count && same ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     try {
+        if (argc >= 5 && std::strcmp(argv[1], "weld") == 0)
+            return weldStrip(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 5 && std::strcmp(argv[1], "certify") == 0)
             return certifyBlock(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), static_cast<int>(std::strtol(argv[4], nullptr, 10)));
         if (argc >= 5 && std::strcmp(argv[1], "elevate") == 0)
@@ -561,7 +587,7 @@ int main(int argc, char** argv) {
             return thomasMiddlecoff(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "ranks") == 0) return runRank(argc, argv);
         if (argc < 5) {
-            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-elevate <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-certify <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-elevate <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-certify <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n       %s weld <ni> <nj> <nblocks>\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 2;
         }
         int a = 2;

@@ -800,6 +800,53 @@ inline Certified3d certify(const std::vector<discrete::Mesh*>& cuts, const Optio
 }
 }  // namespace stack
 
+// welded unstructured mesh (tm_hip.h, kernel K18): one node numbering across the connections of a mesh, welded points and cells
+namespace weld {
+struct Map {
+    std::vector<int32_t> map;     // welded id per node, plane order (block after block, j*ni + i)
+    tm_weld_info info{};
+};
+struct Points {                   // nodes_out values per component
+    std::vector<double> x, y;
+    tm_weld_info info{};
+};
+inline Map map(discrete::Mesh& mesh, bool host = false) {
+    smoothing::smooth::Desc d(mesh);
+    Map r;
+    std::size_t n = 0;
+    for (const auto& b : mesh.blocks) n += b.points.size[0] * b.points.size[1];
+    r.map.resize(n + 1);
+    core::check((host ? tm_weld_map_host : tm_weld_map)(&d.desc, r.map.data(), &r.info));
+    r.map.resize(n);
+    return r;
+}
+// from the coordinates RESIDENT in the handle (tm_smoother_weld): the interleaved blocks are read in place
+inline Points points(const smoothing::smooth::Smoother& s, Map* map_out = nullptr) {
+    const tm_mesh_desc& d = s.desc();
+    std::size_t n = 0;
+    for (uint64_t b = 0; b < d.nblocks; ++b) n += d.blocks[b].ni * d.blocks[b].nj;
+    Points r;
+    r.x.resize(n + 1), r.y.resize(n + 1);
+    if (map_out) map_out->map.resize(n + 1);
+    core::check(tm_smoother_weld(s.handle(), map_out ? map_out->map.data() : nullptr, r.x.data(), r.y.data(), &r.info));
+    r.x.resize(r.info.nodes_out), r.y.resize(r.info.nodes_out);
+    if (map_out) map_out->map.resize(n), map_out->info = r.info;
+    return r;
+}
+// quadrilaterals of `order` (nk <= 1) or hexahedra across nk layers: (order+1)^2 or (order+1)^3 ids per element, VTK's Lagrange order
+inline std::vector<int32_t> cells(discrete::Mesh& mesh, const Map& m, int order = 1, std::size_t nk = 0, bool host = false) {
+    if (order < 1 || order > TM_HO_MAX_ORDER) throw Error(TM_E_ARG, "the order must be 1 .. TM_HO_MAX_ORDER");
+    smoothing::smooth::Desc d(mesh);
+    const std::size_t p = static_cast<std::size_t>(order), Eg = nk >= 2 ? (nk - 1) / p : 1, npe = nk >= 2 ? (p + 1) * (p + 1) * (p + 1) : (p + 1) * (p + 1);
+    std::size_t n = 0;
+    for (const auto& b : mesh.blocks) n += ((b.points.size[0] - 1) / p) * ((b.points.size[1] - 1) / p) * Eg;
+    std::vector<int32_t> c(n * npe + 1);
+    core::check((host ? tm_weld_cells_host : tm_weld_cells)(&d.desc, m.map.data(), m.info.nodes_out, order, nk, c.data()));
+    c.resize(n * npe);
+    return c;
+}
+}  // namespace weld
+
 namespace discrete {
 inline Quality Mesh::quality(bool host) {
     smoothing::smooth::Desc d(*this);

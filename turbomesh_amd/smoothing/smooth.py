@@ -152,6 +152,14 @@ class Smoother:
         handle (tm_smoother_certify); see Elevation.certify."""
         return elevation.certify(self, block, max_depth=max_depth)
 
+    def weld(self, order=1):
+        """weld.UnstructuredMesh of the coordinates resident in the handle: the blocks welded into one conforming mesh of quadrilaterals
+        (tm_smoother_weld: map and points formed on the device from the resident coordinates; order > 1: the fine nodes as equidistant
+        Lagrange elements, the sizes checked by tm_ho_check)."""
+        from .. import weld
+
+        return weld.Weld(self._mesh).mesh(self, order)
+
     def write_quality(self, filename):
         """The per-cell planes of every block as a PLOT3D function file (one variable, sizes (ni-1, nj-1))."""
         from .. import output

@@ -1,0 +1,205 @@
+"""Blocks welded into one conforming unstructured mesh (include/tm_hip.h, "welded unstructured mesh"; kernel K18): one node numbering
+across the connections of a mesh, and from it welded points and cells -- what an unstructured or high-order solver reads as ONE mesh.
+
+The numbering is a function of sizes and connections alone, and the node grid of a block's high-order elements is the block's own
+ni x nj index space, so one Weld serves every product of the library:
+
+    w = Weld(mesh)                                 # .map (int32 per node, plane order), .nodes, .info
+    w.points(smoother)                             # (nodes, 2): the coordinates resident in the handle, read in place on the device
+    w.points(elevation.mesh(smoother))             # the elevated nodes of a highorder.HighOrderMesh
+    w.points(stack.mesh3d(cuts))                   # (nk * nodes, 3), layer-major: stack.Mesh3d, highorder.HighOrderMesh3d or [(X, Y, Z)]
+    w.cells(order=2)                               # (elements, 9) ids in the order of VTK's Lagrange quadrilateral
+    w.cells(order=1, layers=nk)                    # hexahedra across nk layers
+    smoother.weld().write("blade.vtk")             # UnstructuredMesh: legacy ASCII VTK, %.17g
+    w.periodic_pairs()                             # [(pairs (n, 2), (tx, ty))] per periodic connection: periodic sides are not glued
+
+A welded node has the coordinates of its owner (the class member with the smallest index), bit for bit; `info.max_gap` says by how much the
+other members differ from it -- the rounding "the two sides agree to", or the size of the mesh when a connection is wrong.
+Evaluated on the MI355X; `host=True` evaluates the same definition on the CPU, with the same results.
+Not served: boundary patches (wall / inlet / outlet edge lists), .vtu / CGNS / Gmsh / HOPR writers, gluing periodic sides, blocks spread
+over ranks, averaging the two sides of an interface."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _capi
+
+VTK_QUAD, VTK_HEXAHEDRON = 9, 12
+VTK_LAGRANGE_QUADRILATERAL, VTK_LAGRANGE_HEXAHEDRON = 70, 72
+_I32P = C.POINTER(C.c_int32)
+
+
+def _i32ptr(a):
+    return a.ctypes.data_as(_I32P)
+
+
+@dataclass
+class WeldInfo:
+    """tm_weld_info: node counts, classes by size, the largest class, periodic pairs and the gaps (0 until points() has run)."""
+
+    nodes_in: int = 0
+    nodes_out: int = 0
+    classes_2: int = 0
+    classes_3: int = 0
+    classes_4: int = 0
+    classes_5_up: int = 0
+    max_class: int = 1
+    periodic_pairs: int = 0
+    gap_node: int = 0
+    max_gap: float = 0.0
+    periodic_gap: float = 0.0
+
+    @classmethod
+    def from_struct(cls, s):
+        return cls(**s.as_dict())
+
+
+def log_report(log, info, name="mesh"):
+    """One line on `log` (the `weld` logger of the program): nodes in -> out, classes by size, periodic pairs, max_gap."""
+    log.info("%s: %d -> %d nodes, classes of 2 / 3 / 4 / 5+: %d / %d / %d / %d (largest %d), %d periodic pairs (gap %.3e), max_gap %.3e at node %d", name,
+             info.nodes_in, info.nodes_out, info.classes_2, info.classes_3, info.classes_4, info.classes_5_up, info.max_class, info.periodic_pairs,
+             info.periodic_gap, info.max_gap, info.gap_node)
+
+
+class UnstructuredMesh:
+    """Welded points (n, 2) or (n, 3), cells (elements, nodes per element) and the VTK cell type: VTK_QUAD 9 / VTK_HEXAHEDRON 12 at order 1,
+    VTK_LAGRANGE_QUADRILATERAL 70 / VTK_LAGRANGE_HEXAHEDRON 72 above."""
+
+    def __init__(self, points, cells, cell_type, order, info=None, distribution="equidistant"):
+        self.points = np.ascontiguousarray(points, dtype=np.float64)
+        self.cells = np.ascontiguousarray(cells)
+        self.cell_type = int(cell_type)
+        self.order = int(order)
+        self.info = info
+        self.distribution = distribution
+        if self.points.ndim != 2 or self.points.shape[1] not in (2, 3) or self.cells.ndim != 2:
+            raise ValueError("points: (n, 2) or (n, 3); cells: (elements, nodes per element)")
+
+    def write(self, filename):
+        """`*.vtk`: legacy ASCII VTK unstructured grid, coordinates as %.17g (z = 0 for a plane mesh): output.read_vtk_lagrange reads it
+        back bit for bit.  VTK's Lagrange cells assume equidistant nodes, so any other distribution raises ValueError."""
+        if not str(filename).lower().endswith(".vtk"):
+            raise ValueError(f"a welded mesh is written as legacy VTK (*.vtk), not {filename!r}")
+        if self.order > 1 and self.distribution != "equidistant":
+            raise ValueError(f"VTK Lagrange cells assume equidistant nodes, not a {self.distribution} elevation")
+        kind = "quadrilaterals" if self.cell_type in (VTK_QUAD, VTK_LAGRANGE_QUADRILATERAL) else "hexahedra"
+        with open(filename, "w") as fh:
+            fh.write(f"# vtk DataFile Version 4.2\nwelded {kind} of order {self.order}\nASCII\nDATASET UNSTRUCTURED_GRID\n")
+            fh.write(f"POINTS {len(self.points)} double\n")
+            if self.points.shape[1] == 2:
+                fh.write("".join("%.17g %.17g 0\n" % (x, y) for x, y in self.points.tolist()))
+            else:
+                fh.write("".join("%.17g %.17g %.17g\n" % (x, y, z) for x, y, z in self.points.tolist()))
+            per = self.cells.shape[1]
+            fh.write(f"CELLS {len(self.cells)} {len(self.cells) * (per + 1)}\n")
+            head = str(per)
+            fh.write("".join(head + " " + " ".join(map(str, row)) + "\n" for row in self.cells.tolist()))
+            fh.write(f"CELL_TYPES {len(self.cells)}\n")
+            fh.write(f"{self.cell_type}\n" * len(self.cells))
+
+
+def cell_type_of(order, hex):
+    if order == 1:
+        return VTK_HEXAHEDRON if hex else VTK_QUAD
+    return VTK_LAGRANGE_HEXAHEDRON if hex else VTK_LAGRANGE_QUADRILATERAL
+
+
+class Weld:
+    """The welded numbering of a discrete.Mesh (tm_weld_map; host=True: tm_weld_map_host, no GPU)."""
+
+    def __init__(self, mesh, host=False):
+        self._mesh = mesh
+        self.host = bool(host)
+        self._md = _capi.MeshDesc(mesh, with_coordinates=False)
+        self.sizes = [tuple(int(v) for v in b.points.size) for b in mesh.blocks]
+        self.map = np.empty(sum(ni * nj for ni, nj in self.sizes), dtype=np.int32)
+        rec = _capi.tm_weld_info()
+        L = _capi.lib()
+        _capi.check((L.tm_weld_map_host if self.host else L.tm_weld_map)(self._md.ref(), _i32ptr(self.map), C.byref(rec)))
+        self._rec = rec
+        self.info = WeldInfo.from_struct(rec)
+        self.nodes = self.info.nodes_out
+
+    def periodic_pairs(self):
+        """Per periodic connection (pairs, translation): pairs an (n, 2) int32 array of welded ids (side of ranges[0], side of ranges[1]),
+        translation the connection's (tx, ty), which maps the first onto the second (tm_weld_periodic_pairs: host only)."""
+        flat = np.empty((max(1, self.info.periodic_pairs), 2), dtype=np.int32)
+        _capi.check(_capi.lib().tm_weld_periodic_pairs(self._md.ref(), _i32ptr(self.map), _i32ptr(flat)))
+        out, at = [], 0
+        for c in self._mesh.connections:
+            if c.periodicity is None:
+                continue
+            n = abs(int(c.ranges[0].end) - int(c.ranges[0].start)) + 1
+            out.append((flat[at:at + n].copy(), (float(c.periodicity[0]), float(c.periodicity[1]))))
+            at += n
+        return out
+
+    def _planes_of(self, src):
+        """-> (ncomp, nk, [per component a list of per-block arrays of nk * nj * ni doubles, i fastest])"""
+        blocks = getattr(src, "blocks", src)
+        if len(blocks) != len(self.sizes):
+            raise ValueError(f"{len(blocks)} blocks for a weld of {len(self.sizes)}")
+        if hasattr(blocks[0], "points"):   # discrete.Mesh: (ni, nj, 2) interleaved
+            comps = [[np.ascontiguousarray(b.points.data[:, :, c].T) for b in blocks] for c in range(2)]
+            nk = 1
+        else:
+            ncomp = len(blocks[0])
+            comps = [[np.ascontiguousarray(b[c], dtype=np.float64) for b in blocks] for c in range(ncomp)]
+            nk = comps[0][0].shape[0] if comps[0][0].ndim == 3 else 1
+        for plane in comps:
+            for a, (ni, nj) in zip(plane, self.sizes):
+                if a.shape != ((nk, nj, ni) if a.ndim == 3 else (nj, ni)):
+                    raise ValueError(f"a block of shape {a.shape} where {(nj, ni)} nodes{' per layer' if a.ndim == 3 else ''} are welded")
+        return len(comps), nk, comps
+
+    def points(self, src):
+        """Welded points of `src`: a discrete.Mesh, a smooth.Smoother (the coordinates resident in the handle, tm_smoother_weld), a
+        highorder.HighOrderMesh -> (nodes, 2); a stack.Mesh3d, a highorder.HighOrderMesh3d or a list of (X, Y, Z) blocks as (nk, nj, ni)
+        arrays -> (nk * nodes, 3), layer-major.  Updates info.max_gap, info.gap_node and info.periodic_gap."""
+        L = _capi.lib()
+        if hasattr(src, "_h"):
+            if self.host:
+                raise ValueError("host=True evaluates host coordinates: pass the mesh, not the handle")
+            if [tuple(int(v) for v in b.points.size) for b in src._mesh.blocks] != self.sizes:
+                raise ValueError("the handle holds another mesh")
+            X, Y = np.empty(self.nodes), np.empty(self.nodes)
+            rec = _capi.tm_weld_info()
+            _capi.check(L.tm_smoother_weld(src._h, None, _capi.f64ptr(X), _capi.f64ptr(Y), C.byref(rec)))
+            if rec.nodes_out != self.nodes:
+                raise ValueError("the handle holds another mesh")
+            self.info = WeldInfo.from_struct(rec)
+            return np.stack([X, Y], axis=1)
+        ncomp, nk, comps = self._planes_of(src)
+        nb = len(self.sizes)
+        dp = C.POINTER(C.c_double)
+        planes = (dp * (ncomp * nb))(*[_capi.f64ptr(a) for plane in comps for a in plane])
+        outs = [np.empty(nk * self.nodes) for _ in range(ncomp)]
+        out = (dp * ncomp)(*[_capi.f64ptr(o) for o in outs])
+        rec = self._rec
+        _capi.check((L.tm_weld_points_host if self.host else L.tm_weld_points)(self._md.ref(), _i32ptr(self.map), ncomp, nk, planes, out, C.byref(rec)))
+        self.info = WeldInfo.from_struct(rec)
+        return np.stack(outs, axis=1)
+
+    def cells(self, order=1, layers=None):
+        """(elements, (order+1)^2) int32 ids of the quadrilaterals of `order` (1 .. 8) in the order of highorder.lagrange_quad_order,
+        elements with e fastest and blocks in order; layers=nk >= 2: (elements, (order+1)^3) hexahedra (order 1 .. 4) across nk layers in
+        the order of highorder.lagrange_hex_order, ids k * nodes + map (tm_weld_cells; host=True: tm_weld_cells_host)."""
+        p = int(order)
+        nk = int(layers) if layers else 0
+        hex = nk >= 2
+        if not 1 <= p <= (_capi.TM_HO3_MAX_ORDER if hex else _capi.TM_HO_MAX_ORDER):
+            raise ValueError(f"order {p}: 1 .. {_capi.TM_HO3_MAX_ORDER if hex else _capi.TM_HO_MAX_ORDER}")
+        n = sum(((ni - 1) // p) * ((nj - 1) // p) for ni, nj in self.sizes) * (max(0, nk - 1) // p if hex else 1)
+        cells = np.empty((n, (p + 1) ** (3 if hex else 2)), dtype=np.int32)
+        L = _capi.lib()
+        _capi.check((L.tm_weld_cells_host if self.host else L.tm_weld_cells)(self._md.ref(), _i32ptr(self.map), self.nodes, p, nk, _i32ptr(cells)))
+        return cells
+
+    def mesh(self, src, order=1, distribution="equidistant"):
+        """UnstructuredMesh of `src` (see points) with cells of `order`; the layers follow from the source."""
+        pts = self.points(src)
+        nk = len(pts) // max(1, self.nodes) if pts.shape[1] == 3 else 0
+        return UnstructuredMesh(pts, self.cells(order, nk), cell_type_of(order, nk >= 2), order, info=self.info, distribution=distribution)
