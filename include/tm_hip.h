@@ -1008,8 +1008,8 @@ int tm_ho3_certificate_total(const tm_ho3_certificate* per_block, uint64_t n, tm
  *   or nj < 2: TM_E_SIZE; a block index past the mesh, a side that does not exist, more than 65535 blocks or connections: TM_E_ARG.
  *   Cells of order p: tm_ho_check (tm_ho3_check with nk >= 2) is the precondition and its answer is returned.
  * Device and host agree exactly in map, info, planes and cells: integers, copies, |a - b| and max are all that is computed.
- * Not served: boundary patches (wall / inlet / outlet edge lists); .vtu, CGNS, Gmsh and HOPR writers; gluing periodic sides; cuts or blocks
- *   spread over ranks (a handle with rank hooks answers TM_E_UNSUPPORTED); averaging the two sides of an interface. */
+ * Not served: .vtu, CGNS, Gmsh and HOPR writers; gluing periodic sides; cuts or blocks spread over ranks (a handle with rank hooks
+ *   answers TM_E_UNSUPPORTED); averaging the two sides of an interface.  Boundary patches: "boundary of the welded mesh" below. */
 typedef struct tm_weld_info {            /* 88 bytes */
     uint64_t nodes_in, nodes_out;
     uint64_t classes_2, classes_3, classes_4, classes_5_up;   /* classes of that many nodes */
@@ -1044,6 +1044,96 @@ int tm_weld_cells(const tm_mesh_desc* mesh, const int32_t* map, uint64_t nodes_o
 int tm_weld_cells_host(const tm_mesh_desc* mesh, const int32_t* map, uint64_t nodes_out, int32_t order, uint64_t nk, int32_t* cells);
 /* pairs: 2 * periodic_pairs ids.  Host only: the perimeter is small */
 int tm_weld_periodic_pairs(const tm_mesh_desc* mesh, const int32_t* map, int32_t* pairs);
+
+/* ------------------------------------------------------------------ boundary of the welded mesh (kernel K19)
+ * The welded mesh above has cells and no boundary.  This section lists its boundary faces -- edges of the plane mesh, quadrilaterals of
+ * the stacked one -- over the SAME welded ids, grouped into patches that a flow solver reads: the conditions of the description (inlet,
+ * outlet, wall), the two sides of every periodic connection as matched faces, whatever is left (the reference's O4H template leaves the
+ * blade there: its "TODO: add wall boundary condition"), and with layers hub and shroud.  Like the numbering, the face lists are a pure
+ * function of sizes, connections and conditions; the measures of the patches are sums over the welded points.
+ * Definition.
+ *   Segments     at order p a side of block b has E = (length - 1) / p segments, segment e covering positions e*p .. (e+1)*p of the side.
+ *                tm_ho_check (tm_ho3_check with nk >= 2) is the precondition and its answer is returned.
+ *   Coverage     a range (of a connection or a condition) covers a segment when both end positions of the segment lie inside it.  A range
+ *                that covers some but not all of the p fine edges of a segment is off the element grid: TM_E_MISMATCH, naming the range
+ *                (connections are refused by the precondition already; this is the rule for conditions).
+ *   Interior     a segment covered by a connection WITHOUT periodicity is interior.  Every other segment is a boundary face.
+ *   Patches      in this order: the nbcs conditions in order (kind = their TM_BC_* value, source = index of the condition, also when no
+ *                face falls to them); per periodic connection in order two patches, the side of r[0] then the side of r[1] (kind
+ *                TM_PATCH_PERIODIC, source = index of the connection, partner = the other patch, translation = the connection's for the
+ *                side of r[0] and its negative for the side of r[1]: own face + translation = partner's face); one patch
+ *                TM_PATCH_UNASSIGNED; with nk >= 2 TM_PATCH_HUB (layer 0) and TM_PATCH_SHROUD (layer nk-1).  A boundary segment belongs to
+ *                the patch of the first periodic connection range that covers it (connections in order, r[0] before r[1]), otherwise to
+ *                the first condition that covers it, otherwise it is unassigned.
+ *   Face order   patch-major: patches[q].face_begin and .faces form a CSR over the face list.  Inside a condition patch or the unassigned
+ *                patch: block, then side 0 .. 3 (the TM_SIDE_* value), then e ascending.  Inside a periodic patch: the element index t along
+ *                the connection's own pair order (pairs t*p .. (t+1)*p), ascending, so that face t of one side is the partner of face t
+ *                of the other.  With layers the span element g = 0 .. (nk-1)/p - 1 is slowest inside every lateral patch; the caps list
+ *                the plane elements in the order of tm_weld_cells (e fastest, then f, blocks in order).
+ *   Local nodes  the block sense of a side is counter-clockwise in index space: TM_SIDE_I_MIN (j = 0) i ascending, TM_SIDE_J_MAX
+ *                (i = ni-1) j ascending, TM_SIDE_I_MAX (j = nj-1) i descending, TM_SIDE_J_MIN (i = 0) j descending; a = 0 .. p runs along it.
+ *                Plane faces are VTK Lagrange curves: a = 0, then a = p, then a = 1 .. p-1 (VTK_LINE at p = 1).  Lateral faces of a stacked
+ *                mesh are VTK Lagrange quadrilaterals over (a, c), c the span, in the order given for cells above; id = (g*p + c)*nodes_out
+ *                + map[...].  Cap faces are the same quadrilateral over (a, b'): on the hub a runs along j and b' along i, on the shroud a
+ *                along i and b' along j; shroud ids are offset by (nk-1)*nodes_out.
+ *   Orientation  block_orientation[b] = +-1 (0 and a NULL array count as +1): tm_mesh_quality's orientation of the block for a plane mesh,
+ *                tm_stack_quality's for a stacked one.  A block with -1 lists a -> p - a on its curves and lateral faces, and on its caps the
+ *                two directions are exchanged.  With these values every normal points OUT of the mesh: for a curve the tangent turned by
+ *                -90 degrees, for a quadrilateral the right-hand rule of its ring.  Node (a, c) of periodic face t is then the image of
+ *                node (p - a, c) of its partner.
+ *   origin       four values per face: block, side, e, g.  Caps: side 4 (hub) / 5 (shroud), e = f*Ei + e the block's own element index,
+ *                g = 0 / (nk-1)/p - 1.  Plane faces: g = 0.
+ *   Measures     per patch the sums over the fine sub-faces of its faces (p per curve, p*p per quadrilateral), every term in IEEE fp64,
+ *                nothing fused.  Plane, fine edge A -> B: n = (yB - yA, -(xB - xA)), length = sqrt(dx*dx + dy*dy), moment = xA*yB - xB*yA;
+ *                sum moment / 2 over a closed boundary is the enclosed area.  Stacked, fine quadrilateral A, B, C, D in ring order:
+ *                n = 0.5 * (C - A) x (D - B), measure = |n|, moment = 0.25*(A + B + C + D) . n; sum moment / 3 is the volume when the faces
+ *                are planar.  Host and device form identical terms and differ in the order of the sums only: each patch value agrees
+ *                within 2 (n-1) 2^-53 sum |t| over its n terms.  The device result is the same from run to run (no floating-point atomics).
+ *   Diagnostics  of the plane boundary, from the end nodes of the segments: loops = connected components, irregular_nodes = boundary
+ *                nodes whose degree is not 2.
+ * Not served: gluing periodic sides; telling wall from hub inside `unassigned`; blocks spread over ranks; .vtu / CGNS writers (they
+ *   now need a writer only). */
+enum { TM_PATCH_PERIODIC = 16, TM_PATCH_UNASSIGNED = 17, TM_PATCH_HUB = 18, TM_PATCH_SHROUD = 19 };   /* kinds beside TM_BC_* */
+typedef struct tm_weld_patch {           /* 88 bytes */
+    int32_t  kind;                       /* TM_BC_* or TM_PATCH_* */
+    int32_t  source;                     /* index of the condition / the periodic connection; -1 otherwise */
+    int32_t  partner;                    /* the other patch of a periodic connection; -1 otherwise */
+    int32_t  _pad;
+    uint64_t face_begin, faces;
+    double   translation[2];             /* periodic patches; 0 otherwise */
+    double   measure, normal[3], moment; /* tm_weld_faces_measure */
+} tm_weld_patch;
+typedef struct tm_weld_boundary_info {   /* 56 bytes */
+    uint64_t patches, faces, nodes_per_face;
+    uint64_t lateral_faces, cap_faces;   /* cap_faces: hub and shroud together; 0 for a plane mesh */
+    uint64_t loops, irregular_nodes;
+} tm_weld_boundary_info;
+/* Host only; the perimeter is small.  info may be NULL; patches: info->patches records (nbcs + 2 * periodic connections + 1, + 2 with
+ * nk >= 2) with kind, source, partner, translation and the CSR, measures zeroed -- NULL only counts. */
+int tm_weld_boundary_plan(const tm_mesh_desc* mesh, int32_t order, uint64_t nk, tm_weld_boundary_info* info, tm_weld_patch* patches_or_null);
+/* faces: info.faces * info.nodes_per_face ids; face_patch: the patch of every face; origin: 4 values per face.  map and nodes_out:
+ * tm_weld_map's.  Sizes are checked before anything is read; errors as tm_weld_cells, and more than 2^31 - 1 faces: TM_E_ARG.  On the
+ * device the ids are expanded by the kernels (k_weld_faces_lateral over the host's segment table, k_weld_faces_caps over all plane
+ * elements); face_patch and origin are integers of the plan and are written by the host in both. */
+int tm_weld_boundary_faces(const tm_mesh_desc* mesh, const int32_t* map, uint64_t nodes_out, int32_t order, uint64_t nk,
+                           const int32_t* block_orientation, int32_t* faces, int32_t* face_patch_or_null, int32_t* origin_or_null);
+int tm_weld_boundary_faces_host(const tm_mesh_desc* mesh, const int32_t* map, uint64_t nodes_out, int32_t order, uint64_t nk,
+                                const int32_t* block_orientation, int32_t* faces, int32_t* face_patch_or_null, int32_t* origin_or_null);
+/* Measures of ANY face list over welded planes (points[c]: component c, npoints doubles, as tm_weld_points wrote them): dim = 2 curves of
+ * order 1 .. TM_HO_MAX_ORDER over components 0, 1 (ncomp >= 2); dim = 3 quadrilaterals of order 1 .. TM_HO3_MAX_ORDER (ncomp = 3).
+ * face_patch must not decrease (patch-major) and stay below npatches; ids lie in 0 .. npoints-1: TM_E_ARG otherwise, checked before
+ * anything is launched.  Writes measure, normal and moment of patches[0 .. npatches-1] and nothing else of them.  On the device: a gather
+ * through the ids, wave -> workgroup -> one partial per (workgroup, patch), and a finalize launch that sums the partials in fixed order. */
+int tm_weld_faces_measure(int32_t dim, int32_t order, uint64_t nfaces, const int32_t* faces, const int32_t* face_patch, uint64_t npatches,
+                          uint64_t npoints, int32_t ncomp, const double* const* points, tm_weld_patch* patches);
+int tm_weld_faces_measure_host(int32_t dim, int32_t order, uint64_t nfaces, const int32_t* faces, const int32_t* face_patch, uint64_t npatches,
+                               uint64_t npoints, int32_t ncomp, const double* const* points, tm_weld_patch* patches);
+/* Boundary of the coordinates RESIDENT in a handle, behind its pending work; modifies nothing.  Defined as tm_smoother_weld followed by
+ * tm_weld_boundary_faces and tm_weld_faces_measure on its map, X, Y -- the welded points stay on the device.  faces / face_patch (may be
+ * NULL) / patches sized by tm_weld_boundary_plan(mesh, order, 0).  A NULL block_orientation is taken by the rule of tm_smoother_quality.
+ * A dead handle, NULL patches: TM_E_ARG; rank hooks: TM_E_UNSUPPORTED. */
+int tm_smoother_weld_boundary(tm_smoother* s, int32_t order, const int32_t* block_orientation_or_null, int32_t* faces, int32_t* face_patch,
+                              tm_weld_patch* patches);
 
 /* ------------------------------------------------------------------ host-only planning (no GPU needed)
  * The perimeter-row table the device kernels consume, exported as CSR so it can be compared with

@@ -38,7 +38,12 @@ not go with --stack.
 (weld.py, include/tm_hip.h "welded unstructured mesh") -- the interface nodes merged, quadrilaterals / hexahedra (Lagrange cells with --order)
 over one node numbering -- and NAME.vtk holds that mesh; one line per mesh on the `weld` logger: nodes in -> out, classes by size, periodic
 pairs (periodic sides are not glued), max_gap.  Any other output format with --weld is refused.
-Without --order nothing changes; without --certify neither does --order; without --weld every output is what it was."""
+--boundary with --weld: NAME.boundary.vtk and NAME.boundary.json next to NAME.vtk -- the boundary faces of the welded mesh over the SAME points,
+in patches (the conditions of the template, the two sides of every periodic connection with partner and translation, `unassigned` -- where
+the O4H template leaves the blade -- and with --stack hub and shroud), one line per patch on the `weld` logger.  The orientation of the
+blocks comes from the quality rule (the handle's, with --stack the 3-D report's), so that every normal points out of the mesh.
+Without --order nothing changes; without --certify neither does --order; without --weld every output is what it was, and so it is
+without --boundary."""
 from __future__ import annotations
 
 import argparse
@@ -136,8 +141,14 @@ def _run(ap, args, config, keep=None, tag="", stack=None):
         if getattr(args, "weld", False) and stack is None:   # while the handle lives: the linear mesh comes from the resident coordinates
             from . import weld
 
-            welded = stats["highorder"].weld(mesh) if elevation is not None else sm.weld()
+            want_boundary = getattr(args, "boundary", False)
+            if elevation is not None:   # the orientation by the quality rule, from the handle
+                welded = stats["highorder"].weld(mesh, boundary=want_boundary, orientation=[q.orientation for q in sm.quality()[0]] if want_boundary else None)
+            else:
+                welded = sm.weld(boundary=want_boundary)
             weld.log_report(logging.getLogger("weld"), welded.info, tag + os.path.basename(config))
+            if want_boundary:
+                weld.log_boundary(logging.getLogger("weld"), welded.boundary, tag + os.path.basename(config))
             stats["welded"] = welded
     return inp, mesh, sm, stats, after
 
@@ -215,13 +226,17 @@ def _main_stack(ap, args):
                     if n:
                         logging.getLogger("stack").warning("block %d (%s), cut %d: %d nodes lie outside the meridional table %s and are extrapolated", b, name, c,
                                                            int(n), args.meridional[c])
-        q3 = st.quality(handles) if (args.stack_quality or args.fail_on_inverted_3d) else None   # from the resident cuts: no 3-D block is formed
+        q3 = st.quality(handles) if (args.stack_quality or args.fail_on_inverted_3d or args.boundary) else None   # from the resident cuts: no 3-D block is formed
     if args.weld:   # sizes and connections are those of any cut
         from . import weld
 
-        welded = weld.Weld(mesh).mesh(m3, args.order or 1, args.nodes or "equidistant")
+        welded = weld.Weld(mesh).mesh(m3, args.order or 1, args.nodes or "equidistant", boundary=args.boundary,
+                                      orientation=[q.orientation for q in q3[0]] if args.boundary else None)   # the 3-D report's orientation
         weld.log_report(logging.getLogger("weld"), welded.info, "stacked mesh")
         welded.write(args.output)
+        if args.boundary:
+            weld.log_boundary(logging.getLogger("weld"), welded.boundary, "stacked mesh")
+            logging.getLogger("output").info("wrote %s and %s", *welded.write_boundary(args.output))
     else:
         m3.write(args.output)
     logging.getLogger("output").info("wrote %s (%d blocks, %d cuts, %d layers, %d nodes)", args.output, len(m3.blocks), len(files), st.nlayers,
@@ -323,9 +338,15 @@ def main(argv=None):
     ap.add_argument("--weld", action="store_true",
                     help="with --output NAME.vtk: weld the blocks into one conforming unstructured mesh (interface nodes merged; quadrilaterals, "
                          "hexahedra with --stack, Lagrange cells with --order) and write that; logs node counts, classes and max_gap on the `weld` logger")
+    ap.add_argument("--boundary", action="store_true",
+                    help="with --weld: also the boundary of the welded mesh -- NAME.boundary.vtk (the faces over the volume file's points, CELL_DATA patch and "
+                         "kind) and NAME.boundary.json (the patch table: conditions, periodic sides with partner and translation, unassigned, hub and shroud "
+                         "with --stack) next to --output; one line per patch on the `weld` logger")
     args = ap.parse_args(argv)
     if args.weld and not (args.output and args.output.lower().endswith(".vtk")):
         ap.error(f"--weld writes one welded unstructured mesh as legacy VTK: --output NAME.vtk, not {args.output!r}")
+    if args.boundary and not args.weld:
+        ap.error("--boundary lists the boundary faces of the welded mesh: it goes with --weld and --output NAME.vtk")
     if args.stack is None and (args.span or args.layers is not None):
         ap.error("--span and --layers go with --stack")
     if args.stack is None and (args.meridional or args.reference_radius or args.meridional_interpolation):
@@ -402,6 +423,8 @@ def main(argv=None):
         welded = stats["welded"]
         welded.write(out)
         logging.getLogger("output").info("wrote %s (%d welded nodes, %d cells of type %d)", out, len(welded.points), len(welded.cells), welded.cell_type)
+        if args.boundary:
+            logging.getLogger("output").info("wrote %s and %s", *welded.write_boundary(out))
     elif out and hom is not None:
         hom.write(out)
         logging.getLogger("output").info("wrote %s (%d blocks, %d elements of order %d, %s nodes)", out, len(hom.blocks), hom.total.elements, hom.order, hom.distribution)

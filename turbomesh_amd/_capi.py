@@ -35,6 +35,8 @@ TM_HO_CERT_MAX_DEPTH = 4
 TM_HO3_MAX_ORDER = 4
 TM_HO3_CERT_MAX_DEPTH = 3
 TM_HO_PROVEN, TM_HO_INVALID, TM_HO_UNDECIDED = 0, 1, 2
+TM_BC_WALL, TM_BC_INLET, TM_BC_OUTLET = 0, 1, 2
+TM_PATCH_PERIODIC, TM_PATCH_UNASSIGNED, TM_PATCH_HUB, TM_PATCH_SHROUD = 16, 17, 18, 19
 
 
 class TmError(RuntimeError):
@@ -197,6 +199,19 @@ class tm_weld_info(C.Structure):   # 88 bytes
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class tm_weld_patch(C.Structure):   # 88 bytes
+    _fields_ = [("kind", C.c_int32), ("source", C.c_int32), ("partner", C.c_int32), ("_pad", C.c_int32), ("face_begin", C.c_uint64), ("faces", C.c_uint64),
+                ("translation", C.c_double * 2), ("measure", C.c_double), ("normal", C.c_double * 3), ("moment", C.c_double)]
+
+
+class tm_weld_boundary_info(C.Structure):   # 56 bytes
+    _fields_ = [("patches", C.c_uint64), ("faces", C.c_uint64), ("nodes_per_face", C.c_uint64), ("lateral_faces", C.c_uint64), ("cap_faces", C.c_uint64),
+                ("loops", C.c_uint64), ("irregular_nodes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/tm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "tm_last_error", "tm_abi_version", "tm_set_log", "tm_csr_solve", "tm_tfi_block", "tm_tfi_linear2d", "tm_smooth_mesh", "tm_smoother_create",
@@ -220,6 +235,8 @@ EXPORTS = [
     "tm_stack_smoothers_certify", "tm_ho3_certificate_total",
     "tm_weld_map", "tm_weld_map_host", "tm_weld_points", "tm_weld_points_host", "tm_smoother_weld", "tm_weld_cells", "tm_weld_cells_host",
     "tm_weld_periodic_pairs",
+    "tm_weld_boundary_plan", "tm_weld_boundary_faces", "tm_weld_boundary_faces_host", "tm_weld_faces_measure", "tm_weld_faces_measure_host",
+    "tm_smoother_weld_boundary",
     "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
 ]
 
@@ -365,6 +382,13 @@ def lib():
         L.tm_weld_cells.argtypes = [C.POINTER(tm_mesh_desc), _i32p, C.c_uint64, C.c_int32, C.c_uint64, _i32p]
         L.tm_weld_cells_host.argtypes = L.tm_weld_cells.argtypes
         L.tm_weld_periodic_pairs.argtypes = [C.POINTER(tm_mesh_desc), _i32p, _i32p]
+        _wpp = C.POINTER(tm_weld_patch)
+        L.tm_weld_boundary_plan.argtypes = [C.POINTER(tm_mesh_desc), C.c_int32, C.c_uint64, C.POINTER(tm_weld_boundary_info), _wpp]
+        L.tm_weld_boundary_faces.argtypes = [C.POINTER(tm_mesh_desc), _i32p, C.c_uint64, C.c_int32, C.c_uint64, _i32p, _i32p, _i32p, _i32p]
+        L.tm_weld_boundary_faces_host.argtypes = L.tm_weld_boundary_faces.argtypes
+        L.tm_weld_faces_measure.argtypes = [C.c_int32, C.c_int32, C.c_uint64, _i32p, _i32p, C.c_uint64, C.c_uint64, C.c_int32, _dpp, _wpp]
+        L.tm_weld_faces_measure_host.argtypes = L.tm_weld_faces_measure.argtypes
+        L.tm_smoother_weld_boundary.argtypes = [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _wpp]
         L.tm_rccl_unique_id.argtypes =[C.c_char_p, C.c_void_p]
         L.tm_rccl_comm_create.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.tm_rccl_comm_destroy.argtypes = [C.c_void_p]

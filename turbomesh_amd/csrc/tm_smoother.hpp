@@ -216,6 +216,9 @@ struct Smoother {
     // welded map and points of the resident coordinates (tm_weld.hip, K18): reads X only; buffers as for the quality report
     WeldDev* welddev = nullptr;
     void weld_host(int32_t* map, double* x, double* y, tm_weld_info* info);
+    void weld_tables(std::vector<tm_block>& tb, std::vector<tm_connection>& tc, std::vector<tm_condition>& tq, std::vector<const double2*>& blocks_x);
+    // boundary faces and patch measures of the resident coordinates (tm_weld_boundary.hip, K19): the welded planes stay on the device
+    void weld_boundary_host(int order, const int32_t* block_orientation, int32_t* faces, int32_t* face_patch, tm_weld_patch* patches);
 
     // building blocks
     void exchange(double2* vec, hipStream_t on = nullptr);   // start (and, without a split hook, finish) the halo exchange of `vec`; on = the handle's stream unless given

@@ -554,8 +554,8 @@ void WeldDev::points_resident(const WeldPlan& pl, hipStream_t st, const std::vec
         HIPCHK(hipGetLastError());
     }
     gap_run(pl, st, WeldSrc{nullptr, 0, static_cast<const double2* const*>(ptrs.p), 2, 1}, nodes_out, host_gap);
-    HIPCHK(hipMemcpyAsync(x, ox, sizeof(double) * nodes_out, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(y, oy, sizeof(double) * nodes_out, hipMemcpyDeviceToHost, st));
+    if (x) HIPCHK(hipMemcpyAsync(x, ox, sizeof(double) * nodes_out, hipMemcpyDeviceToHost, st));   // null: the planes are wanted on the device only (K19)
+    if (y) HIPCHK(hipMemcpyAsync(y, oy, sizeof(double) * nodes_out, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
 }
 
@@ -581,10 +581,8 @@ void WeldDev::cells_run(const WeldPlan& pl, hipStream_t st, const std::vector<in
 }
 
 // ------------------------------------------------------------------ handle: the coordinates resident in X
-void Smoother::weld_host(int32_t* map_out, double* x, double* y, tm_weld_info* info) {
-    if (lp.nranks > 1) throw TmError(TM_E_UNSUPPORTED, "welding needs every block in one handle: not served with rank hooks");
-    std::vector<tm_block> tb;
-    std::vector<tm_connection> tc;
+// the handle's topology as a mesh description without coordinates, and the resident interleaved blocks
+void Smoother::weld_tables(std::vector<tm_block>& tb, std::vector<tm_connection>& tc, std::vector<tm_condition>& tq, std::vector<const double2*>& blocks_x) {
     for (int64_t b = 0; b < topo.nblocks(); ++b) tb.push_back(tm_block{nullptr, static_cast<uint64_t>(topo.ni[b]), static_cast<uint64_t>(topo.nj[b])});
     for (const TopoConn& c : topo.conns) {
         tm_connection t{};
@@ -594,14 +592,24 @@ void Smoother::weld_host(int32_t* map_out, double* x, double* y, tm_weld_info* i
         t.periodicity[1] = c.per[1];
         tc.push_back(t);
     }
-    tm_mesh_desc desc{tb.data(), tb.size(), tc.data(), tc.size(), nullptr, 0};
-    const WeldPlan pl = weld_plan(&desc);
-    std::vector<const double2*> blocks_x;
+    for (const TopoCond& c : topo.bcs)
+        tq.push_back(tm_condition{tm_range{static_cast<uint64_t>(c.range.block), c.range.side, 0, static_cast<uint64_t>(c.range.start), static_cast<uint64_t>(c.range.end)}, c.kind, 0});
     for (int64_t b = 0; b < topo.nblocks(); ++b) {
         const auto it = std::lower_bound(lp.owned_blocks.begin(), lp.owned_blocks.end(), b);
         if (it == lp.owned_blocks.end() || *it != b) throw TmError(TM_E_UNSUPPORTED, "a block is not owned by this handle");
         blocks_x.push_back(X + lp.local_start[it - lp.owned_blocks.begin()]);
     }
+}
+
+void Smoother::weld_host(int32_t* map_out, double* x, double* y, tm_weld_info* info) {
+    if (lp.nranks > 1) throw TmError(TM_E_UNSUPPORTED, "welding needs every block in one handle: not served with rank hooks");
+    std::vector<tm_block> tb;
+    std::vector<tm_connection> tc;
+    std::vector<tm_condition> tq;
+    std::vector<const double2*> blocks_x;
+    weld_tables(tb, tc, tq, blocks_x);
+    tm_mesh_desc desc{tb.data(), tb.size(), tc.data(), tc.size(), nullptr, 0};
+    const WeldPlan pl = weld_plan(&desc);
     if (!welddev) welddev = new WeldDev();
     tm_weld_info rec;
     welddev->link(pl, stream);

@@ -152,12 +152,15 @@ class HighOrderMesh3d:
         output._format_of(filename)
         output.write_plot3d_3d(filename, self.sizes(), self.blocks)
 
-    def weld(self, mesh, host=False):
+    def weld(self, mesh, host=False, boundary=False, orientation=None):
         """weld.UnstructuredMesh of these blocks: the interface nodes of `mesh` (the cut the blocks were stacked from: sizes and
-        connections) merged, one Lagrange hexahedron of `order` per element (include/tm_hip.h, "welded unstructured mesh")."""
+        connections) merged, one Lagrange hexahedron of `order` per element (include/tm_hip.h, "welded unstructured mesh").
+        boundary=True: with .boundary, the faces in patches (hub and shroud included); orientation: per block, None = that of the elements."""
         from . import weld
 
-        return weld.Weld(mesh, host=host).mesh(self, self.order, self.distribution)
+        if boundary and orientation is None:
+            orientation = [q.orientation for q in self.per_block]
+        return weld.Weld(mesh, host=host).mesh(self, self.order, self.distribution, boundary=boundary, orientation=orientation)
 
 
 @dataclass
@@ -195,12 +198,15 @@ class HighOrderMesh:
         output._format_of(filename)
         output.write_plot3d(filename, self.sizes(), [(x.reshape(-1), y.reshape(-1)) for x, y in self.blocks])
 
-    def weld(self, mesh, host=False):
+    def weld(self, mesh, host=False, boundary=False, orientation=None):
         """weld.UnstructuredMesh of these blocks: the interface nodes of `mesh` (sizes and connections) merged, one Lagrange
-        quadrilateral of `order` per element (include/tm_hip.h, "welded unstructured mesh")."""
+        quadrilateral of `order` per element (include/tm_hip.h, "welded unstructured mesh").  boundary=True: with .boundary, the
+        faces in patches; orientation: per block, None = that of the elements."""
         from . import weld
 
-        return weld.Weld(mesh, host=host).mesh(self, self.order, self.distribution)
+        if boundary and orientation is None:
+            orientation = [q.orientation for q in self.per_block]
+        return weld.Weld(mesh, host=host).mesh(self, self.order, self.distribution, boundary=boundary, orientation=orientation)
 
 
 class Elevation:

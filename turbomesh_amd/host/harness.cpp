@@ -12,6 +12,7 @@
 //   tm_harness stack-elevate <ni> <nj> <ncuts> <nlayers> <order>   the same cuts: curved hexahedra of that order from the stacked block (kernel K16; exit 0: corners unchanged, equal to the CPU's)
 //   tm_harness stack-quality <ni> <nj> <ncuts> <nlayers>   the same cuts: the 3-D quality record of the stacked block (kernel K12; exit 0: equal to the CPU's)
 //   tm_harness weld <ni> <nj> <nblocks>   the strip welded into one unstructured mesh from the resident coordinates (kernel K18; exit 0: equal to the CPU's)
+//   tm_harness weld-boundary <ni> <nj> <nblocks> [nlayers]   its boundary faces in patches and their measures (kernel K19; exit 0: equal to the CPU's)
 //   tm_harness csr                                     the linear-solver slot (seam 2) on the reference's 5 x 5 known answer
 //   tm_harness ranks <world> <rank> <idfile> <nblocks> <ni> <nj> <iterations> [relax|bicgstab] [dump.bin]
 //        one process per GPU (start each with HIP_VISIBLE_DEVICES=<its GPU>): the strip's blocks are dealt to the ranks in order, the
@@ -562,8 +563,62 @@ static int weldStrip(std::size_t ni, std::size_t nj, std::size_t nb) {
     return count && same ? 0 : 1;
 }
 
+// tm_harness weld-boundary <ni> <nj> <nblocks> [nlayers]: the boundary of the welded strip (kernel K19).  Without layers: faces and measured
+// patches from the coordinates resident in the handle (weld::boundary(sm) -> tm_smoother_weld_boundary) against the CPU's faces and sums on
+// the welded points.  With layers: the welded plane repeated at z = 0.1 k, faces and sums on the device against the CPU's.  The strip has
+// 2 (nj - 1) + 2 nblocks (ni - 1) boundary edges in one loop.
+static int weldBoundaryStrip(std::size_t ni, std::size_t nj, std::size_t nb, std::size_t nk) {
+    discrete::Mesh mesh = buildStrip(nb, ni, nj);
+    smoothing::smooth::Smoother sm(mesh, smoothing::solver::Option{}, smoothing::wall_control_function::Algorithm::laplace());
+    sm.iterate(2);
+    weld::Map map;
+    const weld::Points pts = weld::points(sm, &map);
+    std::vector<int32_t> orientation;
+    for (const auto& q : sm.quality().per_block) orientation.push_back(q.orientation);
+    weld::Boundary dev, host = weld::boundary(mesh, map, 1, nk, orientation, true);
+    if (nk < 2) {
+        dev = weld::boundary(sm);
+        weld::measure(host, 1, pts.x, pts.y, nullptr, true);
+    } else {
+        std::vector<double> x, y, z;
+        for (std::size_t k = 0; k < nk; ++k) {
+            x.insert(x.end(), pts.x.begin(), pts.x.end());
+            y.insert(y.end(), pts.y.begin(), pts.y.end());
+            z.insert(z.end(), pts.x.size(), 0.1 * static_cast<double>(k));
+        }
+        dev = weld::boundary(mesh, map, 1, nk, orientation);
+        weld::measure(dev, 1, x, y, &z);
+        weld::measure(host, 1, x, y, &z, true);
+    }
+    const std::size_t edges = 2 * (nj - 1) + 2 * nb * (ni - 1);
+    std::printf("weld-boundary: %llu faces of %llu nodes in %zu patches, %llu loop(s), %llu irregular nodes\n", static_cast<unsigned long long>(host.info.faces),
+                static_cast<unsigned long long>(host.info.nodes_per_face), host.patches.size(), static_cast<unsigned long long>(host.info.loops),
+                static_cast<unsigned long long>(host.info.irregular_nodes));
+    const bool count = host.info.loops == 1 && host.info.irregular_nodes == 0 &&
+                       host.info.faces == (nk < 2 ? edges : edges * (nk - 1) + 2 * nb * (ni - 1) * (nj - 1));
+    std::printf("weld-boundary: face count and loops: %s\n", count ? "yes" : "no");
+    bool same = dev.faces == host.faces && dev.face_patch == host.face_patch && dev.patches.size() == host.patches.size();
+    double total = 0.0, normal[3] = {0.0, 0.0, 0.0};
+    for (std::size_t q = 0; same && q < host.patches.size(); ++q) {
+        const tm_weld_patch &a = dev.patches[q], &b = host.patches[q];
+        std::printf("weld-boundary: patch %zu kind %d: %llu faces, measure %.15e (device) %.15e (host), moment %.15e\n", q, a.kind,
+                    static_cast<unsigned long long>(a.faces), a.measure, b.measure, a.moment);
+        // the terms of the measure are all positive: the two orders of summation differ by at most 2 (n - 1) 2^-53 of it
+        same = same && a.faces == b.faces && std::fabs(a.measure - b.measure) <= 2.0 * static_cast<double>(a.faces) * 0x1p-53 * b.measure;
+        total += a.moment;
+        for (int d = 0; d < 3; ++d) normal[d] += a.normal[d];
+    }
+    std::printf("weld-boundary: sum of normals (%.3e, %.3e, %.3e), enclosed %s %.15e\n", normal[0], normal[1], normal[2], nk < 2 ? "area" : "volume",
+                total / (nk < 2 ? 2.0 : 3.0));
+    std::printf("weld-boundary: device equals host: %s\n", same ? "yes" : "no");
+    return count && same ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     try {
+        if (argc >= 5 && std::strcmp(argv[1], "weld-boundary") == 0)
+            return weldBoundaryStrip(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10),
+                                     argc >= 6 ? std::strtoull(argv[5], nullptr, 10) : 0);
         if (argc >= 5 && std::strcmp(argv[1], "weld") == 0)
             return weldStrip(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 5 && std::strcmp(argv[1], "certify") == 0)
@@ -587,7 +642,7 @@ int main(int argc, char** argv) {
             return thomasMiddlecoff(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "ranks") == 0) return runRank(argc, argv);
         if (argc < 5) {
-            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-elevate <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-certify <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n       %s weld <ni> <nj> <nblocks>\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-elevate <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-certify <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n       %s weld <ni> <nj> <nblocks>\n       %s weld-boundary <ni> <nj> <nblocks> [nlayers]\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 2;
         }
         int a = 2;

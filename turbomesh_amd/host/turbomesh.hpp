@@ -845,6 +845,44 @@ inline std::vector<int32_t> cells(discrete::Mesh& mesh, const Map& m, int order 
     c.resize(n * npe);
     return c;
 }
+// boundary of the welded mesh (tm_hip.h, kernel K19): the faces over the welded ids in patches, and the sums per patch
+struct Boundary {
+    tm_weld_boundary_info info{};
+    std::vector<tm_weld_patch> patches;      // kind, source, partner, translation, the CSR; measure / normal / moment once measured
+    std::vector<int32_t> faces, face_patch;  // info.faces * info.nodes_per_face ids; the patch of every face
+    std::vector<int32_t> origin;             // block, side (4 / 5: hub / shroud), e, g per face
+};
+// orientation: +-1 per block from the quality report (Mesh::quality, with layers the 3-D report), empty = +1; nk >= 2: the stacked mesh
+inline Boundary boundary(discrete::Mesh& mesh, const Map& m, int order = 1, std::size_t nk = 0, const std::vector<int32_t>& orientation = {}, bool host = false) {
+    smoothing::smooth::Desc d(mesh);
+    Boundary r;
+    core::check(tm_weld_boundary_plan(&d.desc, order, nk, &r.info, nullptr));
+    r.patches.resize(r.info.patches);
+    core::check(tm_weld_boundary_plan(&d.desc, order, nk, &r.info, r.patches.data()));
+    if (!orientation.empty() && orientation.size() != mesh.blocks.size()) throw Error(TM_E_ARG, "one orientation per block");
+    r.faces.resize(r.info.faces * r.info.nodes_per_face + 1), r.face_patch.resize(r.info.faces + 1), r.origin.resize(4 * r.info.faces + 1);
+    core::check((host ? tm_weld_boundary_faces_host : tm_weld_boundary_faces)(&d.desc, m.map.data(), m.info.nodes_out, order, nk,
+                                                                              orientation.empty() ? nullptr : orientation.data(), r.faces.data(), r.face_patch.data(),
+                                                                              r.origin.data()));
+    r.faces.resize(r.info.faces * r.info.nodes_per_face), r.face_patch.resize(r.info.faces), r.origin.resize(4 * r.info.faces);
+    return r;
+}
+// measure, normal and moment of every patch on welded planes (x, y and, for a stacked mesh, z: npoints values each)
+inline void measure(Boundary& b, int order, const std::vector<double>& x, const std::vector<double>& y, const std::vector<double>* z = nullptr, bool host = false) {
+    const double* planes[3] = {x.data(), y.data(), z ? z->data() : nullptr};
+    core::check((host ? tm_weld_faces_measure_host : tm_weld_faces_measure)(z ? 3 : 2, order, b.info.faces, b.faces.data(), b.face_patch.data(), b.patches.size(), x.size(),
+                                                                            z ? 3 : 2, planes, b.patches.data()));
+}
+// from the coordinates RESIDENT in the handle (tm_smoother_weld_boundary): faces and measured patches, the welded points stay on the device
+inline Boundary boundary(const smoothing::smooth::Smoother& s, int order = 1, const std::vector<int32_t>& orientation = {}) {
+    Boundary r;
+    core::check(tm_weld_boundary_plan(&s.desc(), order, 0, &r.info, nullptr));
+    r.patches.resize(r.info.patches);
+    r.faces.resize(r.info.faces * r.info.nodes_per_face + 1), r.face_patch.resize(r.info.faces + 1);
+    core::check(tm_smoother_weld_boundary(s.handle(), order, orientation.empty() ? nullptr : orientation.data(), r.faces.data(), r.face_patch.data(), r.patches.data()));
+    r.faces.resize(r.info.faces * r.info.nodes_per_face), r.face_patch.resize(r.info.faces);
+    return r;
+}
 }  // namespace weld
 
 namespace discrete {

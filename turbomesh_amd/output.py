@@ -202,6 +202,49 @@ def read_vtk_lagrange(filename):
     return points, rows[:, 1:].copy(), types
 
 
+def read_vtk_boundary(filename):
+    """-> (points (n, 3) float64, faces (nfaces, nodes per face) int64, cell_types (nfaces,) int64, patch (nfaces,) int64, kind (nfaces,)
+    int64) of a NAME.boundary.vtk written by weld.UnstructuredMesh.write_boundary (legacy ASCII: lines 3, Lagrange curves 68, quadrilaterals
+    9 or Lagrange quadrilaterals 70 over the points of the volume file, CELL_DATA `patch` and `kind`)."""
+    with open(filename) as fh:
+        tok = fh.read().split("\n", 4)
+    if len(tok) < 5 or not tok[0].startswith("# vtk DataFile") or tok[2].strip() != "ASCII" or tok[3].split() != ["DATASET", "UNSTRUCTURED_GRID"]:
+        raise ValueError(f"{filename}: not a legacy ASCII VTK unstructured grid")
+    w = tok[4].split()
+    if w[0] != "POINTS" or w[2] != "double":
+        raise ValueError(f"{filename}: POINTS <n> double expected")
+    n = int(w[1])
+    k = 3
+    points = np.array([float(v) for v in w[k:k + 3 * n]], dtype=np.float64).reshape(n, 3)
+    k += 3 * n
+    if w[k] != "CELLS":
+        raise ValueError(f"{filename}: CELLS expected")
+    nc, size = int(w[k + 1]), int(w[k + 2])
+    k += 3
+    flat = np.array([int(v) for v in w[k:k + size]], dtype=np.int64)
+    k += size
+    per = size // nc - 1 if nc else 0
+    rows = flat.reshape(nc, per + 1) if nc else flat.reshape(0, 1)
+    if nc and not np.all(rows[:, 0] == per):
+        raise ValueError(f"{filename}: faces of different sizes")
+    if w[k] != "CELL_TYPES" or int(w[k + 1]) != nc:
+        raise ValueError(f"{filename}: CELL_TYPES expected")
+    types = np.array([int(v) for v in w[k + 2:k + 2 + nc]], dtype=np.int64)
+    k += 2 + nc
+    if w[k] != "CELL_DATA" or int(w[k + 1]) != nc:
+        raise ValueError(f"{filename}: CELL_DATA expected")
+    k += 2
+    data = {}
+    for _ in range(2):
+        if w[k] != "SCALARS" or w[k + 4:k + 6] != ["LOOKUP_TABLE", "default"]:
+            raise ValueError(f"{filename}: SCALARS <name> int 1 expected")
+        data[w[k + 1]] = np.array([int(v) for v in w[k + 6:k + 6 + nc]], dtype=np.int64)
+        k += 6 + nc
+    if set(data) != {"patch", "kind"}:
+        raise ValueError(f"{filename}: CELL_DATA patch and kind expected")
+    return points, rows[:, 1:].copy(), types, data["patch"], data["kind"]
+
+
 def _format_of(filename):
     ext = os.path.splitext(filename)[1].lower()
     if ext == ".cgns":

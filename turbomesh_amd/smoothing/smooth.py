@@ -152,13 +152,22 @@ class Smoother:
         handle (tm_smoother_certify); see Elevation.certify."""
         return elevation.certify(self, block, max_depth=max_depth)
 
-    def weld(self, order=1):
+    def weld(self, order=1, boundary=False):
         """weld.UnstructuredMesh of the coordinates resident in the handle: the blocks welded into one conforming mesh of quadrilaterals
         (tm_smoother_weld: map and points formed on the device from the resident coordinates; order > 1: the fine nodes as equidistant
-        Lagrange elements, the sizes checked by tm_ho_check)."""
+        Lagrange elements, the sizes checked by tm_ho_check).  boundary=True: with .boundary, the faces in patches, oriented by quality()."""
         from .. import weld
 
-        return weld.Weld(self._mesh).mesh(self, order)
+        orientation = [q.orientation for q in self.quality()[0]] if boundary else None
+        return weld.Weld(self._mesh).mesh(self, order, boundary=boundary, orientation=orientation)
+
+    def weld_boundary(self, order=1, orientation=None):
+        """(faces, face_patch, patches) of the boundary of the welded mesh of the coordinates resident in the handle, measured there
+        (tm_smoother_weld_boundary: map, welded points, faces and the sums per patch on the device; the welded points are not
+        downloaded).  patches: weld.Patch records with measure, normal and moment; orientation None: the rule of quality()."""
+        from .. import weld
+
+        return weld.resident_boundary(self, order, orientation)
 
     def write_quality(self, filename):
         """The per-cell planes of every block as a PLOT3D function file (one variable, sizes (ni-1, nj-1))."""

@@ -12,16 +12,20 @@ ni x nj index space, so one Weld serves every product of the library:
     w.cells(order=1, layers=nk)                    # hexahedra across nk layers
     smoother.weld().write("blade.vtk")             # UnstructuredMesh: legacy ASCII VTK, %.17g
     w.periodic_pairs()                             # [(pairs (n, 2), (tx, ty))] per periodic connection: periodic sides are not glued
+    w.boundary(order=1, orientation=o)             # Boundary: faces over the same ids in patches (inlet, outlet, periodic sides, unassigned,
+                                                   # hub and shroud with layers=nk); .measure(points) sums length / area, normal, moment per patch
+    w.mesh(src, boundary=True).write_boundary("blade.vtk")   # blade.boundary.vtk + blade.boundary.json beside the volume file
 
 A welded node has the coordinates of its owner (the class member with the smallest index), bit for bit; `info.max_gap` says by how much the
 other members differ from it -- the rounding "the two sides agree to", or the size of the mesh when a connection is wrong.
 Evaluated on the MI355X; `host=True` evaluates the same definition on the CPU, with the same results.
-Not served: boundary patches (wall / inlet / outlet edge lists), .vtu / CGNS / Gmsh / HOPR writers, gluing periodic sides, blocks spread
-over ranks, averaging the two sides of an interface."""
+Not served: .vtu / CGNS / Gmsh / HOPR writers (they now need a writer only), gluing periodic sides, telling wall from hub inside the
+`unassigned` patch, blocks spread over ranks, averaging the two sides of an interface."""
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+import json
+from dataclasses import asdict, dataclass
 
 import numpy as np
 
@@ -29,6 +33,9 @@ from . import _capi
 
 VTK_QUAD, VTK_HEXAHEDRON = 9, 12
 VTK_LAGRANGE_QUADRILATERAL, VTK_LAGRANGE_HEXAHEDRON = 70, 72
+VTK_LINE, VTK_LAGRANGE_CURVE = 3, 68
+PATCH_NAMES = {_capi.TM_BC_WALL: "wall", _capi.TM_BC_INLET: "inlet", _capi.TM_BC_OUTLET: "outlet", _capi.TM_PATCH_PERIODIC: "periodic",
+               _capi.TM_PATCH_UNASSIGNED: "unassigned", _capi.TM_PATCH_HUB: "hub", _capi.TM_PATCH_SHROUD: "shroud"}
 _I32P = C.POINTER(C.c_int32)
 
 
@@ -99,6 +106,191 @@ class UnstructuredMesh:
             fh.write("".join(head + " " + " ".join(map(str, row)) + "\n" for row in self.cells.tolist()))
             fh.write(f"CELL_TYPES {len(self.cells)}\n")
             fh.write(f"{self.cell_type}\n" * len(self.cells))
+
+    def _write_points(self, fh):
+        fh.write(f"POINTS {len(self.points)} double\n")
+        if self.points.shape[1] == 2:
+            fh.write("".join("%.17g %.17g 0\n" % (x, y) for x, y in self.points.tolist()))
+        else:
+            fh.write("".join("%.17g %.17g %.17g\n" % (x, y, z) for x, y, z in self.points.tolist()))
+
+    def write_boundary(self, name):
+        """The boundary of a mesh made with boundary=True, beside the volume file NAME.vtk: NAME.boundary.vtk -- the SAME points as the
+        volume file, so ids are shared, the faces as cells (VTK_LINE 3 / VTK_LAGRANGE_CURVE 68 / VTK_QUAD 9 / VTK_LAGRANGE_QUADRILATERAL 70)
+        and the CELL_DATA `patch` and `kind` -- and NAME.boundary.json, the patch table.  output.read_vtk_boundary reads the first back bit
+        for bit.  Returns the two file names."""
+        b = getattr(self, "boundary", None)
+        if b is None:
+            raise ValueError("the mesh carries no boundary: Weld.mesh(..., boundary=True)")
+        if self.order > 1 and self.distribution != "equidistant":
+            raise ValueError(f"VTK Lagrange cells assume equidistant nodes, not a {self.distribution} elevation")
+        stem = str(name)[:-4] if str(name).lower().endswith(".vtk") else str(name)
+        vtk, js = stem + ".boundary.vtk", stem + ".boundary.json"
+        with open(vtk, "w") as fh:
+            fh.write(f"# vtk DataFile Version 4.2\nboundary faces of order {self.order} in {len(b.patches)} patches\nASCII\nDATASET UNSTRUCTURED_GRID\n")
+            self._write_points(fh)
+            per = b.faces.shape[1]
+            fh.write(f"CELLS {len(b.faces)} {len(b.faces) * (per + 1)}\n")
+            head = str(per)
+            fh.write("".join(head + " " + " ".join(map(str, row)) + "\n" for row in b.faces.tolist()))
+            fh.write(f"CELL_TYPES {len(b.faces)}\n")
+            fh.write(f"{b.cell_type}\n" * len(b.faces))
+            fh.write(f"CELL_DATA {len(b.faces)}\nSCALARS patch int 1\nLOOKUP_TABLE default\n")
+            fh.write("".join(f"{q}\n" for q in b.face_patch.tolist()))
+            kinds = [b.patches[q].kind for q in b.face_patch.tolist()]
+            fh.write("SCALARS kind int 1\nLOOKUP_TABLE default\n")
+            fh.write("".join(f"{k}\n" for k in kinds))
+        with open(js, "w") as fh:
+            json.dump(b.table(), fh, indent=1)
+        return vtk, js
+
+
+@dataclass
+class Patch:
+    """tm_weld_patch: kind (TM_BC_* / TM_PATCH_*), name, source (index of the condition / the periodic connection, else -1), partner (the
+    other patch of a periodic connection, else -1), translation (own face + translation = partner's face), begin / faces (the CSR over
+    Boundary.faces), and the sums of Boundary.measure: measure (length / area), normal, moment."""
+
+    kind: int
+    name: str
+    source: int
+    partner: int
+    translation: tuple
+    begin: int
+    faces: int
+    measure: float = 0.0
+    normal: tuple = (0.0, 0.0, 0.0)
+    moment: float = 0.0
+
+
+@dataclass
+class BoundaryInfo:
+    patches: int = 0
+    faces: int = 0
+    nodes_per_face: int = 0
+    lateral_faces: int = 0
+    cap_faces: int = 0
+    loops: int = 0
+    irregular_nodes: int = 0
+
+
+def face_type_of(order, layered):
+    if layered:
+        return VTK_QUAD if order == 1 else VTK_LAGRANGE_QUADRILATERAL
+    return VTK_LINE if order == 1 else VTK_LAGRANGE_CURVE
+
+
+class Boundary:
+    """The boundary faces of a Weld (include/tm_hip.h, "boundary of the welded mesh"; kernel K19): .faces (faces, nodes per face) int32
+    welded ids, patch-major; .face_patch; .origin (faces, 4): block, side (4 / 5: hub / shroud), e, g; .patches (Patch records); .info
+    (BoundaryInfo: counts, loops, irregular_nodes); .cell_type (VTK).  orientation: +-1 per block, from the quality report of the
+    coordinates (quality.Quality.orientation, with layers quality.Quality3d.orientation) -- with it every normal points outward; None: +1."""
+
+    def __init__(self, weld, order=1, layers=None, orientation=None):
+        p = int(order)
+        nk = int(layers) if layers else 0
+        self.order, self.layers, self.host = p, nk, weld.host
+        self._weld = weld
+        L = _capi.lib()
+        rec = _capi.tm_weld_boundary_info()
+        _capi.check(L.tm_weld_boundary_plan(weld._md.ref(), p, nk, C.byref(rec), None))
+        self.info = BoundaryInfo(**rec.as_dict())
+        self._patches = (_capi.tm_weld_patch * max(1, self.info.patches))()
+        _capi.check(L.tm_weld_boundary_plan(weld._md.ref(), p, nk, C.byref(rec), self._patches))
+        o = None
+        if orientation is not None:
+            o = np.ascontiguousarray([int(v) for v in orientation], dtype=np.int32)
+            if len(o) != len(weld.sizes):
+                raise ValueError(f"{len(o)} orientations for {len(weld.sizes)} blocks")
+        self.orientation = o
+        self.faces = np.empty((self.info.faces, self.info.nodes_per_face), dtype=np.int32)
+        self.face_patch = np.empty(self.info.faces, dtype=np.int32)
+        self.origin = np.empty((self.info.faces, 4), dtype=np.int32)
+        fn = L.tm_weld_boundary_faces_host if self.host else L.tm_weld_boundary_faces
+        _capi.check(fn(weld._md.ref(), _i32ptr(weld.map), weld.nodes, p, nk, None if o is None else _i32ptr(o), _i32ptr(self.faces), _i32ptr(self.face_patch),
+                       _i32ptr(self.origin)))
+        self.cell_type = face_type_of(p, nk >= 2)
+        self.patches = self._records()
+
+    def _records(self):
+        out, seen = [], {}
+        for q in range(self.info.patches):
+            r = self._patches[q]
+            name = PATCH_NAMES.get(r.kind, f"kind{r.kind}")
+            if r.kind == _capi.TM_PATCH_PERIODIC:
+                name = f"periodic{r.source}" + ("a" if r.partner > q else "b")
+            seen[name] = seen.get(name, 0) + 1
+            if seen[name] > 1:
+                name += str(seen[name])
+            out.append(Patch(int(r.kind), name, int(r.source), int(r.partner), (float(r.translation[0]), float(r.translation[1])), int(r.face_begin),
+                             int(r.faces), float(r.measure), tuple(float(v) for v in r.normal), float(r.moment)))
+        return out
+
+    def measure(self, points):
+        """Per patch the sums over the fine sub-faces of its faces on the welded `points` ((nodes, 2), or (nk * nodes, 3) with layers; or a
+        list of the component planes):
+        measure (length / area), normal (outward with the right orientation), moment (sum / 2 = enclosed area; sum / 3 = volume for planar
+        faces).  tm_weld_faces_measure (host=True: tm_weld_faces_measure_host).  Updates and returns .patches."""
+        dim = 3 if self.layers >= 2 else 2
+        if isinstance(points, (list, tuple)):   # the planes themselves, one array per component: nothing is copied
+            planes = [np.ascontiguousarray(a, dtype=np.float64) for a in points[:dim]]
+            if len(planes) < dim or any(a.ndim != 1 or len(a) != len(planes[0]) for a in planes):
+                raise ValueError(f"points: {dim} planes of one length")
+            pts = planes[0]
+        else:
+            pts = np.ascontiguousarray(points, dtype=np.float64)
+            if pts.ndim != 2 or pts.shape[1] < dim:
+                raise ValueError(f"points: (n, {dim}) welded coordinates")
+            planes = [np.ascontiguousarray(pts[:, c]) for c in range(dim)]
+        dp = C.POINTER(C.c_double)
+        arr = (dp * dim)(*[_capi.f64ptr(a) for a in planes])
+        L = _capi.lib()
+        fn = L.tm_weld_faces_measure_host if self.host else L.tm_weld_faces_measure
+        _capi.check(fn(dim, self.order, len(self.faces), _i32ptr(self.faces), _i32ptr(self.face_patch), self.info.patches, len(pts), dim, arr, self._patches))
+        self.patches = self._records()
+        return self.patches
+
+    def periodic_faces(self):
+        """Per periodic connection (faces of the side of ranges[0], faces of the side of ranges[1], translation): face t of one is the partner
+        of face t of the other, node (a, c) of one the image of node (p - a, c) of the other."""
+        out = []
+        for q, r in enumerate(self.patches):
+            if r.kind == _capi.TM_PATCH_PERIODIC and r.partner > q:
+                o = self.patches[r.partner]
+                out.append((self.faces[r.begin:r.begin + r.faces], self.faces[o.begin:o.begin + o.faces], r.translation))
+        return out
+
+    def table(self):
+        """The patch table as plain data (what NAME.boundary.json holds)."""
+        return {"order": self.order, "layers": self.layers, "cell_type": self.cell_type, "info": asdict(self.info),
+                "patches": [dict(asdict(r), translation=list(r.translation), normal=list(r.normal)) for r in self.patches]}
+
+
+def resident_boundary(smoother, order=1, orientation=None):
+    """smooth.Smoother.weld_boundary: (faces, face_patch, patches) from the coordinates resident in the handle."""
+    L = _capi.lib()
+    md = _capi.MeshDesc(smoother._mesh, with_coordinates=False)
+    rec = _capi.tm_weld_boundary_info()
+    _capi.check(L.tm_weld_boundary_plan(md.ref(), int(order), 0, C.byref(rec), None))
+    faces = np.empty((rec.faces, rec.nodes_per_face), dtype=np.int32)
+    face_patch = np.empty(rec.faces, dtype=np.int32)
+    patches = (_capi.tm_weld_patch * max(1, rec.patches))()
+    o = None if orientation is None else np.ascontiguousarray([int(v) for v in orientation], dtype=np.int32)
+    if o is not None and len(o) != len(smoother._mesh.blocks):
+        raise ValueError(f"{len(o)} orientations for {len(smoother._mesh.blocks)} blocks")
+    _capi.check(L.tm_smoother_weld_boundary(smoother._h, int(order), None if o is None else _i32ptr(o), _i32ptr(faces), _i32ptr(face_patch), patches))
+    b = Boundary.__new__(Boundary)
+    b.info, b._patches = BoundaryInfo(**rec.as_dict()), patches
+    return faces, face_patch, b._records()
+
+
+def log_boundary(log, boundary, name="mesh"):
+    """One line per patch on `log` (the `weld` logger of the program)."""
+    i = boundary.info
+    log.info("%s: boundary of %d faces in %d patches, %d loop(s), %d irregular nodes", name, i.faces, i.patches, i.loops, i.irregular_nodes)
+    for q, r in enumerate(boundary.patches):
+        log.info("%s: patch %d %-12s %7d faces, measure %.6e, normal (%+.3e, %+.3e, %+.3e), moment %+.6e%s", name, q, r.name, r.faces, r.measure, *r.normal,
+                 r.moment, f", partner {r.partner}, translation ({r.translation[0]:g}, {r.translation[1]:g})" if r.partner >= 0 else "")
 
 
 def cell_type_of(order, hex):
@@ -198,8 +390,18 @@ class Weld:
         _capi.check((L.tm_weld_cells_host if self.host else L.tm_weld_cells)(self._md.ref(), _i32ptr(self.map), self.nodes, p, nk, _i32ptr(cells)))
         return cells
 
-    def mesh(self, src, order=1, distribution="equidistant"):
-        """UnstructuredMesh of `src` (see points) with cells of `order`; the layers follow from the source."""
+    def boundary(self, order=1, layers=None, orientation=None):
+        """The Boundary of this weld at `order` (with layers=nk >= 2 of the stacked mesh): faces in patches over the welded ids
+        (tm_weld_boundary_faces; host=True: tm_weld_boundary_faces_host)."""
+        return Boundary(self, order, layers, orientation)
+
+    def mesh(self, src, order=1, distribution="equidistant", boundary=False, orientation=None):
+        """UnstructuredMesh of `src` (see points) with cells of `order`; the layers follow from the source.  boundary=True: the mesh
+        carries .boundary, the Boundary at that order measured on the welded points (orientation: see Boundary)."""
         pts = self.points(src)
         nk = len(pts) // max(1, self.nodes) if pts.shape[1] == 3 else 0
-        return UnstructuredMesh(pts, self.cells(order, nk), cell_type_of(order, nk >= 2), order, info=self.info, distribution=distribution)
+        um = UnstructuredMesh(pts, self.cells(order, nk), cell_type_of(order, nk >= 2), order, info=self.info, distribution=distribution)
+        if boundary:
+            um.boundary = self.boundary(order, nk, orientation)
+            um.boundary.measure(pts)
+        return um
