@@ -52,6 +52,10 @@ def shapes(p):
 
 
 CASES = [(p,) + s for p in (1, 2, 3, 4) for s in shapes(p)]
+# The records of more than 256 workgroups meet in two stages (records_first_stage, tm_records.hpp).  At p = 4 a workgroup owns 4 x 3
+# elements: 245 x 193 nodes are 61 x 48 elements = 16 x 16 = 256 workgroups, the last block with one stage; 245 x 197 nodes are 61 x 49
+# elements = 16 x 17 = 272 workgroups, the smallest block above it.  One span element, two cuts: the host takes 0.1 s.
+CASES += [(4, 245, 193, 2, 1, "linear", "planar", "gauss_lobatto"), (4, 245, 197, 2, 1, "linear", "planar", "gauss_lobatto")]
 
 
 def stack_for(K, nk, interpolation, mapping, seed):

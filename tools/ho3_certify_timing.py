@@ -114,7 +114,7 @@ def report(trace_csv, out, n):
         lines.append(f"  p {p}  K11 windows ({windows:2d} per call) {len(planes):2d} calls  median {m11 * 1e-3:9.3f} ms  min {min(planes) * 1e-3:9.3f}  max {max(planes) * 1e-3:9.3f}")
         lines.append(f"  p {p}  K17 ({windows:2d} per call)         {len(runs):2d} calls  median {m17 * 1e-3:9.3f} ms  min {min(runs) * 1e-3:9.3f}  max {max(runs) * 1e-3:9.3f}   "
                      f"{m17 * 1e3 / elements:.2f} ns per element   K17 : K16-report = {ratio:.2f} (aim: at most 1) -- {'HIT' if ratio <= 1.0 else f'MISSED by {ratio:.1f} x'}")
-    for label, pattern in (("k_h3_reduce   (records, first stage)", r"\bk_h3_reduce\("), ("k_h3_finalize (records -> tm_ho3_certificate)", r"\bk_h3_finalize\(")):
+    for label, pattern in (("k_hc_reduce   (records, first stage)", r"\bk_hc_reduce\("), ("k_h3_finalize (records -> tm_ho3_certificate)", r"\bk_h3_finalize\(")):
         hits = [us(r) for r in rows if re.search(pattern, r["Kernel_Name"])]
         if hits:
             lines.append(f"  {label:46s} {len(hits):3d} dispatches  median {statistics.median(hits):8.1f} us  min {min(hits):8.1f}  max {max(hits):8.1f}")

@@ -9,6 +9,7 @@
 using namespace tmh;
 
 #include "tm_api_util.hpp"
+#include "tm_devbuf.hpp"
 #include "tm_ilu.hpp"
 #include "tm_refine.hpp"
 #include "tm_quality_dev.hpp"
@@ -25,31 +26,6 @@ bool tmh::smoother_is_live(const tm_smoother* s) {
     std::lock_guard<std::mutex> lock(g_live_mutex);
     return g_live_handles.count(s) != 0;
 }
-
-static void require_gfx950() {
-    static int checked = 0;
-    if (checked) return;
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, dev));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        throw TmError(TM_E_HIP, std::string("libtm_hip is built for gfx950 (MI355X) only, found ") + prop.gcnArchName);
-    checked = 1;
-}
-
-// RAII device buffer for the host-pointer entry points
-struct DevBuf {
-    void* p = nullptr;
-    explicit DevBuf(size_t bytes) {
-        if (hipMalloc(&p, bytes ? bytes : 256) != hipSuccess) throw TmError(TM_E_MEMORY, "hipMalloc failed");
-    }
-    ~DevBuf() { (void)hipFree(p); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    template <class T>
-    T* as() { return static_cast<T*>(p); }
-};
 
 static bool close2(const double* a, const double* b, double tol) { return std::fabs(a[0] - b[0]) <= tol && std::fabs(a[1] - b[1]) <= tol; }
 
@@ -82,8 +58,8 @@ int tm_debug_ilu0_apply_ms(uint64_t n64, const int32_t* Ap, const int32_t* Ai, c
         const size_t nnz = static_cast<size_t>(Ap[n]);
         for (size_t k = 0; k < nnz; ++k)
             if (Ai[k] < 0 || Ai[k] >= n) throw TmError(TM_E_ARG, "InvalidMatrix: column index out of range");
-        Dev d_p(sizeof(int32_t) * (static_cast<size_t>(n) + 1)), d_i(sizeof(int32_t) * nnz), d_v(sizeof(double) * nnz), d_r(sizeof(double2) * static_cast<size_t>(n)),
-            d_z(sizeof(double2) * static_cast<size_t>(n));
+        DevBuf d_p(sizeof(int32_t) * (static_cast<size_t>(n) + 1), "csr p"), d_i(sizeof(int32_t) * nnz, "csr i"), d_v(sizeof(double) * nnz, "csr v"), d_r(sizeof(double2) * static_cast<size_t>(n), "csr r"),
+            d_z(sizeof(double2) * static_cast<size_t>(n), "csr z");
         HIPCHK(hipMemcpy(d_p.p, Ap, sizeof(int32_t) * (static_cast<size_t>(n) + 1), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d_i.p, Ai, sizeof(int32_t) * nnz, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d_v.p, Ax, sizeof(double) * nnz, hipMemcpyHostToDevice));
@@ -125,7 +101,7 @@ int tm_debug_csr_residual_ms(uint64_t n64, const int32_t* Ap, const int32_t* Ai,
         for (size_t k = 0; k < nnz; ++k)
             if (Ai[k] < 0 || Ai[k] >= n) throw TmError(TM_E_ARG, "InvalidMatrix: column index out of range");
         const size_t vb = sizeof(double2) * static_cast<size_t>(n);
-        Dev d_p(sizeof(int32_t) * (static_cast<size_t>(n) + 1)), d_i(sizeof(int32_t) * nnz), d_v(sizeof(double) * nnz), d_x(vb), d_b(vb), d_r(vb), d_dinv(vb);
+        DevBuf d_p(sizeof(int32_t) * (static_cast<size_t>(n) + 1), "csr p"), d_i(sizeof(int32_t) * nnz, "csr i"), d_v(sizeof(double) * nnz, "csr v"), d_x(vb, "csr x"), d_b(vb, "csr b"), d_r(vb, "csr r"), d_dinv(vb, "csr dinv");
         HIPCHK(hipMemcpy(d_p.p, Ap, sizeof(int32_t) * (static_cast<size_t>(n) + 1), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d_i.p, Ai, sizeof(int32_t) * nnz, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d_v.p, Ax, sizeof(double) * nnz, hipMemcpyHostToDevice));
@@ -220,7 +196,7 @@ int tm_stream_probe(uint64_t bytes, int32_t iters, double* copy_GBps, double* tr
         if (bytes < 4096 || iters < 1 || !copy_GBps || !triad_GBps) throw TmError(TM_E_ARG, "bad argument");
         require_gfx950();
         const int64_t n = static_cast<int64_t>(bytes / sizeof(double2));
-        DevBuf a(sizeof(double2) * n), b(sizeof(double2) * n), c(sizeof(double2) * n);
+        DevBuf a(sizeof(double2) * n, "entry point a"), b(sizeof(double2) * n, "entry point b"), c(sizeof(double2) * n, "entry point c");
         ProbeStream ps;
         HIPCHK(hipMemsetAsync(a.p, 0, sizeof(double2) * n, ps.s));
         HIPCHK(hipMemsetAsync(b.p, 0, sizeof(double2) * n, ps.s));
@@ -256,7 +232,7 @@ int tm_white_math_probe(const double* x, const double* y, uint64_t n, double* ou
         if (!x || !y || !out_acos || !out_atan2) throw TmError(TM_E_ARG, "null argument");
         require_gfx950();
         const size_t nb = sizeof(double) * n;
-        DevBuf dx(nb), dy(nb), da(nb), dt(nb);
+        DevBuf dx(nb, "entry point dx"), dy(nb, "entry point dy"), da(nb, "entry point da"), dt(nb, "entry point dt");
         HIPCHK(hipMemcpy(dx.p, x, nb, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(dy.p, y, nb, hipMemcpyHostToDevice));
         HIPCHK(launch_debug_white_math(dx.as<double>(), dy.as<double>(), n, da.as<double>(), dt.as<double>(), nullptr));
@@ -284,7 +260,7 @@ int tm_mg_transfer_probe(int32_t kind, uint64_t nif64, uint64_t njf64, int32_t c
         g.njc = g.cj ? g.njf / 2 + 1 : g.njf;
         const size_t nf = sizeof(double2) * static_cast<size_t>(g.nif) * g.njf, nc = sizeof(double2) * static_cast<size_t>(g.nic) * g.njc;
         const bool in_fine = kind != 2, out_fine = kind >= 2;
-        DevBuf din(in_fine ? nf : nc), dout(out_fine ? nf : nc), dx(kind == 1 ? nc : 0);
+        DevBuf din(in_fine ? nf : nc, "entry point din"), dout(out_fine ? nf : nc, "entry point dout"), dx(kind == 1 ? nc : 0, "entry point dx");
         HIPCHK(hipMemcpy(din.p, in, in_fine ? nf : nc, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(dout.p, out, out_fine ? nf : nc, hipMemcpyHostToDevice));   // (what a kernel leaves alone comes back as it went in)
         if (kind == 1) HIPCHK(hipMemcpy(dx.p, x_coarse, nc, hipMemcpyHostToDevice));
@@ -313,7 +289,7 @@ int tm_tfi_block(double* xy_out, uint64_t ni, uint64_t nj, const double* x_i_min
             throw TmError(TM_E_MISMATCH, "edge end points do not meet at the block corners (tfi.zig:150-162)");
         require_gfx950();
         const size_t ei = sizeof(double) * 2 * ni, ej = sizeof(double) * 2 * nj;
-        DevBuf out(sizeof(double) * 2 * ni * nj), a(ei), b(ei), c(ej), d(ej), ds1(ei / 2), ds2(ei / 2), dt1(ej / 2), dt2(ej / 2);
+        DevBuf out(sizeof(double) * 2 * ni * nj, "entry point out"), a(ei, "entry point a"), b(ei, "entry point b"), c(ej, "entry point c"), d(ej, "entry point d"), ds1(ei / 2, "entry point ds1"), ds2(ei / 2, "entry point ds2"), dt1(ej / 2, "entry point dt1"), dt2(ej / 2, "entry point dt2");
         HIPCHK(hipMemcpy(a.p, x_i_min, ei, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(b.p, x_i_max, ei, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(c.p, x_j_min, ej, hipMemcpyHostToDevice));
@@ -336,7 +312,7 @@ int tm_tfi_linear2d(double* xy_out, uint64_t ni, uint64_t nj, const double* e_i_
         if (ni < 2 || nj < 2 || ni * nj >= (uint64_t{1} << 31)) throw TmError(TM_E_SIZE, "InconsistentSize (tfi.zig:30)");
         require_gfx950();
         const size_t ei = sizeof(double) * 2 * ni, ej = sizeof(double) * 2 * nj;
-        DevBuf out(sizeof(double) * 2 * ni * nj), a(ei), b(ei), c(ej), d(ej);
+        DevBuf out(sizeof(double) * 2 * ni * nj, "entry point out"), a(ei, "entry point a"), b(ei, "entry point b"), c(ej, "entry point c"), d(ej, "entry point d");
         HIPCHK(hipMemcpy(a.p, e_i_min, ei, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(b.p, e_i_max, ei, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(c.p, e_j_min, ej, hipMemcpyHostToDevice));
@@ -583,7 +559,7 @@ int tm_export_soa(const double* xy, uint64_t ni, uint64_t nj, double* x_out, dou
         if (ni < 1 || nj < 1 || ni * nj >= (uint64_t{1} << 31)) throw TmError(TM_E_SIZE, "block size out of range");
         require_gfx950();
         const size_t n = static_cast<size_t>(ni) * nj;
-        DevBuf in(sizeof(double) * 2 * n), out(sizeof(double) * 2 * n);
+        DevBuf in(sizeof(double) * 2 * n, "entry point in"), out(sizeof(double) * 2 * n, "entry point out");
         HIPCHK(hipMemcpy(in.p, xy, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
         HIPCHK(launch_soa_planes(in.as<double2>(), out.as<double>(), out.as<double>() + n, static_cast<int>(ni), static_cast<int>(nj), nullptr));
         HIPCHK(hipMemcpy(x_out, out.p, sizeof(double) * n, hipMemcpyDeviceToHost));
@@ -604,7 +580,7 @@ int tm_mesh_quality(const tm_mesh_desc* mesh, tm_quality* per_block, tm_quality*
             bytes += sizeof(double2) * k.ni * k.nj;
         }
         require_gfx950();
-        DevBuf xy(bytes);
+        DevBuf xy(bytes, "entry point xy");
         std::vector<QualityBlock> blocks;
         size_t off = 0;
         for (uint64_t b = 0; b < mesh->nblocks; ++b) {

@@ -393,17 +393,17 @@ void IluPacked::build(int n, const int32_t* p, const int32_t* ci, const IluLevel
                 ++s;
             }
     }
-    d_col.reset(sizeof(int32_t) * nslots);
-    d_src.reset(sizeof(int32_t) * nslots);
-    d_val.reset(sizeof(double2) * nslots);
-    d_piv.reset(sizeof(double2) * static_cast<size_t>(n));
+    d_col.grow(sizeof(int32_t) * nslots, "ilu col");
+    d_src.grow(sizeof(int32_t) * nslots, "ilu src");
+    d_val.grow(sizeof(double2) * nslots, "ilu val");
+    d_piv.grow(sizeof(double2) * static_cast<size_t>(n), "ilu piv");
     HIPCHK(hipMemcpy(d_col.p, col.data(), sizeof(int32_t) * nslots, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_src.p, src.data(), sizeof(int32_t) * nslots, hipMemcpyHostToDevice));
 }
 
 IluState::IluState(int n_, const int32_t* Ap, const int32_t* Ai, size_t nnz, bool two, int use_packed)
-    : d_diag(sizeof(int32_t) * static_cast<size_t>(n_)), d_lux(sizeof(double) * nnz), d_luy(two ? sizeof(double) * nnz : 0),
-      d_ordL(sizeof(int32_t) * static_cast<size_t>(n_)), d_ptrL(0), d_ordU(sizeof(int32_t) * static_cast<size_t>(n_)), d_ptrU(0), n(n_) {
+    : d_diag(sizeof(int32_t) * static_cast<size_t>(n_), "ilu diag"), d_lux(sizeof(double) * nnz, "ilu lux"), d_luy(two ? sizeof(double) * nnz : 0, "ilu luy"),
+      d_ordL(sizeof(int32_t) * static_cast<size_t>(n_), "ilu ordL"), d_ordU(sizeof(int32_t) * static_cast<size_t>(n_), "ilu ordU"), n(n_) {
     std::vector<int32_t> diag(static_cast<size_t>(n), -1);
     for (int row = 0; row < n; ++row)
         for (int k = Ap[row]; k < Ap[row + 1]; ++k)
@@ -416,8 +416,8 @@ IluState::IluState(int n_, const int32_t* Ap, const int32_t* Ai, size_t nnz, boo
     HIPCHK(hipMemcpy(d_diag.p, diag.data(), sizeof(int32_t) * diag.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_ordL.p, L.order.data(), sizeof(int32_t) * L.order.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_ordU.p, U.order.data(), sizeof(int32_t) * U.order.size(), hipMemcpyHostToDevice));
-    d_ptrL.reset(sizeof(int32_t) * L.ptr.size());
-    d_ptrU.reset(sizeof(int32_t) * U.ptr.size());
+    d_ptrL.grow(sizeof(int32_t) * L.ptr.size(), "ilu ptrL");
+    d_ptrU.grow(sizeof(int32_t) * U.ptr.size(), "ilu ptrU");
     HIPCHK(hipMemcpy(d_ptrL.p, L.ptr.data(), sizeof(int32_t) * L.ptr.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_ptrU.p, U.ptr.data(), sizeof(int32_t) * U.ptr.size(), hipMemcpyHostToDevice));
     if (use_packed < 0) {
@@ -524,7 +524,7 @@ extern "C" int tm_csr_ilu0_probe(uint64_t n64, const int32_t* Ap, const int32_t*
         }
         const int n = static_cast<int>(n64);
         const size_t nnz = static_cast<size_t>(Ap[n]);
-        Dev d_p(sizeof(int32_t) * (static_cast<size_t>(n) + 1)), d_i(sizeof(int32_t) * nnz), d_v(sizeof(double) * nnz);
+        DevBuf d_p(sizeof(int32_t) * (static_cast<size_t>(n) + 1), "csr p"), d_i(sizeof(int32_t) * nnz, "csr i"), d_v(sizeof(double) * nnz, "csr v");
         HIPCHK(hipMemcpy(d_p.p, Ap, sizeof(int32_t) * (static_cast<size_t>(n) + 1), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d_i.p, Ai, sizeof(int32_t) * nnz, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d_v.p, Ax, sizeof(double) * nnz, hipMemcpyHostToDevice));
@@ -535,7 +535,7 @@ extern "C" int tm_csr_ilu0_probe(uint64_t n64, const int32_t* Ap, const int32_t*
         if (rhs && z_out) {
             std::vector<double2> r2(static_cast<size_t>(n));
             for (int k = 0; k < n; ++k) r2[k] = make_double2(rhs[k], rhs[k]);
-            Dev d_r(sizeof(double2) * static_cast<size_t>(n)), d_z(sizeof(double2) * static_cast<size_t>(n));
+            DevBuf d_r(sizeof(double2) * static_cast<size_t>(n), "csr r"), d_z(sizeof(double2) * static_cast<size_t>(n), "csr z");
             HIPCHK(hipMemcpy(d_r.p, r2.data(), sizeof(double2) * r2.size(), hipMemcpyHostToDevice));
             ilu.apply(d_r.as<double2>(), d_z.as<double2>(), nullptr);
             HIPCHK(hipDeviceSynchronize());
@@ -580,14 +580,14 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
         const bool two = Ax_y != nullptr && Ax_y != Ax_x;
         const bool use_ilu = (opt.flags & TM_OPT_PRECOND_ILU0) != 0;
         const size_t vb = sizeof(double2) * static_cast<size_t>(n);
-        Dev d_p(sizeof(int32_t) * (static_cast<size_t>(n) + 1)), d_i(sizeof(int32_t) * nnz), d_vx(sizeof(double) * nnz), d_vy(two ? sizeof(double) * nnz : 0);
-        Dev d_dinv(vb), d_b(vb), d_u(vb), d_r(vb), d_rh(vb), d_pv(vb), d_v(vb), d_s(vb), d_t(vb), d_tmp(sizeof(double) * 2 * static_cast<size_t>(n));
+        DevBuf d_p(sizeof(int32_t) * (static_cast<size_t>(n) + 1), "csr p"), d_i(sizeof(int32_t) * nnz, "csr i"), d_vx(sizeof(double) * nnz, "csr vx"), d_vy(two ? sizeof(double) * nnz : 0, "csr vy");
+        DevBuf d_dinv(vb, "csr dinv"), d_b(vb, "csr b"), d_u(vb, "csr u"), d_r(vb, "csr r"), d_rh(vb, "csr rh"), d_pv(vb, "csr pv"), d_v(vb, "csr v"), d_s(vb, "csr s"), d_t(vb, "csr t"), d_tmp(sizeof(double) * 2 * static_cast<size_t>(n), "csr tmp");
         const int nwg = (n + 255) / 256, nwg_vec = vec_nwg(n);
         // small systems are bound by dependent launches: the scalar steps travel with the kernels that consume them (LazyScalars,
         // tm_kernels.h; three partial-sum buffers in rotation, two scalar blocks) -- 5 launches per iteration instead of 9
         const int npart = std::max(nwg, nwg_vec);
         const bool lazy = npart <= 512 && !(opt.flags & TM_OPT_EAGER_SCALARS);
-        Dev d_part(sizeof(double) * MAX_PARTIALS * static_cast<size_t>(npart) * (lazy ? 3 : 1)), d_red(sizeof(double) * MAX_PARTIALS), d_S(sizeof(KrylovScalars) * 2);
+        DevBuf d_part(sizeof(double) * MAX_PARTIALS * static_cast<size_t>(npart) * (lazy ? 3 : 1), "csr part"), d_red(sizeof(double) * MAX_PARTIALS, "csr red"), d_S(sizeof(KrylovScalars) * 2, "csr S");
         hipStream_t st = nullptr;
         HIPCHK(hipMemcpyAsync(d_p.p, Ap, sizeof(int32_t) * (static_cast<size_t>(n) + 1), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d_i.p, Ai, sizeof(int32_t) * nnz, hipMemcpyHostToDevice, st));
@@ -603,7 +603,7 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
         upload2(bx, by, d_b.as<double2>());
         upload2(x, y, d_u.as<double2>());   // warm start: the caller's x_new / y_new (BiCGStab.zig:136-153 seeds them from the coordinates)
         CsrDev A{n, d_p.as<int32_t>(), d_i.as<int32_t>(), d_vx.as<double>(), two ? d_vy.as<double>() : d_vx.as<double>(), d_dinv.as<double2>()};
-        Dev d_dvec(use_ilu ? vb : 0), d_ph(use_ilu ? vb : 0), d_sh(use_ilu ? vb : 0);
+        DevBuf d_dvec(use_ilu ? vb : 0, "csr dvec"), d_ph(use_ilu ? vb : 0, "csr ph"), d_sh(use_ilu ? vb : 0, "csr sh");
         hipLaunchKernelGGL(k_csr_dinv, dim3(nwg), dim3(256), 0, st, n, A.p, A.i, A.vx, A.vy, d_dinv.as<double2>(), use_ilu ? d_dvec.as<double2>() : nullptr);
         HIPCHK(hipGetLastError());
         // ILU(0) as RIGHT preconditioner (BiCGStab.zig:314-316, 340-342) of the row-equilibrated operator B = D^-1 A the device iterates on:
@@ -638,7 +638,7 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
             double rr0[2] = {0.0, 0.0};
         };
         const bool use_gmres = opt.inner == TM_INNER_GMRES;
-        Dev d_W(use_gmres ? vb : 0), d_V(use_gmres ? vb * (GMRES_M + 1) : 0), d_G(use_gmres ? sizeof(GmresScalars) : 0);
+        DevBuf d_W(use_gmres ? vb : 0, "csr W"), d_V(use_gmres ? vb * (GMRES_M + 1) : 0, "csr V"), d_G(use_gmres ? sizeof(GmresScalars) : 0, "csr G");
         auto solve = [&](const double2* bvec, double2* u, double rtol) -> SolveOut {
         SolveOut out;
         hipLaunchKernelGGL(k_csr_bnorm, dim3(nwg), dim3(256), 0, st, n, bvec, A.dinv, partials);
@@ -788,7 +788,7 @@ extern "C" int tm_csr_solve(uint64_t n64, const int32_t* Ap, const int32_t* Ai, 
             double rtol_c = opt.rtol;
             if (const char* e = std::getenv("TM_REFINE_RTOL"))
                 if (std::atof(e) > 0.0) rtol_c = std::atof(e);
-            Dev d_rr(vb), d_d(vb);
+            DevBuf d_rr(vb, "csr rr"), d_d(vb, "csr d");
             double h_red[MAX_PARTIALS] = {0.0};
             uint32_t steps = 0;
             uint64_t it_corr = 0;
@@ -855,8 +855,8 @@ extern "C" int tm_csr_residual(uint64_t n64, const int32_t* Ap, const int32_t* A
 
         const bool two = Ax_y != nullptr && Ax_y != Ax_x;
         const size_t vb = sizeof(double2) * static_cast<size_t>(n);
-        Dev d_p(sizeof(int32_t) * (static_cast<size_t>(n) + 1)), d_i(sizeof(int32_t) * nnz), d_vx(sizeof(double) * nnz), d_vy(two ? sizeof(double) * nnz : 0);
-        Dev d_b(vb), d_u(vb), d_tmp(sizeof(double) * 2 * static_cast<size_t>(n));
+        DevBuf d_p(sizeof(int32_t) * (static_cast<size_t>(n) + 1), "csr p"), d_i(sizeof(int32_t) * nnz, "csr i"), d_vx(sizeof(double) * nnz, "csr vx"), d_vy(two ? sizeof(double) * nnz : 0, "csr vy");
+        DevBuf d_b(vb, "csr b"), d_u(vb, "csr u"), d_tmp(sizeof(double) * 2 * static_cast<size_t>(n), "csr tmp");
         const int nwg = csr_nwg(n);
         hipStream_t st = nullptr;
         HIPCHK(hipMemcpyAsync(d_p.p, Ap, sizeof(int32_t) * (static_cast<size_t>(n) + 1), hipMemcpyHostToDevice, st));

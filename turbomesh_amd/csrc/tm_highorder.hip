@@ -20,6 +20,7 @@
 // floating-point atomics: results do not depend on scheduling.
 #include "tm_highorder_dev.hpp"
 #include "tm_stack_dev.hpp"
+#include "tm_dispatch.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -30,7 +31,6 @@ namespace tmh {
 // p = 4) were measured and are slower (437 / 602 us against 306 / 327 us on 4097^2): fewer workgroups fit a CU, and the kernel lives on
 // the overlap of one workgroup's loads with another's arithmetic.
 constexpr int HO_THREADS = 256, HO_WAVES = HO_THREADS / 64;
-constexpr int HO_REDUCE_FROM = 256, HO_REDUCE_GROUPS = 64;   // records from which the finalize gets a first stage, and its workgroups
 constexpr int ho_tile_elements(int p) { return p == 1 ? 16 : 32 / p; }
 
 __device__ __forceinline__ unsigned long long ho_shfl(unsigned long long v, int off) { return __shfl_down(v, off, 64); }
@@ -147,43 +147,23 @@ __global__ __launch_bounds__(HO_THREADS) void k_ho_elevate(const double2* __rest
     }
 }
 
-// large blocks: workgroup g reduces the records [g * chunk, (g+1) * chunk) to one (a lone wave over the 16 641 records of a 4097^2 block
-// takes as long as the elevation itself)
+// large blocks: workgroup g reduces the records [g * chunk, (g+1) * chunk) to one
 __global__ __launch_bounds__(64) void k_ho_reduce(const HoAcc* __restrict__ partials, int nwg, int chunk, HoAcc* __restrict__ out) {
     __shared__ HoAcc sh[64];
     const int begin = static_cast<int>(blockIdx.x) * chunk, end = begin + chunk < nwg ? begin + chunk : nwg;
-    ho_reduce_wave(partials, begin, end, sh);
+    records_reduce_wave<HoAcc, ho_init, ho_combine>(partials, begin, end, sh);
     if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
 }
 __global__ __launch_bounds__(64) void k_ho_finalize(const HoAcc* __restrict__ partials, int nwg, unsigned long long block, int Ei, int Ej, int order,
                                                     tm_ho_quality* __restrict__ out) {
     __shared__ HoAcc sh[64];
-    ho_reduce_wave(partials, 0, nwg, sh);
+    records_reduce_wave<HoAcc, ho_init, ho_combine>(partials, 0, nwg, sh);
     if (threadIdx.x == 0) ho_finish(sh[0], block, static_cast<uint64_t>(Ei), static_cast<uint64_t>(Ej), order, out);
 }
 
 // ------------------------------------------------------------------ host driver
-HoDev::~HoDev() {
-    if (tab) (void)hipFree(tab);
-    if (planes) (void)hipFree(planes);
-    if (pairs) (void)hipFree(pairs);
-    if (partials) (void)hipFree(partials);
-    if (out) (void)hipFree(out);
-}
-
-static void ho_grow(void** p, size_t* cap, size_t need, size_t elem, const char* what) {
-    if (*cap >= need) return;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, need * elem) != hipSuccess) throw TmError(TM_E_MEMORY, std::string("hipMalloc failed (") + what + ")");
-    *cap = need;
-}
-
-template <int P>
-static void ho_launch(dim3 grid, hipStream_t st, const double2* X, int ni, int nj, int Ei, int Ej, const double* tab, int identity, double* px, double* py,
-                      double2* pairs, HoAcc* partials) {
-    hipLaunchKernelGGL(k_ho_elevate<P>, grid, dim3(HO_THREADS), 0, st, X, ni, nj, Ei, Ej, tab, identity, px, py, pairs, partials);
+void ho_reduce_launch(const HoAcc* partials, int nrec, int chunk, int groups, HoAcc* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_ho_reduce, dim3(groups), dim3(64), 0, st, partials, nrec, chunk, out);
 }
 
 void HoDev::run(const HoPlan& pl, const double2* X, int ni, int nj, uint64_t block, hipStream_t st, double* x, double* y, tm_ho_quality* q, double* sj) {
@@ -192,46 +172,32 @@ void HoDev::run(const HoPlan& pl, const double2* X, int ni, int nj, uint64_t blo
     const dim3 grid((Ej + E - 1) / E, (Ei + E - 1) / E);
     if (grid.y > 65535u) throw TmError(TM_E_SIZE, "InconsistentSize: too many element rows for one launch");
     const size_t nwg = static_cast<size_t>(grid.x) * grid.y;
-    if (!tab && hipMalloc(reinterpret_cast<void**>(&tab), sizeof(double) * 2 * HO_MAX_TABLE) != hipSuccess) throw TmError(TM_E_MEMORY, "hipMalloc failed (elevation tables)");
-    if (!out && hipMalloc(reinterpret_cast<void**>(&out), sizeof(tm_ho_quality)) != hipSuccess) throw TmError(TM_E_MEMORY, "hipMalloc failed (elevation record)");
     const bool want_planes = x && y;
-    if (want_planes) ho_grow(reinterpret_cast<void**>(&planes), &planes_cap, 2 * n, sizeof(double), "elevated planes");
-    ho_grow(reinterpret_cast<void**>(&pairs), &pairs_cap, elements, sizeof(double2), "element pairs");
-    ho_grow(reinterpret_cast<void**>(&partials), &partials_cap, nwg + HO_REDUCE_GROUPS, sizeof(HoAcc), "elevation records");   // + the second stage's
-    HIPCHK(hipMemcpyAsync(tab, pl.tab, sizeof(double) * 2 * (p + 1) * (p + 1), hipMemcpyHostToDevice, st));
-    double* dx = want_planes ? planes : nullptr;
-    double* dy = want_planes ? planes + n : nullptr;
+    tab.grow(sizeof(double) * 2 * HO_MAX_TABLE, "elevation tables");
+    out.grow(sizeof(tm_ho_quality), "elevation record");
+    if (want_planes) planes.grow(sizeof(double) * 2 * n, "elevated planes");
+    pairs.grow(sizeof(double2) * elements, "element pairs");
+    partials.grow(sizeof(HoAcc) * (nwg + RECORDS_REDUCE_GROUPS), "elevation records");   // + the second stage's
+    HIPCHK(hipMemcpyAsync(tab.p, pl.tab, sizeof(double) * 2 * (p + 1) * (p + 1), hipMemcpyHostToDevice, st));
+    double* dx = want_planes ? planes.as<double>() : nullptr;
+    double* dy = want_planes ? planes.as<double>() + n : nullptr;
     const int identity = pl.identity ? 1 : 0;
-    switch (p) {
-    case 1: ho_launch<1>(grid, st, X, ni, nj, Ei, Ej, tab, identity, dx, dy, pairs, partials); break;
-    case 2: ho_launch<2>(grid, st, X, ni, nj, Ei, Ej, tab, identity, dx, dy, pairs, partials); break;
-    case 3: ho_launch<3>(grid, st, X, ni, nj, Ei, Ej, tab, identity, dx, dy, pairs, partials); break;
-    case 4: ho_launch<4>(grid, st, X, ni, nj, Ei, Ej, tab, identity, dx, dy, pairs, partials); break;
-    case 5: ho_launch<5>(grid, st, X, ni, nj, Ei, Ej, tab, identity, dx, dy, pairs, partials); break;
-    case 6: ho_launch<6>(grid, st, X, ni, nj, Ei, Ej, tab, identity, dx, dy, pairs, partials); break;
-    case 7: ho_launch<7>(grid, st, X, ni, nj, Ei, Ej, tab, identity, dx, dy, pairs, partials); break;
-    default: ho_launch<8>(grid, st, X, ni, nj, Ei, Ej, tab, identity, dx, dy, pairs, partials); break;
-    }
+    dispatch_int<1, 8>(p, [&](auto P) {
+        hipLaunchKernelGGL(k_ho_elevate<P()>, grid, dim3(HO_THREADS), 0, st, X, ni, nj, Ei, Ej, tab.as<double>(), identity, dx, dy, pairs.as<double2>(),
+                           partials.as<HoAcc>());
+    });
     HIPCHK(hipGetLastError());
-    const HoAcc* records = partials;
-    int nrec = static_cast<int>(nwg);
-    if (nrec > HO_REDUCE_FROM) {   // two stages: at most HO_REDUCE_GROUPS records are left for the finalize
-        const int chunk = (nrec + HO_REDUCE_GROUPS - 1) / HO_REDUCE_GROUPS, groups = (nrec + chunk - 1) / chunk;
-        hipLaunchKernelGGL(k_ho_reduce, dim3(groups), dim3(64), 0, st, partials, nrec, chunk, partials + nwg);
-        HIPCHK(hipGetLastError());
-        records = partials + nwg;
-        nrec = groups;
-    }
-    hipLaunchKernelGGL(k_ho_finalize, dim3(1), dim3(64), 0, st, records, nrec, static_cast<unsigned long long>(block), Ei, Ej, p, out);
+    const Records<HoAcc> rec_in = records_first_stage(partials.as<HoAcc>(), nwg, st, ho_reduce_launch);   // at most RECORDS_REDUCE_GROUPS records are left for the finalize
+    hipLaunchKernelGGL(k_ho_finalize, dim3(1), dim3(64), 0, st, rec_in.p, rec_in.n, static_cast<unsigned long long>(block), Ei, Ej, p, out.as<tm_ho_quality>());
     HIPCHK(hipGetLastError());
     tm_ho_quality rec;
     std::vector<double> jj(sj ? 2 * elements : 0);
-    HIPCHK(hipMemcpyAsync(&rec, out, sizeof(rec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&rec, out.p, sizeof(rec), hipMemcpyDeviceToHost, st));
     if (want_planes) {
         HIPCHK(hipMemcpyAsync(x, dx, sizeof(double) * n, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(y, dy, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     }
-    if (sj) HIPCHK(hipMemcpyAsync(jj.data(), pairs, sizeof(double2) * elements, hipMemcpyDeviceToHost, st));
+    if (sj) HIPCHK(hipMemcpyAsync(jj.data(), pairs.p, sizeof(double2) * elements, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (sj) ho_sj_from_pairs(jj.data(), elements, rec.orientation, sj);
     if (q) *q = rec;
@@ -257,9 +223,9 @@ extern "C" int tm_ho_elevate(const tm_mesh_desc* mesh, const tm_ho_opt* opt, uin
         if ((x == nullptr) != (y == nullptr)) throw TmError(TM_E_ARG, "x and y come together");
         const HoPlan pl = ho_plan(opt);
         const tm_block& b = ho_block_of(mesh, pl, block);
-        require_gfx950_stack();
+        require_gfx950();
         const size_t n = static_cast<size_t>(b.ni) * b.nj;
-        StackBuf in(sizeof(double2) * n, "block to elevate");
+        DevBuf in(sizeof(double2) * n, "block to elevate");
         HIPCHK(hipMemcpy(in.p, b.xy, sizeof(double2) * n, hipMemcpyHostToDevice));
         HoDev dev;
         dev.run(pl, in.as<double2>(), static_cast<int>(b.ni), static_cast<int>(b.nj), block, nullptr, x, y, q, sj);

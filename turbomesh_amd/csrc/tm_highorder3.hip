@@ -2,33 +2,22 @@
 // k_stack_elevate (tm_highorder3_kernel.hpp, instantiated per order in tm_highorder3_p*.hip), the fixed-order combination of the
 // workgroups' records, and the copies back.
 #include "tm_highorder3_dev.hpp"
+#include "tm_dispatch.hpp"
 
 #include <cstring>
 
 namespace tmh {
 
-// large blocks: workgroup w reduces the records [w * chunk, (w+1) * chunk) to one, as k_ho_reduce does for K13
-__global__ __launch_bounds__(64) void k_ho3_reduce(const HoAcc* __restrict__ partials, int nwg, int chunk, HoAcc* __restrict__ out) {
-    __shared__ HoAcc sh[64];
-    const int begin = static_cast<int>(blockIdx.x) * chunk, end = begin + chunk < nwg ? begin + chunk : nwg;
-    ho_reduce_wave(partials, begin, end, sh);
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
-}
 __global__ __launch_bounds__(64) void k_ho3_finalize(const HoAcc* __restrict__ partials, int nwg, unsigned long long block, int Ei, int Ej, int Eg, int order,
                                                      tm_ho3_quality* __restrict__ out) {
     __shared__ HoAcc sh[64];
-    ho_reduce_wave(partials, 0, nwg, sh);
+    records_reduce_wave<HoAcc, ho_init, ho_combine>(partials, 0, nwg, sh);
     if (threadIdx.x == 0) ho3_finish(sh[0], block, static_cast<uint64_t>(Ei), static_cast<uint64_t>(Ej), static_cast<uint64_t>(Eg), order, out);
 }
 
 static hipError_t ho3_launch_p(int p, int K, const Ho3Launch& a, hipStream_t st) {
-    switch (p) {
-    case 1: return ho3_launch<1>(K, a, st);
-    case 2: return ho3_launch<2>(K, a, st);
-    case 3: return ho3_launch<3>(K, a, st);
-    case 4: return ho3_launch<4>(K, a, st);
-    default: return hipErrorInvalidValue;
-    }
+    if (p < 1 || p > 4) return hipErrorInvalidValue;
+    return dispatch_int<1, 4>(p, [&](auto P) { return ho3_launch<P()>(K, a, st); });
 }
 
 // Tables up, K16 and the finalize on `st`, planes / record / pairs back; returns when they have arrived.  The sizes have been checked.
@@ -41,27 +30,22 @@ void ho3_run(const StackPlan& p, const HoPlan& pl, StackCuts& cuts, uint64_t blo
     stack_fill_radii(p, cuts);
     StackSurfDev sd;
     if (sf) stack_surf_upload(p, *sf, cuts, sd, st);
-    std::unique_ptr<StackBuf> d_outside;
+    DevBuf d_outside;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are copied out as they are");
     if (sf && outside) {
-        d_outside = std::make_unique<StackBuf>(sizeof(unsigned long long) * TM_STACK_MAX_CUTS, "stack outside counts");
-        HIPCHK(hipMemsetAsync(d_outside->p, 0, sizeof(unsigned long long) * TM_STACK_MAX_CUTS, st));
+        d_outside.grow(sizeof(unsigned long long) * TM_STACK_MAX_CUTS, "stack outside counts");
+        HIPCHK(hipMemsetAsync(d_outside.p, 0, sizeof(unsigned long long) * TM_STACK_MAX_CUTS, st));
     }
-    std::vector<double> table(static_cast<size_t>(p.nlayers) * (K + 1) + 2 * HO_MAX_TABLE);   // the weight rows, then T and D
-    for (uint64_t k = 0; k < p.nlayers; ++k) {
-        std::memcpy(&table[k * (K + 1)], &p.weights[k * K], sizeof(double) * K);
-        table[k * (K + 1) + K] = p.layers[k];
-    }
+    std::vector<double> table = stack_weight_table(p, 0, p.nlayers, 2 * HO_MAX_TABLE);   // the weight rows, then T and D
     const size_t tab_at = static_cast<size_t>(p.nlayers) * (K + 1);
     std::memcpy(&table[tab_at], pl.tab, sizeof(double) * 2 * (P + 1) * (P + 1));
     const size_t plane = static_cast<size_t>(ni) * nj, n = planes ? plane * (g_count * P + 1) : 0, elements = static_cast<size_t>(Ei) * Ej * Eg;
     const dim3 grid((Ej + ho3_tile_ej(P) - 1) / ho3_tile_ej(P), (Ei + ho3_tile_ei(P) - 1) / ho3_tile_ei(P));
     if (grid.y > 65535u) throw TmError(TM_E_SIZE, "InconsistentSize: too many element rows for one launch");
     const size_t nwg = static_cast<size_t>(grid.x) * grid.y;   // the records buffer is sized from the very grid the launcher forms
-    StackBuf d_table(sizeof(double) * table.size(), "stack weights and elevation tables"), d_out(sizeof(double) * 3 * n, "elevated planes"),
-        d_pairs(sj && !pairs_dev ? sizeof(double2) * elements : 0, "element pairs"), d_rec(report ? sizeof(HoAcc) * (nwg + HO3_REDUCE_GROUPS) : 0, "elevation records"),
-        d_q(sizeof(tm_ho3_quality), "elevation record");
-    HIPCHK(hipMemcpyAsync(d_table.p, table.data(), sizeof(double) * table.size(), hipMemcpyHostToDevice, st));
+    DevBuf d_table, d_out(sizeof(double) * 3 * n, "elevated planes"), d_pairs(sj && !pairs_dev ? sizeof(double2) * elements : 0, "element pairs"),
+        d_rec(report ? sizeof(HoAcc) * (nwg + RECORDS_REDUCE_GROUPS) : 0, "elevation records"), d_q(sizeof(tm_ho3_quality), "elevation record");
+    d_table.upload(table.data(), table.size(), st, "stack weights and elevation tables");
     Ho3Launch a{};
     a.cuts = cuts;
     a.surf = sd.surf;
@@ -82,27 +66,19 @@ void ho3_run(const StackPlan& p, const HoPlan& pl, StackCuts& cuts, uint64_t blo
     a.Z = planes ? d_out.as<double>() + 2 * n : nullptr;
     a.pairs = pairs_dev ? pairs_dev : sj ? d_pairs.as<double2>() : nullptr;
     a.partials = report ? d_rec.as<HoAcc>() : nullptr;
-    a.outside = d_outside ? d_outside->as<unsigned long long>() : nullptr;
+    a.outside = d_outside.as<unsigned long long>();
     HIPCHK(ho3_launch_p(P, K, a, st));
     tm_ho3_quality rec{};
     if (report) {
-        const HoAcc* records = a.partials;
-        int nrec = static_cast<int>(nwg);
-        if (nrec > HO3_REDUCE_FROM) {   // two stages: at most HO3_REDUCE_GROUPS records are left for the finalize
-            const int chunk = (nrec + HO3_REDUCE_GROUPS - 1) / HO3_REDUCE_GROUPS, groups = (nrec + chunk - 1) / chunk;
-            hipLaunchKernelGGL(k_ho3_reduce, dim3(groups), dim3(64), 0, st, a.partials, nrec, chunk, a.partials + nwg);
-            HIPCHK(hipGetLastError());
-            records = a.partials + nwg;
-            nrec = groups;
-        }
-        hipLaunchKernelGGL(k_ho3_finalize, dim3(1), dim3(64), 0, st, records, nrec, static_cast<unsigned long long>(block), a.Ei, a.Ej, static_cast<int>(Eg), P,
+        const Records<HoAcc> rec_in = records_first_stage(a.partials, nwg, st, ho_reduce_launch);
+        hipLaunchKernelGGL(k_ho3_finalize, dim3(1), dim3(64), 0, st, rec_in.p, rec_in.n, static_cast<unsigned long long>(block), a.Ei, a.Ej, static_cast<int>(Eg), P,
                            d_q.as<tm_ho3_quality>());
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&rec, d_q.p, sizeof(rec), hipMemcpyDeviceToHost, st));
     }
     std::vector<double> jj(sj ? 2 * elements : 0);
     if (sj) HIPCHK(hipMemcpyAsync(jj.data(), d_pairs.p, sizeof(double2) * elements, hipMemcpyDeviceToHost, st));
-    if (d_outside) HIPCHK(hipMemcpyAsync(outside, d_outside->p, sizeof(uint64_t) * K, hipMemcpyDeviceToHost, st));
+    if (d_outside.p) HIPCHK(hipMemcpyAsync(outside, d_outside.p, sizeof(uint64_t) * K, hipMemcpyDeviceToHost, st));
     if (planes) {
         HIPCHK(hipMemcpyAsync(x, a.X, sizeof(double) * n, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(y, a.Y, sizeof(double) * n, hipMemcpyDeviceToHost, st));
@@ -130,23 +106,16 @@ extern "C" int tm_stack_elevate(const tm_mesh_desc* const* cuts, const tm_stack_
                                 uint64_t g_begin, uint64_t g_count, double* x, double* y, double* z, tm_ho3_quality* q, double* sj, uint64_t* outside) {
     return guarded([&]() {
         if ((x == nullptr) != (y == nullptr) || (x == nullptr) != (z == nullptr)) throw TmError(TM_E_ARG, "x, y and z come together");
-        if (!sopt) throw TmError(TM_E_ARG, "null stack options, span or layers");
-        const bool rev = sopt->mapping == TM_STACK_REVOLUTION;
-        if (!rev && surfaces) throw TmError(TM_E_ARG, "meridional tables go with TM_STACK_REVOLUTION only");
         SurfPlan sf;
-        const StackPlan p = rev ? stack_plan_surf(sopt, surfaces, sf) : stack_plan(sopt);
+        const SurfPlan* sfp = nullptr;
+        const StackPlan p = stack_plan_any(sopt, surfaces, sf, &sfp);
         uint64_t ni = 0, nj = 0;
         stack_check_cuts(cuts, p.ncuts, block, &ni, &nj);
         const HoPlan pl = ho3_checked(p, opt, block, ni, nj, g_begin, g_count, x != nullptr);
-        require_gfx950_stack();
-        const size_t n = static_cast<size_t>(ni) * nj;
-        StackBuf in(sizeof(double2) * n * p.ncuts, "stack cuts");
+        DevBuf in;
         StackCuts dc{};
-        for (int c = 0; c < p.ncuts; ++c) {
-            dc.xy[c] = in.as<double2>() + n * c;
-            HIPCHK(hipMemcpy(in.as<double2>() + n * c, cuts[c]->blocks[block].xy, sizeof(double2) * n, hipMemcpyHostToDevice));
-        }
-        ho3_run(p, pl, dc, block, ni, nj, g_begin, g_count, x, y, z, q, sj, nullptr, rev ? &sf : nullptr, outside);
+        stack_upload_cuts(cuts, p.ncuts, block, ni, nj, in, dc);
+        ho3_run(p, pl, dc, block, ni, nj, g_begin, g_count, x, y, z, q, sj, nullptr, sfp, outside);
         return TM_OK;
     });
 }
@@ -156,18 +125,16 @@ extern "C" int tm_stack_smoothers_elevate(tm_smoother* const* cuts, const tm_sta
     return guarded([&]() {
         if (!cuts) throw TmError(TM_E_ARG, "null argument");
         if ((x == nullptr) != (y == nullptr) || (x == nullptr) != (z == nullptr)) throw TmError(TM_E_ARG, "x, y and z come together");
-        if (!sopt) throw TmError(TM_E_ARG, "null stack options, span or layers");
-        const bool rev = sopt->mapping == TM_STACK_REVOLUTION;
-        if (!rev && surfaces) throw TmError(TM_E_ARG, "meridional tables go with TM_STACK_REVOLUTION only");
         SurfPlan sf;
-        const StackPlan p = rev ? stack_plan_surf(sopt, surfaces, sf) : stack_plan(sopt);
+        const SurfPlan* sfp = nullptr;
+        const StackPlan p = stack_plan_any(sopt, surfaces, sf, &sfp);
         StackCuts dc{};
         uint64_t ni = 0, nj = 0;
         stack_resident_cuts(cuts, p, block, dc, &ni, &nj);
         const HoPlan pl = ho3_checked(p, opt, block, ni, nj, g_begin, g_count, x != nullptr);
         std::vector<std::unique_ptr<StackEvent>> events;
         const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
-        ho3_run(p, pl, dc, block, ni, nj, g_begin, g_count, x, y, z, q, sj, st, rev ? &sf : nullptr, outside);   // synchronises st
+        ho3_run(p, pl, dc, block, ni, nj, g_begin, g_count, x, y, z, q, sj, st, sfp, outside);   // synchronises st
         return TM_OK;
     });
 }

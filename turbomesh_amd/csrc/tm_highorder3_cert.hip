@@ -19,8 +19,9 @@
 // another); no floating-point atomics, no sums.  The walk's control flow is uniform over the workgroup: every thread holds the same
 // reduced extremes.
 //
-// Records.  One HcAcc per workgroup; k_h3_finalize (behind k_h3_reduce from 257 records on) combines them, the scheme of K14.
+// Records.  One HcAcc per workgroup; k_h3_finalize (behind K14's k_hc_reduce from 257 records on) combines them, the scheme of K14.
 #include "tm_highorder3_cert_dev.hpp"
+#include "tm_dispatch.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -28,7 +29,6 @@
 namespace tmh {
 
 constexpr int h3_rounds(int p) { return p == 1 ? 16 : p == 2 ? 8 : 4; }   // consecutive elements per workgroup
-constexpr int H3_REDUCE_FROM = 256, H3_REDUCE_GROUPS = 64;
 constexpr size_t H3_WINDOW_BYTES = size_t{256} << 20;
 constexpr int h3_threads(int p) { return p == 1 ? 64 : 256; }
 constexpr int h3_cmax(int a, int b) { return a > b ? a : b; }
@@ -247,39 +247,17 @@ __global__ __launch_bounds__(h3_threads(P)) void k_ho3_certify(H3Args A) {
     if (tid == 0) A.partials[blockIdx.x] = acc;
 }
 
-__device__ __forceinline__ void h3_reduce_wave(const HcAcc* __restrict__ partials, int begin, int end, HcAcc* sh) {
-    HcAcc a;
-    hc_init(a);
-    for (int r = begin + static_cast<int>(threadIdx.x); r < end; r += 64) hc_combine(a, partials[r]);
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int off = 32; off > 0; off >>= 1) {
-        if (static_cast<int>(threadIdx.x) < off) hc_combine(sh[threadIdx.x], sh[threadIdx.x + off]);
-        __syncthreads();
-    }
-}
-__global__ __launch_bounds__(64) void k_h3_reduce(const HcAcc* __restrict__ partials, int nwg, int chunk, HcAcc* __restrict__ out) {
-    __shared__ HcAcc sh[64];
-    const int begin = static_cast<int>(blockIdx.x) * chunk, end = begin + chunk < nwg ? begin + chunk : nwg;
-    h3_reduce_wave(partials, begin, end, sh);
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
-}
 __global__ __launch_bounds__(64) void k_h3_finalize(const HcAcc* __restrict__ partials, int nwg, unsigned long long block, int Ei, int Ej, int Eg, int order,
                                                     int orientation, int max_depth, tm_ho3_certificate* __restrict__ out) {
     __shared__ HcAcc sh[64];
-    h3_reduce_wave(partials, 0, nwg, sh);
+    records_reduce_wave<HcAcc, hc_init, hc_combine>(partials, 0, nwg, sh);
     if (threadIdx.x == 0)
         h3_finish(sh[0], block, static_cast<uint64_t>(Ei), static_cast<uint64_t>(Ej), static_cast<uint64_t>(Eg), order, orientation, max_depth, out);
 }
 
 // ------------------------------------------------------------------ host driver
 static void h3_launch(int p, unsigned groups, hipStream_t st, const H3Args& a) {
-    switch (p) {
-    case 1: hipLaunchKernelGGL(k_ho3_certify<1>, dim3(groups), dim3(h3_threads(1)), 0, st, a); break;
-    case 2: hipLaunchKernelGGL(k_ho3_certify<2>, dim3(groups), dim3(h3_threads(2)), 0, st, a); break;
-    case 3: hipLaunchKernelGGL(k_ho3_certify<3>, dim3(groups), dim3(h3_threads(3)), 0, st, a); break;
-    default: hipLaunchKernelGGL(k_ho3_certify<4>, dim3(groups), dim3(h3_threads(4)), 0, st, a); break;
-    }
+    dispatch_int<1, 4>(p, [&](auto P) { hipLaunchKernelGGL(k_ho3_certify<P()>, dim3(groups), dim3(h3_threads(P())), 0, st, a); });
 }
 
 uint64_t h3_window_elements(int p, uint64_t ni, uint64_t nj, uint64_t Eg) {
@@ -302,7 +280,7 @@ void h3_run(const StackPlan& p, const HoPlan& pl, StackCuts& cuts, uint64_t bloc
     const size_t elements = static_cast<size_t>(Ei) * Ej * Eg, per_layer = static_cast<size_t>(Ei) * Ej;
     const size_t rounds = static_cast<size_t>(h3_rounds(P));
     if (elements / rounds + Eg >= (uint64_t{1} << 31)) throw TmError(TM_E_SIZE, "InconsistentSize: too many elements for one call");
-    StackBuf d_pairs(sizeof(double2) * elements, "element pairs");
+    DevBuf d_pairs(sizeof(double2) * elements, "element pairs");
     tm_ho3_quality rec{};
     ho3_run(p, pl, cuts, block, ni, nj, 0, 0, nullptr, nullptr, nullptr, &rec, nullptr, st, sf, outside, d_pairs.as<double2>());   // synchronises st
 
@@ -311,20 +289,16 @@ void h3_run(const StackPlan& p, const HoPlan& pl, StackCuts& cuts, uint64_t bloc
     StackSurfDev sd;
     if (sf) stack_surf_upload(p, *sf, cuts, sd, st);
     const size_t rows = static_cast<size_t>(p.nlayers) * (K + 1);
-    std::vector<double> table(rows + H3_MAX_TAB);   // the weight rows of every layer, then the certificate's tables
-    for (uint64_t k = 0; k < p.nlayers; ++k) {
-        std::memcpy(&table[k * (K + 1)], &p.weights[k * K], sizeof(double) * K);
-        table[k * (K + 1) + K] = p.layers[k];
-    }
+    std::vector<double> table = stack_weight_table(p, 0, p.nlayers, H3_MAX_TAB);   // the weight rows of every layer, then the certificate's tables
     std::memcpy(&table[rows], hp.tab, sizeof(double) * h3_tab_size(P));
     const uint64_t gw = h3_window_elements(P, ni, nj, Eg);
     const size_t plane = static_cast<size_t>(ni) * nj, nmax = plane * (gw * P + 1);
     size_t nwg = 0;
     for (uint64_t g0 = 0; g0 < Eg; g0 += gw) nwg += (std::min(gw, Eg - g0) * per_layer + rounds - 1) / rounds;
-    StackBuf d_table(sizeof(double) * table.size(), "stack weights and certificate tables"), d_planes(sizeof(double) * 3 * nmax, "fine planes of a window"),
-        d_status(elements, "element status"), d_bounds(sizeof(double2) * elements, "element bounds"),
-        d_rec(sizeof(HcAcc) * (nwg + H3_REDUCE_GROUPS), "certificate records"), d_out(sizeof(tm_ho3_certificate), "certificate record");
-    HIPCHK(hipMemcpyAsync(d_table.p, table.data(), sizeof(double) * table.size(), hipMemcpyHostToDevice, st));
+    DevBuf d_table, d_planes(sizeof(double) * 3 * nmax, "fine planes of a window"), d_status(elements, "element status"),
+        d_bounds(sizeof(double2) * elements, "element bounds"), d_rec(sizeof(HcAcc) * (nwg + RECORDS_REDUCE_GROUPS), "certificate records"),
+        d_out(sizeof(tm_ho3_certificate), "certificate record");
+    d_table.upload(table.data(), table.size(), st, "stack weights and certificate tables");
     H3Args a{};
     a.X = d_planes.as<double>();
     a.Y = a.X + nmax;
@@ -353,16 +327,8 @@ void h3_run(const StackPlan& p, const HoPlan& pl, StackCuts& cuts, uint64_t bloc
         HIPCHK(hipGetLastError());
         wg_at += groups;
     }
-    const HcAcc* records = d_rec.as<HcAcc>();
-    int nrec = static_cast<int>(nwg);
-    if (nrec > H3_REDUCE_FROM) {
-        const int chunk = (nrec + H3_REDUCE_GROUPS - 1) / H3_REDUCE_GROUPS, rgroups = (nrec + chunk - 1) / chunk;
-        hipLaunchKernelGGL(k_h3_reduce, dim3(rgroups), dim3(64), 0, st, records, nrec, chunk, d_rec.as<HcAcc>() + nwg);
-        HIPCHK(hipGetLastError());
-        records = d_rec.as<HcAcc>() + nwg;
-        nrec = rgroups;
-    }
-    hipLaunchKernelGGL(k_h3_finalize, dim3(1), dim3(64), 0, st, records, nrec, static_cast<unsigned long long>(block), a.Ei, a.Ej, static_cast<int>(Eg), P,
+    const Records<HcAcc> rec_in = records_first_stage(d_rec.as<HcAcc>(), nwg, st, hc_reduce_launch);
+    hipLaunchKernelGGL(k_h3_finalize, dim3(1), dim3(64), 0, st, rec_in.p, rec_in.n, static_cast<unsigned long long>(block), a.Ei, a.Ej, static_cast<int>(Eg), P,
                        rec.orientation, max_depth, d_out.as<tm_ho3_certificate>());
     HIPCHK(hipGetLastError());
     tm_ho3_certificate c;
@@ -380,26 +346,19 @@ using namespace tmh;
 extern "C" int tm_stack_certify(const tm_mesh_desc* const* cuts, const tm_stack_opt* sopt, const tm_stack_surfaces* surfaces, const tm_ho_opt* opt, int32_t max_depth,
                                 uint64_t block, tm_ho3_certificate* cert, uint8_t* status, double* bounds, uint64_t* outside) {
     return guarded([&]() {
-        if (!sopt) throw TmError(TM_E_ARG, "null stack options, span or layers");
-        const bool rev = sopt->mapping == TM_STACK_REVOLUTION;
-        if (!rev && surfaces) throw TmError(TM_E_ARG, "meridional tables go with TM_STACK_REVOLUTION only");
         SurfPlan sf;
-        const StackPlan p = rev ? stack_plan_surf(sopt, surfaces, sf) : stack_plan(sopt);
+        const SurfPlan* sfp = nullptr;
+        const StackPlan p = stack_plan_any(sopt, surfaces, sf, &sfp);
         uint64_t ni = 0, nj = 0;
         stack_check_cuts(cuts, p.ncuts, block, &ni, &nj);
         const HoPlan pl = ho3_plan(opt);
         h3_check_depth(max_depth);
         ho3_check_block(pl, block, ni, nj);
         ho3_check_layers(pl, p.nlayers);
-        require_gfx950_stack();
-        const size_t n = static_cast<size_t>(ni) * nj;
-        StackBuf in(sizeof(double2) * n * p.ncuts, "stack cuts");
+        DevBuf in;
         StackCuts dc{};
-        for (int c = 0; c < p.ncuts; ++c) {
-            dc.xy[c] = in.as<double2>() + n * c;
-            HIPCHK(hipMemcpy(in.as<double2>() + n * c, cuts[c]->blocks[block].xy, sizeof(double2) * n, hipMemcpyHostToDevice));
-        }
-        h3_run(p, pl, dc, block, ni, nj, max_depth, cert, status, bounds, nullptr, rev ? &sf : nullptr, outside);
+        stack_upload_cuts(cuts, p.ncuts, block, ni, nj, in, dc);
+        h3_run(p, pl, dc, block, ni, nj, max_depth, cert, status, bounds, nullptr, sfp, outside);
         return TM_OK;
     });
 }
@@ -408,11 +367,9 @@ extern "C" int tm_stack_smoothers_certify(tm_smoother* const* cuts, const tm_sta
                                           int32_t max_depth, uint64_t block, tm_ho3_certificate* cert, uint8_t* status, double* bounds, uint64_t* outside) {
     return guarded([&]() {
         if (!cuts) throw TmError(TM_E_ARG, "null argument");
-        if (!sopt) throw TmError(TM_E_ARG, "null stack options, span or layers");
-        const bool rev = sopt->mapping == TM_STACK_REVOLUTION;
-        if (!rev && surfaces) throw TmError(TM_E_ARG, "meridional tables go with TM_STACK_REVOLUTION only");
         SurfPlan sf;
-        const StackPlan p = rev ? stack_plan_surf(sopt, surfaces, sf) : stack_plan(sopt);
+        const SurfPlan* sfp = nullptr;
+        const StackPlan p = stack_plan_any(sopt, surfaces, sf, &sfp);
         StackCuts dc{};
         uint64_t ni = 0, nj = 0;
         stack_resident_cuts(cuts, p, block, dc, &ni, &nj);
@@ -422,7 +379,7 @@ extern "C" int tm_stack_smoothers_certify(tm_smoother* const* cuts, const tm_sta
         ho3_check_layers(pl, p.nlayers);
         std::vector<std::unique_ptr<StackEvent>> events;
         const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
-        h3_run(p, pl, dc, block, ni, nj, max_depth, cert, status, bounds, st, rev ? &sf : nullptr, outside);   // synchronises st
+        h3_run(p, pl, dc, block, ni, nj, max_depth, cert, status, bounds, st, sfp, outside);   // synchronises st
         return TM_OK;
     });
 }

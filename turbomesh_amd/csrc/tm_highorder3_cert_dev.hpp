@@ -2,6 +2,7 @@
 #pragma once
 #include "tm_highorder3_cert.hpp"
 #include "tm_highorder3_dev.hpp"
+#include "tm_highorder_cert_dev.hpp"
 
 namespace tmh {
 

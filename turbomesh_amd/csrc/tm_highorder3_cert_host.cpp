@@ -3,6 +3,7 @@
 // in this file: it works in a process without a device.
 #include "tm_highorder3_cert.hpp"
 #include "tm_api_util.hpp"
+#include "tm_dispatch.hpp"
 #include "tm_stack.hpp"
 
 #include <cmath>
@@ -189,12 +190,7 @@ void bezier_host3(const H3Plan& pl, const Planes& X, uint64_t e, uint64_t f, uin
 void h3_block_host(const H3Plan& pl, const double* x, const double* y, const double* z, uint64_t ni, uint64_t nj, uint64_t nk, uint64_t block, int orientation,
                    const double* jj, int max_depth, tm_ho3_certificate* cert, uint8_t* status, double* bounds) {
     const Planes X{{x, y, z}, ni, nj};
-    switch (pl.order) {
-    case 1: return block_host3<1>(pl, X, nk, block, orientation, jj, max_depth, cert, status, bounds);
-    case 2: return block_host3<2>(pl, X, nk, block, orientation, jj, max_depth, cert, status, bounds);
-    case 3: return block_host3<3>(pl, X, nk, block, orientation, jj, max_depth, cert, status, bounds);
-    default: return block_host3<4>(pl, X, nk, block, orientation, jj, max_depth, cert, status, bounds);
-    }
+    dispatch_int<1, 4>(pl.order, [&](auto P) { block_host3<P()>(pl, X, nk, block, orientation, jj, max_depth, cert, status, bounds); });
 }
 
 void h3_report_host(const HoPlan& pl, const double* x, const double* y, const double* z, uint64_t ni, uint64_t nj, uint64_t nk, uint64_t block, tm_ho3_quality* rec,
@@ -321,12 +317,7 @@ extern "C" int tm_ho3_jacobian_bezier_host(const double* x, const double* y, con
         if (e >= (ni - 1) / p || f >= (nj - 1) / p || g >= (nk - 1) / p) throw TmError(TM_E_ARG, "element index past the block");
         const H3Plan pl = h3_plan(ho.order);
         const Planes X{{x, y, z}, ni, nj};
-        switch (ho.order) {
-        case 1: bezier_host3<1>(pl, X, e, f, g, B); break;
-        case 2: bezier_host3<2>(pl, X, e, f, g, B); break;
-        case 3: bezier_host3<3>(pl, X, e, f, g, B); break;
-        default: bezier_host3<4>(pl, X, e, f, g, B); break;
-        }
+        dispatch_int<1, 4>(ho.order, [&](auto P) { bezier_host3<P()>(pl, X, e, f, g, B); });
         return TM_OK;
     });
 }

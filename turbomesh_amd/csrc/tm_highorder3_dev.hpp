@@ -9,7 +9,6 @@
 namespace tmh {
 
 constexpr int HO3_THREADS = 256, HO3_WAVES = HO3_THREADS / 64;
-constexpr int HO3_REDUCE_FROM = 256, HO3_REDUCE_GROUPS = 64;   // records from which the finalize gets a first stage, and its workgroups
 // whole elements of a tile along i and j: (EI*p + 1) * (EJ*p + 1) nodes <= HO3_THREADS, one thread per node
 constexpr int ho3_tile_ei(int p) { return p == 3 ? 5 : 16 / p; }
 constexpr int ho3_tile_ej(int p) { return p == 3 ? 5 : 14 / p; }

@@ -3,6 +3,7 @@
 // tm_stack_elevate_host on K cuts with p+1 fine layers held at a time.  No HIP call in this file: it works in a process without a device.
 #include "tm_highorder3.hpp"
 #include "tm_api_util.hpp"
+#include "tm_dispatch.hpp"
 #include "tm_stack.hpp"
 
 #include <cmath>
@@ -121,12 +122,7 @@ static void element_layer_host(Ho3Stream& s, uint64_t g, const double* const* fx
 }
 
 void Ho3Stream::element_layer(uint64_t g, const double* const* fx, const double* const* fy, const double* const* fz) {
-    switch (plan.order) {
-    case 1: return element_layer_host<1>(*this, g, fx, fy, fz);
-    case 2: return element_layer_host<2>(*this, g, fx, fy, fz);
-    case 3: return element_layer_host<3>(*this, g, fx, fy, fz);
-    default: return element_layer_host<4>(*this, g, fx, fy, fz);
-    }
+    dispatch_int<1, 4>(plan.order, [&](auto P) { element_layer_host<P()>(*this, g, fx, fy, fz); });
 }
 
 void Ho3Stream::finish(uint64_t block, tm_ho3_quality* out) const { ho3_finish(acc, block, Ei, Ej, Eg, plan.order, out); }

@@ -31,7 +31,7 @@
 // lanes meet 2-way.  Table entries are read by at most p+1 distinct addresses per wave (broadcast).
 //
 // Records: in-lane over the march, in-wave by shuffles, across the waves through LDS, one HoAcc per workgroup, the histogram by integer
-// LDS atomics; k_ho3_finalize (behind k_ho3_reduce from 257 workgroups on) combines them in fixed order and picks the orientation's
+// LDS atomics; k_ho3_finalize (behind K13's k_ho_reduce from 257 workgroups on) combines them in fixed order and picks the orientation's
 // candidate set (ho3_finish).  No floating-point atomics.  `outside` as in K11: ballots, LDS counters, one integer atomic per workgroup
 // and cut; a seam node is counted by the tile that owns it.
 //
@@ -39,6 +39,7 @@
 // nodes and the lines are); the four orders are compiled in four translation units (tm_highorder3_p1.hip ..) so that the build takes
 // them in parallel.  Compiler's resource usage: DESIGN.md section 4, K16.
 #include "tm_highorder3_dev.hpp"
+#include "tm_dispatch.hpp"
 
 namespace tmh {
 
@@ -329,14 +330,8 @@ static void ho3_launch_k(const Ho3Launch& a, hipStream_t st) {
 
 template <int P>
 hipError_t ho3_launch(int K, const Ho3Launch& a, hipStream_t st) {
-    switch (K) {
-#define TM_STACK_CASE(n) \
-    case n: ho3_launch_k<P, n>(a, st); break;
-        TM_STACK_CASE(2) TM_STACK_CASE(3) TM_STACK_CASE(4) TM_STACK_CASE(5) TM_STACK_CASE(6) TM_STACK_CASE(7) TM_STACK_CASE(8) TM_STACK_CASE(9)
-        TM_STACK_CASE(10) TM_STACK_CASE(11) TM_STACK_CASE(12) TM_STACK_CASE(13) TM_STACK_CASE(14) TM_STACK_CASE(15) TM_STACK_CASE(16)
-#undef TM_STACK_CASE
-        default: return hipErrorInvalidValue;
-    }
+    if (K < 2 || K > TM_STACK_MAX_CUTS) return hipErrorInvalidValue;
+    dispatch_int<2, TM_STACK_MAX_CUTS>(K, [&](auto k) { ho3_launch_k<P, k()>(a, st); });
     return hipGetLastError();
 }
 

@@ -21,13 +21,13 @@
 // Records.  One HcAcc per workgroup; k_hc_finalize (behind k_hc_reduce from 257 workgroups on) combines them, the scheme of K13.
 #include "tm_highorder_cert_dev.hpp"
 #include "tm_stack_dev.hpp"
+#include "tm_dispatch.hpp"
 
 #include <algorithm>
 
 namespace tmh {
 
 constexpr int HC_ROUNDS = 8;
-constexpr int HC_REDUCE_FROM = 256, HC_REDUCE_GROUPS = 64;
 constexpr int hc_group(int p) { return p == 1 ? 4 : p == 2 ? 16 : 64; }
 
 template <int GS>
@@ -262,54 +262,23 @@ __global__ __launch_bounds__(64) void k_ho_certify(const double2* __restrict__ X
     }
 }
 
-// lane t combines records t, t + 64, ..., then the 64 lanes' records pairwise through LDS: K13's scheme (the fields are counts and
-// minima, so the order does not reach the result)
-__device__ __forceinline__ void hc_reduce_wave(const HcAcc* __restrict__ partials, int begin, int end, HcAcc* sh) {
-    HcAcc a;
-    hc_init(a);
-    for (int r = begin + static_cast<int>(threadIdx.x); r < end; r += 64) hc_combine(a, partials[r]);
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int off = 32; off > 0; off >>= 1) {
-        if (static_cast<int>(threadIdx.x) < off) hc_combine(sh[threadIdx.x], sh[threadIdx.x + off]);
-        __syncthreads();
-    }
-}
+// the records are combined in K13's fixed order (the fields are counts and minima, so the order does not reach the result)
 __global__ __launch_bounds__(64) void k_hc_reduce(const HcAcc* __restrict__ partials, int nwg, int chunk, HcAcc* __restrict__ out) {
     __shared__ HcAcc sh[64];
     const int begin = static_cast<int>(blockIdx.x) * chunk, end = begin + chunk < nwg ? begin + chunk : nwg;
-    hc_reduce_wave(partials, begin, end, sh);
+    records_reduce_wave<HcAcc, hc_init, hc_combine>(partials, begin, end, sh);
     if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
 }
 __global__ __launch_bounds__(64) void k_hc_finalize(const HcAcc* __restrict__ partials, int nwg, unsigned long long block, int Ei, int Ej, int order, int orientation,
                                                     int max_depth, tm_ho_certificate* __restrict__ out) {
     __shared__ HcAcc sh[64];
-    hc_reduce_wave(partials, 0, nwg, sh);
+    records_reduce_wave<HcAcc, hc_init, hc_combine>(partials, 0, nwg, sh);
     if (threadIdx.x == 0) hc_finish(sh[0], block, static_cast<uint64_t>(Ei), static_cast<uint64_t>(Ej), order, orientation, max_depth, out);
 }
 
 // ------------------------------------------------------------------ host driver
-HcDev::~HcDev() {
-    if (tab) (void)hipFree(tab);
-    if (status) (void)hipFree(status);
-    if (bounds) (void)hipFree(bounds);
-    if (partials) (void)hipFree(partials);
-    if (out) (void)hipFree(out);
-}
-
-static void hc_grow(void** p, size_t* cap, size_t need, size_t elem, const char* what) {
-    if (*cap >= need) return;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, need * elem) != hipSuccess) throw TmError(TM_E_MEMORY, std::string("hipMalloc failed (") + what + ")");
-    *cap = need;
-}
-
-template <int P>
-static void hc_launch(unsigned groups, hipStream_t st, const double2* X, int nj, int Ei, int Ej, const double* tab, double G, const double2* pairs, int orientation,
-                      int max_depth, unsigned char* status, double2* bounds, HcAcc* partials) {
-    hipLaunchKernelGGL(k_ho_certify<P>, dim3(groups), dim3(64), 0, st, X, nj, Ei, Ej, tab, G, pairs, orientation, max_depth, status, bounds, partials);
+void hc_reduce_launch(const HcAcc* partials, int nrec, int chunk, int groups, HcAcc* out, hipStream_t st) {
+    hipLaunchKernelGGL(k_hc_reduce, dim3(groups), dim3(64), 0, st, partials, nrec, chunk, out);
 }
 
 int hc_workgroups(int p, uint64_t elements) {
@@ -324,46 +293,31 @@ void HcDev::run(HoDev& ho, const HoPlan& hopl, const double2* X, int ni, int nj,
     tm_ho_quality rec;
     ho.run(hopl, X, ni, nj, block, st, nullptr, nullptr, &rec, nullptr);   // K13's report: the orientation, and the nodal pairs stay in ho.pairs
     const int nwg = hc_workgroups(p, elements);
-    if (!tab && hipMalloc(reinterpret_cast<void**>(&tab), sizeof(double) * HC_MAX_TAB) != hipSuccess) throw TmError(TM_E_MEMORY, "hipMalloc failed (certificate tables)");
-    if (!out && hipMalloc(reinterpret_cast<void**>(&out), sizeof(tm_ho_certificate)) != hipSuccess) throw TmError(TM_E_MEMORY, "hipMalloc failed (certificate record)");
-    hc_grow(reinterpret_cast<void**>(&status), &status_cap, elements, 1, "element status");
-    hc_grow(reinterpret_cast<void**>(&bounds), &bounds_cap, elements, sizeof(double2), "element bounds");
-    hc_grow(reinterpret_cast<void**>(&partials), &partials_cap, static_cast<size_t>(nwg) + HC_REDUCE_GROUPS, sizeof(HcAcc), "certificate records");
+    tab.grow(sizeof(double) * HC_MAX_TAB, "certificate tables");
+    out.grow(sizeof(tm_ho_certificate), "certificate record");
+    status.grow(elements, "element status");
+    bounds.grow(sizeof(double2) * elements, "element bounds");
+    partials.grow(sizeof(HcAcc) * (static_cast<size_t>(nwg) + RECORDS_REDUCE_GROUPS), "certificate records");
     if (plan.order != p) {   // a call always waits for its stream at the end, so no earlier launch still reads the old tables
         plan = hc_plan(p);
-        const hipError_t up = hipMemcpyAsync(tab, plan.tab, sizeof(double) * plan.tab_size(), hipMemcpyHostToDevice, st);
+        const hipError_t up = hipMemcpyAsync(tab.p, plan.tab, sizeof(double) * plan.tab_size(), hipMemcpyHostToDevice, st);
         if (up != hipSuccess) plan.order = 0;
         HIPCHK(up);
     }
-    const HcPlan& pl = plan;
-    const unsigned groups = static_cast<unsigned>(nwg);
     const int o = rec.orientation;
-    switch (p) {
-    case 1: hc_launch<1>(groups, st, X, nj, Ei, Ej, tab, pl.G, ho.pairs, o, max_depth, status, bounds, partials); break;
-    case 2: hc_launch<2>(groups, st, X, nj, Ei, Ej, tab, pl.G, ho.pairs, o, max_depth, status, bounds, partials); break;
-    case 3: hc_launch<3>(groups, st, X, nj, Ei, Ej, tab, pl.G, ho.pairs, o, max_depth, status, bounds, partials); break;
-    case 4: hc_launch<4>(groups, st, X, nj, Ei, Ej, tab, pl.G, ho.pairs, o, max_depth, status, bounds, partials); break;
-    case 5: hc_launch<5>(groups, st, X, nj, Ei, Ej, tab, pl.G, ho.pairs, o, max_depth, status, bounds, partials); break;
-    case 6: hc_launch<6>(groups, st, X, nj, Ei, Ej, tab, pl.G, ho.pairs, o, max_depth, status, bounds, partials); break;
-    case 7: hc_launch<7>(groups, st, X, nj, Ei, Ej, tab, pl.G, ho.pairs, o, max_depth, status, bounds, partials); break;
-    default: hc_launch<8>(groups, st, X, nj, Ei, Ej, tab, pl.G, ho.pairs, o, max_depth, status, bounds, partials); break;
-    }
+    dispatch_int<1, 8>(p, [&](auto P) {
+        hipLaunchKernelGGL(k_ho_certify<P()>, dim3(static_cast<unsigned>(nwg)), dim3(64), 0, st, X, nj, Ei, Ej, tab.as<double>(), plan.G, ho.pairs.as<double2>(), o,
+                           max_depth, status.as<unsigned char>(), bounds.as<double2>(), partials.as<HcAcc>());
+    });
     HIPCHK(hipGetLastError());
-    const HcAcc* records = partials;
-    int nrec = nwg;
-    if (nrec > HC_REDUCE_FROM) {
-        const int chunk = (nrec + HC_REDUCE_GROUPS - 1) / HC_REDUCE_GROUPS, rgroups = (nrec + chunk - 1) / chunk;
-        hipLaunchKernelGGL(k_hc_reduce, dim3(rgroups), dim3(64), 0, st, partials, nrec, chunk, partials + nwg);
-        HIPCHK(hipGetLastError());
-        records = partials + nwg;
-        nrec = rgroups;
-    }
-    hipLaunchKernelGGL(k_hc_finalize, dim3(1), dim3(64), 0, st, records, nrec, static_cast<unsigned long long>(block), Ei, Ej, p, o, max_depth, out);
+    const Records<HcAcc> rec_in = records_first_stage(partials.as<HcAcc>(), static_cast<size_t>(nwg), st, hc_reduce_launch);
+    hipLaunchKernelGGL(k_hc_finalize, dim3(1), dim3(64), 0, st, rec_in.p, rec_in.n, static_cast<unsigned long long>(block), Ei, Ej, p, o, max_depth,
+                       out.as<tm_ho_certificate>());
     HIPCHK(hipGetLastError());
     tm_ho_certificate c;
-    HIPCHK(hipMemcpyAsync(&c, out, sizeof(c), hipMemcpyDeviceToHost, st));
-    if (h_status) HIPCHK(hipMemcpyAsync(h_status, status, elements, hipMemcpyDeviceToHost, st));
-    if (h_bounds) HIPCHK(hipMemcpyAsync(h_bounds, bounds, sizeof(double2) * elements, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&c, out.p, sizeof(c), hipMemcpyDeviceToHost, st));
+    if (h_status) HIPCHK(hipMemcpyAsync(h_status, status.p, elements, hipMemcpyDeviceToHost, st));
+    if (h_bounds) HIPCHK(hipMemcpyAsync(h_bounds, bounds.p, sizeof(double2) * elements, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (cert) *cert = c;
 }
@@ -391,9 +345,9 @@ extern "C" int tm_ho_certify(const tm_mesh_desc* mesh, const tm_ho_opt* opt, int
         const HoPlan pl = ho_plan(opt);
         hc_check_depth(max_depth);
         const tm_block& b = ho_block_of(mesh, pl, block);
-        require_gfx950_stack();
+        require_gfx950();
         const size_t n = static_cast<size_t>(b.ni) * b.nj;
-        StackBuf in(sizeof(double2) * n, "block to certify");
+        DevBuf in(sizeof(double2) * n, "block to certify");
         HIPCHK(hipMemcpy(in.p, b.xy, sizeof(double2) * n, hipMemcpyHostToDevice));
         HoDev ho;
         HcDev dev;

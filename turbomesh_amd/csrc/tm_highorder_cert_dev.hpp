@@ -5,20 +5,11 @@
 
 namespace tmh {
 
-// Tables, one status byte and one (lo, hi) pair per element, partial records and the result: hipMalloc'ed on first use, grown on demand,
+// Tables, one status byte and one (lo, hi) pair per element, partial records and the result: allocated on first use, grown on demand,
 // freed with the owner.
 struct HcDev {
-    HcDev() = default;
-    ~HcDev();
-    HcDev(const HcDev&) = delete;
-    HcDev& operator=(const HcDev&) = delete;
-    double* tab = nullptr;
+    DevBuf tab, status, bounds, partials, out;
     HcPlan plan;                       // the tables in `tab`: formed and uploaded when the order changes (plan.order == 0: none yet)
-    unsigned char* status = nullptr;
-    double2* bounds = nullptr;
-    HcAcc* partials = nullptr;
-    tm_ho_certificate* out = nullptr;
-    size_t status_cap = 0, bounds_cap = 0, partials_cap = 0;
     // K13's report through `ho` (the orientation; its pairs stay on the device), one k_ho_certify launch and the finalize on the block X
     // (already checked against the plan); cert, status, bounds as tm_ho_certify; synchronises
     void run(HoDev& ho, const HoPlan& hoplan, const double2* X, int ni, int nj, uint64_t block, hipStream_t st, int max_depth,
@@ -26,5 +17,7 @@ struct HcDev {
 };
 // workgroups of the K14 launch on a block with that many elements
 int hc_workgroups(int order, uint64_t elements);
+// the first stage of records_first_stage over HcAcc: k_hc_reduce (tm_highorder_cert.hip), also K17's
+void hc_reduce_launch(const HcAcc* partials, int nrec, int chunk, int groups, HcAcc* out, hipStream_t st);
 
 }  // namespace tmh

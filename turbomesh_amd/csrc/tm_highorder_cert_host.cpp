@@ -3,6 +3,7 @@
 // call in this file: it works in a process without a device.
 #include "tm_highorder_cert.hpp"
 #include "tm_api_util.hpp"
+#include "tm_dispatch.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -202,16 +203,7 @@ void bezier_host(const HcPlan& pl, const double* xy, uint64_t nj, uint64_t e, ui
 
 void hc_block_host(const HcPlan& pl, const double* xy, uint64_t ni, uint64_t nj, uint64_t block, int orientation, const double* jj, int max_depth,
                    tm_ho_certificate* cert, uint8_t* status, double* bounds) {
-    switch (pl.order) {
-    case 1: return block_host<1>(pl, xy, ni, nj, block, orientation, jj, max_depth, cert, status, bounds);
-    case 2: return block_host<2>(pl, xy, ni, nj, block, orientation, jj, max_depth, cert, status, bounds);
-    case 3: return block_host<3>(pl, xy, ni, nj, block, orientation, jj, max_depth, cert, status, bounds);
-    case 4: return block_host<4>(pl, xy, ni, nj, block, orientation, jj, max_depth, cert, status, bounds);
-    case 5: return block_host<5>(pl, xy, ni, nj, block, orientation, jj, max_depth, cert, status, bounds);
-    case 6: return block_host<6>(pl, xy, ni, nj, block, orientation, jj, max_depth, cert, status, bounds);
-    case 7: return block_host<7>(pl, xy, ni, nj, block, orientation, jj, max_depth, cert, status, bounds);
-    default: return block_host<8>(pl, xy, ni, nj, block, orientation, jj, max_depth, cert, status, bounds);
-    }
+    dispatch_int<1, 8>(pl.order, [&](auto P) { block_host<P()>(pl, xy, ni, nj, block, orientation, jj, max_depth, cert, status, bounds); });
 }
 
 void hc_certificate_total(const tm_ho_certificate* pb, uint64_t n, tm_ho_certificate* t) {
@@ -293,16 +285,7 @@ extern "C" int tm_ho_jacobian_bezier_host(const tm_mesh_desc* mesh, const tm_ho_
         const uint64_t p = static_cast<uint64_t>(ho.order);
         if (e >= (b.ni - 1) / p || f >= (b.nj - 1) / p) throw TmError(TM_E_ARG, "element index past the block");
         const HcPlan pl = hc_plan(ho.order);
-        switch (ho.order) {
-        case 1: bezier_host<1>(pl, b.xy, b.nj, e, f, B); break;
-        case 2: bezier_host<2>(pl, b.xy, b.nj, e, f, B); break;
-        case 3: bezier_host<3>(pl, b.xy, b.nj, e, f, B); break;
-        case 4: bezier_host<4>(pl, b.xy, b.nj, e, f, B); break;
-        case 5: bezier_host<5>(pl, b.xy, b.nj, e, f, B); break;
-        case 6: bezier_host<6>(pl, b.xy, b.nj, e, f, B); break;
-        case 7: bezier_host<7>(pl, b.xy, b.nj, e, f, B); break;
-        default: bezier_host<8>(pl, b.xy, b.nj, e, f, B); break;
-        }
+        dispatch_int<1, 8>(ho.order, [&](auto P) { bezier_host<P()>(pl, b.xy, b.nj, e, f, B); });
         return TM_OK;
     });
 }

@@ -3,6 +3,7 @@
 // (tm_highorder.hpp).  No HIP call in this file: it works in a process without a device.
 #include "tm_highorder.hpp"
 #include "tm_api_util.hpp"
+#include "tm_dispatch.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -158,16 +159,7 @@ static void block_host(const HoPlan& pl, const double* xy, uint64_t ni, uint64_t
 }
 
 void ho_block_host(const HoPlan& pl, const double* xy, uint64_t ni, uint64_t nj, uint64_t block, double* x, double* y, tm_ho_quality* q, double* jj) {
-    switch (pl.order) {
-    case 1: return block_host<1>(pl, xy, ni, nj, block, x, y, q, jj);
-    case 2: return block_host<2>(pl, xy, ni, nj, block, x, y, q, jj);
-    case 3: return block_host<3>(pl, xy, ni, nj, block, x, y, q, jj);
-    case 4: return block_host<4>(pl, xy, ni, nj, block, x, y, q, jj);
-    case 5: return block_host<5>(pl, xy, ni, nj, block, x, y, q, jj);
-    case 6: return block_host<6>(pl, xy, ni, nj, block, x, y, q, jj);
-    case 7: return block_host<7>(pl, xy, ni, nj, block, x, y, q, jj);
-    default: return block_host<8>(pl, xy, ni, nj, block, x, y, q, jj);
-    }
+    dispatch_int<1, 8>(pl.order, [&](auto P) { block_host<P()>(pl, xy, ni, nj, block, x, y, q, jj); });
 }
 
 void ho_sj_from_pairs(const double* jj, uint64_t elements, int orientation, double* sj) {

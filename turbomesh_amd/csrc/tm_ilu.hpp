@@ -2,28 +2,11 @@
 // slot (tm_csr_solve, tm_csr_ilu0_probe) and by the handle's TM_INNER_REFERENCE_GMRES mode (Smoother::picard_reference), which keeps one
 // IluState for its lifetime: analysis once, factorisation per outer iteration, two substitutions per inner iteration.
 #pragma once
-#include "tm_smoother.hpp"
+#include "tm_devbuf.hpp"
 #include <array>
 #include <vector>
 
 namespace tmh {
-
-struct Dev {   // RAII device buffer
-    void* p = nullptr;
-    explicit Dev(size_t bytes) {
-        if (hipMalloc(&p, bytes ? bytes : 256) != hipSuccess) throw TmError(TM_E_MEMORY, "hipMalloc failed (" + std::to_string(bytes) + " bytes)");
-    }
-    ~Dev() { (void)hipFree(p); }
-    void reset(size_t bytes) {
-        (void)hipFree(p);
-        p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 256) != hipSuccess) throw TmError(TM_E_MEMORY, "hipMalloc failed (" + std::to_string(bytes) + " bytes)");
-    }
-    Dev(const Dev&) = delete;
-    Dev& operator=(const Dev&) = delete;
-    template <class T>
-    T* as() { return static_cast<T*>(p); }
-};
 
 struct IluDev {
     int n;
@@ -51,14 +34,14 @@ struct IluPackedDev {
 };
 struct IluPacked {
     int width = 0;                // slots per row = the most entries any row has on this side of the diagonal; rounded up to 4, 8 or 16
-    Dev d_col{0}, d_src{0}, d_val{0}, d_piv{0};
+    DevBuf d_col, d_src, d_val, d_piv;   // allocated by build()
     void build(int n, const int32_t* p, const int32_t* ci, const IluLevels& lv, bool lower);
 };
 
 // analysis on the host, factorisation level by level (k_ilu_levels), the two substitutions on the level-packed form
 struct IluState {
     IluLevels L, U;
-    Dev d_diag, d_lux, d_luy, d_ordL, d_ptrL, d_ordU, d_ptrU;
+    DevBuf d_diag, d_lux, d_luy, d_ordL, d_ptrL, d_ordU, d_ptrU;
     IluPacked PL, PU;
     bool packed = false;          // false: a row has more than 16 entries on one side, or TM_ILU_PACKED=0 -- substitutions by k_ilu_levels
     IluDev M{};

@@ -171,47 +171,22 @@ __global__ __launch_bounds__(Q_THREADS) void k_quality(const double2* __restrict
     }
 }
 
-// one workgroup (one wave) per block: lane t combines records t, t + 64, ... in that order, then the 64 lanes' records pairwise
-// through LDS (32, 16, ... 1) -- a fixed order, so the sums are the same on every run
+// one workgroup (one wave) per block combines the block's records in the fixed order of records_reduce_wave, so the sums are the same on every run
 __global__ __launch_bounds__(64) void k_quality_finalize(const QAcc* __restrict__ partials, const QBlockDesc* __restrict__ desc, tm_quality* __restrict__ out) {
     __shared__ QAcc sh[64];
     const QBlockDesc d = desc[blockIdx.x];
-    QAcc a;
-    q_init(a);
-    for (int r = threadIdx.x; r < d.nwg; r += 64) q_combine(a, partials[d.first + r]);
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int off = 32; off > 0; off >>= 1) {
-        if (static_cast<int>(threadIdx.x) < off) q_combine(sh[threadIdx.x], sh[threadIdx.x + off]);
-        __syncthreads();
-    }
+    records_reduce_wave<QAcc, q_init, q_combine>(partials + d.first, 0, d.nwg, sh);
     if (threadIdx.x == 0) q_finish(sh[0], d.block, static_cast<uint64_t>(d.ni), static_cast<uint64_t>(d.nj), &out[blockIdx.x]);
 }
 
 // ------------------------------------------------------------------ host driver
 QualityDev::~QualityDev() { release(); }
 void QualityDev::release() {
-    if (partials) (void)hipFree(partials);
-    if (desc) (void)hipFree(desc);
-    if (out) (void)hipFree(out);
-    if (field) (void)hipFree(field);
+    for (DevBuf* b : {&partials, &desc, &out, &field}) b->release();
     if (h_out) (void)hipHostFree(h_out);
     h_out = nullptr;
     desc_host.clear();
-    partials = nullptr;
-    desc = nullptr;
-    out = nullptr;
-    field = nullptr;
-    partials_cap = blocks_cap = field_cap = 0;
-}
-
-static void grow(void** p, size_t* cap, size_t need, size_t elem, const char* what) {
-    if (*cap >= need) return;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, need * elem) != hipSuccess) throw TmError(TM_E_MEMORY, std::string("hipMalloc failed (") + what + ")");
-    *cap = need;
+    blocks_cap = 0;
 }
 
 void QualityDev::run(const std::vector<QualityBlock>& blocks, hipStream_t st, tm_quality* host_out) {
@@ -223,31 +198,31 @@ void QualityDev::run(const std::vector<QualityBlock>& blocks, hipStream_t st, tm
         d[k] = QBlockDesc{static_cast<long long>(nrec), quality_nwg(blocks[k].ni, blocks[k].nj), blocks[k].ni, blocks[k].nj, 0, blocks[k].block};
         nrec += static_cast<size_t>(d[k].nwg);
     }
-    grow(reinterpret_cast<void**>(&partials), &partials_cap, nrec, sizeof(QAcc), "quality records");
+    partials.grow(sizeof(QAcc) * nrec, "quality records");
     if (blocks_cap < blocks.size()) {
-        size_t cap2 = blocks_cap;
-        grow(reinterpret_cast<void**>(&desc), &blocks_cap, blocks.size(), sizeof(QBlockDesc), "quality block table");
-        grow(reinterpret_cast<void**>(&out), &cap2, blocks.size(), sizeof(tm_quality), "quality results");
+        desc.grow(sizeof(QBlockDesc) * blocks.size(), "quality block table");
+        out.grow(sizeof(tm_quality) * blocks.size(), "quality results");
+        blocks_cap = blocks.size();
         if (h_out) (void)hipHostFree(h_out);
         h_out = nullptr;
         desc_host.clear();
         if (hipHostMalloc(reinterpret_cast<void**>(&h_out), sizeof(tm_quality) * blocks.size(), hipHostMallocDefault) != hipSuccess) throw TmError(TM_E_MEMORY, "hipHostMalloc failed (quality results)");
     }
     if (desc_host.size() != d.size() || std::memcmp(desc_host.data(), d.data(), sizeof(QBlockDesc) * d.size()) != 0) {
-        HIPCHK(hipMemcpy(desc, d.data(), sizeof(QBlockDesc) * d.size(), hipMemcpyHostToDevice));   // blocking: d is a local
+        HIPCHK(hipMemcpy(desc.p, d.data(), sizeof(QBlockDesc) * d.size(), hipMemcpyHostToDevice));   // blocking: d is a local
         desc_host = d;
     }
     for (size_t k = 0; k < blocks.size(); ++k) {
         const dim3 grid = quality_grid(blocks[k].ni, blocks[k].nj);
-        if (d[k].first + static_cast<long long>(grid.x) * grid.y > static_cast<long long>(partials_cap))
+        if (d[k].first + static_cast<long long>(grid.x) * grid.y > static_cast<long long>(partials.cap / sizeof(QAcc)))
             throw TmError(TM_E_OVERFLOW, "quality records buffer smaller than the launch grid");
-        hipLaunchKernelGGL(k_quality, grid, dim3(Q_THREADS), 0, st, blocks[k].xy, blocks[k].ni, blocks[k].nj, quality_rows(blocks[k].ni, blocks[k].nj), partials + d[k].first,
+        hipLaunchKernelGGL(k_quality, grid, dim3(Q_THREADS), 0, st, blocks[k].xy, blocks[k].ni, blocks[k].nj, quality_rows(blocks[k].ni, blocks[k].nj), partials.as<QAcc>() + d[k].first,
                            static_cast<double*>(nullptr), 0);
         HIPCHK(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_quality_finalize, dim3(static_cast<unsigned>(blocks.size())), dim3(64), 0, st, partials, desc, out);
+    hipLaunchKernelGGL(k_quality_finalize, dim3(static_cast<unsigned>(blocks.size())), dim3(64), 0, st, partials.as<QAcc>(), desc.as<QBlockDesc>(), out.as<tm_quality>());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_out, out, sizeof(tm_quality) * blocks.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(h_out, out.p, sizeof(tm_quality) * blocks.size(), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (host_out) {
         std::memcpy(host_out, h_out, sizeof(tm_quality) * blocks.size());
@@ -257,10 +232,10 @@ void QualityDev::run(const std::vector<QualityBlock>& blocks, hipStream_t st, tm
 
 void QualityDev::run_field(const QualityBlock& b, int orientation, hipStream_t st, double* host_field) {
     const size_t cells = static_cast<size_t>(b.ni - 1) * (b.nj - 1);
-    grow(reinterpret_cast<void**>(&field), &field_cap, cells, sizeof(double), "quality cell plane");
-    hipLaunchKernelGGL(k_quality, quality_grid(b.ni, b.nj), dim3(Q_THREADS), 0, st, b.xy, b.ni, b.nj, quality_rows(b.ni, b.nj), static_cast<QAcc*>(nullptr), field, orientation);
+    field.grow(sizeof(double) * cells, "quality cell plane");
+    hipLaunchKernelGGL(k_quality, quality_grid(b.ni, b.nj), dim3(Q_THREADS), 0, st, b.xy, b.ni, b.nj, quality_rows(b.ni, b.nj), static_cast<QAcc*>(nullptr), field.as<double>(), orientation);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(host_field, field, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(host_field, field.p, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
 }
 

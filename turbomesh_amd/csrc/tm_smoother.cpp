@@ -100,8 +100,8 @@ void Smoother::sync() { HIPCHK(hipStreamSynchronize(stream)); }
 // device state of TM_INNER_REFERENCE_GMRES beside the arena's vectors (picard_reference)
 struct Smoother::ReferenceSolve {
     std::unique_ptr<IluState> ilu;   // TM_OPT_PRECOND_ILU0; else the diagonal
-    Dev dinv, part;                  // 1 / a_ii per row and component; the partial sums of the CSR kernels (256 rows per workgroup)
-    ReferenceSolve(int64_t n) : dinv(sizeof(double2) * static_cast<size_t>(n)), part(sizeof(double) * MAX_PARTIALS * static_cast<size_t>(csr_nwg(n))) {}
+    DevBuf dinv, part;                  // 1 / a_ii per row and component; the partial sums of the CSR kernels (256 rows per workgroup)
+    ReferenceSolve(int64_t n) : dinv(sizeof(double2) * static_cast<size_t>(n), "reference solve dinv"), part(sizeof(double) * MAX_PARTIALS * static_cast<size_t>(csr_nwg(n)), "reference solve partials") {}
 };
 
 // Everything the handle owns outside the arena; also runs when create() throws half-way (pinned buffers already allocated).

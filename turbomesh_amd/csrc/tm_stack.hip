@@ -13,6 +13,7 @@
 // Traffic per node: 16 K bytes read, 24 k_count bytes written, each byte once: plain coalesced loads and stores, the three output
 // streams dominate.  Compiler's resource usage (cross-compile, -Rpass-analysis=kernel-resource-usage): see DESIGN.md section 4, K11.
 #include "tm_stack_dev.hpp"
+#include "tm_dispatch.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -118,14 +119,8 @@ static void stack_launch_k(const StackCuts& cuts, const StackSurf& surf, int map
 
 hipError_t launch_stack_planes(int K, const StackCuts& cuts, const StackSurf& surf, int mapping, const double* table, int nk, int ni, int nj, double* X, double* Y,
                                double* Z, unsigned long long* outside, hipStream_t st) {
-    switch (K) {
-#define TM_STACK_CASE(n) \
-    case n: stack_launch_k<n>(cuts, surf, mapping, table, nk, ni, nj, X, Y, Z, outside, st); break;
-        TM_STACK_CASE(2) TM_STACK_CASE(3) TM_STACK_CASE(4) TM_STACK_CASE(5) TM_STACK_CASE(6) TM_STACK_CASE(7) TM_STACK_CASE(8) TM_STACK_CASE(9)
-        TM_STACK_CASE(10) TM_STACK_CASE(11) TM_STACK_CASE(12) TM_STACK_CASE(13) TM_STACK_CASE(14) TM_STACK_CASE(15) TM_STACK_CASE(16)
-#undef TM_STACK_CASE
-        default: return hipErrorInvalidValue;
-    }
+    if (K < 2 || K > TM_STACK_MAX_CUTS) return hipErrorInvalidValue;
+    dispatch_int<2, TM_STACK_MAX_CUTS>(K, [&](auto k) { stack_launch_k<k()>(cuts, surf, mapping, table, nk, ni, nj, X, Y, Z, outside, st); });
     return hipGetLastError();
 }
 
@@ -137,25 +132,21 @@ static void stack_run(const StackPlan& p, StackCuts& cuts, uint64_t k_begin, uin
     if (k_count >= (uint64_t{1} << 31)) throw TmError(TM_E_SIZE, "layer window out of range");
     stack_fill_radii(p, cuts);
     StackSurfDev sd;
-    std::unique_ptr<StackBuf> d_outside;
+    DevBuf d_outside;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are copied out as they are");
     if (sf) stack_surf_upload(p, *sf, cuts, sd, st);
     if (sf && outside) {
-        d_outside = std::make_unique<StackBuf>(sizeof(unsigned long long) * TM_STACK_MAX_CUTS, "stack outside counts");
-        HIPCHK(hipMemsetAsync(d_outside->p, 0, sizeof(unsigned long long) * TM_STACK_MAX_CUTS, st));
+        d_outside.grow(sizeof(unsigned long long) * TM_STACK_MAX_CUTS, "stack outside counts");
+        HIPCHK(hipMemsetAsync(d_outside.p, 0, sizeof(unsigned long long) * TM_STACK_MAX_CUTS, st));
     }
-    std::vector<double> table(static_cast<size_t>(k_count) * (K + 1));
-    for (uint64_t k = 0; k < k_count; ++k) {
-        std::memcpy(&table[k * (K + 1)], &p.weights[(k_begin + k) * K], sizeof(double) * K);
-        table[k * (K + 1) + K] = p.layers[k_begin + k];
-    }
+    const std::vector<double> table = stack_weight_table(p, k_begin, k_count);
     const size_t n = static_cast<size_t>(ni) * nj * k_count;
-    StackBuf d_table(sizeof(double) * table.size(), "stack weights"), d_out(sizeof(double) * 3 * n, "stack planes");
-    HIPCHK(hipMemcpyAsync(d_table.p, table.data(), sizeof(double) * table.size(), hipMemcpyHostToDevice, st));
+    DevBuf d_table, d_out(sizeof(double) * 3 * n, "stack planes");
+    d_table.upload(table.data(), table.size(), st, "stack weights");
     double* out = d_out.as<double>();
     HIPCHK(launch_stack_planes(K, cuts, sd.surf, p.mapping, d_table.as<double>(), static_cast<int>(k_count), static_cast<int>(ni), static_cast<int>(nj), out, out + n,
-                               out + 2 * n, d_outside ? d_outside->as<unsigned long long>() : nullptr, st));
-    if (d_outside) HIPCHK(hipMemcpyAsync(outside, d_outside->p, sizeof(uint64_t) * K, hipMemcpyDeviceToHost, st));
+                               out + 2 * n, d_outside.as<unsigned long long>(), st));
+    if (d_outside.p) HIPCHK(hipMemcpyAsync(outside, d_outside.p, sizeof(uint64_t) * K, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(x, out, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(y, out + n, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(z, out + 2 * n, sizeof(double) * n, hipMemcpyDeviceToHost, st));
@@ -167,15 +158,41 @@ void stack_surf_upload(const StackPlan& p, const SurfPlan& sf, StackCuts& cuts, 
     d.host.assign(nknots + sf.coef.size(), 0.0);
     std::copy(sf.knots.begin(), sf.knots.end(), d.host.begin());
     std::copy(sf.coef.begin(), sf.coef.end(), d.host.begin() + nknots);
-    d.dev = std::make_unique<StackBuf>(sizeof(double) * d.host.size(), "stack meridional tables");
-    HIPCHK(hipMemcpyAsync(d.dev->p, d.host.data(), sizeof(double) * d.host.size(), hipMemcpyHostToDevice, st));
-    d.surf.knots = d.dev->as<double>();
-    d.surf.coef = d.dev->as<double>() + nknots;
+    d.surf.knots = d.dev.upload(d.host.data(), d.host.size(), st, "stack meridional tables");
+    d.surf.coef = d.surf.knots + nknots;
     for (int c = 0; c < TM_STACK_MAX_CUTS; ++c) {
         d.surf.first[c] = c < p.ncuts ? sf.first[c] : 0;
         d.surf.nknots[c] = c < p.ncuts ? sf.nknots[c] : 2;
         if (c < p.ncuts) cuts.radius[c] = sf.rref[c];
     }
+}
+
+StackPlan stack_plan_any(const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, SurfPlan& sf, const SurfPlan** used) {
+    if (!opt) throw TmError(TM_E_ARG, "null stack options, span or layers");
+    const bool rev = opt->mapping == TM_STACK_REVOLUTION;
+    if (!rev && surfaces) throw TmError(TM_E_ARG, "meridional tables go with TM_STACK_REVOLUTION only");
+    *used = rev ? &sf : nullptr;
+    return rev ? stack_plan_surf(opt, surfaces, sf) : stack_plan(opt);
+}
+
+void stack_upload_cuts(const tm_mesh_desc* const* cuts, int ncuts, uint64_t block, uint64_t ni, uint64_t nj, DevBuf& in, StackCuts& dc) {
+    require_gfx950();
+    const size_t n = static_cast<size_t>(ni) * nj;
+    in.grow(sizeof(double2) * n * ncuts, "stack cuts");
+    for (int c = 0; c < ncuts; ++c) {
+        dc.xy[c] = in.as<double2>() + n * c;
+        HIPCHK(hipMemcpy(in.as<double2>() + n * c, cuts[c]->blocks[block].xy, sizeof(double2) * n, hipMemcpyHostToDevice));
+    }
+}
+
+std::vector<double> stack_weight_table(const StackPlan& p, uint64_t k_begin, uint64_t k_count, size_t extra) {
+    const int K = p.ncuts;
+    std::vector<double> table(static_cast<size_t>(k_count) * (K + 1) + extra);
+    for (uint64_t k = 0; k < k_count; ++k) {
+        std::memcpy(&table[k * (K + 1)], &p.weights[(k_begin + k) * K], sizeof(double) * K);
+        table[k * (K + 1) + K] = p.layers[k_begin + k];
+    }
+    return table;
 }
 
 void stack_resident_cuts(tm_smoother* const* cuts, const StackPlan& p, uint64_t block, StackCuts& dc, uint64_t* ni, uint64_t* nj) {
@@ -212,23 +229,33 @@ hipStream_t stack_order_behind(tm_smoother* const* cuts, int ncuts, std::vector<
 
 using namespace tmh;
 
+// sf: the filled meridional plan of the _surf entry points, null for the plain ones (`p` then comes from stack_plan)
+static void stack_block(const tm_mesh_desc* const* cuts, const StackPlan& p, const SurfPlan* sf, uint64_t block, uint64_t k_begin, uint64_t k_count, double* x, double* y,
+                        double* z, uint64_t* outside) {
+    stack_check_window(p, k_begin, k_count);
+    uint64_t ni = 0, nj = 0;
+    stack_check_cuts(cuts, p.ncuts, block, &ni, &nj);
+    DevBuf in;
+    StackCuts dc{};
+    stack_upload_cuts(cuts, p.ncuts, block, ni, nj, in, dc);
+    stack_run(p, dc, k_begin, k_count, ni, nj, x, y, z, nullptr, sf, outside);
+}
+static void stack_smoothers(tm_smoother* const* cuts, const StackPlan& p, const SurfPlan* sf, uint64_t block, uint64_t k_begin, uint64_t k_count, double* x, double* y,
+                            double* z, uint64_t* outside) {
+    stack_check_window(p, k_begin, k_count);
+    StackCuts dc{};
+    uint64_t ni = 0, nj = 0;
+    stack_resident_cuts(cuts, p, block, dc, &ni, &nj);
+    std::vector<std::unique_ptr<StackEvent>> events;
+    const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
+    stack_run(p, dc, k_begin, k_count, ni, nj, x, y, z, st, sf, outside);   // synchronises st: the other handles' coordinates have been read when it returns
+}
+
 extern "C" int tm_stack_block(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt, uint64_t block, uint64_t k_begin, uint64_t k_count, double* x,
                               double* y, double* z) {
     return guarded([&]() {
         if (!x || !y || !z) throw TmError(TM_E_ARG, "null argument");
-        const StackPlan p = stack_plan(opt);
-        stack_check_window(p, k_begin, k_count);
-        uint64_t ni = 0, nj = 0;
-        stack_check_cuts(cuts, p.ncuts, block, &ni, &nj);
-        require_gfx950_stack();
-        const size_t n = static_cast<size_t>(ni) * nj;
-        StackBuf in(sizeof(double2) * n * p.ncuts, "stack cuts");
-        StackCuts dc{};
-        for (int c = 0; c < p.ncuts; ++c) {
-            dc.xy[c] = in.as<double2>() + n * c;
-            HIPCHK(hipMemcpy(in.as<double2>() + n * c, cuts[c]->blocks[block].xy, sizeof(double2) * n, hipMemcpyHostToDevice));
-        }
-        stack_run(p, dc, k_begin, k_count, ni, nj, x, y, z, nullptr);
+        stack_block(cuts, stack_plan(opt), nullptr, block, k_begin, k_count, x, y, z, nullptr);
         return TM_OK;
     });
 }
@@ -237,14 +264,7 @@ extern "C" int tm_stack_smoothers(tm_smoother* const* cuts, const tm_stack_opt* 
                                   double* y, double* z) {
     return guarded([&]() {
         if (!cuts || !x || !y || !z) throw TmError(TM_E_ARG, "null argument");
-        const StackPlan p = stack_plan(opt);
-        stack_check_window(p, k_begin, k_count);
-        StackCuts dc{};
-        uint64_t ni = 0, nj = 0;
-        stack_resident_cuts(cuts, p, block, dc, &ni, &nj);
-        std::vector<std::unique_ptr<StackEvent>> events;
-        const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
-        stack_run(p, dc, k_begin, k_count, ni, nj, x, y, z, st);   // synchronises st: the other handles' coordinates have been read when it returns
+        stack_smoothers(cuts, stack_plan(opt), nullptr, block, k_begin, k_count, x, y, z, nullptr);
         return TM_OK;
     });
 }
@@ -255,18 +275,7 @@ extern "C" int tm_stack_block_surf(const tm_mesh_desc* const* cuts, const tm_sta
         if (!x || !y || !z) throw TmError(TM_E_ARG, "null argument");
         SurfPlan sf;
         const StackPlan p = stack_plan_surf(opt, surfaces, sf);
-        stack_check_window(p, k_begin, k_count);
-        uint64_t ni = 0, nj = 0;
-        stack_check_cuts(cuts, p.ncuts, block, &ni, &nj);
-        require_gfx950_stack();
-        const size_t n = static_cast<size_t>(ni) * nj;
-        StackBuf in(sizeof(double2) * n * p.ncuts, "stack cuts");
-        StackCuts dc{};
-        for (int c = 0; c < p.ncuts; ++c) {
-            dc.xy[c] = in.as<double2>() + n * c;
-            HIPCHK(hipMemcpy(in.as<double2>() + n * c, cuts[c]->blocks[block].xy, sizeof(double2) * n, hipMemcpyHostToDevice));
-        }
-        stack_run(p, dc, k_begin, k_count, ni, nj, x, y, z, nullptr, &sf, outside);
+        stack_block(cuts, p, &sf, block, k_begin, k_count, x, y, z, outside);
         return TM_OK;
     });
 }
@@ -277,13 +286,7 @@ extern "C" int tm_stack_smoothers_surf(tm_smoother* const* cuts, const tm_stack_
         if (!cuts || !x || !y || !z) throw TmError(TM_E_ARG, "null argument");
         SurfPlan sf;
         const StackPlan p = stack_plan_surf(opt, surfaces, sf);
-        stack_check_window(p, k_begin, k_count);
-        StackCuts dc{};
-        uint64_t ni = 0, nj = 0;
-        stack_resident_cuts(cuts, p, block, dc, &ni, &nj);
-        std::vector<std::unique_ptr<StackEvent>> events;
-        const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
-        stack_run(p, dc, k_begin, k_count, ni, nj, x, y, z, st, &sf, outside);   // synchronises st
+        stack_smoothers(cuts, p, &sf, block, k_begin, k_count, x, y, z, outside);
         return TM_OK;
     });
 }

@@ -1,10 +1,11 @@
-// What the device entry points over K cuts share (tm_stack.hip: K11, tm_stack_quality.hip: K12): the kernels' argument block, RAII
-// buffers and events, the gfx950 check, and the K handles of a call resolved to device pointers behind their pending work.
+// What the device entry points over K cuts share (tm_stack.hip: K11, tm_stack_quality.hip: K12, K16, K17): the kernels' argument block,
+// RAII events, the preambles of the entry points (plan, cuts to the device or resolved from K handles behind their pending work) and
+// the weight table.
 #pragma once
 #include "tm_stack.hpp"
 #include "tm_stack_surface.hpp"
 #include "tm_api_util.hpp"
-#include "tm_smoother.hpp"
+#include "tm_devbuf.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -28,17 +29,6 @@ struct StackSurf {
     int nknots[TM_STACK_MAX_CUTS];   // 2 .. TM_STACK_MAX_KNOTS
 };
 
-struct StackBuf {   // RAII device buffer
-    void* p = nullptr;
-    explicit StackBuf(size_t bytes, const char* what) {
-        if (hipMalloc(&p, bytes ? bytes : 256) != hipSuccess) throw TmError(TM_E_MEMORY, std::string("hipMalloc failed (") + what + ")");
-    }
-    ~StackBuf() { (void)hipFree(p); }
-    StackBuf(const StackBuf&) = delete;
-    StackBuf& operator=(const StackBuf&) = delete;
-    template <class T>
-    T* as() { return static_cast<T*>(p); }
-};
 struct StackEvent {
     hipEvent_t e = nullptr;
     StackEvent() { HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
@@ -81,7 +71,7 @@ __device__ __forceinline__ bool stack_surf_node(const double* sh_u, const StackS
 // The tables of `sf` into one device buffer on `st` (`host` must live until st has been synchronised); reference radii into cuts.radius.
 struct StackSurfDev {
     std::vector<double> host;
-    std::unique_ptr<struct StackBuf> dev;
+    DevBuf dev;
     StackSurf surf{};
 };
 void stack_surf_upload(const StackPlan& p, const SurfPlan& sf, StackCuts& cuts, StackSurfDev& d, hipStream_t st);
@@ -89,15 +79,15 @@ void stack_surf_upload(const StackPlan& p, const SurfPlan& sf, StackCuts& cuts, 
 hipError_t launch_stack_planes(int K, const StackCuts& cuts, const StackSurf& surf, int mapping, const double* table, int nk, int ni, int nj, double* X, double* Y,
                                double* Z, unsigned long long* outside, hipStream_t st);
 
-inline void require_gfx950_stack() {
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, dev));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        throw TmError(TM_E_HIP, std::string("libtm_hip is built for gfx950 (MI355X) only, found ") + prop.gcnArchName);
-}
-
+// The plan of an entry point that may come with meridional tables: TM_E_ARG for null options or tables without TM_STACK_REVOLUTION;
+// *used = &sf (filled) with TM_STACK_REVOLUTION, null otherwise.
+StackPlan stack_plan_any(const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, SurfPlan& sf, const SurfPlan** used);
+// Block `block` of K host descriptions (checked already: ni x nj nodes each) into `in`, cut after cut, and their addresses into dc; makes
+// the gfx950 check first.
+void stack_upload_cuts(const tm_mesh_desc* const* cuts, int ncuts, uint64_t block, uint64_t ni, uint64_t nj, DevBuf& in, StackCuts& dc);
+// Layers [k_begin, k_begin + k_count) of the plan as the kernels read them: per layer K weights followed by s[k]; `extra` doubles of room
+// behind the rows for a caller's own tables.
+std::vector<double> stack_weight_table(const StackPlan& p, uint64_t k_begin, uint64_t k_count, size_t extra = 0);
 // Block `block` of K live handles: TM_E_ARG / TM_E_SIZE as include/tm_hip.h says for tm_stack_smoothers; the device pointers into dc and
 // the block's size into ni, nj.
 void stack_resident_cuts(tm_smoother* const* cuts, const StackPlan& p, uint64_t block, StackCuts& dc, uint64_t* ni, uint64_t* nj);

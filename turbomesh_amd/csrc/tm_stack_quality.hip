@@ -26,6 +26,8 @@
 // Compiler's resource usage (cross-compile, -Rpass-analysis=kernel-resource-usage): DESIGN.md section 4, K12.
 #include "tm_quality3d.h"
 #include "tm_stack_dev.hpp"
+#include "tm_dispatch.hpp"
+#include "tm_records.hpp"
 
 #include <cstring>
 
@@ -186,20 +188,11 @@ __global__ __launch_bounds__(SQ_THREADS) void k_stack_quality(StackCuts cuts, St
     }
 }
 
-// one wave: lane t combines records t, t + 64, ... in that order, then the 64 lanes' records pairwise through LDS (32, 16, ... 1) -- a
-// fixed order, so the sums are the same on every run
+// one wave combines the records in the fixed order of records_reduce_wave, so the sums are the same on every run
 __global__ __launch_bounds__(64) void k_stack_quality_finalize(const Q3Acc* __restrict__ partials, long long nrec, uint64_t block, uint64_t ni, uint64_t nj,
                                                                uint64_t nk, tm_quality3d* __restrict__ out) {
     __shared__ Q3Acc sh[64];
-    Q3Acc a;
-    q3_init(a);
-    for (long long r = threadIdx.x; r < nrec; r += 64) q3_combine(a, partials[r]);
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int off = 32; off > 0; off >>= 1) {
-        if (static_cast<int>(threadIdx.x) < off) q3_combine(sh[threadIdx.x], sh[threadIdx.x + off]);
-        __syncthreads();
-    }
+    records_reduce_wave<Q3Acc, q3_init, q3_combine>(partials, 0ll, nrec, sh);
     if (threadIdx.x == 0) q3_finish(sh[0], block, ni, nj, nk, out);
 }
 
@@ -219,25 +212,9 @@ static void stack_quality_launch_k(const StackCuts& cuts, const StackSurf& surf,
 
 static hipError_t launch_stack_quality(int K, const StackCuts& cuts, const StackSurf& surf, int mapping, const double* table, int k0, int k1, int ni, int nj, Q3Acc* partials,
                                        double* field, int orientation, hipStream_t st) {
-    switch (K) {
-#define TM_STACK_CASE(n) \
-    case n: stack_quality_launch_k<n>(cuts, surf, mapping, table, k0, k1, ni, nj, partials, field, orientation, st); break;
-        TM_STACK_CASE(2) TM_STACK_CASE(3) TM_STACK_CASE(4) TM_STACK_CASE(5) TM_STACK_CASE(6) TM_STACK_CASE(7) TM_STACK_CASE(8) TM_STACK_CASE(9)
-        TM_STACK_CASE(10) TM_STACK_CASE(11) TM_STACK_CASE(12) TM_STACK_CASE(13) TM_STACK_CASE(14) TM_STACK_CASE(15) TM_STACK_CASE(16)
-#undef TM_STACK_CASE
-        default: return hipErrorInvalidValue;
-    }
+    if (K < 2 || K > TM_STACK_MAX_CUTS) return hipErrorInvalidValue;
+    dispatch_int<2, TM_STACK_MAX_CUTS>(K, [&](auto k) { stack_quality_launch_k<k()>(cuts, surf, mapping, table, k0, k1, ni, nj, partials, field, orientation, st); });
     return hipGetLastError();
-}
-
-// every layer's weight row and s[k] on the device (copied on `st`; `host` must live until st has been synchronised)
-static void stack_quality_table(const StackPlan& p, std::vector<double>& host, StackBuf& dev, hipStream_t st) {
-    const int K = p.ncuts;
-    for (uint64_t k = 0; k < p.nlayers; ++k) {
-        std::memcpy(&host[k * (K + 1)], &p.weights[k * K], sizeof(double) * K);
-        host[k * (K + 1) + K] = p.layers[k];
-    }
-    HIPCHK(hipMemcpyAsync(dev.p, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, st));
 }
 
 static void stack_quality_check_sizes(const StackPlan& p, uint64_t ni, uint64_t nj) {
@@ -255,9 +232,9 @@ static void stack_quality_run(const StackPlan& p, StackCuts& cuts, uint64_t bloc
     if (sf) stack_surf_upload(p, *sf, cuts, sd, st);
     const dim3 grid = stack_quality_grid(static_cast<int>(ni), static_cast<int>(nj));
     const size_t nrec = static_cast<size_t>(grid.x) * grid.y;   // the records buffer is sized from the very grid that writes it
-    std::vector<double> table(static_cast<size_t>(p.nlayers) * (K + 1));
-    StackBuf d_table(sizeof(double) * table.size(), "stack weights"), d_rec(sizeof(Q3Acc) * nrec, "stack quality records"), d_out(sizeof(tm_quality3d), "stack quality result");
-    stack_quality_table(p, table, d_table, st);
+    const std::vector<double> table = stack_weight_table(p, 0, p.nlayers);
+    DevBuf d_table, d_rec(sizeof(Q3Acc) * nrec, "stack quality records"), d_out(sizeof(tm_quality3d), "stack quality result");
+    d_table.upload(table.data(), table.size(), st, "stack weights");
     HIPCHK(launch_stack_quality(K, cuts, sd.surf, p.mapping, d_table.as<double>(), 0, static_cast<int>(p.nlayers) - 1, static_cast<int>(ni), static_cast<int>(nj), d_rec.as<Q3Acc>(),
                                 nullptr, 0, st));
     hipLaunchKernelGGL(k_stack_quality_finalize, dim3(1), dim3(64), 0, st, d_rec.as<Q3Acc>(), static_cast<long long>(nrec), block, ni, nj, p.nlayers, d_out.as<tm_quality3d>());
@@ -274,9 +251,9 @@ static void stack_quality_field_run(const StackPlan& p, StackCuts& cuts, uint64_
     StackSurfDev sd;
     if (sf) stack_surf_upload(p, *sf, cuts, sd, st);
     const size_t cells = static_cast<size_t>(k_count) * (ni - 1) * (nj - 1);
-    std::vector<double> table(static_cast<size_t>(p.nlayers) * (K + 1));
-    StackBuf d_table(sizeof(double) * table.size(), "stack weights"), d_field(sizeof(double) * cells, "stack quality cells");
-    stack_quality_table(p, table, d_table, st);
+    const std::vector<double> table = stack_weight_table(p, 0, p.nlayers);
+    DevBuf d_table, d_field(sizeof(double) * cells, "stack quality cells");
+    d_table.upload(table.data(), table.size(), st, "stack weights");
     HIPCHK(launch_stack_quality(K, cuts, sd.surf, p.mapping, d_table.as<double>(), static_cast<int>(k_begin), static_cast<int>(k_begin + k_count), static_cast<int>(ni),
                                 static_cast<int>(nj), nullptr, d_field.as<double>(), orientation, st));
     HIPCHK(hipMemcpyAsync(host_field, d_field.p, sizeof(double) * cells, hipMemcpyDeviceToHost, st));
@@ -287,22 +264,36 @@ static void stack_quality_field_run(const StackPlan& p, StackCuts& cuts, uint64_
 
 using namespace tmh;
 
+// sf: the filled meridional plan of the _surf entry points, null for the plain ones (`p` then comes from stack_plan)
+static void stack_quality_host_cuts(const tm_mesh_desc* const* cuts, const StackPlan& p, const SurfPlan* sf, uint64_t block, tm_quality3d* out) {
+    uint64_t ni = 0, nj = 0;
+    stack_check_cuts(cuts, p.ncuts, block, &ni, &nj);
+    stack_quality_check_sizes(p, ni, nj);
+    DevBuf in;
+    StackCuts dc{};
+    stack_upload_cuts(cuts, p.ncuts, block, ni, nj, in, dc);
+    stack_quality_run(p, dc, block, ni, nj, out, nullptr, sf);
+}
+// want_field false: the report into *out; true: the orientation from the report, then the cell layers [k_begin, k_begin + k_count) into field
+static void stack_quality_smoothers(tm_smoother* const* cuts, const StackPlan& p, const SurfPlan* sf, uint64_t block, tm_quality3d* out, bool want_field,
+                                    uint64_t k_begin, uint64_t k_count, double* field) {
+    StackCuts dc{};
+    uint64_t ni = 0, nj = 0;
+    stack_resident_cuts(cuts, p, block, dc, &ni, &nj);
+    stack_quality_check_sizes(p, ni, nj);
+    if (want_field && (k_count < 1 || k_begin >= p.nlayers - 1 || k_count > p.nlayers - 1 - k_begin))
+        throw TmError(TM_E_ARG, "the window of cell layers is empty or reaches past nlayers - 1");
+    std::vector<std::unique_ptr<StackEvent>> events;
+    const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
+    tm_quality3d q;
+    stack_quality_run(p, dc, block, ni, nj, want_field ? &q : out, st, sf);   // synchronises st: the other handles' coordinates have been read when it returns
+    if (want_field) stack_quality_field_run(p, dc, ni, nj, k_begin, k_count, q.orientation, field, st, sf);
+}
+
 extern "C" int tm_stack_quality(const tm_mesh_desc* const* cuts, const tm_stack_opt* opt, uint64_t block, tm_quality3d* out) {
     return guarded([&]() {
         if (!out) throw TmError(TM_E_ARG, "null argument");
-        const StackPlan p = stack_plan(opt);
-        uint64_t ni = 0, nj = 0;
-        stack_check_cuts(cuts, p.ncuts, block, &ni, &nj);
-        stack_quality_check_sizes(p, ni, nj);
-        require_gfx950_stack();
-        const size_t n = static_cast<size_t>(ni) * nj;
-        StackBuf in(sizeof(double2) * n * p.ncuts, "stack cuts");
-        StackCuts dc{};
-        for (int c = 0; c < p.ncuts; ++c) {
-            dc.xy[c] = in.as<double2>() + n * c;
-            HIPCHK(hipMemcpy(in.as<double2>() + n * c, cuts[c]->blocks[block].xy, sizeof(double2) * n, hipMemcpyHostToDevice));
-        }
-        stack_quality_run(p, dc, block, ni, nj, out, nullptr);
+        stack_quality_host_cuts(cuts, stack_plan(opt), nullptr, block, out);
         return TM_OK;
     });
 }
@@ -310,14 +301,7 @@ extern "C" int tm_stack_quality(const tm_mesh_desc* const* cuts, const tm_stack_
 extern "C" int tm_stack_smoothers_quality(tm_smoother* const* cuts, const tm_stack_opt* opt, uint64_t block, tm_quality3d* out) {
     return guarded([&]() {
         if (!cuts || !out) throw TmError(TM_E_ARG, "null argument");
-        const StackPlan p = stack_plan(opt);
-        StackCuts dc{};
-        uint64_t ni = 0, nj = 0;
-        stack_resident_cuts(cuts, p, block, dc, &ni, &nj);
-        stack_quality_check_sizes(p, ni, nj);
-        std::vector<std::unique_ptr<StackEvent>> events;
-        const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
-        stack_quality_run(p, dc, block, ni, nj, out, st);   // synchronises st: the other handles' coordinates have been read when it returns
+        stack_quality_smoothers(cuts, stack_plan(opt), nullptr, block, out, false, 0, 0, nullptr);
         return TM_OK;
     });
 }
@@ -326,17 +310,7 @@ extern "C" int tm_stack_smoothers_quality_field(tm_smoother* const* cuts, const 
                                                 double* min_scaled_jacobian) {
     return guarded([&]() {
         if (!cuts || !min_scaled_jacobian) throw TmError(TM_E_ARG, "null argument");
-        const StackPlan p = stack_plan(opt);
-        StackCuts dc{};
-        uint64_t ni = 0, nj = 0;
-        stack_resident_cuts(cuts, p, block, dc, &ni, &nj);
-        stack_quality_check_sizes(p, ni, nj);
-        if (k_count < 1 || k_begin >= p.nlayers - 1 || k_count > p.nlayers - 1 - k_begin) throw TmError(TM_E_ARG, "the window of cell layers is empty or reaches past nlayers - 1");
-        std::vector<std::unique_ptr<StackEvent>> events;
-        const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
-        tm_quality3d q;
-        stack_quality_run(p, dc, block, ni, nj, &q, st);   // the orientation first
-        stack_quality_field_run(p, dc, ni, nj, k_begin, k_count, q.orientation, min_scaled_jacobian, st);
+        stack_quality_smoothers(cuts, stack_plan(opt), nullptr, block, nullptr, true, k_begin, k_count, min_scaled_jacobian);
         return TM_OK;
     });
 }
@@ -347,18 +321,7 @@ extern "C" int tm_stack_quality_surf(const tm_mesh_desc* const* cuts, const tm_s
         if (!out) throw TmError(TM_E_ARG, "null argument");
         SurfPlan sf;
         const StackPlan p = stack_plan_surf(opt, surfaces, sf);
-        uint64_t ni = 0, nj = 0;
-        stack_check_cuts(cuts, p.ncuts, block, &ni, &nj);
-        stack_quality_check_sizes(p, ni, nj);
-        require_gfx950_stack();
-        const size_t n = static_cast<size_t>(ni) * nj;
-        StackBuf in(sizeof(double2) * n * p.ncuts, "stack cuts");
-        StackCuts dc{};
-        for (int c = 0; c < p.ncuts; ++c) {
-            dc.xy[c] = in.as<double2>() + n * c;
-            HIPCHK(hipMemcpy(in.as<double2>() + n * c, cuts[c]->blocks[block].xy, sizeof(double2) * n, hipMemcpyHostToDevice));
-        }
-        stack_quality_run(p, dc, block, ni, nj, out, nullptr, &sf);
+        stack_quality_host_cuts(cuts, p, &sf, block, out);
         return TM_OK;
     });
 }
@@ -369,13 +332,7 @@ extern "C" int tm_stack_smoothers_quality_surf(tm_smoother* const* cuts, const t
         if (!cuts || !out) throw TmError(TM_E_ARG, "null argument");
         SurfPlan sf;
         const StackPlan p = stack_plan_surf(opt, surfaces, sf);
-        StackCuts dc{};
-        uint64_t ni = 0, nj = 0;
-        stack_resident_cuts(cuts, p, block, dc, &ni, &nj);
-        stack_quality_check_sizes(p, ni, nj);
-        std::vector<std::unique_ptr<StackEvent>> events;
-        const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
-        stack_quality_run(p, dc, block, ni, nj, out, st, &sf);   // synchronises st
+        stack_quality_smoothers(cuts, p, &sf, block, out, false, 0, 0, nullptr);
         return TM_OK;
     });
 }
@@ -386,16 +343,7 @@ extern "C" int tm_stack_smoothers_quality_field_surf(tm_smoother* const* cuts, c
         if (!cuts || !min_scaled_jacobian) throw TmError(TM_E_ARG, "null argument");
         SurfPlan sf;
         const StackPlan p = stack_plan_surf(opt, surfaces, sf);
-        StackCuts dc{};
-        uint64_t ni = 0, nj = 0;
-        stack_resident_cuts(cuts, p, block, dc, &ni, &nj);
-        stack_quality_check_sizes(p, ni, nj);
-        if (k_count < 1 || k_begin >= p.nlayers - 1 || k_count > p.nlayers - 1 - k_begin) throw TmError(TM_E_ARG, "the window of cell layers is empty or reaches past nlayers - 1");
-        std::vector<std::unique_ptr<StackEvent>> events;
-        const hipStream_t st = stack_order_behind(cuts, p.ncuts, events);
-        tm_quality3d q;
-        stack_quality_run(p, dc, block, ni, nj, &q, st, &sf);   // the orientation first
-        stack_quality_field_run(p, dc, ni, nj, k_begin, k_count, q.orientation, min_scaled_jacobian, st, &sf);
+        stack_quality_smoothers(cuts, p, &sf, block, nullptr, true, k_begin, k_count, min_scaled_jacobian);
         return TM_OK;
     });
 }

@@ -404,44 +404,29 @@ __global__ __launch_bounds__(WELD_THREADS) void k_weld_cells(const int32_t* __re
 }
 
 // ------------------------------------------------------------------ host driver
-WeldDev::~WeldDev() {
-    for (Buf* b : {&blocks, &conns, &parent, &count, &map, &part1, &off1, &part2, &off2, &counters, &src, &out, &gaps, &gap, &ptrs, &local, &cells})
-        if (b->p) (void)hipFree(b->p);
-}
-
-static void weld_grow(WeldDev::Buf& b, size_t bytes, const char* what) {
-    if (b.cap >= bytes && b.p) return;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    if (hipMalloc(&b.p, bytes ? bytes : 256) != hipSuccess) throw TmError(TM_E_MEMORY, std::string("hipMalloc failed (") + what + ")");
-    b.cap = bytes ? bytes : 256;
-}
-template <class T>
-static T* as(const WeldDev::Buf& b) { return static_cast<T*>(b.p); }
 static unsigned weld_groups(int64_t n, int per) { return static_cast<unsigned>((n + per - 1) / per); }
 
 void WeldDev::link(const WeldPlan& pl, hipStream_t st) {
     const int nslots = static_cast<int>(pl.slots);
-    weld_grow(blocks, sizeof(WeldBlock) * pl.blocks.size(), "weld block table");
-    weld_grow(conns, sizeof(tm_connection) * pl.conns.size(), "weld connection table");
-    weld_grow(parent, sizeof(int32_t) * nslots, "weld labels");
-    weld_grow(count, sizeof(int32_t) * nslots, "weld class counts");
-    weld_grow(counters, sizeof(unsigned long long) * WELD_COUNTERS, "weld counters");
+    blocks.grow(sizeof(WeldBlock) * pl.blocks.size(), "weld block table");
+    conns.grow(sizeof(tm_connection) * pl.conns.size(), "weld connection table");
+    parent.grow(sizeof(int32_t) * nslots, "weld labels");
+    count.grow(sizeof(int32_t) * nslots, "weld class counts");
+    counters.grow(sizeof(unsigned long long) * WELD_COUNTERS, "weld counters");
     HIPCHK(hipMemcpyAsync(blocks.p, pl.blocks.data(), sizeof(WeldBlock) * pl.blocks.size(), hipMemcpyHostToDevice, st));
     if (!pl.conns.empty()) HIPCHK(hipMemcpyAsync(conns.p, pl.conns.data(), sizeof(tm_connection) * pl.conns.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(counters.p, 0, sizeof(unsigned long long) * WELD_COUNTERS, st));
     const dim3 over_slots(weld_groups(nslots, WELD_THREADS));
-    hipLaunchKernelGGL(k_weld_init, over_slots, dim3(WELD_THREADS), 0, st, as<int32_t>(parent), as<int32_t>(count), nslots);
+    hipLaunchKernelGGL(k_weld_init, over_slots, dim3(WELD_THREADS), 0, st, parent.as<int32_t>(), count.as<int32_t>(), nslots);
     HIPCHK(hipGetLastError());
     if (pl.max_pairs > 0) {   // the connection table as it stands: grid.y = connection (at most 65535: weld_plan)
         hipLaunchKernelGGL(k_weld_hook, dim3(weld_groups(pl.max_pairs, WELD_THREADS), static_cast<unsigned>(pl.conns.size())), dim3(WELD_THREADS), 0, st,
-                           as<WeldBlock>(blocks), as<tm_connection>(conns), as<int32_t>(parent));
+                           blocks.as<WeldBlock>(), conns.as<tm_connection>(), parent.as<int32_t>());
         HIPCHK(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_weld_compress, over_slots, dim3(WELD_THREADS), 0, st, as<int32_t>(parent), as<int32_t>(count), nslots);
+    hipLaunchKernelGGL(k_weld_compress, over_slots, dim3(WELD_THREADS), 0, st, parent.as<int32_t>(), count.as<int32_t>(), nslots);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_weld_classes, over_slots, dim3(WELD_THREADS), 0, st, as<int32_t>(parent), as<int32_t>(count), nslots, as<unsigned long long>(counters));
+    hipLaunchKernelGGL(k_weld_classes, over_slots, dim3(WELD_THREADS), 0, st, parent.as<int32_t>(), count.as<int32_t>(), nslots, counters.as<unsigned long long>());
     HIPCHK(hipGetLastError());
 }
 
@@ -454,29 +439,29 @@ static int weld_max_perimeter(const WeldPlan& pl) {
 void WeldDev::number(const WeldPlan& pl, hipStream_t st) {
     const int N = static_cast<int>(pl.nodes), nb = pl.nblocks();
     const int t1 = static_cast<int>(weld_groups(N, WELD_TILE)), t2 = static_cast<int>(weld_groups(t1, WELD_PTILE));   // t1 <= 2^20, t2 <= 1024
-    weld_grow(map, sizeof(int32_t) * static_cast<size_t>(N), "weld map");
-    weld_grow(part1, sizeof(int32_t) * t1, "weld tile sums");
-    weld_grow(off1, sizeof(int32_t) * t1, "weld tile offsets");
-    weld_grow(part2, sizeof(int32_t) * t2, "weld tile sums, second level");
-    weld_grow(off2, sizeof(int32_t) * t2, "weld tile offsets, second level");
+    map.grow(sizeof(int32_t) * static_cast<size_t>(N), "weld map");
+    part1.grow(sizeof(int32_t) * t1, "weld tile sums");
+    off1.grow(sizeof(int32_t) * t1, "weld tile offsets");
+    part2.grow(sizeof(int32_t) * t2, "weld tile sums, second level");
+    off2.grow(sizeof(int32_t) * t2, "weld tile offsets, second level");
     const dim3 wg(WELD_THREADS);
-    hipLaunchKernelGGL(k_weld_count, dim3(t1), wg, 0, st, as<WeldBlock>(blocks), nb, as<int32_t>(parent), N, as<int32_t>(part1));
+    hipLaunchKernelGGL(k_weld_count, dim3(t1), wg, 0, st, blocks.as<WeldBlock>(), nb, parent.as<int32_t>(), N, part1.as<int32_t>());
     HIPCHK(hipGetLastError());
     if (t2 == 1) {
-        hipLaunchKernelGGL(k_weld_pscan, dim3(1), wg, 0, st, as<int32_t>(part1), t1, static_cast<const int32_t*>(nullptr), as<int32_t>(off1));
+        hipLaunchKernelGGL(k_weld_pscan, dim3(1), wg, 0, st, part1.as<int32_t>(), t1, static_cast<const int32_t*>(nullptr), off1.as<int32_t>());
     } else {   // the tile sums span more than one tile themselves: their sums, scanned by one workgroup (t2 <= WELD_PTILE), come back as tile offsets
-        hipLaunchKernelGGL(k_weld_psum, dim3(t2), wg, 0, st, as<int32_t>(part1), t1, as<int32_t>(part2));
+        hipLaunchKernelGGL(k_weld_psum, dim3(t2), wg, 0, st, part1.as<int32_t>(), t1, part2.as<int32_t>());
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_weld_pscan, dim3(1), wg, 0, st, as<int32_t>(part2), t2, static_cast<const int32_t*>(nullptr), as<int32_t>(off2));
+        hipLaunchKernelGGL(k_weld_pscan, dim3(1), wg, 0, st, part2.as<int32_t>(), t2, static_cast<const int32_t*>(nullptr), off2.as<int32_t>());
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_weld_pscan, dim3(t2), wg, 0, st, as<int32_t>(part1), t1, as<int32_t>(off2), as<int32_t>(off1));
+        hipLaunchKernelGGL(k_weld_pscan, dim3(t2), wg, 0, st, part1.as<int32_t>(), t1, off2.as<int32_t>(), off1.as<int32_t>());
     }
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_weld_number, dim3(t1), wg, 0, st, as<WeldBlock>(blocks), nb, as<int32_t>(parent), N, as<int32_t>(off1), as<int32_t>(map),
-                       as<unsigned long long>(counters));
+    hipLaunchKernelGGL(k_weld_number, dim3(t1), wg, 0, st, blocks.as<WeldBlock>(), nb, parent.as<int32_t>(), N, off1.as<int32_t>(), map.as<int32_t>(),
+                       counters.as<unsigned long long>());
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_weld_slaves, dim3(weld_groups(weld_max_perimeter(pl), WELD_THREADS), nb), wg, 0, st, as<WeldBlock>(blocks), nb, as<int32_t>(parent),
-                       as<int32_t>(map));
+    hipLaunchKernelGGL(k_weld_slaves, dim3(weld_groups(weld_max_perimeter(pl), WELD_THREADS), nb), wg, 0, st, blocks.as<WeldBlock>(), nb, parent.as<int32_t>(),
+                       map.as<int32_t>());
     HIPCHK(hipGetLastError());
 }
 
@@ -498,19 +483,19 @@ void WeldDev::read_map(const WeldPlan& pl, hipStream_t st, int32_t* host_map, tm
 }
 
 void WeldDev::upload_map(const WeldPlan& pl, hipStream_t st, const int32_t* host_map) {
-    weld_grow(map, sizeof(int32_t) * static_cast<size_t>(pl.nodes), "weld map");
+    map.grow(sizeof(int32_t) * static_cast<size_t>(pl.nodes), "weld map");
     HIPCHK(hipMemcpyAsync(map.p, host_map, sizeof(int32_t) * static_cast<size_t>(pl.nodes), hipMemcpyHostToDevice, st));
 }
 
 void WeldDev::gap_run(const WeldPlan& pl, hipStream_t st, const WeldSrc& s, int64_t nodes_out, WeldGap* host_gap) {
     const dim3 grid(weld_groups(weld_max_perimeter(pl), WELD_THREADS), pl.nblocks());
     const int npart = static_cast<int>(grid.x * grid.y);
-    weld_grow(gaps, sizeof(WeldGap) * npart, "weld gap records");
-    weld_grow(gap, sizeof(WeldGap), "weld gap record");
-    hipLaunchKernelGGL(k_weld_gap, grid, dim3(WELD_THREADS), 0, st, as<WeldBlock>(blocks), as<int32_t>(parent), as<int32_t>(map), static_cast<int>(pl.nodes),
-                       static_cast<int>(nodes_out), s, as<double>(out), static_cast<long long>(s.layers) * nodes_out, as<WeldGap>(gaps));
+    gaps.grow(sizeof(WeldGap) * npart, "weld gap records");
+    gap.grow(sizeof(WeldGap), "weld gap record");
+    hipLaunchKernelGGL(k_weld_gap, grid, dim3(WELD_THREADS), 0, st, blocks.as<WeldBlock>(), parent.as<int32_t>(), map.as<int32_t>(), static_cast<int>(pl.nodes),
+                       static_cast<int>(nodes_out), s, out.as<double>(), static_cast<long long>(s.layers) * nodes_out, gaps.as<WeldGap>());
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_weld_gap_final, dim3(1), dim3(WELD_THREADS), 0, st, as<WeldGap>(gaps), npart, as<WeldGap>(gap));
+    hipLaunchKernelGGL(k_weld_gap_final, dim3(1), dim3(WELD_THREADS), 0, st, gaps.as<WeldGap>(), npart, gap.as<WeldGap>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(host_gap, gap.p, sizeof(WeldGap), hipMemcpyDeviceToHost, st));
 }
@@ -521,36 +506,36 @@ void WeldDev::points_planes(const WeldPlan& pl, hipStream_t st, int ncomp, int64
     const int nb = pl.nblocks();
     if (layers > 65535) throw TmError(TM_E_ARG, "more than 65535 layers");
     const size_t src_stride = static_cast<size_t>(layers) * N, out_stride = static_cast<size_t>(layers) * nodes_out;
-    weld_grow(src, sizeof(double) * src_stride * ncomp, "weld source planes");
-    weld_grow(out, sizeof(double) * out_stride * ncomp, "welded planes");
+    src.grow(sizeof(double) * src_stride * ncomp, "weld source planes");
+    out.grow(sizeof(double) * out_stride * ncomp, "welded planes");
     for (int c = 0; c < ncomp; ++c)
         for (int b = 0; b < nb; ++b) {
             const size_t n = static_cast<size_t>(pl.blocks[b].ni) * pl.blocks[b].nj;
             for (int64_t k = 0; k < layers; ++k)
-                HIPCHK(hipMemcpyAsync(as<double>(src) + c * src_stride + k * N + pl.blocks[b].off, planes[static_cast<size_t>(c) * nb + b] + k * n, sizeof(double) * n,
+                HIPCHK(hipMemcpyAsync(src.as<double>() + c * src_stride + k * N + pl.blocks[b].off, planes[static_cast<size_t>(c) * nb + b] + k * n, sizeof(double) * n,
                                       hipMemcpyHostToDevice, st));
         }
-    hipLaunchKernelGGL(k_weld_gather, dim3(weld_groups(N, WELD_TILE), static_cast<unsigned>(layers)), dim3(WELD_THREADS), 0, st, as<WeldBlock>(blocks), nb,
-                       as<int32_t>(parent), as<int32_t>(map), static_cast<int>(N), static_cast<int>(nodes_out), ncomp, as<double>(src),
-                       static_cast<long long>(src_stride), as<double>(out), static_cast<long long>(out_stride));
+    hipLaunchKernelGGL(k_weld_gather, dim3(weld_groups(N, WELD_TILE), static_cast<unsigned>(layers)), dim3(WELD_THREADS), 0, st, blocks.as<WeldBlock>(), nb,
+                       parent.as<int32_t>(), map.as<int32_t>(), static_cast<int>(N), static_cast<int>(nodes_out), ncomp, src.as<double>(),
+                       static_cast<long long>(src_stride), out.as<double>(), static_cast<long long>(out_stride));
     HIPCHK(hipGetLastError());
-    gap_run(pl, st, WeldSrc{as<double>(src), static_cast<long long>(src_stride), nullptr, ncomp, static_cast<int>(layers)}, nodes_out, host_gap);
-    for (int c = 0; c < ncomp; ++c) HIPCHK(hipMemcpyAsync(host_out[c], as<double>(out) + c * out_stride, sizeof(double) * out_stride, hipMemcpyDeviceToHost, st));
+    gap_run(pl, st, WeldSrc{src.as<double>(), static_cast<long long>(src_stride), nullptr, ncomp, static_cast<int>(layers)}, nodes_out, host_gap);
+    for (int c = 0; c < ncomp; ++c) HIPCHK(hipMemcpyAsync(host_out[c], out.as<double>() + c * out_stride, sizeof(double) * out_stride, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
 }
 
 void WeldDev::points_resident(const WeldPlan& pl, hipStream_t st, const std::vector<const double2*>& X, int64_t nodes_out, double* x, double* y, WeldGap* host_gap) {
     const int nb = pl.nblocks();
-    weld_grow(out, sizeof(double) * 2 * static_cast<size_t>(nodes_out), "welded planes");
-    weld_grow(ptrs, sizeof(const double2*) * nb, "weld block pointers");
+    out.grow(sizeof(double) * 2 * static_cast<size_t>(nodes_out), "welded planes");
+    ptrs.grow(sizeof(const double2*) * nb, "weld block pointers");
     HIPCHK(hipMemcpyAsync(ptrs.p, X.data(), sizeof(const double2*) * nb, hipMemcpyHostToDevice, st));
-    double* ox = as<double>(out);
+    double* ox = out.as<double>();
     double* oy = ox + nodes_out;
     for (int b = 0; b < nb; ++b) {
         const WeldBlock& B = pl.blocks[b];
         const dim3 grid((B.nj + 31) / 32, (B.ni + 31) / 32);
         if (grid.y > 65535u) throw TmError(TM_E_SIZE, "InconsistentSize: too many rows for one launch");
-        hipLaunchKernelGGL(k_weld_gather_resident, grid, dim3(WELD_THREADS), 0, st, X[b], B, as<int32_t>(parent), as<int32_t>(map), ox, oy);
+        hipLaunchKernelGGL(k_weld_gather_resident, grid, dim3(WELD_THREADS), 0, st, X[b], B, parent.as<int32_t>(), map.as<int32_t>(), ox, oy);
         HIPCHK(hipGetLastError());
     }
     gap_run(pl, st, WeldSrc{nullptr, 0, static_cast<const double2* const*>(ptrs.p), 2, 1}, nodes_out, host_gap);
@@ -564,16 +549,16 @@ void WeldDev::cells_run(const WeldPlan& pl, hipStream_t st, const std::vector<in
     const std::vector<int32_t> order_table = weld_local_order(order, hex);
     const int npe = static_cast<int>(order_table.size()), per_wg = WELD_TILE / npe;   // npe <= WELD_MAX_NPE: orders 1 .. 8 flat, 1 .. 4 in 3-D
     const size_t total = static_cast<size_t>(cells_of.back()) * npe;
-    weld_grow(local, sizeof(int32_t) * WELD_MAX_NPE, "weld local order");
-    weld_grow(cells, sizeof(int32_t) * total, "welded cells");
+    local.grow(sizeof(int32_t) * WELD_MAX_NPE, "weld local order");
+    cells.grow(sizeof(int32_t) * total, "welded cells");
     HIPCHK(hipMemcpyAsync(local.p, order_table.data(), sizeof(int32_t) * npe, hipMemcpyHostToDevice, st));
     for (int b = 0; b < pl.nblocks(); ++b) {
         const WeldBlock& B = pl.blocks[b];
         const int ncells = static_cast<int>(cells_of[b + 1] - cells_of[b]);
         if (ncells == 0) continue;
-        hipLaunchKernelGGL(k_weld_cells, dim3(weld_groups(ncells, per_wg)), dim3(WELD_THREADS), 0, st, as<int32_t>(map), B, order, (B.ni - 1) / order,
-                           (B.nj - 1) / order, ncells, npe, per_wg, as<int32_t>(local), static_cast<int>(nodes_out),
-                           as<int32_t>(cells) + static_cast<size_t>(cells_of[b]) * npe);
+        hipLaunchKernelGGL(k_weld_cells, dim3(weld_groups(ncells, per_wg)), dim3(WELD_THREADS), 0, st, map.as<int32_t>(), B, order, (B.ni - 1) / order,
+                           (B.nj - 1) / order, ncells, npe, per_wg, local.as<int32_t>(), static_cast<int>(nodes_out),
+                           cells.as<int32_t>() + static_cast<size_t>(cells_of[b]) * npe);
         HIPCHK(hipGetLastError());
     }
     if (total) HIPCHK(hipMemcpyAsync(host_cells, cells.p, sizeof(int32_t) * total, hipMemcpyDeviceToHost, st));
@@ -640,7 +625,7 @@ using namespace tmh;
 extern "C" int tm_weld_map(const tm_mesh_desc* mesh, int32_t* map, tm_weld_info* info) {
     return guarded([&]() {
         const WeldPlan pl = weld_plan(mesh);
-        require_gfx950_stack();
+        require_gfx950();
         WeldDev dev;
         dev.link(pl, nullptr);
         dev.number(pl, nullptr);
@@ -656,7 +641,7 @@ extern "C" int tm_weld_points(const tm_mesh_desc* mesh, const int32_t* map, int3
         weld_points_check(pl, map, ncomp, planes, out);
         const uint64_t nodes_out = weld_nodes_out(pl, map);
         const int64_t layers = weld_layers(nk, nodes_out);
-        require_gfx950_stack();
+        require_gfx950();
         WeldDev dev;
         dev.link(pl, nullptr);   // the owner flags; the ids are the caller's
         dev.upload_map(pl, nullptr, map);
@@ -681,7 +666,7 @@ extern "C" int tm_weld_cells(const tm_mesh_desc* mesh, const int32_t* map, uint6
         std::vector<int64_t> cells_of;
         weld_cells_plan(mesh, pl, order, nk, cells_of);
         if (!map || !cells) throw TmError(TM_E_ARG, "null argument");
-        require_gfx950_stack();
+        require_gfx950();
         WeldDev dev;
         dev.upload_map(pl, nullptr, map);
         dev.cells_run(pl, nullptr, cells_of, order, nk, static_cast<int64_t>(nodes_out), cells);

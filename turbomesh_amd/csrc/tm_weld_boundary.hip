@@ -14,6 +14,7 @@
 #include "tm_weld_boundary.hpp"
 #include "tm_weld_dev.hpp"
 #include "tm_stack_dev.hpp"
+#include "tm_devutil.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -110,8 +111,7 @@ __device__ __forceinline__ void wb_face_terms(int dim, int p, int npf, const int
 
 // sum over the workgroup in a fixed order: shuffle tree inside the wave, then waves 0 .. 3 in order on lane 0 of wave 0
 __device__ __forceinline__ double wb_block_sum(double v, double* sh) {   // sh[WB_WAVES]
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
     double total = 0.0;
@@ -173,29 +173,6 @@ __global__ __launch_bounds__(WB_THREADS) void k_weld_faces_final(const int32_t* 
 // ------------------------------------------------------------------ host driver
 namespace {
 
-struct DevBuf {
-    void* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    template <class T>
-    T* alloc(size_t n, const char* what) {
-        if (hipMalloc(&p, std::max<size_t>(256, n * sizeof(T))) != hipSuccess) {
-            p = nullptr;
-            throw TmError(TM_E_MEMORY, std::string("hipMalloc failed (") + what + ")");
-        }
-        return static_cast<T*>(p);
-    }
-    template <class T>
-    T* upload(const T* host, size_t n, hipStream_t st, const char* what) {
-        T* d = alloc<T>(n, what);
-        if (n) HIPCHK(hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, st));
-        return d;
-    }
-};
 unsigned groups(int64_t n, int per) { return static_cast<unsigned>((n + per - 1) / per); }
 
 std::vector<int32_t> face_local_table(const WeldBoundaryPlan& bp) {   // a | c << 8 per local node
@@ -271,8 +248,10 @@ void measure_run(hipStream_t st, int dim, int p, int npf, int64_t nfaces, const 
         const int32_t* d_pb = b_pb.upload(part_begin.data(), part_begin.size(), st, "partial table");
         const int32_t* d_pp = b_pp.upload(part_patch.data(), part_patch.size(), st, "partial table");
         const int32_t* d_qp = b_qp.upload(patch_part.data(), patch_part.size(), st, "partial table");
-        double* d_part = b_part.alloc<double>(part_patch.size() * WB_TERMS, "boundary partials");
-        double* d_sums = b_sums.alloc<double>(sums.size(), "boundary sums");
+        b_part.grow(sizeof(double) * part_patch.size() * WB_TERMS, "boundary partials");
+        b_sums.grow(sizeof(double) * sums.size(), "boundary sums");
+        double* d_part = b_part.as<double>();
+        double* d_sums = b_sums.as<double>();
         hipLaunchKernelGGL(k_weld_faces_measure, dim3(nwg), dim3(WB_THREADS), 0, st, dim, p, npf, static_cast<int>(nfaces), d_faces, d_fp, d_inv, px, py, pz, d_pb, d_pp,
                            d_part);
         HIPCHK(hipGetLastError());
@@ -321,9 +300,9 @@ void Smoother::weld_boundary_host(int order, const int32_t* block_orientation, i
     WeldGap gap{0.0, 0ull};
     welddev->points_resident(pl, stream, blocks_x, nodes_out, nullptr, nullptr, &gap);   // the welded planes stay in welddev->out
     FaceTables keep;
-    DevBuf b_faces;
     const size_t nids = static_cast<size_t>(bp.faces) * bp.npf;
-    int32_t* d_faces = b_faces.alloc<int32_t>(nids, "boundary faces");
+    DevBuf b_faces(sizeof(int32_t) * nids, "boundary faces");
+    int32_t* d_faces = b_faces.as<int32_t>();
     faces_run(pl, bp, stream, static_cast<const int32_t*>(welddev->map.p), nodes_out, 0, orient.data(), d_faces, keep);
     if (faces && nids) HIPCHK(hipMemcpyAsync(faces, d_faces, sizeof(int32_t) * nids, hipMemcpyDeviceToHost, stream));
     std::vector<int32_t> own_patch;
@@ -351,12 +330,13 @@ extern "C" int tm_weld_boundary_faces(const tm_mesh_desc* mesh, const int32_t* m
         if (!map || (!faces && bp.faces)) throw TmError(TM_E_ARG, "null argument");
         for (int64_t n = 0; n < pl.nodes; ++n)   // the kernels add layer offsets to these ids
             if (map[n] < 0 || static_cast<uint64_t>(map[n]) >= nodes_out) throw TmError(TM_E_ARG, "map holds an id outside 0 .. nodes_out - 1");
-        require_gfx950_stack();
+        require_gfx950();
         FaceTables keep;
-        DevBuf b_map, b_faces;
+        DevBuf b_map;
         const int32_t* d_map = b_map.upload(map, static_cast<size_t>(pl.nodes), nullptr, "weld map");
         const size_t nids = static_cast<size_t>(bp.faces) * bp.npf;
-        int32_t* d_faces = b_faces.alloc<int32_t>(nids, "boundary faces");
+        DevBuf b_faces(sizeof(int32_t) * nids, "boundary faces");
+        int32_t* d_faces = b_faces.as<int32_t>();
         faces_run(pl, bp, nullptr, d_map, static_cast<int64_t>(nodes_out), nk, block_orientation, d_faces, keep);
         if (nids) HIPCHK(hipMemcpyAsync(faces, d_faces, sizeof(int32_t) * nids, hipMemcpyDeviceToHost, nullptr));
         HIPCHK(hipStreamSynchronize(nullptr));
@@ -369,10 +349,10 @@ extern "C" int tm_weld_faces_measure(int32_t dim, int32_t order, uint64_t nfaces
                                      uint64_t npoints, int32_t ncomp, const double* const* points, tm_weld_patch* patches) {
     return guarded([&]() {
         const int npf = weld_measure_check(dim, order, nfaces, faces, face_patch, npatches, npoints, ncomp, points, patches);
-        require_gfx950_stack();
-        DevBuf b_faces, b_pts;
+        require_gfx950();
+        DevBuf b_faces, b_pts(sizeof(double) * npoints * dim, "welded planes");
         const int32_t* d_faces = b_faces.upload(faces, static_cast<size_t>(nfaces) * npf, nullptr, "boundary faces");
-        double* d_pts = b_pts.alloc<double>(static_cast<size_t>(npoints) * dim, "welded planes");
+        double* d_pts = b_pts.as<double>();
         for (int c = 0; c < dim; ++c)
             if (npoints) HIPCHK(hipMemcpyAsync(d_pts + static_cast<size_t>(c) * npoints, points[c], sizeof(double) * npoints, hipMemcpyHostToDevice, nullptr));
         measure_run(nullptr, dim, order, npf, static_cast<int64_t>(nfaces), d_faces, face_patch, static_cast<int64_t>(npatches), d_pts, d_pts + npoints,

@@ -1,6 +1,7 @@
 // Device side of K18 (tm_weld.hip): the buffers a caller keeps between calls and the stages of a weld.
 #pragma once
 #include "tm_weld.hpp"
+#include "tm_devbuf.hpp"
 #include <hip/hip_runtime.h>
 
 namespace tmh {
@@ -19,17 +20,9 @@ struct WeldSrc {
 };
 enum { WELD_C2 = 0, WELD_C3, WELD_C4, WELD_C5, WELD_MAX_CLASS, WELD_NODES_OUT, WELD_COUNTERS };
 
-// Tables, labels, partial sums, the map, welded planes and cells: hipMalloc'ed on first use, grown on demand, freed with the owner.
+// Tables, labels, partial sums, the map, welded planes and cells: allocated on first use, grown on demand, freed with the owner.
 struct WeldDev {
-    WeldDev() = default;
-    ~WeldDev();
-    WeldDev(const WeldDev&) = delete;
-    WeldDev& operator=(const WeldDev&) = delete;
-    struct Buf {
-        void* p = nullptr;
-        size_t cap = 0;
-    };
-    Buf blocks, conns, parent, count, map, part1, off1, part2, off2, counters, src, out, gaps, gap, ptrs, local, cells;
+    DevBuf blocks, conns, parent, count, map, part1, off1, part2, off2, counters, src, out, gaps, gap, ptrs, local, cells;
     // 1. tables up, labels of the perimeter slots, hook, compress, class counts (asynchronous on st)
     void link(const WeldPlan& pl, hipStream_t st);
     // 2. owner flags -> exclusive prefix sum -> map on the device; nodes_out into the counters (asynchronous)
