@@ -1135,6 +1135,80 @@ int tm_weld_faces_measure_host(int32_t dim, int32_t order, uint64_t nfaces, cons
 int tm_smoother_weld_boundary(tm_smoother* s, int32_t order, const int32_t* block_orientation_or_null, int32_t* faces, int32_t* face_patch,
                               tm_weld_patch* patches);
 
+/* ------------------------------------------------------------------ wall distance of the welded mesh (kernel K20)
+ * The distance of every welded node to the nearest wall face: the per-node field that Spalart-Allmaras, SST and wall functions read
+ * from a mesh.  On a blade passage the nearest wall of a node near a periodic side is the NEIGHBOURING blade -- the same wall shifted by
+ * the pitch -- so a query is also made under images: the translations K19 hands out with its periodic patches, or rotations about x.
+ * Definition (csrc/tm_wall_distance.hpp holds it as code; every expression order below is fixed, nothing is fused).
+ *   Input        dim = 2 or 3; points[c]: component c, npoints doubles, as tm_weld_points wrote them; wall faces of order 1 over the same
+ *                ids: 2 ids per face (edge A -> B) for dim = 2, 4 ids in ring order A, B, C, D for dim = 3; 1 .. 16 images.
+ *   Images       an image maps the QUERY, not the wall: P' = (x - t0, (c*y + s*z) - t1, (-s*y + c*z) - t2), formed once per point and image;
+ *                the distance is defined from this rounded P'.  dim = 2: z, t2 and s are ignored, c must be 1 and P'_y = y - t1.  Image 0
+ *                must be the identity {0, 0, 0, 1, 0}.
+ *   Primitives   a 2-D face is one segment; a 3-D face is the triangles (A, B, C) and (A, C, D), primitives 2f and 2f + 1.  The distance is
+ *                to these LINEAR faces: with curved elements the wall is still the fine mesh the equidistant nodes lie on.
+ *   Segment      a = B - A, L = a.a, iL = 1 / L (once per face), p = P' - A, t = p.a; t <= 0: d2 = p.p; t >= L: d2 = |P' - B|^2; otherwise
+ *                r = t * iL, q = p - r*a, d2 = q.q.  A = B falls into the first branch.  Sums run left to right over the components.
+ *   Triangle     closest point by Voronoi region, tested in this order with ab = B - A, ac = C - A, bc = C - B, ap = P' - A, bp = P' - B,
+ *                cp = P' - C, d1 = ab.ap, d2 = ac.ap, d3 = ab.bp, d4 = ac.bp, d5 = ab.cp, d6 = ac.cp, tb = bc.bp:
+ *                vertex A (d1 <= 0, d2 <= 0): ap.ap; vertex B (d3 >= 0, d4 <= d3): bp.bp; edge AB (d1*d4 - d3*d2 <= 0, d1 >= 0, d3 <= 0):
+ *                q = ap - (d1 * iLab) ab; vertex C (d6 >= 0, d5 <= d6): cp.cp; edge AC (d5*d2 - d1*d6 <= 0, d2 >= 0, d6 <= 0):
+ *                q = ap - (d2 * iLac) ac; edge BC (d3*d6 - d5*d4 <= 0, 0 <= tb <= bc.bc): q = bp - (tb * iLbc) bc; otherwise the interior,
+ *                d2 = (ap.n)^2 with n the unit normal: ab x ac, each component a difference of two error-free products (two fma), divided by its
+ *                length once per triangle.  No division and no square root per pair.  A triangle with ab x ac = 0 (collinear) is replaced by (A', B', B') of its longest edge, which
+ *                the vertex and edge regions of A'B' serve for every query: the distance to that edge, never 0/0.
+ *   Error        |d2 - exact d2| <= 32 * 2^-53 * rho2, rho2 = the largest squared distance from P' to the nodes of the face + its longest
+ *                squared edge, independent of the aspect ratio; derived for triangles whose largest angle sine is at least 2^-20
+ *                (DESIGN section 4, K20).
+ *   Result       per point the key (d2, face, image) is minimised lexicographically over all faces and images -- the smallest d2, then the
+ *                smallest face index, then the smallest image index; a NaN d2 never wins.  distance = sqrt(d2), face = index into the given
+ *                face list, image = index of the image.  A point with a NaN coordinate (or that no pair serves): NaN, -1, -1.  The minimum
+ *                does not depend on the order of evaluation, so host, device, culled and not culled give the same three outputs bit for bit.
+ *   Record       points, faces, primitives, images, groups (runs of 64 consecutive primitives); on_wall: points with distance exactly 0;
+ *                nan_points; nearest_via_image: points whose image is not 0; max_distance with max_point, the smallest id at the maximum
+ *                (0 and 0 when no point has a distance); pairs_evaluated: point-primitive evaluations made (host: points x primitives x
+ *                images).  Host and device agree in every field but pairs_evaluated.
+ * Errors: a NULL input or distance, an id outside 0 .. npoints-1, dim other than 2 or 3, nfaces = 0, more than 2^31 - 1 faces or points,
+ *   nimages outside 1 .. 16, an image 0 that is not the identity, c != 1 with dim = 2: TM_E_ARG, before anything is launched.
+ * Not served: distance to curved high-order faces; cell-centre queries; blocks spread over ranks; telling blade from hub inside
+ *   `unassigned`; signed distance; Eikonal or PDE wall distance. */
+typedef struct tm_wall_image {           /* 40 bytes */
+    double t[3];
+    double c, s;
+} tm_wall_image;
+typedef struct tm_wall_info {            /* 88 bytes */
+    uint64_t points, faces, primitives, images, groups;
+    uint64_t on_wall, nan_points, nearest_via_image;
+    uint64_t max_point;
+    uint64_t pairs_evaluated;
+    double   max_distance;
+} tm_wall_info;
+enum { TM_WALL_NO_CULL = 1 };            /* evaluate every pair; same results */
+/* distance: npoints doubles; face / image (may be NULL): npoints int32 each; info may be NULL.  On the device: one launch gathers the
+ * faces into a primitive table with the bounding box of every group, one launch takes a point per lane and walks the groups wave by
+ * wave -- a group is evaluated when any lane cannot rule it out by box bound > best + guard (guard = 40 * 2^-53 * rho2 of lane and group:
+ * the error bound above plus the rounding of the box bound) -- and one launch combines the per-workgroup records in fixed order. */
+int tm_wall_distance(int32_t dim, uint64_t nfaces, const int32_t* faces, uint64_t npoints, const double* const* points, uint64_t nimages,
+                     const tm_wall_image* images, uint32_t flags, double* distance, int32_t* face_or_null, int32_t* image_or_null,
+                     tm_wall_info* info_or_null);
+/* the same definition as plain loops over all pairs: no GPU touched; flags are ignored */
+int tm_wall_distance_host(int32_t dim, uint64_t nfaces, const int32_t* faces, uint64_t npoints, const double* const* points, uint64_t nimages,
+                          const tm_wall_image* images, uint32_t flags, double* distance, int32_t* face_or_null, int32_t* image_or_null,
+                          tm_wall_info* info_or_null);
+/* Host only.  From tm_weld_boundary_plan(mesh, 1, nk): the faces of all patches whose kind bit is set in kinds_mask (bit k for kind k:
+ * wall 1 << 0, unassigned 1 << 17, hub 1 << 18, shroud 1 << 19), patch-major, as indices into K19's face list; and the images: image 0,
+ * then +T and -T for each distinct periodic translation of the plan (T and -T count as one) in first-occurrence order, t2 = 0, c = 1,
+ * s = 0.  *nfaces and *nimages are written always; face_index / images may be NULL to count.  More than 16 images: TM_E_ARG. */
+int tm_wall_select(const tm_mesh_desc* mesh, uint64_t nk, uint32_t kinds_mask, uint64_t* nfaces, int32_t* face_index_or_null, uint64_t* nimages,
+                   tm_wall_image* images_or_null);
+/* Wall distance of the coordinates RESIDENT in a handle, behind its pending work; modifies nothing.  Defined as tm_smoother_weld ->
+ * tm_weld_boundary_faces (order 1) -> tm_wall_select -> tm_wall_distance on the welded X, Y: the points stay on the device, only the
+ * outputs cross.  distance / face / image: nodes_out values; face is an index into K19's face list of the plan.  A NULL
+ * block_orientation is taken by the rule of tm_smoother_quality.  No face selected, a dead handle, NULL distance: TM_E_ARG; rank hooks:
+ * TM_E_UNSUPPORTED. */
+int tm_smoother_wall_distance(tm_smoother* s, uint32_t kinds_mask, uint32_t flags, const int32_t* block_orientation_or_null, double* distance,
+                              int32_t* face_or_null, int32_t* image_or_null, tm_wall_info* info_or_null);
+
 /* ------------------------------------------------------------------ host-only planning (no GPU needed)
  * The perimeter-row table the device kernels consume, exported as CSR so it can be compared with
  * the reference's assembled rows (smooth.zig:421-921).  Only sizes/topology are read from `mesh`

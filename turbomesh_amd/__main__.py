@@ -42,8 +42,11 @@ pairs (periodic sides are not glued), max_gap.  Any other output format with --w
 in patches (the conditions of the template, the two sides of every periodic connection with partner and translation, `unassigned` -- where
 the O4H template leaves the blade -- and with --stack hub and shroud), one line per patch on the `weld` logger.  The orientation of the
 blocks comes from the quality rule (the handle's, with --stack the 3-D report's), so that every normal points out of the mesh.
+--wall-distance [KINDS] with --weld: NAME.vtk also holds POINT_DATA wall_distance, the distance of every welded node to the nearest face of
+the patches of those kinds (default wall,unassigned; hub,shroud too with --stack), the neighbouring blades seen through the periodic
+translations (planar) or the rotation of --blades N (cylindrical, revolution); one line on the `weld` logger.
 Without --order nothing changes; without --certify neither does --order; without --weld every output is what it was, and so it is
-without --boundary."""
+without --boundary and without --wall-distance."""
 from __future__ import annotations
 
 import argparse
@@ -149,6 +152,9 @@ def _run(ap, args, config, keep=None, tag="", stack=None):
             weld.log_report(logging.getLogger("weld"), welded.info, tag + os.path.basename(config))
             if want_boundary:
                 weld.log_boundary(logging.getLogger("weld"), welded.boundary, tag + os.path.basename(config))
+            if getattr(args, "wall_distance", None) is not None:   # of the fine welded nodes, which the element nodes of an equidistant elevation are
+                welded.wall_distance = sm.wall_distance(args.wall_kinds)
+                weld.log_wall_distance(logging.getLogger("weld"), welded.wall_distance, tag + os.path.basename(config))
             stats["welded"] = welded
     return inp, mesh, sm, stats, after
 
@@ -233,6 +239,17 @@ def _main_stack(ap, args):
         welded = weld.Weld(mesh).mesh(m3, args.order or 1, args.nodes or "equidistant", boundary=args.boundary,
                                       orientation=[q.orientation for q in q3[0]] if args.boundary else None)   # the 3-D report's orientation
         weld.log_report(logging.getLogger("weld"), welded.info, "stacked mesh")
+        if args.wall_distance is not None:
+            images = None   # planar: the periodic translations of the plan
+            if args.stack_mapping != "planar":
+                import math
+
+                images = weld.rotation_images(2.0 * math.pi / args.blades)[:3 if args.blades else 1] if args.blades else weld.rotation_images(0.0)[:1]
+                if not args.blades:
+                    logging.getLogger("weld").warning("--wall-distance on a %s stack without --blades N: no periodic images, the neighbouring blades are not seen",
+                                                      args.stack_mapping)
+            welded.wall_distance = weld.Weld(mesh).wall_distance(welded.points, kinds=args.wall_kinds, images=images)
+            weld.log_wall_distance(logging.getLogger("weld"), welded.wall_distance, "stacked mesh")
         welded.write(args.output)
         if args.boundary:
             weld.log_boundary(logging.getLogger("weld"), welded.boundary, "stacked mesh")
@@ -342,7 +359,28 @@ def main(argv=None):
                     help="with --weld: also the boundary of the welded mesh -- NAME.boundary.vtk (the faces over the volume file's points, CELL_DATA patch and "
                          "kind) and NAME.boundary.json (the patch table: conditions, periodic sides with partner and translation, unassigned, hub and shroud "
                          "with --stack) next to --output; one line per patch on the `weld` logger")
+    ap.add_argument("--wall-distance", nargs="?", const="", default=None, metavar="KINDS",
+                    help="with --weld: the distance of every welded node to the nearest wall face as POINT_DATA wall_distance of NAME.vtk; KINDS: "
+                         "comma-separated patch kinds that count as wall (default wall,unassigned -- the blade of the O4H template -- and with --stack "
+                         "hub,shroud as well).  The nearest wall may be the neighbouring blade: planar meshes use the periodic translations of the "
+                         "input, cylindrical and revolution stacks the rotation by 2 pi / N of --blades N.  With --order the distances are those of "
+                         "the fine welded nodes, which the equidistant element nodes are; one line on the `weld` logger")
+    ap.add_argument("--blades", type=int, default=None, metavar="N", help="with --wall-distance and --stack-mapping cylindrical|revolution: the blade count of the row")
     args = ap.parse_args(argv)
+    if args.wall_distance is not None:
+        if not args.weld:
+            ap.error("--wall-distance is a field of the welded mesh: it goes with --weld and --output NAME.vtk")
+        if args.order is not None and args.nodes not in (None, "equidistant"):
+            ap.error("wall distance is defined on the fine mesh: --nodes equidistant with --wall-distance")
+        from . import weld as _weld
+
+        args.wall_kinds = [k.strip() for k in args.wall_distance.split(",") if k.strip()] or None   # None: the default kinds
+        try:
+            _weld.kinds_mask(args.wall_kinds or ())
+        except ValueError as e:
+            ap.error(f"--wall-distance: {e}")
+    if args.blades is not None and (args.wall_distance is None or args.blades < 1):
+        ap.error("--blades N >= 1 goes with --wall-distance")
     if args.weld and not (args.output and args.output.lower().endswith(".vtk")):
         ap.error(f"--weld writes one welded unstructured mesh as legacy VTK: --output NAME.vtk, not {args.output!r}")
     if args.boundary and not args.weld:

@@ -212,6 +212,24 @@ class tm_weld_boundary_info(C.Structure):   # 56 bytes
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class tm_wall_image(C.Structure):   # 40 bytes
+    _fields_ = [("t", C.c_double * 3), ("c", C.c_double), ("s", C.c_double)]
+
+
+class tm_wall_info(C.Structure):   # 88 bytes
+    _fields_ = [("points", C.c_uint64), ("faces", C.c_uint64), ("primitives", C.c_uint64), ("images", C.c_uint64), ("groups", C.c_uint64),
+                ("on_wall", C.c_uint64), ("nan_points", C.c_uint64), ("nearest_via_image", C.c_uint64), ("max_point", C.c_uint64),
+                ("pairs_evaluated", C.c_uint64), ("max_distance", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+TM_WALL_NO_CULL = 1
+WD_G = 32.0        # csrc/tm_wall_distance.hpp: |d2 - exact d2| <= WD_G * 2^-53 * rho2
+WD_GROUP = 64      # primitives per group
+WD_CHUNK = 64      # group records per LDS chunk of the kernel
+
 # every symbol include/tm_hip.h declares (checked by tests/test_capi_symbols.py)
 EXPORTS = [
     "tm_last_error", "tm_abi_version", "tm_set_log", "tm_csr_solve", "tm_tfi_block", "tm_tfi_linear2d", "tm_smooth_mesh", "tm_smoother_create",
@@ -237,6 +255,7 @@ EXPORTS = [
     "tm_weld_periodic_pairs",
     "tm_weld_boundary_plan", "tm_weld_boundary_faces", "tm_weld_boundary_faces_host", "tm_weld_faces_measure", "tm_weld_faces_measure_host",
     "tm_smoother_weld_boundary",
+    "tm_wall_distance", "tm_wall_distance_host", "tm_wall_select", "tm_smoother_wall_distance",
     "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
 ]
 
@@ -389,6 +408,11 @@ def lib():
         L.tm_weld_faces_measure.argtypes = [C.c_int32, C.c_int32, C.c_uint64, _i32p, _i32p, C.c_uint64, C.c_uint64, C.c_int32, _dpp, _wpp]
         L.tm_weld_faces_measure_host.argtypes = L.tm_weld_faces_measure.argtypes
         L.tm_smoother_weld_boundary.argtypes = [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _wpp]
+        _wimp, _winp = C.POINTER(tm_wall_image), C.POINTER(tm_wall_info)
+        L.tm_wall_distance.argtypes = [C.c_int32, C.c_uint64, _i32p, C.c_uint64, _dpp, C.c_uint64, _wimp, C.c_uint32, _dp, _i32p, _i32p, _winp]
+        L.tm_wall_distance_host.argtypes = L.tm_wall_distance.argtypes
+        L.tm_wall_select.argtypes = [C.POINTER(tm_mesh_desc), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), _i32p, C.POINTER(C.c_uint64), _wimp]
+        L.tm_smoother_wall_distance.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _i32p, _dp, _i32p, _i32p, _winp]
         L.tm_rccl_unique_id.argtypes =[C.c_char_p, C.c_void_p]
         L.tm_rccl_comm_create.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.tm_rccl_comm_destroy.argtypes = [C.c_void_p]

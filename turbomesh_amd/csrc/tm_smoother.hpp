@@ -219,6 +219,9 @@ struct Smoother {
     void weld_tables(std::vector<tm_block>& tb, std::vector<tm_connection>& tc, std::vector<tm_condition>& tq, std::vector<const double2*>& blocks_x);
     // boundary faces and patch measures of the resident coordinates (tm_weld_boundary.hip, K19): the welded planes stay on the device
     void weld_boundary_host(int order, const int32_t* block_orientation, int32_t* faces, int32_t* face_patch, tm_weld_patch* patches);
+    // wall distance of the resident coordinates (tm_wall_distance.hip, K20): welded planes and outputs stay on the device until the end
+    void wall_distance_host(uint32_t kinds_mask, uint32_t flags, const int32_t* block_orientation, double* distance, int32_t* face, int32_t* image,
+                            tm_wall_info* info);
 
     // building blocks
     void exchange(double2* vec, hipStream_t on = nullptr);   // start (and, without a split hook, finish) the halo exchange of `vec`; on = the handle's stream unless given

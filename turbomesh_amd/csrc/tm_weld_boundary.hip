@@ -11,8 +11,7 @@
 //    short run, which the host lists for it (part_begin / part_patch): nothing is sorted and no atomic is used.  k_weld_faces_final sums
 //    the partials of a patch -- consecutive, since both orders ascend -- per lane in strides and then by a fixed tree: the result does not
 //    depend on scheduling.
-#include "tm_weld_boundary.hpp"
-#include "tm_weld_dev.hpp"
+#include "tm_weld_boundary_dev.hpp"
 #include "tm_stack_dev.hpp"
 #include "tm_devutil.hpp"
 
@@ -182,12 +181,6 @@ std::vector<int32_t> face_local_table(const WeldBoundaryPlan& bp) {   // a | c <
     return t;
 }
 
-// the small tables of a faces pass, host and device side: they live until the caller has synchronised
-struct FaceTables {
-    DevBuf blocks, orient, segs, local;
-    std::vector<int32_t> h_orient, h_local;
-};
-
 // the face ids of a plan on the device (asynchronous on st); d_map: the welded map on the device; d_faces: bp.faces * bp.npf ids
 void faces_run(const WeldPlan& pl, const WeldBoundaryPlan& bp, hipStream_t st, const int32_t* d_map, int64_t nodes_out, uint64_t nk, const int32_t* orientation,
                int32_t* d_faces, FaceTables& keep) {
@@ -271,6 +264,11 @@ void measure_run(hipStream_t st, int dim, int p, int npf, int64_t nfaces, const 
 }
 
 }  // namespace
+
+void weld_faces_run(const WeldPlan& pl, const WeldBoundaryPlan& bp, hipStream_t st, const int32_t* d_map, int64_t nodes_out, uint64_t nk, const int32_t* orientation,
+                    int32_t* d_faces, FaceTables& keep) {
+    faces_run(pl, bp, st, d_map, nodes_out, nk, orientation, d_faces, keep);
+}
 
 // ------------------------------------------------------------------ handle: the coordinates resident in X
 void Smoother::weld_boundary_host(int order, const int32_t* block_orientation, int32_t* faces, int32_t* face_patch, tm_weld_patch* patches) {

@@ -13,6 +13,7 @@
 //   tm_harness stack-quality <ni> <nj> <ncuts> <nlayers>   the same cuts: the 3-D quality record of the stacked block (kernel K12; exit 0: equal to the CPU's)
 //   tm_harness weld <ni> <nj> <nblocks>   the strip welded into one unstructured mesh from the resident coordinates (kernel K18; exit 0: equal to the CPU's)
 //   tm_harness weld-boundary <ni> <nj> <nblocks> [nlayers]   its boundary faces in patches and their measures (kernel K19; exit 0: equal to the CPU's)
+//   tm_harness wall-distance <ni> <nj> <nblocks> [nlayers]   the wall distance of its nodes and the record (kernel K20; exit 0: equal to the host twin's)
 //   tm_harness csr                                     the linear-solver slot (seam 2) on the reference's 5 x 5 known answer
 //   tm_harness ranks <world> <rank> <idfile> <nblocks> <ni> <nj> <iterations> [relax|bicgstab] [dump.bin]
 //        one process per GPU (start each with HIP_VISIBLE_DEVICES=<its GPU>): the strip's blocks are dealt to the ranks in order, the
@@ -614,8 +615,54 @@ static int weldBoundaryStrip(std::size_t ni, std::size_t nj, std::size_t nb, std
     return count && same ? 0 : 1;
 }
 
+// tm_harness wall-distance <ni> <nj> <nblocks> [nlayers]: the wall distance of the welded strip (kernel K20), every boundary face a wall.
+// Without layers: from the coordinates resident in the handle (weld::wall_distance(sm) -> tm_smoother_wall_distance) against the host twin
+// on the welded points.  With layers: the welded plane repeated at z = 0.1 k, device against host twin, culled against not culled.
+static int wallDistanceStrip(std::size_t ni, std::size_t nj, std::size_t nb, std::size_t nk) {
+    discrete::Mesh mesh = buildStrip(nb, ni, nj);
+    smoothing::smooth::Smoother sm(mesh, smoothing::solver::Option{}, smoothing::wall_control_function::Algorithm::laplace());
+    sm.iterate(2);
+    weld::Map map;
+    const weld::Points pts = weld::points(sm, &map);
+    std::vector<int32_t> orientation;
+    for (const auto& q : sm.quality().per_block) orientation.push_back(q.orientation);
+    const weld::Boundary b = weld::boundary(mesh, map, 1, nk, orientation, true);
+    std::vector<double> x = pts.x, y = pts.y, z;
+    if (nk >= 2) {
+        x.clear(), y.clear();
+        for (std::size_t k = 0; k < nk; ++k) {
+            x.insert(x.end(), pts.x.begin(), pts.x.end());
+            y.insert(y.end(), pts.y.begin(), pts.y.end());
+            z.insert(z.end(), pts.x.size(), 0.1 * static_cast<double>(k));
+        }
+    }
+    const weld::WallDistance host = weld::wall_distance(mesh, b, nk, x, y, nk >= 2 ? &z : nullptr, 0, {}, true);
+    const weld::WallDistance dev = nk < 2 ? weld::wall_distance(sm) : weld::wall_distance(mesh, b, nk, x, y, &z);
+    const weld::WallDistance every = weld::wall_distance(mesh, b, nk, x, y, nk >= 2 ? &z : nullptr, 0, {}, false, TM_WALL_NO_CULL);
+    const tm_wall_info& i = dev.info;
+    std::printf("wall-distance: %llu points, %llu faces, %llu primitives in %llu groups, %llu image(s)\n", static_cast<unsigned long long>(i.points),
+                static_cast<unsigned long long>(i.faces), static_cast<unsigned long long>(i.primitives), static_cast<unsigned long long>(i.groups),
+                static_cast<unsigned long long>(i.images));
+    std::printf("wall-distance: %llu on the wall, %llu NaN, %llu nearest to an image, maximum %.15e at node %llu\n", static_cast<unsigned long long>(i.on_wall),
+                static_cast<unsigned long long>(i.nan_points), static_cast<unsigned long long>(i.nearest_via_image), i.max_distance,
+                static_cast<unsigned long long>(i.max_point));
+    std::printf("wall-distance: pairs evaluated %llu culled, %llu not culled, %llu on the host\n", static_cast<unsigned long long>(i.pairs_evaluated),
+                static_cast<unsigned long long>(every.info.pairs_evaluated), static_cast<unsigned long long>(host.info.pairs_evaluated));
+    auto equal = [](const weld::WallDistance& a, const weld::WallDistance& c) {
+        return a.distance == c.distance && a.face == c.face && a.image == c.image && a.info.on_wall == c.info.on_wall && a.info.max_point == c.info.max_point &&
+               a.info.max_distance == c.info.max_distance && a.info.nearest_via_image == c.info.nearest_via_image && a.info.nan_points == c.info.nan_points;
+    };
+    const bool same = equal(dev, host), cull = equal(dev, every);
+    std::printf("wall-distance: device equals host: %s\n", same ? "yes" : "no");
+    std::printf("wall-distance: culled equals not culled: %s\n", cull ? "yes" : "no");
+    return same && cull && i.on_wall > 0 ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     try {
+        if (argc >= 5 && std::strcmp(argv[1], "wall-distance") == 0)
+            return wallDistanceStrip(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10),
+                                     argc >= 6 ? std::strtoull(argv[5], nullptr, 10) : 0);
         if (argc >= 5 && std::strcmp(argv[1], "weld-boundary") == 0)
             return weldBoundaryStrip(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10),
                                      argc >= 6 ? std::strtoull(argv[5], nullptr, 10) : 0);
@@ -642,7 +689,7 @@ int main(int argc, char** argv) {
             return thomasMiddlecoff(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "ranks") == 0) return runRank(argc, argv);
         if (argc < 5) {
-            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-elevate <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-certify <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n       %s weld <ni> <nj> <nblocks>\n       %s weld-boundary <ni> <nj> <nblocks> [nlayers]\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-elevate <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-certify <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n       %s weld <ni> <nj> <nblocks>\n       %s weld-boundary <ni> <nj> <nblocks> [nlayers]\n       %s wall-distance <ni> <nj> <nblocks> [nlayers]\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 2;
         }
         int a = 2;

@@ -883,6 +883,54 @@ inline Boundary boundary(const smoothing::smooth::Smoother& s, int order = 1, co
     r.faces.resize(r.info.faces * r.info.nodes_per_face), r.face_patch.resize(r.info.faces);
     return r;
 }
+// wall distance of the welded mesh (tm_hip.h, kernel K20): per welded node the distance to the nearest face of the patches whose kind
+// bit is set, the index of that face in Boundary::faces and the image under which it is nearest
+struct WallDistance {
+    std::vector<double> distance;
+    std::vector<int32_t> face, image;
+    tm_wall_info info{};
+};
+constexpr uint32_t wall_kinds_plane = (1u << TM_BC_WALL) | (1u << TM_PATCH_UNASSIGNED);
+constexpr uint32_t wall_kinds_stacked = wall_kinds_plane | (1u << TM_PATCH_HUB) | (1u << TM_PATCH_SHROUD);
+// b: the Boundary of order 1 (nk as it was made); x, y and, for a stacked mesh, z: the welded planes; images empty: the periodic
+// translations of the mesh (tm_wall_select), otherwise the caller's (image 0 the identity)
+inline WallDistance wall_distance(discrete::Mesh& mesh, const Boundary& b, std::size_t nk, const std::vector<double>& x, const std::vector<double>& y,
+                                  const std::vector<double>* z = nullptr, uint32_t kinds = 0, std::vector<tm_wall_image> images = {}, bool host = false,
+                                  uint32_t flags = 0) {
+    smoothing::smooth::Desc d(mesh);
+    if (kinds == 0) kinds = nk >= 2 ? wall_kinds_stacked : wall_kinds_plane;
+    uint64_t nf = 0, ni = 0;
+    core::check(tm_wall_select(&d.desc, nk, kinds, &nf, nullptr, &ni, nullptr));
+    std::vector<int32_t> index(nf + 1);
+    std::vector<tm_wall_image> plan(ni + 1);
+    core::check(tm_wall_select(&d.desc, nk, kinds, &nf, index.data(), &ni, plan.data()));
+    plan.resize(ni);
+    if (images.empty()) images = plan;
+    const std::size_t npf = b.info.nodes_per_face;
+    std::vector<int32_t> faces(nf * npf + 1);
+    for (uint64_t f = 0; f < nf; ++f)
+        for (std::size_t k = 0; k < npf; ++k) faces[f * npf + k] = b.faces[static_cast<std::size_t>(index[f]) * npf + k];
+    WallDistance r;
+    r.distance.resize(x.size() + 1), r.face.resize(x.size() + 1), r.image.resize(x.size() + 1);
+    const double* planes[3] = {x.data(), y.data(), z ? z->data() : nullptr};
+    core::check((host ? tm_wall_distance_host : tm_wall_distance)(z ? 3 : 2, nf, faces.data(), x.size(), planes, images.size(), images.data(), flags, r.distance.data(),
+                                                                  r.face.data(), r.image.data(), &r.info));
+    r.distance.resize(x.size()), r.face.resize(x.size()), r.image.resize(x.size());
+    for (int32_t& f : r.face)
+        if (f >= 0) f = index[static_cast<std::size_t>(f)];
+    return r;
+}
+// from the coordinates RESIDENT in the handle (tm_smoother_wall_distance): only the outputs cross
+inline WallDistance wall_distance(const smoothing::smooth::Smoother& s, uint32_t kinds = wall_kinds_plane, uint32_t flags = 0) {
+    const tm_mesh_desc& d = s.desc();
+    std::size_t n = 0;
+    for (uint64_t b = 0; b < d.nblocks; ++b) n += d.blocks[b].ni * d.blocks[b].nj;
+    WallDistance r;
+    r.distance.resize(n + 1), r.face.resize(n + 1), r.image.resize(n + 1);
+    core::check(tm_smoother_wall_distance(s.handle(), kinds, flags, nullptr, r.distance.data(), r.face.data(), r.image.data(), &r.info));
+    r.distance.resize(r.info.points), r.face.resize(r.info.points), r.image.resize(r.info.points);
+    return r;
+}
 }  // namespace weld
 
 namespace discrete {

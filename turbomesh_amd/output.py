@@ -202,6 +202,26 @@ def read_vtk_lagrange(filename):
     return points, rows[:, 1:].copy(), types
 
 
+def read_vtk_point_data(filename):
+    """-> {name: (n,) float64} of the POINT_DATA scalars of a legacy ASCII VTK file written by weld.UnstructuredMesh.write (the
+    `wall_distance` of a mesh made with wall_distance=True, %.17g: read back bit for bit); {} when the file has no POINT_DATA."""
+    with open(filename) as fh:
+        text = fh.read()
+    if not text.startswith("# vtk DataFile"):
+        raise ValueError(f"{filename}: not a legacy VTK file")
+    at = text.find("\nPOINT_DATA ")
+    if at < 0:
+        return {}
+    w = text[at:].split()
+    n, k, data = int(w[1]), 2, {}
+    while k < len(w) and w[k] == "SCALARS":
+        if w[k + 2] != "double" or w[k + 3] != "1" or w[k + 4:k + 6] != ["LOOKUP_TABLE", "default"]:
+            raise ValueError(f"{filename}: SCALARS <name> double 1 expected")
+        data[w[k + 1]] = np.array([float(v) for v in w[k + 6:k + 6 + n]], dtype=np.float64)
+        k += 6 + n
+    return data
+
+
 def read_vtk_boundary(filename):
     """-> (points (n, 3) float64, faces (nfaces, nodes per face) int64, cell_types (nfaces,) int64, patch (nfaces,) int64, kind (nfaces,)
     int64) of a NAME.boundary.vtk written by weld.UnstructuredMesh.write_boundary (legacy ASCII: lines 3, Lagrange curves 68, quadrilaterals

@@ -169,6 +169,15 @@ class Smoother:
 
         return weld.resident_boundary(self, order, orientation)
 
+    def wall_distance(self, kinds=None, cull=True, orientation=None):
+        """weld.WallDistance of the welded nodes of the coordinates resident in the handle to the boundary faces whose kind is in `kinds`
+        (default wall and unassigned -- the blade of the O4H template), under the periodic translations of the mesh
+        (tm_smoother_wall_distance: weld, faces, primitive table and distances on the device; only the outputs cross).  face indexes the
+        faces of weld_boundary(1)."""
+        from .. import weld
+
+        return weld.resident_wall_distance(self, kinds, cull, orientation)
+
     def write_quality(self, filename):
         """The per-cell planes of every block as a PLOT3D function file (one variable, sizes (ni-1, nj-1))."""
         from .. import output

@@ -106,6 +106,13 @@ class UnstructuredMesh:
             fh.write("".join(head + " " + " ".join(map(str, row)) + "\n" for row in self.cells.tolist()))
             fh.write(f"CELL_TYPES {len(self.cells)}\n")
             fh.write(f"{self.cell_type}\n" * len(self.cells))
+            wd = getattr(self, "wall_distance", None)
+            if wd is not None:   # only when present: a file without the field is byte for byte what it was
+                d = wd.distance if hasattr(wd, "distance") else np.asarray(wd, dtype=np.float64)
+                if len(d) != len(self.points):
+                    raise ValueError(f"{len(d)} wall distances for {len(self.points)} points")
+                fh.write(f"POINT_DATA {len(d)}\nSCALARS wall_distance double 1\nLOOKUP_TABLE default\n")
+                fh.write("".join("%.17g\n" % v for v in d.tolist()))
 
     def _write_points(self, fh):
         fh.write(f"POINTS {len(self.points)} double\n")
@@ -260,6 +267,26 @@ class Boundary:
                 out.append((self.faces[r.begin:r.begin + r.faces], self.faces[o.begin:o.begin + o.faces], r.translation))
         return out
 
+    def wall_faces(self, kinds=None):
+        """(faces, face_index, images) of the patches whose kind is named in `kinds` -- names of PATCH_NAMES; default ("wall", "unassigned"),
+        with layers ("wall", "unassigned", "hub", "shroud") -- for Weld.wall_distance: the selected rows of .faces, patch-major, their
+        indices into .faces, and the images of the periodic translations ((n, 5) rows t0, t1, t2, c, s: the identity, then +T and -T per
+        distinct translation).  tm_wall_select; needs order 1."""
+        if self.order != 1:
+            raise ValueError("wall distance is defined on the fine mesh: a Boundary of order 1")
+        if kinds is None:
+            kinds = ("wall", "unassigned", "hub", "shroud") if self.layers >= 2 else ("wall", "unassigned")
+        mask = kinds_mask(kinds)
+        L = _capi.lib()
+        nf, ni = C.c_uint64(0), C.c_uint64(0)
+        md = self._weld._md.ref()
+        _capi.check(L.tm_wall_select(md, self.layers, mask, C.byref(nf), None, C.byref(ni), None))
+        index = np.empty(nf.value, dtype=np.int32)
+        im = (_capi.tm_wall_image * max(1, ni.value))()
+        _capi.check(L.tm_wall_select(md, self.layers, mask, C.byref(nf), _i32ptr(index), C.byref(ni), im))
+        images = np.array([[m.t[0], m.t[1], m.t[2], m.c, m.s] for m in im[:ni.value]], dtype=np.float64).reshape(-1, 5)
+        return np.ascontiguousarray(self.faces[index]), index, images
+
     def table(self):
         """The patch table as plain data (what NAME.boundary.json holds)."""
         return {"order": self.order, "layers": self.layers, "cell_type": self.cell_type, "info": asdict(self.info),
@@ -291,6 +318,116 @@ def log_boundary(log, boundary, name="mesh"):
     for q, r in enumerate(boundary.patches):
         log.info("%s: patch %d %-12s %7d faces, measure %.6e, normal (%+.3e, %+.3e, %+.3e), moment %+.6e%s", name, q, r.name, r.faces, r.measure, *r.normal,
                  r.moment, f", partner {r.partner}, translation ({r.translation[0]:g}, {r.translation[1]:g})" if r.partner >= 0 else "")
+
+
+KIND_BITS = {name: kind for kind, name in PATCH_NAMES.items()}
+
+
+def kinds_mask(kinds):
+    """Bit k for kind k (tm_wall_select) from names of PATCH_NAMES, a comma-separated string or an integer mask."""
+    if isinstance(kinds, int):
+        return kinds
+    if isinstance(kinds, str):
+        kinds = [k.strip() for k in kinds.split(",") if k.strip()]
+    mask = 0
+    for k in kinds:
+        if k not in KIND_BITS:
+            raise ValueError(f"patch kind {k!r}: one of {sorted(KIND_BITS)}")
+        mask |= 1 << KIND_BITS[k]
+    return mask
+
+
+def rotation_images(angle):
+    """Images for cylindrical and revolution stacks, where the blades repeat by a rotation about the x axis and K19's planar translation
+    does not apply: the identity, +angle, -angle as (3, 5) rows t0, t1, t2, c, s."""
+    import math
+
+    c, s = math.cos(angle), math.sin(angle)
+    return np.array([[0.0, 0.0, 0.0, 1.0, 0.0], [0.0, 0.0, 0.0, c, s], [0.0, 0.0, 0.0, c, -s]], dtype=np.float64)
+
+
+@dataclass
+class WallInfo:
+    """tm_wall_info: sizes of the call, on_wall (distance exactly 0), nan_points, nearest_via_image, the maximum with its smallest node,
+    pairs_evaluated (device: evaluations made; host: points x primitives x images)."""
+
+    points: int = 0
+    faces: int = 0
+    primitives: int = 0
+    images: int = 0
+    groups: int = 0
+    on_wall: int = 0
+    nan_points: int = 0
+    nearest_via_image: int = 0
+    max_point: int = 0
+    pairs_evaluated: int = 0
+    max_distance: float = 0.0
+
+
+@dataclass
+class WallDistance:
+    """distance (n,) float64, face (n,) int32 index into Boundary.faces of the nearest wall face, image (n,) int32 index of the image under
+    which it is nearest (0: the wall itself), info (WallInfo).  A point with a NaN coordinate: NaN, -1, -1."""
+
+    distance: np.ndarray
+    face: np.ndarray
+    image: np.ndarray
+    info: WallInfo
+
+
+def _images_struct(images):
+    rows = np.ascontiguousarray(images, dtype=np.float64).reshape(-1, 5)
+    arr = (_capi.tm_wall_image * max(1, len(rows)))()
+    for m, r in zip(arr, rows.tolist()):
+        m.t[0], m.t[1], m.t[2], m.c, m.s = r
+    return arr, len(rows)
+
+
+def wall_distance_of(faces, points, images=None, host=False, cull=True):
+    """tm_wall_distance (host=True: tm_wall_distance_host) on any order-1 face list: faces (n, 2) edges over points (m, 2), or (n, 4)
+    quadrilaterals over points (m, 3); images (k, 5) rows t0, t1, t2, c, s with row 0 the identity (None: the identity alone).
+    cull=False: TM_WALL_NO_CULL, every pair is evaluated -- the results are the same.  -> WallDistance with face indexing `faces`."""
+    faces = np.ascontiguousarray(faces, dtype=np.int32)
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if faces.ndim != 2 or faces.shape[1] not in (2, 4):
+        raise ValueError("faces: (n, 2) edges or (n, 4) quadrilaterals of order 1")
+    dim = 2 if faces.shape[1] == 2 else 3
+    if pts.ndim != 2 or pts.shape[1] < dim:
+        raise ValueError(f"points: (n, {dim}) welded coordinates")
+    planes = [np.ascontiguousarray(pts[:, c]) for c in range(dim)]
+    arr = (C.POINTER(C.c_double) * dim)(*[_capi.f64ptr(a) for a in planes])
+    im, nim = _images_struct(rotation_images(0.0)[:1] if images is None else images)
+    n = len(pts)
+    dist, face, image = np.empty(n), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+    rec = _capi.tm_wall_info()
+    L = _capi.lib()
+    fn = L.tm_wall_distance_host if host else L.tm_wall_distance
+    _capi.check(fn(dim, len(faces), _i32ptr(faces), n, arr, nim, im, 0 if cull else _capi.TM_WALL_NO_CULL, _capi.f64ptr(dist), _i32ptr(face), _i32ptr(image),
+                   C.byref(rec)))
+    return WallDistance(dist, face, image, WallInfo(**rec.as_dict()))
+
+
+def resident_wall_distance(smoother, kinds=None, cull=True, orientation=None):
+    """smooth.Smoother.wall_distance: WallDistance of the coordinates resident in the handle (tm_smoother_wall_distance); face indexes the
+    faces of Smoother.weld_boundary(1)."""
+    L = _capi.lib()
+    n = sum(int(b.points.size[0]) * int(b.points.size[1]) for b in smoother._mesh.blocks)   # nodes before welding: always enough
+    o = None if orientation is None else np.ascontiguousarray([int(v) for v in orientation], dtype=np.int32)
+    if o is not None and len(o) != len(smoother._mesh.blocks):
+        raise ValueError(f"{len(o)} orientations for {len(smoother._mesh.blocks)} blocks")
+    dist, face, image = np.empty(n), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+    info = _capi.tm_wall_info()
+    _capi.check(L.tm_smoother_wall_distance(smoother._h, kinds_mask(("wall", "unassigned") if kinds is None else kinds), 0 if cull else _capi.TM_WALL_NO_CULL,
+                                            None if o is None else _i32ptr(o), _capi.f64ptr(dist), _i32ptr(face), _i32ptr(image), C.byref(info)))
+    n = int(info.points)
+    return WallDistance(dist[:n].copy(), face[:n].copy(), image[:n].copy(), WallInfo(**info.as_dict()))
+
+
+def log_wall_distance(log, wd, name="mesh"):
+    """One line on `log` (the `weld` logger of the program): on-wall nodes, nodes nearest to an image, the maximum with its node."""
+    i = wd.info
+    log.info("%s: wall distance of %d nodes to %d faces under %d image(s): %d nodes on the wall, %d nodes nearest to an image, maximum %.6e at node %d", name,
+             i.points, i.faces, i.images, i.on_wall, i.nearest_via_image, i.max_distance, i.max_point)
 
 
 def cell_type_of(order, hex):
@@ -395,13 +532,38 @@ class Weld:
         (tm_weld_boundary_faces; host=True: tm_weld_boundary_faces_host)."""
         return Boundary(self, order, layers, orientation)
 
-    def mesh(self, src, order=1, distribution="equidistant", boundary=False, orientation=None):
+    def wall_distance(self, points, boundary=None, kinds=None, images=None, periodic=True, host=None, cull=True):
+        """WallDistance of the welded `points` ((nodes, 2), or (nk * nodes, 3) with layers) to the faces of `boundary` (None: the Boundary
+        of order 1 with the layers of the points) whose kind is in `kinds` (see Boundary.wall_faces).  images: (k, 5) rows, e.g.
+        rotation_images(2 pi / blades); None: the periodic translations of the plan, or with periodic=False the wall itself alone.
+        host (None: as this Weld): the host twin, plain loops over all pairs.  face refers to boundary.faces."""
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        host = self.host if host is None else bool(host)
+        if boundary is None:
+            nk = len(pts) // max(1, self.nodes) if pts.ndim == 2 and pts.shape[1] == 3 else 0
+            boundary = self.boundary(1, nk)
+        faces, index, plan_images = boundary.wall_faces(kinds)
+        if len(faces) == 0:
+            raise ValueError("no face of the boundary has one of the kinds asked for")
+        if images is None:
+            images = plan_images if periodic else plan_images[:1]
+        wd = wall_distance_of(faces, pts, images, host=host, cull=cull)
+        wd.face = np.where(wd.face >= 0, index[np.maximum(wd.face, 0)], -1).astype(np.int32)
+        return wd
+
+    def mesh(self, src, order=1, distribution="equidistant", boundary=False, orientation=None, wall_distance=False, kinds=None, images=None):
         """UnstructuredMesh of `src` (see points) with cells of `order`; the layers follow from the source.  boundary=True: the mesh
-        carries .boundary, the Boundary at that order measured on the welded points (orientation: see Boundary)."""
+        carries .boundary, the Boundary at that order measured on the welded points (orientation: see Boundary).  wall_distance=True: it
+        carries .wall_distance (WallDistance, see Weld.wall_distance for kinds and images) and write() emits the field; defined on the
+        fine mesh, so at order 1."""
         pts = self.points(src)
         nk = len(pts) // max(1, self.nodes) if pts.shape[1] == 3 else 0
         um = UnstructuredMesh(pts, self.cells(order, nk), cell_type_of(order, nk >= 2), order, info=self.info, distribution=distribution)
         if boundary:
             um.boundary = self.boundary(order, nk, orientation)
             um.boundary.measure(pts)
+        if wall_distance:
+            if order != 1:
+                raise ValueError("wall distance is defined on the fine mesh: compute it at order 1 and attach it to the element nodes")
+            um.wall_distance = self.wall_distance(pts, self.boundary(1, nk, orientation), kinds=kinds, images=images)
         return um
