@@ -1209,6 +1209,99 @@ int tm_wall_select(const tm_mesh_desc* mesh, uint64_t nk, uint32_t kinds_mask, u
 int tm_smoother_wall_distance(tm_smoother* s, uint32_t kinds_mask, uint32_t flags, const int32_t* block_orientation_or_null, double* distance,
                               int32_t* face_or_null, int32_t* image_or_null, tm_wall_info* info_or_null);
 
+/* ------------------------------------------------------------------ faces of the welded mesh (kernel K21)
+ * A cell-centred finite-volume solver reads FACES with an owner and a neighbour cell, interior faces first in upper-triangular order,
+ * then the boundary patch by patch, and judges a mesh by face non-orthogonality, skewness, closedness and negative volumes.  This section
+ * gives the welded mesh that view at order 1 (the fine cells), over the SAME welded ids, and its metrics.  The lists are a pure function
+ * of sizes and connections; the metrics are sums over the welded points (csrc/tm_fv.hpp holds every expression as code, in a fixed order,
+ * nothing fused).
+ * Definition.
+ *   Cells        the cells of tm_weld_cells at order 1 in its order: cell (e, f) of block b, Ei = ni-1, Ej = nj-1, is cell0_b + f*Ei + e;
+ *                with nk >= 2 layers cell0_b + (g*Ej + f)*Ei + e, g = 0 .. nk-2, cell0_b counting the hexahedra of the earlier blocks.
+ *   Local sides  0 .. 3: the TM_SIDE_* value of the side of the cell (I_MIN the edge j = f, I_MAX j = f+1, J_MIN i = e, J_MAX i = e+1);
+ *                with layers 4 is the side towards layer g and 5 the side towards layer g+1.  A cell has 4 (6) of them.
+ *   Face shown   the face a cell shows on a side is the face the rules of "boundary of the welded mesh" give, at order 1, for a block that
+ *                consists of this one cell and has the block's block_orientation: the ring counter-clockwise in index space (reversed for
+ *                -1), lateral faces quadrilaterals over (a, c), side 4 by the hub rule and side 5 by the shroud rule, ids
+ *                layer*nodes_out + map[...].  A boundary face of tm_weld_boundary_faces is therefore its owner's face on that side, and
+ *                every face's normal (the tangent turned by -90 degrees; the right-hand rule of the ring) points OUT of the cell that shows it.
+ *   Neighbour    across a side: inside the block the adjacent cell; across layers the cell of the same block one layer down / up; on a
+ *                block side the cell behind the partner segment of the first connection WITHOUT periodicity that covers the segment
+ *                (connections in order, r[0] before r[1]), in the same layer; otherwise none -- the side is a boundary face.  Periodic
+ *                connections glue nothing.  A cell that is its own neighbour (a ring one cell around), or a segment whose partner does not
+ *                name it back: TM_E_MISMATCH, naming block and side.
+ *   Interior     one face per pair of sides that face each other: owner = the smaller cell, neighbour = the larger, the face is the
+ *                OWNER's (its normal points owner -> neighbour).  Sorted by (owner, neighbour, owner's local side) ascending: two cells
+ *                that share two faces (a ring two cells around) keep both.  ninternal = (faces_per_cell * cells - boundary faces) / 2.
+ *   Boundary     the list of tm_weld_boundary_faces at order 1 in its order, as faces ninternal + t; the owner follows from `origin`.
+ *   cell_faces   per cell and local side the face index.  The cell is the owner of that face iff owner[face] == cell.
+ *   More than 2^31 - 1 faces: TM_E_ARG before anything is read.
+ *   Face         area vector S: plane edge A -> B (yB - yA, -(xB - xA)); quadrilateral 0.5 (C - A) x (D - B) -- the terms of
+ *                tm_weld_faces_measure, so the reversed ring gives exactly -S.  Centre Cf: the midpoint 0.5 (A + B); for a quadrilateral
+ *                with m = 0.25 (((A + B) + C) + D) and the four triangles (m, P_k, P_k+1), w_k = |0.5 (P_k - m) x (P_k+1 - m)|:
+ *                Cf = m + (sum w_k ((P_k - m) + (P_k+1 - m)) / 3) / sum w_k (m itself when sum w_k = 0).
+ *   Cell         over its faces k in local side order, sign_k = +1 where the cell owns face k, else -1, mean = (sum Cf_k) / faces,
+ *                dim = 2 or 3: v_k = sign_k (S_k . (Cf_k - mean)) / dim (the pyramid on face k with apex mean); volume V = sum v_k; centre =
+ *                mean + (sum v_k * beta (Cf_k - mean)) / V with beta = 2/3 (dim 2) or 3/4 (dim 3) -- the V-weighted mean of the pyramid
+ *                centroids (mean itself when V = 0); closedness = max_c |sum sign_k S_k,c| / max_c sum |S_k,c| (0 when the latter is 0).
+ *   Interior face  d = C_nb - C_own (cell centres): cos = (d . S) / (|d| |S|), the non-orthogonality;
+ *                skewness = |Cf - C_own - ((S . (Cf - C_own)) / (S . d)) d| / |d|: the distance of the face centre from the point where the
+ *                line of centres meets the face's plane, over |d|.  This is THIS definition, not any particular solver's normalisation.
+ *   Boundary face  the same cos with d = Cf - C_own; no skewness.
+ *   Record       tm_fv_info below.  Extremes carry the smallest index at a tie and a NaN never wins one, so every field but total_volume is
+ *                independent of the order of evaluation; an index is 0 when nothing qualifies.  Host and device form identical terms:
+ *                every per-cell and per-face value and every extreme agree bit for bit; total_volume, summed in another order, agrees
+ *                within 2 (n-1) 2^-53 sum |V|.  The device result is the same from run to run (no floating-point atomics).
+ * Not served: high-order faces; gluing periodic sides; blocks spread over ranks; repair of bad cells; any solver's own checkMesh. */
+typedef struct tm_fv_plan {              /* 40 bytes */
+    uint64_t cells, internal_faces, boundary_faces, nodes_per_face, faces_per_cell;
+} tm_fv_plan;
+typedef struct tm_fv_info {              /* 144 bytes */
+    uint64_t cells, internal_faces, boundary_faces;
+    uint64_t min_volume_cell, max_volume_cell;
+    uint64_t negative_cells, first_negative_cell;     /* cells with V <= 0 and the smallest of them */
+    uint64_t max_closedness_cell;
+    uint64_t min_cos_face;                            /* over all faces */
+    uint64_t nonorthogonal_faces;                     /* interior faces with cos < cos 70 degrees */
+    uint64_t inverted_faces;                          /* faces with cos <= 0 */
+    uint64_t max_skewness_face;                       /* over the interior faces */
+    double   min_volume, max_volume, total_volume, max_closedness, min_cos, max_skewness;
+} tm_fv_info;
+typedef struct tm_fv_fields {            /* 56 bytes; optional outputs of tm_fv_metrics, any may be NULL; vectors are component-major planes */
+    double* volume;                      /* cells */
+    double* centre;                      /* dim * cells */
+    double* closedness;                  /* cells */
+    double* area;                        /* dim * faces: S */
+    double* face_centre;                 /* dim * faces: Cf */
+    double* cos;                         /* faces */
+    double* skewness;                    /* internal faces */
+} tm_fv_fields;
+/* Host only, closed form: the counts of the lists below for nk layers (nk <= 1: the plane mesh). */
+int tm_weld_faces_plan(const tm_mesh_desc* mesh, uint64_t nk, tm_fv_plan* plan);
+/* faces: (internal + boundary) * nodes_per_face ids; owner: one per face; neighbour: one per internal face; cell_faces (may be NULL):
+ * faces_per_cell per cell.  map and nodes_out: tm_weld_map's; block_orientation as for tm_weld_boundary_faces.  On the device: the host
+ * builds the table of the block-side segments (the perimeter is small); k_fv_count takes a cell per thread and counts its neighbours above
+ * itself; the counts are scanned by K18's launches; k_fv_interior sorts the owned neighbours with a fixed network and writes owner,
+ * neighbour, ring and both cell_faces slots -- plain stores to distinct addresses; k_fv_boundary adds K19's faces. */
+int tm_weld_faces(const tm_mesh_desc* mesh, const int32_t* map, uint64_t nodes_out, uint64_t nk, const int32_t* block_orientation, int32_t* faces,
+                  int32_t* owner, int32_t* neighbour, int32_t* cell_faces_or_null);
+int tm_weld_faces_host(const tm_mesh_desc* mesh, const int32_t* map, uint64_t nodes_out, uint64_t nk, const int32_t* block_orientation, int32_t* faces,
+                       int32_t* owner, int32_t* neighbour, int32_t* cell_faces_or_null);
+/* Metrics of ANY such lists over welded planes (points[c]: component c, npoints doubles): dim = 2 edges with 4 faces per cell, dim = 3
+ * quadrilaterals with 6.  Ids inside 0 .. npoints-1, owners inside the cells and not decreasing over the internal faces, neighbour >
+ * owner, cell_faces naming faces of which the cell is owner or neighbour: TM_E_ARG otherwise, checked before anything is launched.  On the
+ * device: one pass per cell through cell_faces, one pass per face, the record through the shared wave reduction. */
+int tm_fv_metrics(int32_t dim, uint64_t ncells, uint64_t ninternal, uint64_t nboundary, const int32_t* faces, const int32_t* owner,
+                  const int32_t* neighbour, const int32_t* cell_faces, uint64_t npoints, const double* const* points, const tm_fv_fields* fields_or_null,
+                  tm_fv_info* info);
+int tm_fv_metrics_host(int32_t dim, uint64_t ncells, uint64_t ninternal, uint64_t nboundary, const int32_t* faces, const int32_t* owner,
+                       const int32_t* neighbour, const int32_t* cell_faces, uint64_t npoints, const double* const* points,
+                       const tm_fv_fields* fields_or_null, tm_fv_info* info);
+/* The record of the coordinates RESIDENT in a handle, behind its pending work; modifies nothing.  Defined as tm_smoother_weld ->
+ * tm_weld_faces -> tm_fv_metrics on the welded X, Y: lists and points stay on the device, only the record crosses.  A NULL
+ * block_orientation is taken by the rule of tm_smoother_quality.  A dead handle, NULL info: TM_E_ARG; rank hooks: TM_E_UNSUPPORTED. */
+int tm_smoother_fv_report(tm_smoother* s, const int32_t* block_orientation_or_null, tm_fv_info* info);
+
 /* ------------------------------------------------------------------ host-only planning (no GPU needed)
  * The perimeter-row table the device kernels consume, exported as CSR so it can be compared with
  * the reference's assembled rows (smooth.zig:421-921).  Only sizes/topology are read from `mesh`

@@ -45,8 +45,12 @@ blocks comes from the quality rule (the handle's, with --stack the 3-D report's)
 --wall-distance [KINDS] with --weld: NAME.vtk also holds POINT_DATA wall_distance, the distance of every welded node to the nearest face of
 the patches of those kinds (default wall,unassigned; hub,shroud too with --stack), the neighbouring blades seen through the periodic
 translations (planar) or the rotation of --blades N (cylindrical, revolution); one line on the `weld` logger.
+--polymesh DIR with --weld: an OpenFOAM polyMesh directory of the welded mesh at order 1 (weld.Faces, include/tm_hip.h "faces of the welded
+mesh": interior faces with owner and neighbour in upper-triangular order, then the patches; periodic pairs as cyclic patches) -- the stack's
+layers with --stack, otherwise one layer between z = 0 and z = --polymesh-thickness with hub and shroud written as `empty`; --fv-report
+logs the finite-volume record (volumes, closedness, non-orthogonality, skewness) on the `weld` logger.  --order with --polymesh is an error.
 Without --order nothing changes; without --certify neither does --order; without --weld every output is what it was, and so it is
-without --boundary and without --wall-distance."""
+without --boundary, without --wall-distance, without --polymesh and without --fv-report."""
 from __future__ import annotations
 
 import argparse
@@ -155,6 +159,15 @@ def _run(ap, args, config, keep=None, tag="", stack=None):
             if getattr(args, "wall_distance", None) is not None:   # of the fine welded nodes, which the element nodes of an equidistant elevation are
                 welded.wall_distance = sm.wall_distance(args.wall_kinds)
                 weld.log_wall_distance(logging.getLogger("weld"), welded.wall_distance, tag + os.path.basename(config))
+            if getattr(args, "fv_report", False):   # of the plane cells, from the resident coordinates
+                stats["fv_report"] = sm.fv_report()
+                weld.log_fv_report(logging.getLogger("weld"), stats["fv_report"], tag + os.path.basename(config))
+            if getattr(args, "polymesh", None):   # one layer of hexahedra over the plane mesh, z = 0 and z = T: the planar-layer path
+                import numpy as np
+
+                faces = weld.Weld(mesh).faces(layers=2, orientation=[q.orientation for q in sm.quality()[0]])
+                xy = welded.points[:, :2]
+                stats["polymesh"] = (np.vstack([np.column_stack([xy, np.full(len(xy), z)]) for z in (0.0, args.polymesh_thickness)]), faces)
             stats["welded"] = welded
     return inp, mesh, sm, stats, after
 
@@ -232,7 +245,7 @@ def _main_stack(ap, args):
                     if n:
                         logging.getLogger("stack").warning("block %d (%s), cut %d: %d nodes lie outside the meridional table %s and are extrapolated", b, name, c,
                                                            int(n), args.meridional[c])
-        q3 = st.quality(handles) if (args.stack_quality or args.fail_on_inverted_3d or args.boundary) else None   # from the resident cuts: no 3-D block is formed
+        q3 = st.quality(handles) if (args.stack_quality or args.fail_on_inverted_3d or args.boundary or args.polymesh or args.fv_report) else None   # from the resident cuts: no 3-D block is formed
     if args.weld:   # sizes and connections are those of any cut
         from . import weld
 
@@ -251,6 +264,13 @@ def _main_stack(ap, args):
             welded.wall_distance = weld.Weld(mesh).wall_distance(welded.points, kinds=args.wall_kinds, images=images)
             weld.log_wall_distance(logging.getLogger("weld"), welded.wall_distance, "stacked mesh")
         welded.write(args.output)
+        if args.polymesh or args.fv_report:   # the layers are the stack's; the orientation is the 3-D report's
+            faces = weld.Weld(mesh).faces(layers=len(welded.points) // max(1, welded.info.nodes_out), orientation=[q.orientation for q in q3[0]])
+            if args.fv_report:
+                weld.log_fv_report(logging.getLogger("weld"), faces.metrics(welded.points), "stacked mesh")
+            if args.polymesh:
+                output.write_polymesh(args.polymesh, welded.points, faces)
+                logging.getLogger("output").info("wrote the polyMesh directory %s (%d cells, %d faces)", args.polymesh, faces.ncells, len(faces.faces))
         if args.boundary:
             weld.log_boundary(logging.getLogger("weld"), welded.boundary, "stacked mesh")
             logging.getLogger("output").info("wrote %s and %s", *welded.write_boundary(args.output))
@@ -365,6 +385,13 @@ def main(argv=None):
                          "hub,shroud as well).  The nearest wall may be the neighbouring blade: planar meshes use the periodic translations of the "
                          "input, cylindrical and revolution stacks the rotation by 2 pi / N of --blades N.  With --order the distances are those of "
                          "the fine welded nodes, which the equidistant element nodes are; one line on the `weld` logger")
+    ap.add_argument("--polymesh", metavar="DIR", default=None,
+                    help="with --weld: also an OpenFOAM polyMesh directory DIR (ASCII points, faces, owner, neighbour, boundary) of the welded mesh at "
+                         "order 1: with --stack the stacked hexahedra, otherwise the plane mesh extruded by one layer (hub and shroud written as empty)")
+    ap.add_argument("--polymesh-thickness", type=float, default=1.0, metavar="T", help="with --polymesh and no --stack: the layer lies between z = 0 and z = T (default 1)")
+    ap.add_argument("--fv-report", action="store_true",
+                    help="with --weld: log the finite-volume record of the welded mesh on the `weld` logger -- cells and faces, volumes, cells with "
+                         "V <= 0, closedness, face non-orthogonality and skewness")
     ap.add_argument("--blades", type=int, default=None, metavar="N", help="with --wall-distance and --stack-mapping cylindrical|revolution: the blade count of the row")
     args = ap.parse_args(argv)
     if args.wall_distance is not None:
@@ -383,6 +410,12 @@ def main(argv=None):
         ap.error("--blades N >= 1 goes with --wall-distance")
     if args.weld and not (args.output and args.output.lower().endswith(".vtk")):
         ap.error(f"--weld writes one welded unstructured mesh as legacy VTK: --output NAME.vtk, not {args.output!r}")
+    if (args.polymesh or args.fv_report) and not args.weld:
+        ap.error("--polymesh and --fv-report are views of the welded mesh: they go with --weld and --output NAME.vtk")
+    if args.polymesh and args.order is not None:
+        ap.error("--polymesh writes the fine cells (order 1): it does not go with --order")
+    if args.polymesh and not args.polymesh_thickness > 0:
+        ap.error("--polymesh-thickness: a positive number")
     if args.boundary and not args.weld:
         ap.error("--boundary lists the boundary faces of the welded mesh: it goes with --weld and --output NAME.vtk")
     if args.stack is None and (args.span or args.layers is not None):
@@ -463,6 +496,12 @@ def main(argv=None):
         logging.getLogger("output").info("wrote %s (%d welded nodes, %d cells of type %d)", out, len(welded.points), len(welded.cells), welded.cell_type)
         if args.boundary:
             logging.getLogger("output").info("wrote %s and %s", *welded.write_boundary(out))
+        if args.polymesh:
+            from . import output
+
+            pts3, faces = stats["polymesh"]
+            output.write_polymesh(args.polymesh, pts3, faces, empty_caps=True)
+            logging.getLogger("output").info("wrote the polyMesh directory %s (%d cells, %d faces)", args.polymesh, faces.ncells, len(faces.faces))
     elif out and hom is not None:
         hom.write(out)
         logging.getLogger("output").info("wrote %s (%d blocks, %d elements of order %d, %s nodes)", out, len(hom.blocks), hom.total.elements, hom.order, hom.distribution)

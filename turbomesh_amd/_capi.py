@@ -225,6 +225,26 @@ class tm_wall_info(C.Structure):   # 88 bytes
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class tm_fv_plan(C.Structure):   # 40 bytes
+    _fields_ = [("cells", C.c_uint64), ("internal_faces", C.c_uint64), ("boundary_faces", C.c_uint64), ("nodes_per_face", C.c_uint64),
+                ("faces_per_cell", C.c_uint64)]
+
+
+class tm_fv_info(C.Structure):   # 144 bytes
+    _fields_ = [("cells", C.c_uint64), ("internal_faces", C.c_uint64), ("boundary_faces", C.c_uint64), ("min_volume_cell", C.c_uint64),
+                ("max_volume_cell", C.c_uint64), ("negative_cells", C.c_uint64), ("first_negative_cell", C.c_uint64), ("max_closedness_cell", C.c_uint64),
+                ("min_cos_face", C.c_uint64), ("nonorthogonal_faces", C.c_uint64), ("inverted_faces", C.c_uint64), ("max_skewness_face", C.c_uint64),
+                ("min_volume", C.c_double), ("max_volume", C.c_double), ("total_volume", C.c_double), ("max_closedness", C.c_double),
+                ("min_cos", C.c_double), ("max_skewness", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class tm_fv_fields(C.Structure):   # 56 bytes
+    _fields_ = [(k, C.POINTER(C.c_double)) for k in ("volume", "centre", "closedness", "area", "face_centre", "cos", "skewness")]
+
+
 TM_WALL_NO_CULL = 1
 WD_G = 32.0        # csrc/tm_wall_distance.hpp: |d2 - exact d2| <= WD_G * 2^-53 * rho2
 WD_GROUP = 64      # primitives per group
@@ -256,6 +276,7 @@ EXPORTS = [
     "tm_weld_boundary_plan", "tm_weld_boundary_faces", "tm_weld_boundary_faces_host", "tm_weld_faces_measure", "tm_weld_faces_measure_host",
     "tm_smoother_weld_boundary",
     "tm_wall_distance", "tm_wall_distance_host", "tm_wall_select", "tm_smoother_wall_distance",
+    "tm_weld_faces_plan", "tm_weld_faces", "tm_weld_faces_host", "tm_fv_metrics", "tm_fv_metrics_host", "tm_smoother_fv_report",
     "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
 ]
 
@@ -413,6 +434,13 @@ def lib():
         L.tm_wall_distance_host.argtypes = L.tm_wall_distance.argtypes
         L.tm_wall_select.argtypes = [C.POINTER(tm_mesh_desc), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), _i32p, C.POINTER(C.c_uint64), _wimp]
         L.tm_smoother_wall_distance.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, _i32p, _dp, _i32p, _i32p, _winp]
+        L.tm_weld_faces_plan.argtypes = [C.POINTER(tm_mesh_desc), C.c_uint64, C.POINTER(tm_fv_plan)]
+        L.tm_weld_faces.argtypes = [C.POINTER(tm_mesh_desc), _i32p, C.c_uint64, C.c_uint64, _i32p, _i32p, _i32p, _i32p, _i32p]
+        L.tm_weld_faces_host.argtypes = L.tm_weld_faces.argtypes
+        L.tm_fv_metrics.argtypes = [C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, _i32p, _i32p, _i32p, _i32p, C.c_uint64, _dpp, C.POINTER(tm_fv_fields),
+                                    C.POINTER(tm_fv_info)]
+        L.tm_fv_metrics_host.argtypes = L.tm_fv_metrics.argtypes
+        L.tm_smoother_fv_report.argtypes = [C.c_void_p, _i32p, C.POINTER(tm_fv_info)]
         L.tm_rccl_unique_id.argtypes =[C.c_char_p, C.c_void_p]
         L.tm_rccl_comm_create.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.tm_rccl_comm_destroy.argtypes = [C.c_void_p]

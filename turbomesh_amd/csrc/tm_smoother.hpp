@@ -222,6 +222,8 @@ struct Smoother {
     // wall distance of the resident coordinates (tm_wall_distance.hip, K20): welded planes and outputs stay on the device until the end
     void wall_distance_host(uint32_t kinds_mask, uint32_t flags, const int32_t* block_orientation, double* distance, int32_t* face, int32_t* image,
                             tm_wall_info* info);
+    // finite-volume record of the resident coordinates (tm_fv.hip, K21): welded planes, face lists and fields stay on the device
+    void fv_report_host(const int32_t* block_orientation, tm_fv_info* info);
 
     // building blocks
     void exchange(double2* vec, hipStream_t on = nullptr);   // start (and, without a split hook, finish) the halo exchange of `vec`; on = the handle's stream unless given

@@ -465,6 +465,37 @@ void WeldDev::number(const WeldPlan& pl, hipStream_t st) {
     HIPCHK(hipGetLastError());
 }
 
+void WeldDev::exscan(hipStream_t st, const int32_t* in, int n, int32_t* out_scan) {
+    const int t1 = static_cast<int>(weld_groups(n, WELD_PTILE)), t2 = static_cast<int>(weld_groups(t1, WELD_PTILE));
+    if (t2 > WELD_PTILE) throw TmError(TM_E_ARG, "more than 2^30 values to scan");
+    part1.grow(sizeof(int32_t) * t1, "weld tile sums");
+    off1.grow(sizeof(int32_t) * t1, "weld tile offsets");
+    part2.grow(sizeof(int32_t) * t2, "weld tile sums, second level");
+    off2.grow(sizeof(int32_t) * t2, "weld tile offsets, second level");
+    const dim3 wg(WELD_THREADS);
+    const int32_t* none = nullptr;
+    if (t1 == 1) {
+        hipLaunchKernelGGL(k_weld_pscan, dim3(1), wg, 0, st, in, n, none, out_scan);
+        HIPCHK(hipGetLastError());
+        return;
+    }
+    hipLaunchKernelGGL(k_weld_psum, dim3(t1), wg, 0, st, in, n, part1.as<int32_t>());
+    HIPCHK(hipGetLastError());
+    if (t2 == 1) {
+        hipLaunchKernelGGL(k_weld_pscan, dim3(1), wg, 0, st, static_cast<const int32_t*>(part1.as<int32_t>()), t1, none, off1.as<int32_t>());
+    } else {
+        hipLaunchKernelGGL(k_weld_psum, dim3(t2), wg, 0, st, static_cast<const int32_t*>(part1.as<int32_t>()), t1, part2.as<int32_t>());
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_weld_pscan, dim3(1), wg, 0, st, static_cast<const int32_t*>(part2.as<int32_t>()), t2, none, off2.as<int32_t>());
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_weld_pscan, dim3(t2), wg, 0, st, static_cast<const int32_t*>(part1.as<int32_t>()), t1, static_cast<const int32_t*>(off2.as<int32_t>()),
+                           off1.as<int32_t>());
+    }
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_weld_pscan, dim3(t1), wg, 0, st, in, n, static_cast<const int32_t*>(off1.as<int32_t>()), out_scan);
+    HIPCHK(hipGetLastError());
+}
+
 void WeldDev::read_map(const WeldPlan& pl, hipStream_t st, int32_t* host_map, tm_weld_info* info) {
     unsigned long long c[WELD_COUNTERS];
     HIPCHK(hipMemcpyAsync(c, counters.p, sizeof(c), hipMemcpyDeviceToHost, st));

@@ -36,6 +36,9 @@ struct WeldDev {
     // 4. cells of the map on the device; downloads and synchronises
     void cells_run(const WeldPlan& pl, hipStream_t st, const std::vector<int64_t>& cells_of, int order, uint64_t nk, int64_t nodes_out, int32_t* cells);
     void upload_map(const WeldPlan& pl, hipStream_t st, const int32_t* map);
+    // exclusive prefix sum of n int32 values on the device (n <= 2^30) by the launches of stage 2: sums of tiles, their scan, the scan inside
+    // the tiles (K21 scans its per-cell face counts with it; asynchronous, uses part1 / off1 / part2 / off2)
+    void exscan(hipStream_t st, const int32_t* in, int n, int32_t* out);
 
 private:
     void gap_run(const WeldPlan& pl, hipStream_t st, const WeldSrc& s, int64_t nodes_out, WeldGap* gap);

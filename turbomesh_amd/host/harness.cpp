@@ -12,6 +12,7 @@
 //   tm_harness stack-elevate <ni> <nj> <ncuts> <nlayers> <order>   the same cuts: curved hexahedra of that order from the stacked block (kernel K16; exit 0: corners unchanged, equal to the CPU's)
 //   tm_harness stack-quality <ni> <nj> <ncuts> <nlayers>   the same cuts: the 3-D quality record of the stacked block (kernel K12; exit 0: equal to the CPU's)
 //   tm_harness weld <ni> <nj> <nblocks>   the strip welded into one unstructured mesh from the resident coordinates (kernel K18; exit 0: equal to the CPU's)
+//   tm_harness fv <ni> <nj> <nblocks> [nlayers]              its faces, owners and finite-volume metrics (kernel K21; exit 0: equal to the CPU's)
 //   tm_harness weld-boundary <ni> <nj> <nblocks> [nlayers]   its boundary faces in patches and their measures (kernel K19; exit 0: equal to the CPU's)
 //   tm_harness wall-distance <ni> <nj> <nblocks> [nlayers]   the wall distance of its nodes and the record (kernel K20; exit 0: equal to the host twin's)
 //   tm_harness csr                                     the linear-solver slot (seam 2) on the reference's 5 x 5 known answer
@@ -658,8 +659,59 @@ static int wallDistanceStrip(std::size_t ni, std::size_t nj, std::size_t nb, std
     return same && cull && i.on_wall > 0 ? 0 : 1;
 }
 
+// tm_harness fv <ni> <nj> <nblocks> [nlayers]: the face-based view of the welded strip and its finite-volume metrics (kernel K21).  Without
+// layers: also the record from the coordinates resident in the handle (weld::fv_report(sm) -> tm_smoother_fv_report).  With layers: the
+// welded plane repeated at z = 0.1 k.  Lists, volumes, cosines and every extreme of the record are compared with the CPU's bit for bit;
+// total_volume, summed in another order, within 2 (n - 1) 2^-53 sum |V|.
+static int fvStrip(std::size_t ni, std::size_t nj, std::size_t nb, std::size_t nk) {
+    discrete::Mesh mesh = buildStrip(nb, ni, nj);
+    smoothing::smooth::Smoother sm(mesh, smoothing::solver::Option{}, smoothing::wall_control_function::Algorithm::laplace());
+    sm.iterate(2);
+    weld::Map map;
+    const weld::Points pts = weld::points(sm, &map);
+    std::vector<int32_t> orientation;
+    for (const auto& q : sm.quality().per_block) orientation.push_back(q.orientation);
+    std::vector<double> x = pts.x, y = pts.y, z;
+    if (nk >= 2) {
+        x.clear(), y.clear();
+        for (std::size_t k = 0; k < nk; ++k) {
+            x.insert(x.end(), pts.x.begin(), pts.x.end());
+            y.insert(y.end(), pts.y.begin(), pts.y.end());
+            z.insert(z.end(), pts.x.size(), 0.1 * static_cast<double>(k));
+        }
+    }
+    const weld::Faces host = weld::faces(mesh, map, nk, orientation, true), dev = weld::faces(mesh, map, nk, orientation);
+    const weld::FvMetrics mh = weld::fv_metrics(host, x, y, nk >= 2 ? &z : nullptr, true), md = weld::fv_metrics(dev, x, y, nk >= 2 ? &z : nullptr);
+    const tm_fv_info& i = md.info;
+    std::printf("fv: %llu cells, %llu internal and %llu boundary faces of %llu nodes\n", static_cast<unsigned long long>(i.cells),
+                static_cast<unsigned long long>(i.internal_faces), static_cast<unsigned long long>(i.boundary_faces), static_cast<unsigned long long>(host.plan.nodes_per_face));
+    std::printf("fv: volume %.15e .. %.15e, total %.15e, %llu cells with V <= 0, max closedness %.3e\n", i.min_volume, i.max_volume, i.total_volume,
+                static_cast<unsigned long long>(i.negative_cells), i.max_closedness);
+    std::printf("fv: min cos %.15f at face %llu, max skewness %.15f at face %llu\n", i.min_cos, static_cast<unsigned long long>(i.min_cos_face), i.max_skewness,
+                static_cast<unsigned long long>(i.max_skewness_face));
+    double mag = 0.0;
+    for (double v : mh.volume) mag += std::fabs(v);
+    auto equal = [&](const tm_fv_info& a, const tm_fv_info& b) {
+        tm_fv_info c = a;
+        c.total_volume = b.total_volume;
+        return std::memcmp(&c, &b, sizeof(c)) == 0 && std::fabs(a.total_volume - b.total_volume) <= 2.0 * static_cast<double>(b.cells - 1) * 0x1p-53 * mag;
+    };
+    const std::size_t cells = nb * (ni - 1) * (nj - 1) * (nk >= 2 ? nk - 1 : 1);
+    const bool count = i.cells == cells && i.internal_faces == ((nk >= 2 ? 6 : 4) * cells - i.boundary_faces) / 2 && i.negative_cells == 0;
+    std::printf("fv: cell and face counts: %s\n", count ? "yes" : "no");
+    bool same = dev.faces == host.faces && dev.owner == host.owner && dev.neighbour == host.neighbour && dev.cell_faces == host.cell_faces &&
+                std::memcmp(md.volume.data(), mh.volume.data(), sizeof(double) * mh.volume.size()) == 0 &&
+                std::memcmp(md.cos.data(), mh.cos.data(), sizeof(double) * mh.cos.size()) == 0 && equal(md.info, mh.info);
+    if (nk < 2) same = same && equal(weld::fv_report(sm, orientation), mh.info);
+    std::printf("fv: device equals host: %s\n", same ? "yes" : "no");
+    return count && same ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     try {
+        if (argc >= 5 && std::strcmp(argv[1], "fv") == 0)
+            return fvStrip(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10),
+                           argc >= 6 ? std::strtoull(argv[5], nullptr, 10) : 0);
         if (argc >= 5 && std::strcmp(argv[1], "wall-distance") == 0)
             return wallDistanceStrip(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10),
                                      argc >= 6 ? std::strtoull(argv[5], nullptr, 10) : 0);
@@ -689,7 +741,7 @@ int main(int argc, char** argv) {
             return thomasMiddlecoff(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "ranks") == 0) return runRank(argc, argv);
         if (argc < 5) {
-            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-elevate <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-certify <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n       %s weld <ni> <nj> <nblocks>\n       %s weld-boundary <ni> <nj> <nblocks> [nlayers]\n       %s wall-distance <ni> <nj> <nblocks> [nlayers]\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-elevate <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-certify <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n       %s weld <ni> <nj> <nblocks>\n       %s weld-boundary <ni> <nj> <nblocks> [nlayers]\n       %s wall-distance <ni> <nj> <nblocks> [nlayers]\n       %s fv <ni> <nj> <nblocks> [nlayers]\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 2;
         }
         int a = 2;

@@ -931,6 +931,46 @@ inline WallDistance wall_distance(const smoothing::smooth::Smoother& s, uint32_t
     r.distance.resize(r.info.points), r.face.resize(r.info.points), r.image.resize(r.info.points);
     return r;
 }
+// faces of the welded mesh (tm_hip.h, kernel K21): interior faces with owner and neighbour in upper-triangular order, then the boundary
+// of order 1 in its order; cell_faces: per cell of cells(mesh, m, 1, nk) and local side the face index
+struct Faces {
+    tm_fv_plan plan{};
+    std::vector<int32_t> faces, owner, neighbour, cell_faces;
+};
+inline Faces faces(discrete::Mesh& mesh, const Map& m, std::size_t nk = 0, const std::vector<int32_t>& orientation = {}, bool host = false) {
+    smoothing::smooth::Desc d(mesh);
+    Faces r;
+    core::check(tm_weld_faces_plan(&d.desc, nk, &r.plan));
+    if (!orientation.empty() && orientation.size() != mesh.blocks.size()) throw Error(TM_E_ARG, "one orientation per block");
+    const std::size_t n = r.plan.internal_faces + r.plan.boundary_faces;
+    r.faces.resize(n * r.plan.nodes_per_face + 1), r.owner.resize(n + 1), r.neighbour.resize(r.plan.internal_faces + 1), r.cell_faces.resize(r.plan.cells * r.plan.faces_per_cell + 1);
+    core::check((host ? tm_weld_faces_host : tm_weld_faces)(&d.desc, m.map.data(), m.info.nodes_out, nk, orientation.empty() ? nullptr : orientation.data(), r.faces.data(),
+                                                            r.owner.data(), r.neighbour.data(), r.cell_faces.data()));
+    r.faces.resize(n * r.plan.nodes_per_face), r.owner.resize(n), r.neighbour.resize(r.plan.internal_faces), r.cell_faces.resize(r.plan.cells * r.plan.faces_per_cell);
+    return r;
+}
+// finite-volume metrics of such lists on welded planes (x, y and, for a stacked mesh, z); the optional per-cell and per-face fields
+struct FvMetrics {
+    tm_fv_info info{};
+    std::vector<double> volume, cos;
+};
+inline FvMetrics fv_metrics(const Faces& f, const std::vector<double>& x, const std::vector<double>& y, const std::vector<double>* z = nullptr, bool host = false) {
+    FvMetrics r;
+    r.volume.resize(f.plan.cells + 1), r.cos.resize(f.owner.size() + 1);
+    tm_fv_fields out{};
+    out.volume = r.volume.data(), out.cos = r.cos.data();
+    const double* planes[3] = {x.data(), y.data(), z ? z->data() : nullptr};
+    core::check((host ? tm_fv_metrics_host : tm_fv_metrics)(z ? 3 : 2, f.plan.cells, f.plan.internal_faces, f.plan.boundary_faces, f.faces.data(), f.owner.data(),
+                                                            f.neighbour.data(), f.cell_faces.data(), x.size(), planes, &out, &r.info));
+    r.volume.resize(f.plan.cells), r.cos.resize(f.owner.size());
+    return r;
+}
+// the record of the coordinates RESIDENT in the handle (tm_smoother_fv_report): only the record crosses
+inline tm_fv_info fv_report(const smoothing::smooth::Smoother& s, const std::vector<int32_t>& orientation = {}) {
+    tm_fv_info info{};
+    core::check(tm_smoother_fv_report(s.handle(), orientation.empty() ? nullptr : orientation.data(), &info));
+    return info;
+}
 }  // namespace weld
 
 namespace discrete {

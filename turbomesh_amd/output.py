@@ -265,6 +265,111 @@ def read_vtk_boundary(filename):
     return points, rows[:, 1:].copy(), types, data["patch"], data["kind"]
 
 
+_FOAM_CLASSES = {"points": "vectorField", "faces": "faceList", "owner": "labelList", "neighbour": "labelList", "boundary": "polyBoundaryMesh"}
+
+
+def _foam_header(name, note=None):
+    lines = ["FoamFile", "{", "    version     2.0;", "    format      ascii;", f"    class       {_FOAM_CLASSES[name]};"]
+    if note:
+        lines.append(f'    note        "{note}";')
+    return "\n".join(lines + ['    location    "constant/polyMesh";', f"    object      {name};", "}", "", ""])
+
+
+def polymesh_patch_type(kind, empty_caps=False):
+    """OpenFOAM patch type of a patch kind: wall and unassigned -> wall, inlet / outlet -> patch, periodic -> cyclic, hub / shroud -> wall
+    (empty when the layer is the one-cell extrusion of a plane mesh)."""
+    if kind == _capi.TM_PATCH_PERIODIC:
+        return "cyclic"
+    if kind in (_capi.TM_BC_INLET, _capi.TM_BC_OUTLET):
+        return "patch"
+    if kind in (_capi.TM_PATCH_HUB, _capi.TM_PATCH_SHROUD) and empty_caps:
+        return "empty"
+    return "wall"
+
+
+def write_polymesh(directory, points, faces, boundary=None, empty_caps=False):
+    """An OpenFOAM polyMesh directory -- ASCII `points`, `faces`, `owner`, `neighbour`, `boundary`, doubles with 17 significant digits --
+    from the welded `points` ((nk * nodes, 3)) and a weld.Faces of a stacked mesh (quadrilateral faces: interior faces first in
+    upper-triangular order, every normal owner -> neighbour or outward, then the patches of `boundary`, default faces.boundary, as
+    contiguous startFace / nFaces ranges).  Patch names are the Boundary's; types by polymesh_patch_type; each periodic pair becomes two
+    `cyclic` patches that name each other, `transform translational` with the patch's translation as separationVector (own face +
+    vector = partner's face).  Nobody has run OpenFOAM's checkMesh on such a directory.  Returns the five file names."""
+    boundary = faces.boundary if boundary is None else boundary
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    F = np.ascontiguousarray(faces.faces)
+    if pts.ndim != 2 or pts.shape[1] != 3 or F.ndim != 2 or F.shape[1] != 4:
+        raise ValueError("a polyMesh needs a stacked mesh: points (n, 3) and quadrilateral faces (with a plane mesh: one extruded layer)")
+    if len(boundary.faces) != len(F) - faces.ninternal:
+        raise ValueError("the boundary is not the one of these faces")
+    os.makedirs(directory, exist_ok=True)
+    names = {k: os.path.join(directory, k) for k in _FOAM_CLASSES}
+    note = f"nPoints: {len(pts)} nCells: {faces.ncells} nFaces: {len(F)} nInternalFaces: {faces.ninternal}"
+    with open(names["points"], "w") as fh:
+        fh.write(_foam_header("points") + f"{len(pts)}\n(\n" + "".join("(%.17g %.17g %.17g)\n" % tuple(p) for p in pts.tolist()) + ")\n")
+    with open(names["faces"], "w") as fh:
+        fh.write(_foam_header("faces") + f"{len(F)}\n(\n" + "".join("4(%d %d %d %d)\n" % tuple(r) for r in F.tolist()) + ")\n")
+    with open(names["owner"], "w") as fh:
+        fh.write(_foam_header("owner", note) + f"{len(F)}\n(\n" + "".join(f"{v}\n" for v in faces.owner.tolist()) + ")\n")
+    with open(names["neighbour"], "w") as fh:
+        fh.write(_foam_header("neighbour", note) + f"{faces.ninternal}\n(\n" + "".join(f"{v}\n" for v in faces.neighbour.tolist()) + ")\n")
+    with open(names["boundary"], "w") as fh:
+        fh.write(_foam_header("boundary") + f"{len(boundary.patches)}\n(\n")
+        for r in boundary.patches:
+            kind = polymesh_patch_type(r.kind, empty_caps)
+            fh.write(f"    {r.name}\n    {{\n        type            {kind};\n")
+            if kind == "cyclic":
+                fh.write(f"        neighbourPatch  {boundary.patches[r.partner].name};\n        transform       translational;\n")
+                fh.write("        separationVector (%.17g %.17g 0);\n" % (r.translation[0], r.translation[1]))
+            fh.write(f"        nFaces          {r.faces};\n        startFace       {faces.ninternal + r.begin};\n    }}\n")
+        fh.write(")\n")
+    return [names[k] for k in ("points", "faces", "owner", "neighbour", "boundary")]
+
+
+def _foam_body(filename, name):
+    with open(filename) as fh:
+        text = fh.read()
+    head, sep, body = text.partition("}\n")
+    if not head.startswith("FoamFile") or not sep or f"object      {name};" not in head or f"class       {_FOAM_CLASSES[name]};" not in head:
+        raise ValueError(f"{filename}: not an ASCII OpenFOAM {name} file")
+    count, _, rest = body.lstrip().partition("\n(\n")
+    return int(count), rest[:rest.rindex(")")]
+
+
+def read_polymesh(directory):
+    """-> dict of a directory written by write_polymesh: points (n, 3) float64 bit for bit, faces (n, 4), owner, neighbour (int64) and
+    boundary, a list of dicts name, type, nFaces, startFace and for cyclic patches neighbourPatch, separationVector."""
+    n, body = _foam_body(os.path.join(directory, "points"), "points")
+    points = np.array([float(v) for v in body.replace("(", " ").replace(")", " ").split()], dtype=np.float64).reshape(n, 3)
+    n, body = _foam_body(os.path.join(directory, "faces"), "faces")
+    flat = np.array([int(v) for v in body.replace("4(", " ").replace(")", " ").split()], dtype=np.int64)
+    out = {"points": points, "faces": flat.reshape(n, 4)}
+    for name in ("owner", "neighbour"):
+        n, body = _foam_body(os.path.join(directory, name), name)
+        out[name] = np.array([int(v) for v in body.split()], dtype=np.int64)
+        if len(out[name]) != n:
+            raise ValueError(f"{directory}/{name}: {len(out[name])} labels where {n} are announced")
+    n, body = _foam_body(os.path.join(directory, "boundary"), "boundary")
+    patches = []
+    for chunk in body.split("}")[:-1]:
+        name, _, entries = chunk.partition("{")
+        rec = {"name": name.strip()}
+        for entry in entries.split(";"):
+            w = entry.split()
+            if not w:
+                continue
+            if w[0] == "separationVector":
+                rec[w[0]] = tuple(float(v.strip("()")) for v in w[1:])
+            elif w[0] in ("nFaces", "startFace"):
+                rec[w[0]] = int(w[1])
+            else:
+                rec[w[0]] = w[1]
+        patches.append(rec)
+    if len(patches) != n:
+        raise ValueError(f"{directory}/boundary: {len(patches)} patches where {n} are announced")
+    out["boundary"] = patches
+    return out
+
+
 def _format_of(filename):
     ext = os.path.splitext(filename)[1].lower()
     if ext == ".cgns":

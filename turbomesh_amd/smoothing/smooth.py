@@ -178,6 +178,14 @@ class Smoother:
 
         return weld.resident_wall_distance(self, kinds, cull, orientation)
 
+    def fv_report(self, orientation=None):
+        """weld.FvReport of the welded mesh of the coordinates resident in the handle: cells, faces, volumes, closedness, face
+        non-orthogonality and skewness (tm_smoother_fv_report: weld, face lists and metrics on the device; only the record crosses).
+        orientation None: the rule of quality()."""
+        from .. import weld
+
+        return weld.resident_fv_report(self, orientation)
+
     def write_quality(self, filename):
         """The per-cell planes of every block as a PLOT3D function file (one variable, sizes (ni-1, nj-1))."""
         from .. import output

@@ -15,6 +15,9 @@ ni x nj index space, so one Weld serves every product of the library:
     w.boundary(order=1, orientation=o)             # Boundary: faces over the same ids in patches (inlet, outlet, periodic sides, unassigned,
                                                    # hub and shroud with layers=nk); .measure(points) sums length / area, normal, moment per patch
     w.mesh(src, boundary=True).write_boundary("blade.vtk")   # blade.boundary.vtk + blade.boundary.json beside the volume file
+    f = w.faces(layers=nk, orientation=o)          # Faces: what a finite-volume solver reads -- interior faces with owner < neighbour in
+                                                   # upper-triangular order, then the boundary; f.metrics(points): volumes, closedness,
+                                                   # non-orthogonality, skewness (FvReport); output.write_polymesh(dir, points, f)
 
 A welded node has the coordinates of its owner (the class member with the smallest index), bit for bit; `info.max_gap` says by how much the
 other members differ from it -- the rounding "the two sides agree to", or the size of the mesh when a connection is wrong.
@@ -430,6 +433,123 @@ def log_wall_distance(log, wd, name="mesh"):
              i.points, i.faces, i.images, i.on_wall, i.nearest_via_image, i.max_distance, i.max_point)
 
 
+@dataclass
+class FvReport:
+    """tm_fv_info -- counts; min / max volume with their cells; negative_cells (V <= 0) and the first of them; total_volume; the largest
+    closedness with its cell; the smallest cos with its face; nonorthogonal_faces (interior, cos < cos 70 degrees); inverted_faces
+    (cos <= 0); the largest skewness with its face -- and with fields=True the arrays: volume, closedness (cells,), centre (cells, dim),
+    area, face_centre (faces, dim), cos (faces,), skewness (internal faces,)."""
+
+    cells: int = 0
+    internal_faces: int = 0
+    boundary_faces: int = 0
+    min_volume_cell: int = 0
+    max_volume_cell: int = 0
+    negative_cells: int = 0
+    first_negative_cell: int = 0
+    max_closedness_cell: int = 0
+    min_cos_face: int = 0
+    nonorthogonal_faces: int = 0
+    inverted_faces: int = 0
+    max_skewness_face: int = 0
+    min_volume: float = 0.0
+    max_volume: float = 0.0
+    total_volume: float = 0.0
+    max_closedness: float = 0.0
+    min_cos: float = 0.0
+    max_skewness: float = 0.0
+    volume: np.ndarray = None
+    centre: np.ndarray = None
+    closedness: np.ndarray = None
+    area: np.ndarray = None
+    face_centre: np.ndarray = None
+    cos: np.ndarray = None
+    skewness: np.ndarray = None
+
+
+def fv_metrics_of(faces, owner, neighbour, cell_faces, points, fields=False, host=False):
+    """tm_fv_metrics (host=True: tm_fv_metrics_host) on any face lists: faces (n, 2) edges over points (m, 2) with cell_faces (cells, 4),
+    or (n, 4) quadrilaterals over points (m, 3) with cell_faces (cells, 6); owner (n,), neighbour (internal faces,) -> FvReport."""
+    faces = np.ascontiguousarray(faces, dtype=np.int32)
+    owner = np.ascontiguousarray(owner, dtype=np.int32)
+    neighbour = np.ascontiguousarray(neighbour, dtype=np.int32)
+    cell_faces = np.ascontiguousarray(cell_faces, dtype=np.int32)
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if faces.ndim != 2 or faces.shape[1] not in (2, 4):
+        raise ValueError("faces: (n, 2) edges or (n, 4) quadrilaterals of order 1")
+    dim = 2 if faces.shape[1] == 2 else 3
+    if pts.ndim != 2 or pts.shape[1] < dim:
+        raise ValueError(f"points: (n, {dim}) welded coordinates")
+    if cell_faces.ndim != 2 or cell_faces.shape[1] != 2 * dim or len(owner) != len(faces) or len(neighbour) > len(faces):
+        raise ValueError(f"cell_faces: (cells, {2 * dim}); owner: one per face; neighbour: one per internal face")
+    nc, nf, ni = len(cell_faces), len(faces), len(neighbour)
+    planes = [np.ascontiguousarray(pts[:, c]) for c in range(dim)]
+    arr = (C.POINTER(C.c_double) * dim)(*[_capi.f64ptr(a) for a in planes])
+    out, fs = {}, None
+    if fields:
+        out = {"volume": np.empty(nc), "centre": np.empty((dim, nc)), "closedness": np.empty(nc), "area": np.empty((dim, nf)),
+               "face_centre": np.empty((dim, nf)), "cos": np.empty(nf), "skewness": np.empty(ni)}
+        fs = _capi.tm_fv_fields(**{k: _capi.f64ptr(v) for k, v in out.items()})
+    rec = _capi.tm_fv_info()
+    L = _capi.lib()
+    fn = L.tm_fv_metrics_host if host else L.tm_fv_metrics
+    _capi.check(fn(dim, nc, ni, nf - ni, _i32ptr(faces), _i32ptr(owner), _i32ptr(neighbour), _i32ptr(cell_faces), len(pts), arr,
+                   None if fs is None else C.byref(fs), C.byref(rec)))
+    for k in ("centre", "area", "face_centre"):
+        if k in out:
+            out[k] = np.ascontiguousarray(out[k].T)
+    return FvReport(**rec.as_dict(), **out)
+
+
+class Faces:
+    """The face-based view of a Weld at order 1 (include/tm_hip.h, "faces of the welded mesh"; kernel K21): .faces (faces, 2 or 4) int32
+    welded ids, interior faces first in upper-triangular order, then the faces of .boundary (a Boundary of order 1) in its order; .owner
+    (faces,); .neighbour (ninternal,); .cell_faces (cells, 4 or 6): per cell of Weld.cells(1, layers) and local side the face index;
+    .ninternal.  Every face is its owner's: its normal points owner -> neighbour, or out of the mesh.  orientation: see Boundary."""
+
+    def __init__(self, weld, layers=None, orientation=None):
+        nk = int(layers) if layers else 0
+        self.layers, self.host = nk, weld.host
+        self.boundary = Boundary(weld, 1, nk, orientation)
+        L = _capi.lib()
+        plan = _capi.tm_fv_plan()
+        _capi.check(L.tm_weld_faces_plan(weld._md.ref(), nk, C.byref(plan)))
+        self.ninternal, self.ncells = int(plan.internal_faces), int(plan.cells)
+        n = self.ninternal + int(plan.boundary_faces)
+        self.faces = np.empty((n, plan.nodes_per_face), dtype=np.int32)
+        self.owner = np.empty(n, dtype=np.int32)
+        self.neighbour = np.empty(self.ninternal, dtype=np.int32)
+        self.cell_faces = np.empty((self.ncells, plan.faces_per_cell), dtype=np.int32)
+        o = self.boundary.orientation
+        fn = L.tm_weld_faces_host if self.host else L.tm_weld_faces
+        _capi.check(fn(weld._md.ref(), _i32ptr(weld.map), weld.nodes, nk, None if o is None else _i32ptr(o), _i32ptr(self.faces), _i32ptr(self.owner),
+                       _i32ptr(self.neighbour), _i32ptr(self.cell_faces)))
+
+    def metrics(self, points, fields=False):
+        """FvReport of the welded `points` ((nodes, 2), or (nk * nodes, 3) with layers)."""
+        return fv_metrics_of(self.faces, self.owner, self.neighbour, self.cell_faces, points, fields=fields, host=self.host)
+
+
+def resident_fv_report(smoother, orientation=None):
+    """smooth.Smoother.fv_report: FvReport (the record alone) of the coordinates resident in the handle (tm_smoother_fv_report)."""
+    o = None if orientation is None else np.ascontiguousarray([int(v) for v in orientation], dtype=np.int32)
+    if o is not None and len(o) != len(smoother._mesh.blocks):
+        raise ValueError(f"{len(o)} orientations for {len(smoother._mesh.blocks)} blocks")
+    rec = _capi.tm_fv_info()
+    _capi.check(_capi.lib().tm_smoother_fv_report(smoother._h, None if o is None else _i32ptr(o), C.byref(rec)))
+    return FvReport(**rec.as_dict())
+
+
+def log_fv_report(log, r, name="mesh"):
+    """Three lines on `log` (the `weld` logger of the program): counts, volumes, face metrics."""
+    log.info("%s: %d cells, %d internal and %d boundary faces", name, r.cells, r.internal_faces, r.boundary_faces)
+    log.info("%s: volume %.6e .. %.6e (cells %d, %d), total %.9e, %d cells with V <= 0 (first %d), max closedness %.3e at cell %d", name, r.min_volume,
+             r.max_volume, r.min_volume_cell, r.max_volume_cell, r.total_volume, r.negative_cells, r.first_negative_cell, r.max_closedness,
+             r.max_closedness_cell)
+    log.info("%s: min cos %.6f at face %d, %d internal faces beyond 70 degrees, %d faces with cos <= 0, max skewness %.6f at face %d", name, r.min_cos,
+             r.min_cos_face, r.nonorthogonal_faces, r.inverted_faces, r.max_skewness, r.max_skewness_face)
+
+
 def cell_type_of(order, hex):
     if order == 1:
         return VTK_HEXAHEDRON if hex else VTK_QUAD
@@ -531,6 +651,12 @@ class Weld:
         """The Boundary of this weld at `order` (with layers=nk >= 2 of the stacked mesh): faces in patches over the welded ids
         (tm_weld_boundary_faces; host=True: tm_weld_boundary_faces_host)."""
         return Boundary(self, order, layers, orientation)
+
+    def faces(self, layers=None, orientation=None):
+        """The Faces of this weld (with layers=nk >= 2 of the stacked mesh): interior faces with owner and neighbour in upper-triangular
+        order, then the boundary of order 1; .metrics(points) gives the finite-volume report (tm_weld_faces; host=True:
+        tm_weld_faces_host)."""
+        return Faces(self, layers, orientation)
 
     def wall_distance(self, points, boundary=None, kinds=None, images=None, periodic=True, host=None, cull=True):
         """WallDistance of the welded `points` ((nodes, 2), or (nk * nodes, 3) with layers) to the faces of `boundary` (None: the Boundary
