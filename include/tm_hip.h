@@ -1302,6 +1302,85 @@ int tm_fv_metrics_host(int32_t dim, uint64_t ncells, uint64_t ninternal, uint64_
  * block_orientation is taken by the rule of tm_smoother_quality.  A dead handle, NULL info: TM_E_ARG; rank hooks: TM_E_UNSUPPORTED. */
 int tm_smoother_fv_report(tm_smoother* s, const int32_t* block_orientation_or_null, tm_fv_info* info);
 
+/* ------------------------------------------------------------------ elliptic smoothing of stacked blocks (K22)
+ * Jacobi relaxation of the 3-D Winslow equations on ONE stored block with its six faces held: the only stage that moves a node of a
+ * stacked block.  Planes X, Y, Z in PLOT3D order, element (k*nj + j)*ni + i (what tm_stack_block returns for all layers, or a file read
+ * back).  P(di,dj,dk) is a neighbour of node P; interior nodes have 1 <= i <= ni-2, 1 <= j <= nj-2, 1 <= k <= nk-2; every other node is
+ * copied bit for bit by every sweep, so a node shared by two blocks stays identical on both sides.  ni, nj or nk < 2: TM_E_SIZE.  A block
+ * without interior nodes is valid: no sweep is made, it comes back unchanged with sweeps_done = 0.
+ *
+ * One sweep, everything read from the input state of the sweep, IEEE fp64, nothing fused, sums left to right as written, per component
+ * where a vector is meant:
+ *   r1 = 0.5*(P(1,0,0) - P(-1,0,0)), r2 along j, r3 along k;  s1 = P(1,0,0) + P(-1,0,0), s2, s3 alike
+ *   gab = (ra.x*rb.x + ra.y*rb.y) + ra.z*rb.z
+ *   a11 = g22*g33 - g23*g23   a22 = g11*g33 - g13*g13   a33 = g11*g22 - g12*g12
+ *   a12 = g13*g23 - g12*g33   a13 = g12*g23 - g13*g22   a23 = g12*g13 - g23*g11
+ *   m12 = 0.25*(((P(1,1,0) - P(1,-1,0)) - P(-1,1,0)) + P(-1,-1,0)), m13 over (i, k), m23 over (j, k) alike
+ *   num = (((a11*s1 + a22*s2) + a33*s3) + 2*((a12*m12 + a13*m13) + a23*m23)) + (((a11*f1)*r1 + (a22*f2)*r2) + (a33*f3)*r3)
+ *   den = 2*((a11 + a22) + a33), inv = 1/den (one correctly rounded division per node), new = num*inv, out = P + omega*(new - P)
+ * A node is frozen (out = P, counted) when den is not finite, is not > 0, or a component of num is not finite; den is twice the sum of
+ * the principal 2 x 2 minors of the metric, so apart from overflow that is where r1, r2, r3 span less than a plane.  J = (r1.x*(r2.y*r3.z
+ * - r2.z*r3.y) + r1.y*(r2.z*r3.x - r2.x*r3.z)) + r1.z*(r2.x*r3.y - r2.y*r3.x) is used by the record only.  19 points: the eight cube
+ * corners are not read.
+ *
+ * Control field (f1, f2, f3), one double per node each.  TM_S3_LAPLACE: no field -- the second bracket of num is NOT FORMED (not
+ * multiplied by 0), so a Laplace result does not depend on the field code.  TM_S3_THOMAS_MIDDLECOFF: formed once from the INPUT block
+ * before the first sweep, then frozen.  Along a grid line at its node t (1 <= t <= n-2): d1 = 0.5*(r(t+1) - r(t-1)), d2 = (r(t+1) - r(t))
+ * - (r(t) - r(t-1)), phi = -(d1.d2)/(d1.d1), 0 where d1.d1 is 0 or not finite.  f1 takes lines along i on the faces j = 0, j = nj-1,
+ * k = 0, k = nk-1 and carries them inside by the boolean sum in (j, k), u = j/(nj-1), v = k/(nk-1):
+ *   f1 = ((((1-u)*F_j0 + u*F_j1) + (1-v)*F_k0) + v*F_k1) - (((((1-u)*(1-v))*E00 + (u*(1-v))*E10) + ((1-u)*v)*E01) + (u*v)*E11)
+ * with E the values on the four edge lines at the same i (Euv at u, v in {0, 1}).  f2: lines along j, u = i/(ni-1), v = k/(nk-1); f3:
+ * lines along k, u = i/(ni-1), v = j/(nj-1).  The field is 0 on every node that is not interior.  TM_S3_PRESCRIBED: the caller's planes.
+ *
+ * Stopping: `sweeps` sweeps; with tol > 0 the call ends once sqrt(last_sum_sq / interior) <= tol, tested behind every 8th sweep and
+ * behind the last -- the only host read-back inside a call.  sweeps = 0 returns the input and sweeps_done = 0.
+ * 0 < omega <= 1, tol >= 0, a known algorithm, planes for TM_S3_PRESCRIBED, no NULL: TM_E_ARG otherwise.
+ *
+ * On the device (csrc/tm_smooth3d.hip): the whole block is held -- two states and the field; what does not fit: TM_E_MEMORY.
+ * k_s3_control_faces and k_s3_control_blend form the field; k_s3_sweep takes an (i, j) tile per workgroup and marches along k with
+ * the planes k-1, k, k+1 of the tile and a one-node rim in LDS, ping-pong between the two states; the record is combined in a fixed
+ * order.  Host and device agree bit for bit in the planes, the field and every record field but the two sums; those agree within
+ * 2 (n-1) 2^-53 sum and are the same from run to run. */
+#define TM_S3_LAPLACE 0
+#define TM_S3_THOMAS_MIDDLECOFF 1
+#define TM_S3_PRESCRIBED 2
+typedef struct tm_smooth3d_opt {   /* 56 bytes */
+    int32_t algorithm;             /* TM_S3_* */
+    int32_t _pad;
+    uint64_t sweeps;
+    double omega;                  /* 0 < omega <= 1 */
+    double tol;                    /* 0: run all sweeps */
+    const double* f1;              /* TM_S3_PRESCRIBED: nodes doubles each, read at interior nodes; ignored otherwise */
+    const double* f2;
+    const double* f3;
+} tm_smooth3d_opt;
+typedef struct tm_smooth3d_info {  /* 136 bytes; all counts over interior nodes */
+    uint64_t nodes, interior, sweeps_done;
+    uint64_t frozen;                                      /* of the last sweep */
+    uint64_t first_neg, first_pos, first_zero_or_nan;     /* sign of J in the input of the first sweep */
+    uint64_t last_neg, last_pos, last_zero_or_nan;        /* ... of the last sweep */
+    uint64_t last_max_node;                               /* flat index; ~0 when no sweep was made or every update is a NaN */
+    double first_sum_sq, last_sum_sq;                     /* sum of |out - P|^2 = (dx*dx + dy*dy) + dz*dz of the first / last sweep */
+    double last_max_update;                               /* largest |out - P| by its square, the smallest flat index at a tie; a NaN never wins */
+    double control_max[3];                                /* max |f| over the interior */
+} tm_smooth3d_info;
+int tm_smooth3d_planes(uint64_t ni, uint64_t nj, uint64_t nk, double* x, double* y, double* z /* in/out */, const tm_smooth3d_opt* opt,
+                       tm_smooth3d_info* info);
+/* the same definition on the CPU: no GPU touched */
+int tm_smooth3d_planes_host(uint64_t ni, uint64_t nj, uint64_t nk, double* x, double* y, double* z, const tm_smooth3d_opt* opt,
+                            tm_smooth3d_info* info);
+/* The Thomas-Middlecoff field of a block: f1, f2, f3, nodes doubles each. */
+int tm_smooth3d_control(uint64_t ni, uint64_t nj, uint64_t nk, const double* x, const double* y, const double* z, double* f1, double* f2,
+                        double* f3);
+int tm_smooth3d_control_host(uint64_t ni, uint64_t nj, uint64_t nk, const double* x, const double* y, const double* z, double* f1, double* f2,
+                             double* f3);
+/* All layers of `block` stacked from the K resident handles (K11) into a device buffer, smoothed there; only the planes (nlayers * nj * ni
+ * doubles each) and the record cross to the host.  No handle is modified.  Errors: those of tm_stack_smoothers, and the ones above. */
+int tm_stack_smoothers_smooth(tm_smoother* const* cuts, const tm_stack_opt* opt, uint64_t block, const tm_smooth3d_opt* smooth, double* x,
+                              double* y, double* z, tm_smooth3d_info* info);
+int tm_stack_smoothers_smooth_surf(tm_smoother* const* cuts, const tm_stack_opt* opt, const tm_stack_surfaces* surfaces, uint64_t block,
+                                   const tm_smooth3d_opt* smooth, double* x, double* y, double* z, tm_smooth3d_info* info);
+
 /* ------------------------------------------------------------------ host-only planning (no GPU needed)
  * The perimeter-row table the device kernels consume, exported as CSR so it can be compared with
  * the reference's assembled rows (smooth.zig:421-921).  Only sizes/topology are read from `mesh`

@@ -49,6 +49,10 @@ translations (planar) or the rotation of --blades N (cylindrical, revolution); o
 mesh": interior faces with owner and neighbour in upper-triangular order, then the patches; periodic pairs as cyclic patches) -- the stack's
 layers with --stack, otherwise one layer between z = 0 and z = --polymesh-thickness with hub and shroud written as `empty`; --fv-report
 logs the finite-volume record (volumes, closedness, non-orthogonality, skewness) on the `weld` logger.  --order with --polymesh is an error.
+--stack-smooth N with --stack: N sweeps of the 3-D elliptic equations on every stacked block with its faces held (stack.Stack.smooth,
+include/tm_hip.h "elliptic smoothing of stacked blocks"), --stack-smooth-algorithm laplace|thomas-middlecoff, --stack-smooth-omega W,
+--stack-smooth-tol T; what follows (--weld, --boundary, --wall-distance, --polymesh, --fail-on-inverted-3d) takes the smoothed planes and
+--stack-quality logs the report before and after.  It is refused with --order and --stack-certify, which work straight from the cuts.
 Without --order nothing changes; without --certify neither does --order; without --weld every output is what it was, and so it is
 without --boundary, without --wall-distance, without --polymesh and without --fv-report."""
 from __future__ import annotations
@@ -246,6 +250,19 @@ def _main_stack(ap, args):
                         logging.getLogger("stack").warning("block %d (%s), cut %d: %d nodes lie outside the meridional table %s and are extrapolated", b, name, c,
                                                            int(n), args.meridional[c])
         q3 = st.quality(handles) if (args.stack_quality or args.fail_on_inverted_3d or args.boundary or args.polymesh or args.fv_report) else None   # from the resident cuts: no 3-D block is formed
+        smoothed = bool(args.stack_smooth)
+        if smoothed:   # every block stacked again into a device buffer and smoothed there with its faces held (tm_stack_smoothers_smooth)
+            records = []
+            for b in range(len(m3.blocks)):
+                *planes, rec = st.smooth(handles, b, args.stack_smooth, args.stack_smooth_algorithm, args.stack_smooth_omega, args.stack_smooth_tol)
+                m3.blocks[b] = tuple(planes)
+                records.append(rec)
+            stack.log_smooth3d(logging.getLogger("stack"), m3.names, records)
+            if q3 is not None:   # what follows judges and orients the smoothed planes
+                if args.stack_quality:
+                    quality.log_report_3d(logging.getLogger("quality"), m3.names, *q3)
+                per_block = [stack.quality_of_planes(*planes, block=b) for b, planes in enumerate(m3.blocks)]
+                q3 = (per_block, quality.total_3d(per_block))
     if args.weld:   # sizes and connections are those of any cut
         from . import weld
 
@@ -281,7 +298,7 @@ def _main_stack(ap, args):
     if hom is not None:
         logging.getLogger("output").info("%d hexahedra of order %d, %s nodes", hom.total.elements, hom.order, hom.distribution)
     if q3 is not None and args.stack_quality:
-        quality.log_report_3d(logging.getLogger("quality"), m3.names, *q3)
+        quality.log_report_3d(logging.getLogger("quality"), m3.names, *q3, stage="stack-smooth" if smoothed else "stack")
     if args.fail_on_inverted and worst is not None:
         sys.exit(f"mesh quality: cut {worst[0]} has {worst[1].inverted} inverted and {worst[1].degenerate} degenerate cells after smoothing")
     if args.fail_on_invalid_elements and not hom.total.ok:
@@ -372,6 +389,15 @@ def main(argv=None):
     ap.add_argument("--fail-on-inverted-3d", action="store_true",
                     help="with --stack: exit non-zero, after the file is written, when the stacked mesh has inverted or degenerate hexahedra "
                          "(implies the 3-D quality evaluation)")
+    ap.add_argument("--stack-smooth", type=int, default=None, metavar="N",
+                    help="with --stack: N Jacobi sweeps of the 3-D elliptic (Winslow) equations on every stacked block, its six faces held, before "
+                         "the file is written; --weld, --boundary, --wall-distance and --polymesh take the smoothed planes, --stack-quality logs the "
+                         "report before and after, --fail-on-inverted-3d judges the one after; one line per block on the `stack` logger")
+    ap.add_argument("--stack-smooth-algorithm", default=None, choices=["laplace", "thomas-middlecoff"],
+                    help="with --stack-smooth: plain Laplace, or the Thomas-Middlecoff control field that keeps wall clustering (default)")
+    ap.add_argument("--stack-smooth-omega", type=float, default=None, metavar="W", help="with --stack-smooth: relaxation factor, 0 < W <= 1 (default 1)")
+    ap.add_argument("--stack-smooth-tol", type=float, default=None, metavar="T",
+                    help="with --stack-smooth: stop once the rms update of a sweep is <= T (tested behind every 8th sweep; default 0: all N sweeps)")
     ap.add_argument("--weld", action="store_true",
                     help="with --output NAME.vtk: weld the blocks into one conforming unstructured mesh (interface nodes merged; quadrilaterals, "
                          "hexahedra with --stack, Lagrange cells with --order) and write that; logs node counts, classes and max_gap on the `weld` logger")
@@ -424,6 +450,23 @@ def main(argv=None):
         ap.error("--meridional, --meridional-interpolation and --reference-radius go with --stack")
     if args.stack is None and (args.stack_quality or args.fail_on_inverted_3d):
         ap.error("--stack-quality and --fail-on-inverted-3d go with --stack")
+    if args.stack_smooth is None and (args.stack_smooth_algorithm or args.stack_smooth_omega is not None or args.stack_smooth_tol is not None):
+        ap.error("--stack-smooth-algorithm, --stack-smooth-omega and --stack-smooth-tol go with --stack-smooth N")
+    if args.stack_smooth is not None:
+        if args.stack is None:
+            ap.error("--stack-smooth goes with --stack")
+        if args.order is not None or args.stack_certify is not None:
+            ap.error("--stack-smooth does not go with --order or --stack-certify: curved hexahedra and their certificate are formed straight from the cuts, "
+                     "not from a stored block")
+        if args.stack_smooth < 1:
+            ap.error("--stack-smooth N: at least 1 sweep")
+        args.stack_smooth_algorithm = args.stack_smooth_algorithm or "thomas-middlecoff"
+        args.stack_smooth_omega = 1.0 if args.stack_smooth_omega is None else args.stack_smooth_omega
+        args.stack_smooth_tol = 0.0 if args.stack_smooth_tol is None else args.stack_smooth_tol
+        if not 0.0 < args.stack_smooth_omega <= 1.0:
+            ap.error("--stack-smooth-omega: 0 < W <= 1")
+        if not args.stack_smooth_tol >= 0.0:
+            ap.error("--stack-smooth-tol: T >= 0")
     if args.order is None and (args.nodes or args.fail_on_invalid_elements):
         ap.error("--nodes and --fail-on-invalid-elements go with --order")
     if args.certify is None and args.stack_certify is None and args.fail_on_unproven_elements:

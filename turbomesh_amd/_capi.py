@@ -245,6 +245,19 @@ class tm_fv_fields(C.Structure):   # 56 bytes
     _fields_ = [(k, C.POINTER(C.c_double)) for k in ("volume", "centre", "closedness", "area", "face_centre", "cos", "skewness")]
 
 
+class tm_smooth3d_opt(C.Structure):   # 56 bytes
+    _fields_ = [("algorithm", C.c_int32), ("_pad", C.c_int32), ("sweeps", C.c_uint64), ("omega", C.c_double), ("tol", C.c_double),
+                ("f1", C.POINTER(C.c_double)), ("f2", C.POINTER(C.c_double)), ("f3", C.POINTER(C.c_double))]
+
+
+class tm_smooth3d_info(C.Structure):   # 136 bytes
+    _fields_ = [(k, C.c_uint64) for k in ("nodes", "interior", "sweeps_done", "frozen", "first_neg", "first_pos", "first_zero_or_nan", "last_neg",
+                                          "last_pos", "last_zero_or_nan", "last_max_node")] + \
+               [("first_sum_sq", C.c_double), ("last_sum_sq", C.c_double), ("last_max_update", C.c_double), ("control_max", C.c_double * 3)]
+
+
+TM_S3_LAPLACE, TM_S3_THOMAS_MIDDLECOFF, TM_S3_PRESCRIBED = 0, 1, 2
+S3_TI, S3_TJ, S3_KCHUNK = 32, 8, 16   # csrc/tm_smooth3d.hip: the (i, j) tile of a workgroup and the node layers of a k-chunk
 TM_WALL_NO_CULL = 1
 WD_G = 32.0        # csrc/tm_wall_distance.hpp: |d2 - exact d2| <= WD_G * 2^-53 * rho2
 WD_GROUP = 64      # primitives per group
@@ -277,6 +290,8 @@ EXPORTS = [
     "tm_smoother_weld_boundary",
     "tm_wall_distance", "tm_wall_distance_host", "tm_wall_select", "tm_smoother_wall_distance",
     "tm_weld_faces_plan", "tm_weld_faces", "tm_weld_faces_host", "tm_fv_metrics", "tm_fv_metrics_host", "tm_smoother_fv_report",
+    "tm_smooth3d_planes", "tm_smooth3d_planes_host", "tm_smooth3d_control", "tm_smooth3d_control_host", "tm_stack_smoothers_smooth",
+    "tm_stack_smoothers_smooth_surf",
     "tm_mg_transfer_probe", "tm_smoother_mg_levels", "tm_smoother_precondition_probe", "tm_edge_tables_probe", "tm_edge_tables_free",
 ]
 
@@ -441,6 +456,13 @@ def lib():
                                     C.POINTER(tm_fv_info)]
         L.tm_fv_metrics_host.argtypes = L.tm_fv_metrics.argtypes
         L.tm_smoother_fv_report.argtypes = [C.c_void_p, _i32p, C.POINTER(tm_fv_info)]
+        _s3o, _s3i = C.POINTER(tm_smooth3d_opt), C.POINTER(tm_smooth3d_info)
+        L.tm_smooth3d_planes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, _dp, _dp, _dp, _s3o, _s3i]
+        L.tm_smooth3d_planes_host.argtypes = L.tm_smooth3d_planes.argtypes
+        L.tm_smooth3d_control.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64] + [_dp] * 6
+        L.tm_smooth3d_control_host.argtypes = L.tm_smooth3d_control.argtypes
+        L.tm_stack_smoothers_smooth.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt), C.c_uint64, _s3o, _dp, _dp, _dp, _s3i]
+        L.tm_stack_smoothers_smooth_surf.argtypes = [C.POINTER(C.c_void_p), C.POINTER(tm_stack_opt), C.POINTER(tm_stack_surfaces), C.c_uint64, _s3o, _dp, _dp, _dp, _s3i]
         L.tm_rccl_unique_id.argtypes =[C.c_char_p, C.c_void_p]
         L.tm_rccl_comm_create.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         L.tm_rccl_comm_destroy.argtypes = [C.c_void_p]

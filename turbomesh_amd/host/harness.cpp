@@ -383,6 +383,64 @@ static int stackQuality(std::size_t ni, std::size_t nj, std::size_t ncuts, std::
     return same ? 0 : 1;
 }
 
+// tm_harness stack-smooth <ni> <nj> <nk> <sweeps>: three cuts of `stack` on nk layers; the block stacked from the coordinates resident in
+// the handles and smoothed on the device with the Thomas-Middlecoff field (stack::smooth -> tm_stack_smoothers_smooth), compared with the
+// CPU's sweeps of the planes tm_stack_smoothers returns for the same handles: planes and record bit for bit, the two sums within their bound.
+static int stackSmooth(std::size_t ni, std::size_t nj, std::size_t nlayers, std::size_t sweeps) {
+    if (nlayers < 2) throw Error(TM_E_ARG, "stack-smooth <ni> <nj> <nk> <sweeps>: at least two layers");
+    const std::size_t ncuts = 3;
+    smoothing::solver::Option opt;
+    opt.inner = TM_INNER_RELAX;
+    std::vector<discrete::Mesh> meshes;
+    meshes.reserve(ncuts);
+    for (std::size_t c = 0; c < ncuts; ++c) meshes.push_back(buildSingle(ni, nj, 0.05 + 0.02 * static_cast<double>(c)));
+    std::vector<std::unique_ptr<smoothing::smooth::Smoother>> handles;
+    std::vector<smoothing::smooth::Smoother*> cuts;
+    for (std::size_t c = 0; c < ncuts; ++c) {
+        handles.push_back(std::make_unique<smoothing::smooth::Smoother>(meshes[c], opt, smoothing::wall_control_function::Algorithm::laplace()));
+        handles.back()->iterate(5);
+        cuts.push_back(handles.back().get());
+    }
+    stack::Option so;
+    for (std::size_t c = 0; c < ncuts; ++c) so.span.push_back(static_cast<double>(c));
+    const double z1 = so.span.back();
+    for (std::size_t k = 0; k < nlayers; ++k) so.layers.push_back(k + 1 == nlayers ? z1 : z1 * (static_cast<double>(k) / static_cast<double>(nlayers - 1)));
+    stack::Smooth sm;
+    sm.sweeps = sweeps;
+    tm_smooth3d_info d;
+    const stack::Block3d dev = stack::smooth(cuts, so, 0, sm, &d);
+    stack::Block3d host = stack::stack_block(cuts, so, 0, 0, nlayers);
+    const stack::Block3d before = host;
+    const tm_smooth3d_info h = stack::smooth(host, sm, true);
+    std::printf("stack-smooth: nodes %llu interior %llu sweeps %llu frozen %llu J<0 %llu -> %llu\n", static_cast<unsigned long long>(d.nodes),
+                static_cast<unsigned long long>(d.interior), static_cast<unsigned long long>(d.sweeps_done), static_cast<unsigned long long>(d.frozen),
+                static_cast<unsigned long long>(d.first_neg), static_cast<unsigned long long>(d.last_neg));
+    std::printf("stack-smooth: sum of squared updates first %.17g last %.17g max update %.17g at node %llu\n", d.first_sum_sq, d.last_sum_sq, d.last_max_update,
+                static_cast<unsigned long long>(d.last_max_node));
+    std::printf("stack-smooth: max |f| %.17g %.17g %.17g\n", d.control_max[0], d.control_max[1], d.control_max[2]);
+    const std::size_t n = dev.x.size();
+    bool same = n == host.x.size() && std::memcmp(dev.x.data(), host.x.data(), 8 * n) == 0 && std::memcmp(dev.y.data(), host.y.data(), 8 * n) == 0 &&
+                std::memcmp(dev.z.data(), host.z.data(), 8 * n) == 0;
+    tm_smooth3d_info a = d, b = h;
+    a.first_sum_sq = a.last_sum_sq = b.first_sum_sq = b.last_sum_sq = 0.0;
+    const double bound = 2.0 * static_cast<double>(d.interior) * 0x1p-53;
+    same = same && std::memcmp(&a, &b, sizeof(a)) == 0 && std::fabs(d.first_sum_sq - h.first_sum_sq) <= bound * h.first_sum_sq &&
+           std::fabs(d.last_sum_sq - h.last_sum_sq) <= bound * h.last_sum_sq;
+    bool held = true, moved = false;
+    for (std::size_t k = 0; k < nlayers; ++k)
+        for (std::size_t j = 0; j < nj; ++j)
+            for (std::size_t i = 0; i < ni; ++i) {
+                const std::size_t o = (k * nj + j) * ni + i;
+                const bool face = i == 0 || j == 0 || k == 0 || i + 1 == ni || j + 1 == nj || k + 1 == nlayers;
+                const bool eq = dev.x[o] == before.x[o] && dev.y[o] == before.y[o] && dev.z[o] == before.z[o];
+                if (face && !eq) held = false;
+                if (!face && !eq) moved = true;
+            }
+    std::printf("stack-smooth: faces held: %s\n", held ? "yes" : "no");
+    std::printf("stack-smooth: device equals host: %s\n", same ? "yes" : "no");
+    return same && held && (moved || sweeps == 0 || d.interior == 0) ? 0 : 1;
+}
+
 // tm_harness stack-elevate <ni> <nj> <ncuts> <nlayers> <order>: the cuts of `stack`; Gauss-Lobatto hexahedra of `order` from the
 // coordinates resident in the handles (stack::elevate -> tm_stack_smoothers_elevate), compared with the CPU's evaluation of the downloaded
 // coordinates (the planar mapping: planes, scaled Jacobians and the record bit for bit); the nodes at element corners must be the nodes
@@ -730,6 +788,8 @@ int main(int argc, char** argv) {
         if (argc >= 7 && std::strcmp(argv[1], "stack-elevate") == 0)
             return stackElevate(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10),
                                 static_cast<int>(std::strtol(argv[6], nullptr, 10)));
+        if (argc >= 6 && std::strcmp(argv[1], "stack-smooth") == 0)
+            return stackSmooth(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10));
         if (argc >= 6 && std::strcmp(argv[1], "stack-quality") == 0)
             return stackQuality(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10));
         if (argc >= 6 && std::strcmp(argv[1], "stack-revolution") == 0)
@@ -741,7 +801,7 @@ int main(int argc, char** argv) {
             return thomasMiddlecoff(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
         if (argc >= 2 && std::strcmp(argv[1], "ranks") == 0) return runRank(argc, argv);
         if (argc < 5) {
-            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-elevate <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-certify <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n       %s weld <ni> <nj> <nblocks>\n       %s weld-boundary <ni> <nj> <nblocks> [nlayers]\n       %s wall-distance <ni> <nj> <nblocks> [nlayers]\n       %s fv <ni> <nj> <nblocks> [nlayers]\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+            std::fprintf(stderr, "usage: %s strip <nblocks> <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s single <ni> <nj> <iterations> [relax|bicgstab|mg] [until <tol>] [write <file.xyz>] [dump.bin]\n       %s stack <ni> <nj> <ncuts> <nlayers>\n       %s stack-quality <ni> <nj> <ncuts> <nlayers>\n       %s stack-smooth <ni> <nj> <nk> <sweeps>\n       %s stack-elevate <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-certify <ni> <nj> <ncuts> <nlayers> <order>\n       %s stack-revolution <ni> <nj> <ncuts> <nlayers>\n       %s elevate <ni> <nj> <order>\n       %s certify <ni> <nj> <order>\n       %s weld <ni> <nj> <nblocks>\n       %s weld-boundary <ni> <nj> <nblocks> [nlayers]\n       %s wall-distance <ni> <nj> <nblocks> [nlayers]\n       %s fv <ni> <nj> <nblocks> [nlayers]\n", argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 2;
         }
         int a = 2;

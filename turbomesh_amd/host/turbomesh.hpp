@@ -585,6 +585,41 @@ inline tm_quality3d quality(const Block3d& b, std::size_t block = 0) {
     check(tm_quality3d_planes_host(b.x.data(), b.y.data(), b.z.data(), b.ni, b.nj, b.nk, block, &q, nullptr));
     return q;
 }
+// elliptic smoothing of stacked blocks (tm_hip.h, kernel K22): Jacobi sweeps of the 3-D Winslow equations with the six faces held
+struct Smooth {
+    int32_t algorithm = TM_S3_THOMAS_MIDDLECOFF;
+    uint64_t sweeps = 0;
+    double omega = 1.0, tol = 0.0;
+    const double *f1 = nullptr, *f2 = nullptr, *f3 = nullptr;   // TM_S3_PRESCRIBED
+    tm_smooth3d_opt c_struct() const { return tm_smooth3d_opt{algorithm, 0, sweeps, omega, tol, f1, f2, f3}; }
+};
+// a block held on the host, in place (tm_smooth3d_planes; host = true: tm_smooth3d_planes_host, no GPU)
+inline tm_smooth3d_info smooth(Block3d& b, const Smooth& s, bool host = false) {
+    const tm_smooth3d_opt so = s.c_struct();
+    tm_smooth3d_info info;
+    check((host ? tm_smooth3d_planes_host : tm_smooth3d_planes)(b.ni, b.nj, b.nk, b.x.data(), b.y.data(), b.z.data(), &so, &info));
+    return info;
+}
+// all layers of `block` stacked from the coordinates RESIDENT in one handle per cut and smoothed on the device (tm_stack_smoothers_smooth):
+// only the planes and the record cross to the host, no handle is modified
+inline Block3d smooth(const std::vector<smoothing::smooth::Smoother*>& cuts, const Option& o, std::size_t block, const Smooth& s, tm_smooth3d_info* info = nullptr) {
+    if (cuts.empty() || cuts.size() != o.span.size()) throw Error(TM_E_ARG, "one handle per span position");
+    std::vector<tm_smoother*> h;
+    for (const auto* c : cuts) h.push_back(c ? c->handle() : nullptr);
+    const tm_mesh_desc& d = cuts[0]->desc();
+    if (block >= d.nblocks) throw Error(TM_E_ARG, "block index past the mesh");
+    Block3d b;
+    b.ni = d.blocks[block].ni, b.nj = d.blocks[block].nj, b.nk = o.layers.size();
+    const std::size_t n = b.ni * b.nj * b.nk;
+    b.x.resize(n + 1), b.y.resize(n + 1), b.z.resize(n + 1);
+    const tm_stack_opt so = o.c_struct();
+    const tm_smooth3d_opt ss = s.c_struct();
+    tm_smooth3d_info rec;
+    check(tm_stack_smoothers_smooth(h.data(), &so, block, &ss, b.x.data(), b.y.data(), b.z.data(), &rec));
+    b.x.resize(n), b.y.resize(n), b.z.resize(n);
+    if (info) *info = rec;
+    return b;
+}
 }  // namespace stack
 
 // high-order elements (tm_hip.h): every p x p group of cells of a block is one curved element of order p; its nodes at the wanted

@@ -154,6 +154,105 @@ def quality_of_planes(X, Y, Z, block=0, field=False):
     return (rec, f) if field else rec
 
 
+SMOOTH_ALGORITHM = {"laplace": _capi.TM_S3_LAPLACE, "thomas-middlecoff": _capi.TM_S3_THOMAS_MIDDLECOFF, "prescribed": _capi.TM_S3_PRESCRIBED}
+
+
+@dataclass
+class Smooth3dInfo:
+    """tm_smooth3d_info as a record ("elliptic smoothing of stacked blocks" in the header): counts over the interior nodes, the sign of
+    the Jacobian J of the central differences in the input of the first and of the last sweep, the updates of those two sweeps."""
+
+    nodes: int
+    interior: int
+    sweeps_done: int
+    frozen: int
+    first_neg: int
+    first_pos: int
+    first_zero_or_nan: int
+    last_neg: int
+    last_pos: int
+    last_zero_or_nan: int
+    last_max_node: int           # flat index (k*nj + j)*ni + i; -1: none
+    first_sum_sq: float
+    last_sum_sq: float
+    last_max_update: float
+    control_max: Tuple[float, float, float]
+
+    @classmethod
+    def from_struct(cls, s: "_capi.tm_smooth3d_info") -> "Smooth3dInfo":
+        node = int(s.last_max_node)
+        return cls(int(s.nodes), int(s.interior), int(s.sweeps_done), int(s.frozen), int(s.first_neg), int(s.first_pos), int(s.first_zero_or_nan),
+                   int(s.last_neg), int(s.last_pos), int(s.last_zero_or_nan), -1 if node == 2 ** 64 - 1 else node, float(s.first_sum_sq),
+                   float(s.last_sum_sq), float(s.last_max_update), tuple(float(v) for v in s.control_max))
+
+    @property
+    def last_rms_update(self) -> float:
+        return float(np.sqrt(self.last_sum_sq / self.interior)) if self.interior else 0.0
+
+    def line(self, name: str) -> str:
+        return (f"{name}: sweeps {self.sweeps_done} interior {self.interior} frozen {self.frozen} "
+                f"J<0 {self.first_neg} -> {self.last_neg} J=0/nan {self.first_zero_or_nan} -> {self.last_zero_or_nan} "
+                f"rms update {self.last_rms_update:.3e} max update {self.last_max_update:.3e} at node {self.last_max_node} "
+                f"max |f| {self.control_max[0]:.3e} {self.control_max[1]:.3e} {self.control_max[2]:.3e}")
+
+
+def log_smooth3d(logger, names, per_block, stage="stack-smooth"):
+    """One line per block on `logger` at INFO; every line starts with `stage`."""
+    for name, r in zip(names, per_block):
+        logger.info("%s", r.line(f"{stage} {name}"))
+
+
+def _planes_in(X, Y, Z):
+    X, Y, Z = (np.array(a, dtype=np.float64, order="C") for a in (X, Y, Z))   # copies: the call works in place
+    if X.ndim != 3 or Y.shape != X.shape or Z.shape != X.shape:
+        raise ValueError("X, Y, Z: three (nk, nj, ni) arrays of one shape")
+    return X, Y, Z
+
+
+def _smooth_opt(shape, sweeps, algorithm, omega, tol, control):
+    """(tm_smooth3d_opt, the arrays it points to)"""
+    if algorithm not in SMOOTH_ALGORITHM:
+        raise ValueError(f"algorithm {algorithm!r}: one of {sorted(SMOOTH_ALGORITHM)}")
+    if sweeps < 0:
+        raise ValueError("sweeps >= 0")
+    keep = []
+    if algorithm == "prescribed" and control is not None:
+        keep = [np.ascontiguousarray(a, dtype=np.float64) for a in control]
+        if len(keep) != 3 or any(a.shape != tuple(shape) for a in keep):
+            raise ValueError("control: three arrays of the shape of the planes")
+    ptrs = [_capi.f64ptr(a) for a in keep] if keep else [None] * 3
+    return _capi.tm_smooth3d_opt(SMOOTH_ALGORITHM[algorithm], 0, int(sweeps), float(omega), float(tol), *ptrs), keep
+
+
+def smooth_planes(X, Y, Z, sweeps, algorithm="thomas-middlecoff", omega=1.0, tol=0.0, host=False, control=None):
+    """`sweeps` Jacobi sweeps of the 3-D Winslow equations on a block given as (nk, nj, ni) arrays, its six faces held ("elliptic smoothing
+    of stacked blocks" in the header, kernel K22) -> (X, Y, Z, Smooth3dInfo); the arguments are not modified.  algorithm: "laplace",
+    "thomas-middlecoff" (the control field that keeps wall clustering, formed from the input block) or "prescribed" (control=(f1, f2, f3),
+    arrays of the planes' shape).  tol > 0 ends the call once the rms update is <= tol (tested behind every 8th sweep).  On the MI355X
+    (tm_smooth3d_planes); host=True: the same definition on the CPU (tm_smooth3d_planes_host, no GPU)."""
+    X, Y, Z = _planes_in(X, Y, Z)
+    nk, nj, ni = X.shape
+    opt, keep = _smooth_opt(X.shape, sweeps, algorithm, omega, tol, control)
+    info = _capi.tm_smooth3d_info()
+    L = _capi.lib()
+    _capi.check((L.tm_smooth3d_planes_host if host else L.tm_smooth3d_planes)(ni, nj, nk, _capi.f64ptr(X), _capi.f64ptr(Y), _capi.f64ptr(Z), C.byref(opt),
+                                                                              C.byref(info)))
+    del keep
+    return X, Y, Z, Smooth3dInfo.from_struct(info)
+
+
+def control_of_planes(X, Y, Z, host=False):
+    """The Thomas-Middlecoff control field (f1, f2, f3) of a block given as (nk, nj, ni) arrays, 0 on every node that is not interior
+    (tm_smooth3d_control; host=True: tm_smooth3d_control_host, no GPU)."""
+    X, Y, Z = _planes_in(X, Y, Z)
+    nk, nj, ni = X.shape
+    f = [np.empty_like(X) for _ in range(3)]
+    L = _capi.lib()
+    _capi.check((L.tm_smooth3d_control_host if host else L.tm_smooth3d_control)(ni, nj, nk, _capi.f64ptr(X), _capi.f64ptr(Y), _capi.f64ptr(Z),
+                                                                                *[_capi.f64ptr(a) for a in f]))
+    return tuple(f)
+
+
 @dataclass
 class Mesh3d:
     """Blocks of a stacked mesh: per block the X, Y, Z coordinates as (nk, nj, ni) arrays (PLOT3D order, i fastest)."""
@@ -163,6 +262,15 @@ class Mesh3d:
 
     def sizes(self):
         return [(x.shape[2], x.shape[1], x.shape[0]) for x, _, _ in self.blocks]
+
+    def smooth(self, sweeps, algorithm="thomas-middlecoff", omega=1.0, tol=0.0, host=False):
+        """smooth_planes on every block, in place; -> the per-block Smooth3dInfo.  The faces of a block are held, so blocks stay conforming."""
+        records = []
+        for b, (X, Y, Z) in enumerate(self.blocks):
+            X, Y, Z, info = smooth_planes(X, Y, Z, sweeps, algorithm, omega, tol, host)
+            self.blocks[b] = (X, Y, Z)
+            records.append(info)
+        return records
 
     def write(self, filename):
         """Multi-block 3-D PLOT3D (output.write_plot3d_3d)."""
@@ -254,6 +362,31 @@ class Stack:
                 fn = L.tm_stack_block_surf_host if host else L.tm_stack_block_surf
             _capi.check(fn(*head(arr), b, k_begin, k_count, *ptrs, *extra))
         return tuple(out) + ((outside[:self.ncuts].copy(),) if return_outside else ())
+
+    def smooth(self, cuts, b, sweeps, algorithm="thomas-middlecoff", omega=1.0, tol=0.0, host=False, control=None):
+        """(X, Y, Z, Smooth3dInfo): all layers of block b, stacked and then smoothed with its six faces held (smooth_planes).  cuts as in
+        block(): one smooth.Smoother per cut -- stacked into a device buffer and smoothed there, only planes and record cross to the
+        host, no handle is modified (tm_stack_smoothers_smooth) -- or one discrete.Mesh per cut (block(), then smooth_planes;
+        host=True: both on the CPU)."""
+        self._check_count(cuts)
+        resident = all(hasattr(c, "_h") for c in cuts)
+        if not resident:
+            return smooth_planes(*self.block(cuts, b, host=host), sweeps, algorithm, omega, tol, host, control)
+        if host:
+            raise ValueError("host=True evaluates host coordinates: pass the meshes, not the handles")
+        ni, nj = cuts[0]._mesh.blocks[b].points.size
+        out = [np.empty((self.nlayers, nj, ni), dtype=np.float64) for _ in range(3)]
+        opt, keep = _smooth_opt(out[0].shape, sweeps, algorithm, omega, tol, control)
+        info = _capi.tm_smooth3d_info()
+        handles = (C.c_void_p * len(cuts))(*[c._h for c in cuts])
+        sf = self.surfaces
+        L = _capi.lib()
+        if sf is None:
+            _capi.check(L.tm_stack_smoothers_smooth(handles, C.byref(self._opt), b, C.byref(opt), *[_capi.f64ptr(o) for o in out], C.byref(info)))
+        else:
+            _capi.check(L.tm_stack_smoothers_smooth_surf(handles, C.byref(self._opt), sf.ref(), b, C.byref(opt), *[_capi.f64ptr(o) for o in out], C.byref(info)))
+        del keep
+        return out[0], out[1], out[2], Smooth3dInfo.from_struct(info)
 
     def quality(self, cuts, host=False):
         """(per_block, total): the 3-D quality report of every stacked block (quality.Quality3d) and their total -- negative and degenerate
